@@ -104,13 +104,15 @@ def test_synth_host_generator_properties(lib, oracle_lib):
     assert 0 < (a == ord("N")).sum() < 40
 
 
-def test_find_bounds_matches_oracle_and_the_awk_program(lib, oracle_lib, tmp_path):
-    """hast_kc_find_bounds (host arithmetic of find_bounds.awk) against the oracle's restatement on random histograms and, in the
-    build container, against the reference's own awk program run on the printed rows"""
+def test_find_bounds_matches_oracle_and_the_awk_program(lib, oracle_lib):
+    """hast_kc_find_bounds (host arithmetic of find_bounds.awk) against the oracle's restatement on random histograms and
+    against what the reference's own awk program printed for the same histograms (tests/golden/find_bounds/awk_bounds.json)"""
     import ctypes as C
+    import json
     import random
     rng = random.Random(5)
-    awk = "/root/reference/00.build_unshare_kmers_by_jellyfish/find_bounds.awk"
+    awk = json.load(open(os.path.join(ROOT, "tests", "golden", "find_bounds", "awk_bounds.json")))["cases"]
+    assert len(awk) == 60
     for it in range(60):
         h = np.zeros(hast_amd.KC_HISTO_HIGH + 2, dtype=np.uint64)
         shape = rng.choice(["typical", "sparse", "flat", "empty", "rising", "tail"])
@@ -132,12 +134,9 @@ def test_find_bounds_matches_oracle_and_the_awk_program(lib, oracle_lib, tmp_pat
         out = [C.c_long() for _ in range(4)]
         oracle_lib.ho_s00_find_bounds(h.ctypes.data_as(C.POINTER(C.c_uint64)), *[C.byref(x) for x in out])
         assert got == tuple(x.value for x in out), (shape, got)
-        if os.path.exists(awk):
-            rows = "".join("%d %d\n" % (c, h[c]) for c in range(1, 10002) if h[c])
-            (tmp_path / "h.histo").write_text(rows)
-            r = subprocess.run(["awk", "-f", awk, str(tmp_path / "h.histo")], stdout=subprocess.PIPE, check=True).stdout.decode()
-            ref = tuple(int(l.split("=")[1]) for l in r.splitlines())
-            assert got == ref, (shape, got, ref)
+        # the stored case is this histogram: same shape, same number of non-zero rows given to the awk program
+        assert (awk[it]["shape"], awk[it]["rows"]) == (shape, int(np.count_nonzero(h[1:10002]))), (it, shape)
+        assert got == tuple(awk[it]["bounds"]), (shape, got, awk[it]["bounds"])
 
 
 def test_committed_pmc_profiles_belong_to_these_device_sources(monkeypatch):

@@ -53,7 +53,7 @@ def test_one_rank_over_rccl_self_launched(one_process):
     the rank runs RCCL init, barrier(device_ids), the all_reduce of the int64 view of the (u64) counters and the MAX of the elapsed
     times.  The totals must equal the plain run's and the line must say where the time went."""
     env = {"HAST_BENCH_FORCE_DIST": "1"}
-    r = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "6", "--warmup", "2"] + COMMON, env)
+    r = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "6", "--warmup", "2", "--full"] + COMMON, env)
     assert r["n_gpus"] == 1 and r["hits"] == one_process["hits"] and r["hits"]["c0"] > 0
     assert "all_reduce" in r["config"]["collective"] and "nccl" in r["ranks"]["backend"]
     assert r["allreduce_ms"] > 0 and r["ranks"]["allreduce_ms"]["per_rank"] == [pytest.approx(r["allreduce_ms"], abs=1e-3)]
@@ -75,7 +75,7 @@ def test_ranks_sharing_the_gpu_equal_one_process(one_process, ranks):
     the rank-0 output for N = 2 and N = 4 (the box allows six processes on its GPU)."""
     common = COMMON
     n = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1",
-              "--master-port", str(29533 + ranks), "bench.py", "--gpus", str(ranks), "--steps", "3", "--warmup", "1"] + common,
+              "--master-port", str(29533 + ranks), "bench.py", "--gpus", str(ranks), "--steps", "3", "--warmup", "1", "--full"] + common,
              {"HAST_BENCH_SHARE_GPU": "1", "HAST_BENCH_BACKEND": "gloo"})
     # ranks r = 0..N-1 at timed steps j = 1..3 own batches (N j + r) = N .. 4N-1; one process with warmup N owns the same range
     one = one_process if ranks == 2 else _run([sys.executable, "bench.py", "--steps", str(3 * ranks), "--warmup", str(ranks)] + common, {})

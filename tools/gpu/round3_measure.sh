@@ -4,13 +4,13 @@
 cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
 O=gpurun_out
-python bench.py > $O/round3_bench_default.json 2> $O/round3_bench_default.err; tail -2 $O/round3_bench_default.err
-python bench.py --cpu-seconds 0 --workload c5 > $O/round3_bench_c5.json 2>/dev/null
-python bench.py --cpu-seconds 0 --workload c2 > $O/round3_bench_c2.json 2>/dev/null
-python bench.py --cpu-seconds 0 --clustered > $O/round3_bench_c3_clustered.json 2>/dev/null
-python bench.py --cpu-seconds 0 --steps 60 > $O/round3_bench_c3_2p9Breads.json 2>/dev/null
-HAST_BENCH_FORCE_DIST=1 python bench.py --gpus 1 --cpu-seconds 0 > $O/round3_bench_c3_one_rank_rccl.json 2>/dev/null
-python bench.py --workload s00 > $O/round3_bench_s00.json 2>/dev/null
+python bench.py --full > $O/round3_bench_default.json 2> $O/round3_bench_default.err; tail -2 $O/round3_bench_default.err
+python bench.py --full --cpu-seconds 0 --workload c5 > $O/round3_bench_c5.json 2>/dev/null
+python bench.py --full --cpu-seconds 0 --workload c2 > $O/round3_bench_c2.json 2>/dev/null
+python bench.py --full --cpu-seconds 0 --clustered > $O/round3_bench_c3_clustered.json 2>/dev/null
+python bench.py --full --cpu-seconds 0 --steps 60 > $O/round3_bench_c3_2p9Breads.json 2>/dev/null
+HAST_BENCH_FORCE_DIST=1 python bench.py --full --gpus 1 --cpu-seconds 0 > $O/round3_bench_c3_one_rank_rccl.json 2>/dev/null
+python bench.py --full --workload s00 > $O/round3_bench_s00.json 2>/dev/null
 for f in default c5 c2 c3_clustered c3_2p9Breads c3_one_rank_rccl s00; do python3 -c "
 import json; d=json.load(open('$O/round3_bench_$f.json')); r=d['roofline']; print('$f', round(d['value']/1e9,1), 'Gbp/s', round(d['ms_per_step'],2), 'ms/step kernel', round(r.get('kernel_ms_avg',0) or 0,2), 'frac', r.get('frac'), 'req', (r.get('request_rate') or {}).get('frac_of_ceiling_this_run'), 'allreduce_ms', d.get('allreduce_ms'))"; done
 D=$(mktemp -d /tmp/hast_e2e.XXXXXX)

@@ -5,8 +5,8 @@ export TMPDIR=/tmp
 O=gpurun_out
 mkdir -p $O
 timeout -k 10 900 python -m pytest tests -m gpu -x -q > $O/round4_final_pytest.log 2>&1; echo "pytest rc=$? $(tail -1 $O/round4_final_pytest.log)"
-python bench.py --workload s00 > $O/round4_bench_s00.json 2>/dev/null
-python bench.py > $O/round4_final_bench_default.json 2>/dev/null
+python bench.py --full --workload s00 > $O/round4_bench_s00.json 2>/dev/null
+python bench.py --full > $O/round4_final_bench_default.json 2>/dev/null
 for f in round4_bench_s00 round4_final_bench_default; do python3 -c "
 import json; d=json.load(open('$O/$f.json')); r=d['roofline']; print('$f', round(d['value']/1e9,1), 'Gbp/s; roofline.frac', r.get('frac'), '; traffic', r.get('traffic'), '; useful', json.dumps(r.get('useful'))[:200])"; done
 D=$(mktemp -d /tmp/hast_e2e.XXXXXX)

@@ -5,12 +5,12 @@ cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
 O=gpurun_out
 mkdir -p $O
-python bench.py > $O/round4_bench_default.json 2> $O/round4_bench_default.err; tail -2 $O/round4_bench_default.err
-python bench.py --cpu-seconds 0 --workload c5 > $O/round4_bench_c5.json 2>/dev/null
-python bench.py --cpu-seconds 0 --workload c2 > $O/round4_bench_c2.json 2>/dev/null
-python bench.py --cpu-seconds 0 --clustered > $O/round4_bench_c3_clustered.json 2>/dev/null
-python bench.py --workload s00 > $O/round4_bench_s00.json 2>/dev/null
-HAST_KC_COUNT=atomic python bench.py --workload s00 --cpu-seconds 0 > $O/round4_bench_s00_atomic.json 2>/dev/null
+python bench.py --full > $O/round4_bench_default.json 2> $O/round4_bench_default.err; tail -2 $O/round4_bench_default.err
+python bench.py --full --cpu-seconds 0 --workload c5 > $O/round4_bench_c5.json 2>/dev/null
+python bench.py --full --cpu-seconds 0 --workload c2 > $O/round4_bench_c2.json 2>/dev/null
+python bench.py --full --cpu-seconds 0 --clustered > $O/round4_bench_c3_clustered.json 2>/dev/null
+python bench.py --full --workload s00 > $O/round4_bench_s00.json 2>/dev/null
+HAST_KC_COUNT=atomic python bench.py --full --workload s00 --cpu-seconds 0 > $O/round4_bench_s00_atomic.json 2>/dev/null
 for f in default c5 c2 c3_clustered s00 s00_atomic; do python3 -c "
 import json; d=json.load(open('$O/round4_bench_$f.json')); r=d['roofline']; print('$f', round(d['value']/1e9,1), 'Gbp/s', round(d['ms_per_step'],2) if 'ms_per_step' in d else d.get('seconds'), 'ms/step; kernel', round(r.get('kernel_ms_avg',0) or 0,2), 'ms; roofline.frac', r.get('frac'), '; of the request ceiling', (r.get('request_rate') or {}).get('frac_of_ceiling_this_run'), '; useful', json.dumps(r.get('useful'))[:300])"; done
 D=$(mktemp -d /tmp/hast_e2e.XXXXXX)

@@ -10,9 +10,9 @@ if [ -z "$SKIP_SUITE" ]; then
   python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -1
 fi
 if [ -z "$SKIP_BENCH" ]; then
-  python bench.py > $O/round6_bench_default.json 2> $O/round6_bench_default.err; echo "bench default: $(python3 -c "import json;d=json.load(open('$O/round6_bench_default.json'));print(round(d['value']/1e9,1),'Gbp/s frac',d['roofline'].get('frac'),'frac_survey_8d',d['roofline'].get('frac_survey_8d'),'cpu_baseline',d['cpu_baseline'].get('value'))")"
+  python bench.py --full > $O/round6_bench_default.json 2> $O/round6_bench_default.err; echo "bench default: $(python3 -c "import json;d=json.load(open('$O/round6_bench_default.json'));print(round(d['value']/1e9,1),'Gbp/s frac',d['roofline'].get('frac'),'frac_survey_8d',d['roofline'].get('frac_survey_8d'),'cpu_baseline',d['cpu_baseline'].get('value'))")"
   for wl in c2 c5 s00; do
-    python bench.py --workload $wl > $O/round6_bench_$wl.json 2> $O/round6_bench_$wl.err; echo "bench $wl: $(python3 -c "import json;d=json.load(open('$O/round6_bench_$wl.json'));print(round(d['value']/1e9,1),'Gbp/s frac',d['roofline'].get('frac'))")"
+    python bench.py --full --workload $wl > $O/round6_bench_$wl.json 2> $O/round6_bench_$wl.err; echo "bench $wl: $(python3 -c "import json;d=json.load(open('$O/round6_bench_$wl.json'));print(round(d['value']/1e9,1),'Gbp/s frac',d['roofline'].get('frac'))")"
   done
 fi
 if [ -z "$SKIP_CLI" ]; then

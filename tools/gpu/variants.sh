@@ -11,7 +11,7 @@ for spec in "base:" "$@"; do
   name=${spec%%:*}
   if [ $name = base ]; then unset HAST_LIB; else export HAST_LIB=/tmp/variants/libhast_$name.so; fi
   for wl in "" "--clustered"; do
-    timeout 600 python bench.py --cpu-seconds 0 --steps 10 $wl > /tmp/variants/b.json 2> /tmp/variants/b.err || tail -3 /tmp/variants/b.err
+    timeout 600 python bench.py --full --cpu-seconds 0 --steps 10 $wl > /tmp/variants/b.json 2> /tmp/variants/b.err || tail -3 /tmp/variants/b.err
     python3 -c "
 import json; d=json.load(open('/tmp/variants/b.json')); print('$name $wl', round(d['value']/1e9,1), 'Gbp/s', round(d['roofline']['kernel_ms_avg'],2), 'ms', d['hits']['c0'])"
   done
