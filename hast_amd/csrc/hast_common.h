@@ -129,7 +129,7 @@ HAST_HD uint32_t next_bucket(uint32_t b, uint32_t step, uint64_t key, uint32_t n
 // With PRINTS, a window whose print is in one of its sub-buckets, or whose sub-buckets are all full (then a key may not have
 // found room), is a POSITIVE and is looked up in the exact table, which alone decides hits and tag bits; everything else is a
 // proven miss.  So the filter can only cost time, never change a result.  Where a filed string fits a 16-bit entry exactly
-// ("exact entries" below) a match is the hit itself and only full sub-buckets send a window to the table.
+// ("exact entries" below) a match is the hit itself and only sub-buckets that turned a key away send a window to the table.
 struct FilterGeom {
     int k, m, t;            // k-mer, sampled m-mer (m <= 15, 4^m blocks), ordering t-mer (t <= m)
     int kp;                 // the sampling only looks at the first kp bases of a window (kp <= k): W = kp-m+1 candidates
@@ -165,10 +165,37 @@ HAST_HD uint32_t mul24_forced(uint32_t a, uint32_t b) {
     return (a & 0xFFFFFFu) * (b & 0xFFFFFFu);
 #endif
 }
-// order of a t-mer: 20 hash bits above 12 position bits; smaller wins, equal t-mers (or equal hashes) -> the leftmost.
-// (t-mers are at most 12 bases in every geometry filter_geom_for picks, so the 24-bit product sees the whole t-mer; a
-// longer t-mer forced by an override is ordered by its last 12 bases -- still one order shared by build and probe.)
-HAST_HD uint32_t tmer_order(uint32_t tmer, uint32_t pos) { return ((mul24(tmer + 1u, 0x9E3779u) >> 12) << 12) | pos; }
+// Order of the t-mers: the open-closed order (Groot Koerkamp, Liu & Pibiri 2025) with s = 3 over the t-mer's last 6 bases.
+// Split a 6-mer into its 4 overlapping 3-mers and find the smallest (3-mers ordered by a 32-bit multiplicative hash, a
+// bijection, so only equal 3-mers tie: the leftmost wins).  Class 0 = "open syncmer" (smallest 3-mer second from the left,
+// the middle of 4), 1 = "closed" (at either end), 2 = the rest; t-mers of a lower class always win, a hash orders them inside
+// a class.  Open syncmers are spaced apart in a sequence, so the smallest t-mer of a window jumps less often: 22.9 instead of
+// 23.7 runs of windows with one sampled m-mer per 150-bp read at K = 21, m = 14, t = 6 (profiles/tmer_order_sim.txt).  The
+// class only looks at the low 12 bits -- the whole t-mer at t = 6, which every K = 21 and K = 31 geometry uses -- so the kernel
+// reads it from a 4096-entry, 1-KB table in LDS (tmer_class_word) whatever t is.
+HAST_HD uint32_t tmer_class(uint32_t tmer) {
+    uint32_t best = 0xFFFFFFFFu, at = 0;
+    for (uint32_t j = 0; j < 4; ++j) {
+        const uint32_t h = (((tmer >> (2 * (3 - j))) & 63u) + 1u) * 0x9E3779B1u;
+        if (h < best) { best = h; at = j; }
+    }
+    return at == 1 ? 0u : (at == 0 || at == 3) ? 1u : 2u;
+}
+// the classes of t-mers 16w .. 16w+15 (low 12 bits), 2 bits each, t-mer 16w + i at bit 2i: what the kernel keeps in LDS
+constexpr uint32_t kTmerClassWords = 4096 / 16;
+HAST_HD uint32_t tmer_class_word(uint32_t w) {
+    uint32_t v = 0;
+    for (uint32_t i = 0; i < 16; ++i) v |= tmer_class(16u * w + i) << (2 * i);
+    return v;
+}
+// the order of a t-mer of class `cls` at position `pos`: class in the top 2 bits, 18 hash bits, 12 position bits; smaller wins,
+// and since the hash is injective on 12-bit t-mers, only equal t-mers tie (-> the leftmost).  (t-mers are at most 12 bases in
+// every geometry filter_geom_for picks, so the 24-bit product sees the whole t-mer; a longer t-mer forced by an override is
+// ordered by its last 12 bases -- still one order shared by build and probe.)
+HAST_HD uint32_t tmer_order_cls(uint32_t tmer, uint32_t pos, uint32_t cls) {
+    return (cls << 30) | ((mul24(tmer + 1u, 0x9E3779u) >> 14) << 12) | pos;
+}
+HAST_HD uint32_t tmer_order(uint32_t tmer, uint32_t pos) { return tmer_order_cls(tmer, pos, tmer_class(tmer & 0xFFFu)); }
 // position (0 .. W-1) of the m-mer that names the block of the K-mer string `fwd` (2K bits, first base most significant)
 HAST_HD uint32_t filter_sample_pos(uint64_t fwd, const FilterGeom &g) {
     const uint32_t nt = filter_nt(g), tmask = (uint32_t)kmer_mask(g.t);
@@ -214,7 +241,8 @@ HAST_HD uint32_t filter_print_of(uint32_t keyhash) {
 // are stored above the key's 2 tag bits.  An entry that matches a window then IS the window's string with its tags: a hit
 // needs no look-up in the exact table (with prints every hit costs a second HBM request -- 1.3 per read on random keys, 11 per
 // read on keys with real-data structure), and a window whose sub-bucket holds no match and is not full is a proven miss.
-// Only a window that lands in a FULL sub-bucket without a match still asks the table (a key may have found no room).
+// Only a window that lands in a sub-bucket without a match whose slot 7 holds the overflow mark (kFilterOverflowMark: a key
+// found no room there) still asks the table.
 HAST_HD int filter_pos_bits(const FilterGeom &g) {
     int b = 0;
     while ((1u << b) < filter_w(g)) ++b;
@@ -232,6 +260,9 @@ HAST_HD uint32_t filter_exact_code(uint64_t fwd, uint32_t pm, const FilterGeom &
 }
 HAST_HD uint32_t filter_exact_sub(uint32_t code17) { return code17 >> 14; }
 HAST_HD uint32_t filter_exact_entry(uint32_t code17, uint32_t tags) { return ((code17 & 0x3FFFu) << 2) | tags; }   // tags 1..3: never 0
+// slot 7 of an exact-entry sub-bucket that turned an entry away (the build writes it over that slot's entry).  Tag bits 00: no
+// entry is ever equal to it, and against any window's complemented code bits it gives at most 0xFFFC -- never a hit (>= 0xFFFD).
+constexpr uint32_t kFilterOverflowMark = 0xFFFCu;
 // Geometry for K and a key count (m = 15, a 137-GB filter, only where the key count asks for it: above 537M keys).
 // Geometry for K and a key count.  Measured with tools/sim/filter_load_sim.cpp (unscaled: 400M keys, both strands filed):
 // what limits m from below is not the average load of a block but the skew of the sampling -- the sampled m-mers all hold

@@ -15,8 +15,10 @@ namespace hast {
 // ------------------------------------------------------------------------------------------
 // Filter build: every live key of the exact table is filed under the block of its own string and under the block of its
 // reverse complement (a read window is looked up under the block of the window as it stands).  A sub-bucket holds 8
-// 16-bit prints that fill in order (0 = free); a key that finds its sub-bucket full is simply not filed: lookups treat a
-// full sub-bucket as "ask the exact table".
+// 16-bit prints that fill in order (0 = free); a print that finds its sub-bucket full is simply not filed: lookups treat a
+// full sub-bucket as "ask the exact table".  An EXACT entry that finds no room instead marks its sub-bucket: slot 7 becomes
+// kFilterOverflowMark (hast_common.h), and only a marked sub-bucket sends a window without a match to the table -- most full
+// sub-buckets hold exactly 8 entries and prove a miss like any other (profiles/tmer_order_sim.txt).
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t sub_load(const uint32_t *w) {                 // prints in a sub-bucket (they fill in order)
     uint32_t n = 0;
@@ -41,6 +43,16 @@ __device__ __forceinline__ bool sub_insert(uint32_t *w, uint32_t fp) {
     }
     return false;
 }
+// slot 7 of a full sub-bucket := the overflow mark.  The entry it replaces is one more key without room: the exact table has it
+// and the mark sends its windows there.  Idempotent, so concurrent inserters into the same full sub-bucket need no order.
+__device__ __forceinline__ void sub_mark_overflow(uint32_t *w) {
+    uint32_t v = __hip_atomic_load(&w[kFilterPrints / 2 - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    while ((v >> 16) != kFilterOverflowMark) {
+        const uint32_t old = atomicCAS(&w[kFilterPrints / 2 - 1], v, (v & 0xFFFFu) | (kFilterOverflowMark << 16));
+        if (old == v) break;
+        v = old;
+    }
+}
 __device__ __forceinline__ void filter_insert(uint32_t *filt, const FilterGeom g, uint64_t key, uint32_t tags) {
     for (int o = 0; o < 2; ++o) {
         const uint64_t s = o ? kmer_revcomp(key, g.k) : key;
@@ -51,7 +63,7 @@ __device__ __forceinline__ void filter_insert(uint32_t *filt, const FilterGeom g
             const uint32_t blk = filter_block_of((uint32_t)(s >> (2 * (g.k - g.m - (int)pm))) & (uint32_t)kmer_mask(g.m), g.m);
             const uint32_t c17 = filter_exact_code(s, pm, g);
             uint32_t *w = filt + (size_t)blk * (kFilterSubs * kFilterPrints / 2) + filter_exact_sub(c17) * (kFilterPrints / 2);
-            (void)sub_insert(w, filter_exact_entry(c17, tags));      // full: not filed; windows that land there ask the table
+            if (!sub_insert(w, filter_exact_entry(c17, tags))) sub_mark_overflow(w);     // full: windows that land there ask the table
             continue;
         }
         // block, sub-buckets and print all come from the string AS A READ WOULD SHOW IT: the probe never canonicalises
@@ -109,7 +121,7 @@ hipError_t launch_filter_build(const uint64_t *slots, TableGeom tg, void *filter
 //                 both sub-buckets full) -- the real hits plus a few in 10^5 false ones -- go to the wave's queue in LDS.
 //               exact entries (EXACT): the window's 17-bit code names ONE sub-bucket and 14 stored bits; one 16-B load;
 //                 compare = 4 xor + 3 v_pk_max_u16; a match carries the tag bits and is added to the read's votes at once,
-//                 only "no match in a full sub-bucket" is queued.
+//                 only "no match in a sub-bucket that turned a key away" (slot 7 = kFilterOverflowMark) is queued.
 //   V  verify : when a wave's queue holds 64 entries (and at the end of the tile) each lane takes one, canonicalises it
 //               (v_bfrev) and finds it in the exact table (home bucket by the table's own minimizer, then the chain)
 //               and adds its tag bits to the read's votes in LDS.
@@ -137,6 +149,11 @@ __device__ __forceinline__ uint32_t pk_max_u16(uint32_t a, uint32_t b) {
     const u16x2f r = __builtin_elementwise_max(__builtin_bit_cast(u16x2f, a), __builtin_bit_cast(u16x2f, b));
     return __builtin_bit_cast(uint32_t, r);
 }
+// tmer_order with the t-mer's class from the LDS copy of the class table (tmer_class_word): one ds_read and one v_bfe instead
+// of four 3-mer hashes and their minimum
+__device__ __forceinline__ uint32_t tmer_order_lds(const uint32_t *cls, uint32_t tm, uint32_t pos) {
+    return tmer_order_cls(tm, pos, __builtin_amdgcn_ubfe(cls[(tm >> 4) & 0xFFu], tm << 1, 2u));
+}
 __device__ __forceinline__ uint32_t lanes_below(unsigned long long mask) {          // set bits of mask below my lane
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
@@ -159,6 +176,7 @@ template <> struct GeoConst<2> { static constexpr int k = 31, m = 15, t = 6, kp 
 template <int NTC, bool FAST, bool STRICT, bool WIDE, bool EXACT, bool TWO, int GEO = 0, int RL = 0>
 __global__ void __launch_bounds__(kThreadsF, HAST_F_MINWAVES) k_classify_f(ClassifyArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
+    __shared__ uint32_t s_cls[kTmerClassWords];                     // the t-mer classes of tmer_order, 2 bits each (1 KB)
     typedef GeoConst<GEO> GC0;
     constexpr bool RLC = RL != 0 && GEO != 0;                        // row shape known at compile time
     const uint32_t TR = a.tile_reads;
@@ -201,6 +219,7 @@ __global__ void __launch_bounds__(kThreadsF, HAST_F_MINWAVES) k_classify_f(Class
     const u32x4f *filt = reinterpret_cast<const u32x4f *>(a.filter);
     const u64x2f *tab0 = reinterpret_cast<const u64x2f *>(a.slots);
 
+    for (uint32_t i = tid; i < kTmerClassWords; i += kThreadsF) s_cls[i] = tmer_class_word(i);    // (published by the barrier below)
     if (tid == 0) *s_tile = atomicAdd(a.tile_queue, 1ull);
     __syncthreads();
     for (;;) {
@@ -285,10 +304,19 @@ __global__ void __launch_bounds__(kThreadsF, HAST_F_MINWAVES) k_classify_f(Class
                 const uint32_t q0 = in ? 4 * (gi - r * gpr) : 0;
                 const int nv = in ? (int)s_len[r] - T + 1 - (int)q0 : 0;                  // e[q0 + i] exists iff i < nv
                 const unsigned long long bits = window_bits(s_pack + (size_t)r * WS, nv > 0 ? q0 : 0, t3shift);   // T+3 bases
-                uint32_t e[4];
+                // the four class words first, whether or not position q0 + i exists (in range for any t-mer): the four LDS
+                // reads go out together and wait once, where a read under `i < nv` waits on its own behind a branch
+                uint32_t tm[4], cw[4], e[4];
 #pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    e[i] = i < nv ? tmer_order((uint32_t)(bits >> (2 * (3 - i))) & tmask, q0 + i) : 0xFFFFFFFFu;
+                for (int i = 0; i < 4; ++i) {
+                    tm[i] = (uint32_t)(bits >> (2 * (3 - i))) & tmask;
+                    cw[i] = s_cls[(tm[i] >> 4) & 0xFFu];
+                }
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const uint32_t o = tmer_order_cls(tm[i], q0 + i, __builtin_amdgcn_ubfe(cw[i], tm[i] << 1, 2u));
+                    e[i] = i < nv ? o : 0xFFFFFFFFu;
+                }
                 const uint32_t s2 = min(e[2], e[3]), s1 = min(e[1], s2), s0 = min(e[0], s1);
                 const uint32_t p1 = min(e[0], e[1]), p2 = min(p1, e[2]);
                 // the next lane's values: wave_shl:1 in the VALU's own data path (a ds_bpermute would queue behind the LDS traffic)
@@ -309,7 +337,7 @@ __global__ void __launch_bounds__(kThreadsF, HAST_F_MINWAVES) k_classify_f(Class
                 const bool valid = in && (q + T <= s_len[r]);
                 q = valid ? q : 0;
                 const uint32_t tm = (uint32_t)window_bits(s_pack + (size_t)r * WS, q, tshift);
-                const uint32_t e = valid ? tmer_order(tm, q) : 0xFFFFFFFFu;
+                const uint32_t e = valid ? tmer_order_lds(s_cls, tm, q) : 0xFFFFFFFFu;
                 uint32_t mn = e;
                 if (G >= 2) mn = min(mn, (uint32_t)__shfl_down((int)e, 1));
                 if (G >= 3) mn = min(mn, (uint32_t)__shfl_down((int)e, 2));
@@ -461,7 +489,9 @@ __global__ void __launch_bounds__(kThreadsF, HAST_F_MINWAVES) k_classify_f(Class
                 const bool valid = (int)B.meta < 0;
                 const bool hit = valid && m16 >= 0xFFFDu;
                 if (hit) atomicAdd(&s_vote[B.meta & 0xFFFFu], (unsigned long long)(m16 & 1u) | ((unsigned long long)((m16 >> 1) & 1u) << 32));
-                pos = valid && !hit && (B.v.w >> 16) != 0;               // no match in a FULL sub-bucket: the key may not have found room
+                // no match in a sub-bucket that turned a key away (slot 7 = the overflow mark): that key may be the window's; a full
+                // sub-bucket without the mark holds every string filed there, and proves a miss
+                pos = valid && !hit && (B.v.w >> 16) == kFilterOverflowMark;
             } else {
             uint32_t acc = pk_min_u16(pk_min_u16(B.v.x ^ B.fpw, B.v.y ^ B.fpw), pk_min_u16(B.v.z ^ B.fpw, B.v.w ^ B.fpw));
             bool full = (B.v.w >> 16) != 0;
