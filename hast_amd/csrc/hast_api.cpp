@@ -1212,8 +1212,9 @@ static hast_status classify_rows(hast_ctx *c, const uint8_t *d_bases, size_t bas
         per_read = (size_t)(a.w64 + 1) * 8 + 8 + 8 + 4 + 4 + (size_t)a.mh_stride * 4 + (strict ? (size_t)(2 * a.w64 + 1) * 4 : 0);
         pad = (size_t)wlen * 4 + 64 + 64 + 16;
     }
-    // 5 / 8 workgroups per CU; k_classify_f's static 1 KB (the t-mer class table) comes off its share
-    const size_t lds_budget = c->tile_lds ? c->tile_lds : (filt ? (size_t)32000 - (size_t)kTmerClassWords * 4 : (size_t)19968);
+    // 5 / 8 workgroups per CU; k_classify_f's static 2 KB (the t-mer level table) comes off its share (150-bp reads: 35 reads
+    // per tile, 31768 B in all, as with the 1-KB class table before it)
+    const size_t lds_budget = c->tile_lds ? c->tile_lds : (filt ? (size_t)32000 - (size_t)kTmerLevelTableWords * 4 : (size_t)19968);
     const uint32_t tr_max = (uint32_t)std::min<size_t>(64, std::max<size_t>(1, lds_budget > pad + per_read ? (lds_budget - pad) / per_read : 1));
     uint32_t tr = tr_max;
     if (a.max_pos > 0) {
@@ -1226,7 +1227,7 @@ static hast_status classify_rows(hast_ctx *c, const uint8_t *d_bases, size_t bas
     }
     a.tile_reads = tr;
     const size_t smem = per_read * tr + pad;
-    if (smem + (filt ? (size_t)kTmerClassWords * 4 : 0) > (160u << 10)) return fail(HAST_ERR_INVALID, "read_len %u needs %zu B of LDS", read_len, smem);
+    if (smem + (filt ? (size_t)kTmerLevelTableWords * 4 : 0) > (160u << 10)) return fail(HAST_ERR_INVALID, "read_len %u needs %zu B of LDS", read_len, smem);
     // __umulhi(q, magic) == q / d for every q the kernel forms (exact while q*d < 2^32)
     auto magic = [](uint64_t qmax, uint32_t d) -> uint32_t {
         if (d <= 1 || qmax * d >= (1ull << 32)) return 0;

@@ -7,6 +7,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "tmer_level_table.h"
+
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define HAST_HD __host__ __device__ __forceinline__
@@ -170,9 +172,10 @@ HAST_HD uint32_t mul24_forced(uint32_t a, uint32_t b) {
 // bijection, so only equal 3-mers tie: the leftmost wins).  Class 0 = "open syncmer" (smallest 3-mer second from the left,
 // the middle of 4), 1 = "closed" (at either end), 2 = the rest; t-mers of a lower class always win, a hash orders them inside
 // a class.  Open syncmers are spaced apart in a sequence, so the smallest t-mer of a window jumps less often: 22.9 instead of
-// 23.7 runs of windows with one sampled m-mer per 150-bp read at K = 21, m = 14, t = 6 (profiles/tmer_order_sim.txt).  The
-// class only looks at the low 12 bits -- the whole t-mer at t = 6, which every K = 21 and K = 31 geometry uses -- so the kernel
-// reads it from a 4096-entry, 1-KB table in LDS (tmer_class_word) whatever t is.
+// 23.7 runs of windows with one sampled m-mer per 150-bp read at K = 21, m = 14, t = 6 (profiles/tmer_order_sim.txt).  Inside
+// a class the t-mers are ordered by a searched LEVEL (tools/sim/tmer_rank_search.cpp, tmer_level_table.h) and then a hash.
+// Class and level only look at the low 12 bits -- the whole t-mer at t = 6, which every K = 21 and K = 31 geometry uses -- so
+// the kernel reads them from a 4096-entry, 2-KB table of levels in LDS whatever t is.
 HAST_HD uint32_t tmer_class(uint32_t tmer) {
     uint32_t best = 0xFFFFFFFFu, at = 0;
     for (uint32_t j = 0; j < 4; ++j) {
@@ -188,12 +191,27 @@ HAST_HD uint32_t tmer_class_word(uint32_t w) {
     for (uint32_t i = 0; i < 16; ++i) v |= tmer_class(16u * w + i) << (2 * i);
     return v;
 }
-// the order of a t-mer of class `cls` at position `pos`: class in the top 2 bits, 18 hash bits, 12 position bits; smaller wins,
-// and since the hash is injective on 12-bit t-mers, only equal t-mers tie (-> the leftmost).  (t-mers are at most 12 bases in
-// every geometry filter_geom_for picks, so the 24-bit product sees the whole t-mer; a longer t-mer forced by an override is
-// ordered by its last 12 bases -- still one order shared by build and probe.)
+// The level of a t-mer (low 12 bits): 4 bits, class-major -- every level of class 0 is below every level of class 1, and so on
+// (kTmerLevelClass1 / 2: the first level of class 1 / 2) -- so the level alone orders the classes.  Table (generated, with the
+// class bounds): 8 t-mers per word, t-mer v at bits 4 (v & 7) of word v >> 3; k_classify_f keeps the 512 words in LDS.
+constexpr uint32_t kTmerLevelTableWords = 4096 / 8;
+HAST_HD uint32_t tmer_level(uint32_t tmer) { return (kTmerLevelWords[(tmer >> 3) & 0x1FFu] >> ((tmer & 7u) * 4)) & 15u; }
+HAST_HD uint32_t tmer_level_class(uint32_t lvl) { return lvl >= kTmerLevelClass2 ? 2u : lvl >= kTmerLevelClass1 ? 1u : 0u; }
+// ties inside a level: a bijection of the t-mer's low 12 bits (times an odd number mod 2^12)
+constexpr uint32_t kTmerHashMul = 0x2C5u;
+HAST_HD uint32_t tmer_hash12(uint32_t tmer) { return ((tmer & 0xFFFu) * kTmerHashMul) & 0xFFFu; }
+// The order of a t-mer of level `lvl` at position `pos` as k_classify_f forms it: level in the top 4 bits, 2 zero bits, the
+// 12-bit hash, 2 zero bits, 12 position bits.  The class is a monotone function of the level, so this orders the t-mers exactly as
+// tmer_order does (which has the class above it): only equal t-mers tie (-> the leftmost), and the low 12 bits are the same.
+// On the device: one v_mul_u32_u24 (the hash lands at bits 14..25 of t-mer x (mul << 14)), one v_and_or, one v_lshl_or.
+HAST_HD uint32_t tmer_order_lvl(uint32_t tmer, uint32_t pos, uint32_t lvl) {
+    return (lvl << 28) | (mul24(tmer, kTmerHashMul << 14) & 0x03FFC000u) | pos;
+}
+// the order of a t-mer of class `cls` at position `pos`: class in the top 2 bits, then the level (4 bits), the hash (12 bits
+// and 2 zero bits) and 12 position bits; smaller wins.  (A t-mer longer than 6 bases, forced by an override, is ordered by its
+// last 6 bases and then its position -- still one order shared by build and probe.)
 HAST_HD uint32_t tmer_order_cls(uint32_t tmer, uint32_t pos, uint32_t cls) {
-    return (cls << 30) | ((mul24(tmer + 1u, 0x9E3779u) >> 14) << 12) | pos;
+    return (cls << 30) | ((tmer_level(tmer & 0xFFFu) << 26) | (tmer_order_lvl(tmer, pos, 0) & 0x03FFFFFFu));
 }
 HAST_HD uint32_t tmer_order(uint32_t tmer, uint32_t pos) { return tmer_order_cls(tmer, pos, tmer_class(tmer & 0xFFFu)); }
 // position (0 .. W-1) of the m-mer that names the block of the K-mer string `fwd` (2K bits, first base most significant)

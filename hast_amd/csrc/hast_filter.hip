@@ -107,7 +107,7 @@ hipError_t launch_filter_build(const uint64_t *slots, TableGeom tg, void *filter
 // ------------------------------------------------------------------------------------------
 // k_classify_f.  Workgroup = 256 threads = 4 wave64; tiles of TR reads go through LDS:
 //   A  pack   : as hast_kernels.hip: 16 ASCII bases per lane -> 32 bits of 2-bit codes; 'N' flag / invalid-byte mask.
-//   M  order  : e[q] = tmer_order(t-mer at q, q) for every position, and the first level of the sliding minimum,
+//   M  order  : e[q] = tmer_order_lvl(t-mer at q, q) for every position, and the first level of the sliding minimum,
 //               L1[q] = min(e[q .. q+3]): a lane takes 4 consecutive positions (one funnel shift, four hashes) and needs
 //               the prefix minima of the next lane's four (three DPP moves).  A window's smallest t-mer (leftmost on
 //               ties) is then the minimum of ceil((kp-t+1)/4) L1 entries.
@@ -149,10 +149,11 @@ __device__ __forceinline__ uint32_t pk_max_u16(uint32_t a, uint32_t b) {
     const u16x2f r = __builtin_elementwise_max(__builtin_bit_cast(u16x2f, a), __builtin_bit_cast(u16x2f, b));
     return __builtin_bit_cast(uint32_t, r);
 }
-// tmer_order with the t-mer's class from the LDS copy of the class table (tmer_class_word): one ds_read and one v_bfe instead
-// of four 3-mer hashes and their minimum
-__device__ __forceinline__ uint32_t tmer_order_lds(const uint32_t *cls, uint32_t tm, uint32_t pos) {
-    return tmer_order_cls(tm, pos, __builtin_amdgcn_ubfe(cls[(tm >> 4) & 0xFFu], tm << 1, 2u));
+// the t-mer's level from the LDS copy of the level table (kTmerLevelWords, 4 bits per t-mer): one v_bfe of the word
+// s_lvl[(tm >> 3) & 511]; the key is tmer_order_lvl, which orders the t-mers exactly as tmer_order does
+__device__ __forceinline__ uint32_t tmer_level_of_word(uint32_t word, uint32_t tm) { return __builtin_amdgcn_ubfe(word, tm << 2, 4u); }
+__device__ __forceinline__ uint32_t tmer_order_lds(const uint32_t *lvl, uint32_t tm, uint32_t pos) {
+    return tmer_order_lvl(tm, pos, tmer_level_of_word(lvl[(tm >> 3) & 0x1FFu], tm));
 }
 __device__ __forceinline__ uint32_t lanes_below(unsigned long long mask) {          // set bits of mask below my lane
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
@@ -176,7 +177,7 @@ template <> struct GeoConst<2> { static constexpr int k = 31, m = 15, t = 6, kp 
 template <int NTC, bool FAST, bool STRICT, bool WIDE, bool EXACT, bool TWO, int GEO = 0, int RL = 0>
 __global__ void __launch_bounds__(kThreadsF, HAST_F_MINWAVES) k_classify_f(ClassifyArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
-    __shared__ uint32_t s_cls[kTmerClassWords];                     // the t-mer classes of tmer_order, 2 bits each (1 KB)
+    __shared__ uint32_t s_lvl[kTmerLevelTableWords];                // the t-mer levels of tmer_order, 4 bits each (2 KB)
     typedef GeoConst<GEO> GC0;
     constexpr bool RLC = RL != 0 && GEO != 0;                        // row shape known at compile time
     const uint32_t TR = a.tile_reads;
@@ -219,7 +220,7 @@ __global__ void __launch_bounds__(kThreadsF, HAST_F_MINWAVES) k_classify_f(Class
     const u32x4f *filt = reinterpret_cast<const u32x4f *>(a.filter);
     const u64x2f *tab0 = reinterpret_cast<const u64x2f *>(a.slots);
 
-    for (uint32_t i = tid; i < kTmerClassWords; i += kThreadsF) s_cls[i] = tmer_class_word(i);    // (published by the barrier below)
+    for (uint32_t i = tid; i < kTmerLevelTableWords; i += kThreadsF) s_lvl[i] = kTmerLevelWords[i];    // (published by the barrier below)
     if (tid == 0) *s_tile = atomicAdd(a.tile_queue, 1ull);
     __syncthreads();
     for (;;) {
@@ -304,17 +305,17 @@ __global__ void __launch_bounds__(kThreadsF, HAST_F_MINWAVES) k_classify_f(Class
                 const uint32_t q0 = in ? 4 * (gi - r * gpr) : 0;
                 const int nv = in ? (int)s_len[r] - T + 1 - (int)q0 : 0;                  // e[q0 + i] exists iff i < nv
                 const unsigned long long bits = window_bits(s_pack + (size_t)r * WS, nv > 0 ? q0 : 0, t3shift);   // T+3 bases
-                // the four class words first, whether or not position q0 + i exists (in range for any t-mer): the four LDS
+                // the four level words first, whether or not position q0 + i exists (in range for any t-mer): the four LDS
                 // reads go out together and wait once, where a read under `i < nv` waits on its own behind a branch
-                uint32_t tm[4], cw[4], e[4];
+                uint32_t tm[4], lw[4], e[4];
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     tm[i] = (uint32_t)(bits >> (2 * (3 - i))) & tmask;
-                    cw[i] = s_cls[(tm[i] >> 4) & 0xFFu];
+                    lw[i] = s_lvl[(tm[i] >> 3) & 0x1FFu];
                 }
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const uint32_t o = tmer_order_cls(tm[i], q0 + i, __builtin_amdgcn_ubfe(cw[i], tm[i] << 1, 2u));
+                    const uint32_t o = tmer_order_lvl(tm[i], q0 + i, tmer_level_of_word(lw[i], tm[i]));
                     e[i] = i < nv ? o : 0xFFFFFFFFu;
                 }
                 const uint32_t s2 = min(e[2], e[3]), s1 = min(e[1], s2), s0 = min(e[0], s1);
@@ -337,7 +338,7 @@ __global__ void __launch_bounds__(kThreadsF, HAST_F_MINWAVES) k_classify_f(Class
                 const bool valid = in && (q + T <= s_len[r]);
                 q = valid ? q : 0;
                 const uint32_t tm = (uint32_t)window_bits(s_pack + (size_t)r * WS, q, tshift);
-                const uint32_t e = valid ? tmer_order_lds(s_cls, tm, q) : 0xFFFFFFFFu;
+                const uint32_t e = valid ? tmer_order_lds(s_lvl, tm, q) : 0xFFFFFFFFu;
                 uint32_t mn = e;
                 if (G >= 2) mn = min(mn, (uint32_t)__shfl_down((int)e, 1));
                 if (G >= 3) mn = min(mn, (uint32_t)__shfl_down((int)e, 2));

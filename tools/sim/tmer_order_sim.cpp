@@ -8,9 +8,10 @@
 //   full         windows without a match that land in a full sub-bucket (two full ones with two choices): sent to the table
 //   full_ovf     ... of which the sub-bucket had an insert rejected (exact entries: only these need the table once slot 7
 //                holds the overflow mark; the rest are proven misses)
-// orders: hash = the multiplicative hash alone (the order up to this tool), oc = hast_common.h's tmer_order (open-closed
-// classes, s = 3, above that hash).
-//   tmer_order_sim <hash|oc> N K m t kp exact(0/1) choices [threads]
+// orders: hash = the multiplicative hash alone (the order up to this tool), oc = open-closed classes (s = 3) above that hash
+// (the order up to the level table), table = hast_common.h's tmer_order (open-closed classes, the searched levels inside
+// them -- tmer_level_table.h, tools/sim/tmer_rank_search.cpp -- then a hash).
+//   tmer_order_sim <hash|oc|table> N K m t kp exact(0/1) choices [threads]
 #include <algorithm>
 #include <atomic>
 #include <cstdio>
@@ -22,8 +23,9 @@
 using namespace hast;
 
 int main(int argc, char **argv) {
-    if (argc < 9) { fprintf(stderr, "usage: tmer_order_sim <hash|oc> N K m t kp exact choices [threads]\n"); return 2; }
-    const bool oc = !strcmp(argv[1], "oc");
+    if (argc < 9) { fprintf(stderr, "usage: tmer_order_sim <hash|oc|table> N K m t kp exact choices [threads]\n"); return 2; }
+    const bool oc = !strcmp(argv[1], "oc"), table = !strcmp(argv[1], "table");
+    if (!oc && !table && strcmp(argv[1], "hash")) { fprintf(stderr, "order: hash, oc or table\n"); return 2; }
     const uint64_t N = strtoull(argv[2], 0, 10);
     const int K = atoi(argv[3]), m = atoi(argv[4]), t = atoi(argv[5]), kp = atoi(argv[6]), exact = atoi(argv[7]), choices = atoi(argv[8]);
     const int threads = argc > 9 ? atoi(argv[9]) : 8;
@@ -31,12 +33,13 @@ int main(int argc, char **argv) {
     if (exact && !g.exact) { fprintf(stderr, "exact entries do not fit this geometry\n"); return 2; }
     // filter_sample_pos with the order as a parameter (the window's first kp bases only)
     auto sample = [&](uint64_t s) {
-        if (oc) return filter_sample_pos(s >> (2 * (K - kp)), g);
+        if (table) return filter_sample_pos(s >> (2 * (K - kp)), g);
         const uint32_t nt = filter_nt(g), tmask = (uint32_t)kmer_mask(t);
         uint32_t best = 0xFFFFFFFFu;
         for (uint32_t j = 0; j < nt; ++j) {
             const uint32_t tm = (uint32_t)(s >> (2 * (K - t - (int)j))) & tmask;
-            const uint32_t e = ((mul24(tm + 1u, 0x9E3779u) >> 12) << 12) | j;
+            const uint32_t e = oc ? (tmer_class(tm & 0xFFFu) << 30) | ((mul24(tm + 1u, 0x9E3779u) >> 14) << 12) | j
+                                  : ((mul24(tm + 1u, 0x9E3779u) >> 12) << 12) | j;
             best = e < best ? e : best;
         }
         const uint32_t x = best & 0xFFFu;
