@@ -82,6 +82,7 @@ ABI_SYMBOLS = {
     "hast_ctx_set_filter": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     "hast_filter_build": (C.c_int, [vp]),
     "hast_filter_info": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), u64p]),
+    "hast_filter_dense": (C.c_int, [vp, C.POINTER(C.c_int)]),
     "hast_filter_request_ceiling": (C.c_int, [vp, C.POINTER(C.c_double)]),
     "hast_counts_resize": (C.c_int, [vp, C.c_size_t]),
     "hast_counts_bind": (C.c_int, [vp, vp, C.c_size_t]),
@@ -319,6 +320,12 @@ class Context:
         en = C.c_int()
         _ck(self._lib.hast_filter_info(self._h, C.byref(en), None, None, None, None))
         return en.value
+
+    def filter_dense(self):
+        """True: the built filter holds exact entries filed under every m-mer of a string (hast_common.h, dense filing)"""
+        d = C.c_int()
+        _ck(self._lib.hast_filter_dense(self._h, C.byref(d)))
+        return bool(d.value)
 
     def close(self):
         if self._h:

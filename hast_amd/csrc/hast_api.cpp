@@ -111,9 +111,11 @@ struct hast_ctx {
                                             // freed), and the context probes the table directly -- hast_ctx_options / --stats say so
     bool test_filter_oom = false;           // HAST_TEST_FILTER_OOM=1 (tests): the filter's allocation fails
     int filter_m = 0, filter_t = 0, filter_kp = 0;   // overrides (0 = by K and key count)
-    int filter_exact = -1;                           // -1: exact entries where they fit (hast_common.h), 0: prints always
+    int filter_exact = -1;                           // -1: exact entries where they fit, filed densely where the load allows (hast_common.h),
+                                                     // 0: prints always, 1: exact entries filed once per strand (HAST_FILTER_EXACT=once)
     int text_acgt_only = 0;                          // k-mer text lines must be upper-case A/C/G/T (hast_ctx_set_text_check)
     bool exact_env_off = false;                      // HAST_FILTER_EXACT=0 in the environment
+    bool exact_env_once = false;                     // HAST_FILTER_EXACT=once in the environment
     // measurement switches: read from the environment ONCE, when the context is created (hast_ctx_set_option changes them on a
     // live context); a variable that appears in a user's shell later cannot re-route a running job
     int commit_mode = 0;                             // HAST_COMMIT: 0 by batch size, 1 = one atomic per read, 2 = partitioned
@@ -332,8 +334,12 @@ hast_status hast_ctx_create(int device, int k, hast_ctx **out) {
     if (const char *e = getenv("HAST_FILTER_M")) c->filter_m = atoi(e);
     if (const char *e = getenv("HAST_FILTER_T")) c->filter_t = atoi(e);
     if (const char *e = getenv("HAST_FILTER_KP")) c->filter_kp = atoi(e);
-    if (const char *e = getenv("HAST_FILTER_EXACT")) c->exact_env_off = atoi(e) == 0;
+    if (const char *e = getenv("HAST_FILTER_EXACT")) {
+        if (!strcmp(e, "once")) c->exact_env_once = true;             // (before the atoi, which would read the word as 0 = prints)
+        else c->exact_env_off = atoi(e) == 0;
+    }
     if (c->exact_env_off) c->filter_exact = 0;
+    else if (c->exact_env_once) c->filter_exact = 1;
     if (const char *e = getenv("HAST_COMMIT")) c->commit_mode = !strcmp(e, "atomic") ? 1 : !strcmp(e, "partition") ? 2 : 0;
     if (const char *e = getenv("HAST_F_GEO")) c->kernel_geo = e[0] != '0';
     if (const char *e = getenv("HAST_F_RL")) c->kernel_rl = e[0] != '0';
@@ -1200,7 +1206,8 @@ static hast_status classify_rows(hast_ctx *c, const uint8_t *d_bases, size_t bas
     if (filt) {
         a.filter = c->d_filter;
         a.fg = c->fg;
-        a.l1_stride = ((read_len >= (uint32_t)c->fg.t ? read_len - (uint32_t)c->fg.t + 1 : 0) + 1 + 3) & ~3u;
+        // (a dense filter is probed on a fixed grid: no first-level minima, a read costs its packed bases and header only)
+        a.l1_stride = c->fg.dense ? 0 : ((read_len >= (uint32_t)c->fg.t ? read_len - (uint32_t)c->fg.t + 1 : 0) + 1 + 3) & ~3u;
         per_read = (size_t)(a.w64 + 1) * 8 + 8 + 8 + 4 + 4 + (size_t)a.l1_stride * 4 + (strict ? (size_t)(2 * a.w64 + 1) * 4 : 0);
         pad = 16 + classify_f_queue_bytes() + 64 * 4 + 64;
     } else {
@@ -1269,7 +1276,7 @@ hast_status hast_ctx_set_filter(hast_ctx *c, int enable, int m, int t, int kp) {
     if (kp < 0 || kp > c->k || (kp && m && (kp < m || kp - m >= 32))) return fail(HAST_ERR_INVALID, "filter kp=%d out of [m,K]", kp);
     c->use_filter = enable != 0;
     c->filter_fallback_bytes = 0;
-    c->filter_exact = (enable == 2 || c->exact_env_off) ? 0 : -1;
+    c->filter_exact = (enable == 2 || c->exact_env_off) ? 0 : (c->exact_env_once || c->filter_exact == 1) ? 1 : -1;
     c->filter_m = m;
     c->filter_t = t;
     c->filter_kp = kp;
@@ -1288,6 +1295,10 @@ hast_status hast_ctx_set_option(hast_ctx *c, const char *name, long value) {
     else if (!strcmp(name, "tile_lds")) {
         if (value && (value < 4096 || value > 160 * 1024)) return fail(HAST_ERR_INVALID, "tile_lds %ld out of [4096, 163840]", value);
         c->tile_lds = (size_t)value;
+    } else if (!strcmp(name, "filter_exact_once")) {
+        // exact entries filed once per strand (the sampled scheme) instead of under every m-mer; prints stay prints
+        if (c->filter_exact != 0) c->filter_exact = value ? 1 : (c->exact_env_once ? 1 : -1);
+        c->filter_valid = false;
     } else return fail(HAST_ERR_INVALID, "unknown option %s", name);
     return HAST_OK;
 }
@@ -1299,6 +1310,7 @@ hast_status hast_ctx_options(const hast_ctx *c, char *out, size_t cap) {
     if (!c->use_filter) add("filter", 0);
     if (c->filter_fallback_bytes) add("filter_fallback_table_only_no_room_for_bytes", (long)c->filter_fallback_bytes);
     if (c->filter_exact == 0) add("filter_exact", 0);
+    if (c->filter_exact == 1) add("filter_exact_once", 1);
     if (c->filter_m) add("filter_m", c->filter_m);
     if (c->filter_t) add("filter_t", c->filter_t);
     if (c->filter_kp) add("filter_kp", c->filter_kp);
@@ -1326,6 +1338,13 @@ hast_status hast_filter_info(const hast_ctx *c, int *enabled, int *m, int *t, in
     if (t) *t = c->filter_valid ? c->fg.t : 0;
     if (kp) *kp = c->filter_valid ? c->fg.kp : 0;
     if (bytes) *bytes = c->filter_valid ? c->filter_bytes : 0;
+    return HAST_OK;
+}
+
+// 1: the filter built for the current table holds exact entries filed under every m-mer (FilterGeom::dense), 0: anything else
+hast_status hast_filter_dense(const hast_ctx *c, int *dense) {
+    if (!c || !dense) return fail(HAST_ERR_INVALID, "null argument");
+    *dense = (c->use_filter && c->filter_valid && c->fg.dense) ? 1 : 0;
     return HAST_OK;
 }
 

@@ -139,6 +139,7 @@ struct FilterGeom {
     uint32_t wdiv;          // floor(2^16 / W) + 1: x / W for x < 64 by multiply-shift
     int exact;              // 1: the 16-bit entries are EXACT codes of the filed strings (below), one sub-bucket per string
     int choices;            // prints: sub-buckets a print may sit in (2, or 1 where the blocks are lightly loaded)
+    int dense;              // exact entries filed under EVERY one of the string's W m-mers ("dense filing" below): no sampling, t unused
 };
 constexpr int kFilterSubs = 8;                    // 16-B sub-buckets per 128-B block
 constexpr int kFilterPrints = 8;                  // 16-bit prints per sub-bucket
@@ -281,6 +282,22 @@ HAST_HD uint32_t filter_exact_entry(uint32_t code17, uint32_t tags) { return ((c
 // slot 7 of an exact-entry sub-bucket that turned an entry away (the build writes it over that slot's entry).  Tag bits 00: no
 // entry is ever equal to it, and against any window's complemented code bits it gives at most 0xFFFC -- never a hit (>= 0xFFFD).
 constexpr uint32_t kFilterOverflowMark = 0xFFFCu;
+// ---- dense filing (FilterGeom::dense) ------------------------------------------------------------------------------------
+// The sampled scheme files a string ONCE per strand, and no forward scheme that does so gets below 17.7 blocks per 150-bp read at
+// m = 14, W = 8.  An exact filter of 4^14 blocks is nearly empty, though (400M keys fill 4.7 % of its
+// entries): there is room to file every string under EACH of its W m-mers (W entries with W different pm, i.e. W different
+// codes), and then the probe may pick any position it likes.  It picks the m-mer whose start lies on a fixed grid of the row:
+// the window at position p uses pm = (W - 1 - p) mod W, so the W windows of a grid cell all name the m-mer that starts at the
+// cell's last position -- ceil(windows / W) blocks per read (17 for 150 bp), no t-mer order, no sliding minimum.  Entry format,
+// inversion (block + sub-bucket + entry -> string) and the overflow mark are those of the sampled scheme.  All m-mers of all keys
+// are used, so random keys load the sub-buckets as a Poisson variable of mean 2 W N / (8 * 4^m); the rule below keeps that mean
+// at or under kFilterDenseMaxLoad, where P(>= 9 entries) sends under one window per read to the table (0.47 at 2.98, 0.74 at
+// 3.2, 1.3 at 3.5, 2.8 at 4.0 -- past 3.2 the look-ups eat what the blocks save).  W must be a power of two (the mask below).
+constexpr double kFilterDenseMaxLoad = 3.2;
+HAST_HD uint32_t filter_dense_pm(uint32_t p, uint32_t w) { return (w - 1u - p) & (w - 1u); }
+HAST_HD double filter_dense_load(const FilterGeom &g, uint64_t n_keys) {
+    return 2.0 * (double)filter_w(g) * (double)n_keys / ((double)kFilterSubs * (double)filter_nblocks(g));
+}
 // Geometry for K and a key count (m = 15, a 137-GB filter, only where the key count asks for it: above 537M keys).
 // Geometry for K and a key count.  Measured with tools/sim/filter_load_sim.cpp (unscaled: 400M keys, both strands filed):
 // what limits m from below is not the average load of a block but the skew of the sampling -- the sampled m-mers all hold
@@ -292,7 +309,8 @@ constexpr uint32_t kFilterOverflowMark = 0xFFFCu;
 // kp = min(K, m + 8): longer windows (K = 31) are sampled on their first kp bases only -- more candidates would lower the
 // density further but pile the keys on even fewer blocks.
 // exact_mode: -1 = exact entries where they fit (and, for tables of 16M keys and more, the m that makes them fit: m = K-7,
-// i.e. 14 at K = 21 -- a 34-GB filter next to 288 GB of HBM), 0 = prints always.
+// i.e. 14 at K = 21 -- a 34-GB filter next to 288 GB of HBM) and dense filing where its rule allows it, 0 = prints always,
+// 1 = as -1 but exact entries are filed once per strand whatever the load (the sampled scheme, for A/B runs and tests).
 HAST_HD FilterGeom filter_geom_for(int k, uint64_t n_keys, int m_override, int t_override, int kp_override = 0, int exact_mode = -1) {
     FilterGeom g;
     g.k = k;
@@ -320,6 +338,7 @@ HAST_HD FilterGeom filter_geom_for(int k, uint64_t n_keys, int m_override, int t
     // second load and compare -- config 5 is bound by VALU issue.  At 3 per block (400M keys, m = 14) one choice sends 0.5
     // windows per read to the table and 6 per block (800M keys, m = 14) 11 % of them: two choices there.
     g.choices = (2.0 * (double)n_keys <= 2.2 * (double)(1ull << (2 * m))) ? 1 : 2;
+    g.dense = (g.exact && exact_mode < 0 && w <= 8 && (w & (w - 1)) == 0 && filter_dense_load(g, n_keys) <= kFilterDenseMaxLoad) ? 1 : 0;
     return g;
 }
 

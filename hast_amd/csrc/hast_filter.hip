@@ -58,12 +58,15 @@ __device__ __forceinline__ void filter_insert(uint32_t *filt, const FilterGeom g
         const uint64_t s = o ? kmer_revcomp(key, g.k) : key;
         if (o && s == key) break;                                    // its own reverse complement
         if (g.exact) {
-            // exact entry (hast_common.h): the string's code picks the one sub-bucket it can sit in and is stored with the tags
-            const uint32_t pm = filter_sample_pos(s, g);
-            const uint32_t blk = filter_block_of((uint32_t)(s >> (2 * (g.k - g.m - (int)pm))) & (uint32_t)kmer_mask(g.m), g.m);
-            const uint32_t c17 = filter_exact_code(s, pm, g);
-            uint32_t *w = filt + (size_t)blk * (kFilterSubs * kFilterPrints / 2) + filter_exact_sub(c17) * (kFilterPrints / 2);
-            if (!sub_insert(w, filter_exact_entry(c17, tags))) sub_mark_overflow(w);     // full: windows that land there ask the table
+            // exact entry (hast_common.h): the string's code picks the one sub-bucket it can sit in and is stored with the tags.
+            // Filed under the sampled m-mer, or -- dense filing -- under every one of the W m-mers (W entries, W different codes)
+            const uint32_t pm0 = g.dense ? 0u : filter_sample_pos(s, g), pm1 = g.dense ? filter_w(g) : pm0 + 1u;
+            for (uint32_t pm = pm0; pm < pm1; ++pm) {
+                const uint32_t blk = filter_block_of((uint32_t)(s >> (2 * (g.k - g.m - (int)pm))) & (uint32_t)kmer_mask(g.m), g.m);
+                const uint32_t c17 = filter_exact_code(s, pm, g);
+                uint32_t *w = filt + (size_t)blk * (kFilterSubs * kFilterPrints / 2) + filter_exact_sub(c17) * (kFilterPrints / 2);
+                if (!sub_insert(w, filter_exact_entry(c17, tags))) sub_mark_overflow(w);     // full: windows that land there ask the table
+            }
             continue;
         }
         // block, sub-buckets and print all come from the string AS A READ WOULD SHOW IT: the probe never canonicalises
@@ -132,6 +135,9 @@ constexpr int kQCap = 128;                                    // queue entries p
 #ifndef HAST_F_MINWAVES
 #define HAST_F_MINWAVES 5      // 96 VGPRs: measured best of 4/5/6/8 (242 vs 226-228 Gbp/s with prints; exact entries: 4, 5, 6 within 1.5 %)
 #endif
+#ifndef HAST_F_MINWAVES_DENSE
+#define HAST_F_MINWAVES_DENSE 5     // the DENSE instantiations (a tile takes 6.4 KB of LDS: registers alone set the occupancy)
+#endif
 typedef unsigned long long u64x2f __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4f __attribute__((ext_vector_type(4)));
 typedef unsigned short u16x2f __attribute__((ext_vector_type(2)));
@@ -174,8 +180,11 @@ template <> struct GeoConst<2> { static constexpr int k = 31, m = 15, t = 6, kp 
 
 // RL (only with GEO): the rows' length as a compile-time constant too (150- and 100-bp reads; the 512-base segment rows of long reads):
 // words per row, the L1 stride and the windows per row become immediates and the row/position divisions constant divisions.
-template <int NTC, bool FAST, bool STRICT, bool WIDE, bool EXACT, bool TWO, int GEO = 0, int RL = 0>
-__global__ void __launch_bounds__(kThreadsF, HAST_F_MINWAVES) k_classify_f(ClassifyArgs a) {
+// DENSE (only with EXACT): the filter holds every string under each of its W m-mers (hast_common.h, dense filing): the window at
+// row position p takes pm = filter_dense_pm(p, W) -- no phase M, no s_l1, no level table; everything from the m-mer on is the same.
+template <int NTC, bool FAST, bool STRICT, bool WIDE, bool EXACT, bool TWO, int GEO = 0, int RL = 0, bool DENSE = false>
+__global__ void __launch_bounds__(kThreadsF, DENSE ? HAST_F_MINWAVES_DENSE : HAST_F_MINWAVES) k_classify_f(ClassifyArgs a) {
+    static_assert(!DENSE || EXACT, "dense filing is a property of exact entries");
     extern __shared__ __align__(16) unsigned char smem[];
     __shared__ uint32_t s_lvl[kTmerLevelTableWords];                // the t-mer levels of tmer_order, 4 bits each (2 KB)
     typedef GeoConst<GEO> GC0;
@@ -183,7 +192,7 @@ __global__ void __launch_bounds__(kThreadsF, HAST_F_MINWAVES) k_classify_f(Class
     const uint32_t TR = a.tile_reads;
     const uint32_t W64 = RLC ? (uint32_t)((RL + 31) / 32) : a.w64;
     const uint32_t WS = W64 + 1;                                     // LDS words per read incl. pad
-    const uint32_t L1S = RLC ? (uint32_t)((RL - GC0::t + 1 + 1 + 3) & ~3) : a.l1_stride;
+    const uint32_t L1S = DENSE ? 0u : RLC ? (uint32_t)((RL - GC0::t + 1 + 1 + 3) & ~3) : a.l1_stride;   // (DENSE: no first-level minima)
     unsigned long long *s_tile = reinterpret_cast<unsigned long long *>(smem);            // next tile of this workgroup
     uint32_t *s_dirty = reinterpret_cast<uint32_t *>(s_tile + 1);                          // STRICT: some row of the tile holds a byte outside ACGT
     uint32_t *s_l1 = reinterpret_cast<uint32_t *>(s_tile + 2);                             // [TR][L1S] (+ 64 pad), 16-B aligned rows
@@ -220,7 +229,8 @@ __global__ void __launch_bounds__(kThreadsF, HAST_F_MINWAVES) k_classify_f(Class
     const u32x4f *filt = reinterpret_cast<const u32x4f *>(a.filter);
     const u64x2f *tab0 = reinterpret_cast<const u64x2f *>(a.slots);
 
-    for (uint32_t i = tid; i < kTmerLevelTableWords; i += kThreadsF) s_lvl[i] = kTmerLevelWords[i];    // (published by the barrier below)
+    if (!DENSE)
+        for (uint32_t i = tid; i < kTmerLevelTableWords; i += kThreadsF) s_lvl[i] = kTmerLevelWords[i];    // (published by the barrier below)
     if (tid == 0) *s_tile = atomicAdd(a.tile_queue, 1ull);
     __syncthreads();
     for (;;) {
@@ -292,7 +302,9 @@ __global__ void __launch_bounds__(kThreadsF, HAST_F_MINWAVES) k_classify_f(Class
         __syncthreads();
 
         // ---- M: t-mer order and the first level of the sliding minimum, L1[q] = min(e[q .. q+g-1]) ---------------------
-        if (G == 4) {
+        if (DENSE) {
+            // nothing to order: the probe takes the m-mer on the row's grid
+        } else if (G == 4) {
             // a lane takes 4 consecutive positions (one funnel shift, four hashes); L1 of its positions needs its own
             // suffix minima and the prefix minima of the next lane's four (three shuffles); lane 63 only serves lane 62
             const uint32_t gpr = L1S >> 2, total = tra * gpr;          // groups of 4 positions per read (L1S % 4 == 0)
@@ -345,7 +357,7 @@ __global__ void __launch_bounds__(kThreadsF, HAST_F_MINWAVES) k_classify_f(Class
                 if (lane < step && in) s_l1[idx] = mn;
             }
         }
-        __syncthreads();
+        if (!DENSE) __syncthreads();
         if (!STRICT) {          // reads with 'N' get length 0 (whole-read skip, classify.cpp:190-193)
             if (tid < tra && s_flag[tid]) s_len[tid] = 0;
             __syncthreads();
@@ -436,19 +448,24 @@ __global__ void __launch_bounds__(kThreadsF, HAST_F_MINWAVES) k_classify_f(Class
                 }
             }
             const unsigned long long fwd = window_bits(s_pack + mul24(r, WS), p, kshift);
-            const uint32_t *l1 = s_l1 + mul24(r, L1S) + p;
-            uint32_t x = l1[0];
-            if (NTC) {
-#pragma unroll
-                for (int c = 1; c + 1 < (NTC ? NTC : 1); ++c) x = min(x, l1[c * 4]);
+            uint32_t pm;
+            if (DENSE) {
+                pm = filter_dense_pm(p, W);                           // the m-mer that starts on the row's grid (W: a power of two)
             } else {
-                for (uint32_t c = 1; c + 1 < ntc; ++c) x = min(x, l1[c * G]);
+                const uint32_t *l1 = s_l1 + mul24(r, L1S) + p;
+                uint32_t x = l1[0];
+                if (NTC) {
+#pragma unroll
+                    for (int c = 1; c + 1 < (NTC ? NTC : 1); ++c) x = min(x, l1[c * 4]);
+                } else {
+                    for (uint32_t c = 1; c + 1 < ntc; ++c) x = min(x, l1[c * G]);
+                }
+                if (ntc > 1) x = min(x, l1[NT - G]);
+                // lanes without a window compute on whatever LDS holds: in range by construction, and never used
+                const uint32_t xr = ((x & 0xFFFu) - p) & 63u;         // position of the smallest t-mer inside the window
+                // ... mod W = position of the sampled m-mer (a mask when W is a known power of two)
+                pm = (GEO && (W & (W - 1)) == 0) ? (xr & (W - 1)) : xr - mul24(mul24(xr, fg.wdiv) >> 16, W);
             }
-            if (ntc > 1) x = min(x, l1[NT - G]);
-            // lanes without a window compute on whatever LDS holds: in range by construction, and never used
-            const uint32_t xr = ((x & 0xFFFu) - p) & 63u;             // position of the smallest t-mer inside the window
-            // ... mod W = position of the sampled m-mer (a mask when W is a known power of two)
-            const uint32_t pm = (GEO && (W & (W - 1)) == 0) ? (xr & (W - 1)) : xr - mul24(mul24(xr, fg.wdiv) >> 16, W);
             const uint32_t mm = (uint32_t)(fwd >> (2 * ((uint32_t)(K - M) - pm))) & mmask;
             uint32_t fb = ok ? filter_block_of(mm, M) : 0xFFFFFFFFu;  // real blocks are < 4^15
             // of the window as it stands (no canonical form in the probe): a hash for two sub-buckets and a print, or the
@@ -587,19 +604,20 @@ hipError_t launch_request_ceiling(const void *filter, uint64_t nblocks, uint32_t
     return hipGetLastError();
 }
 
-template <int NTC, bool FAST, bool STRICT, bool WIDE, bool EXACT, bool TWO, int GEO = 0, int RL = 0>
+template <int NTC, bool FAST, bool STRICT, bool WIDE, bool EXACT, bool TWO, int GEO = 0, int RL = 0, bool DENSE = false>
 static hipError_t launch_f_t(const ClassifyArgs &a, int grid, size_t smem, hipStream_t s) {
     if (smem > (48u << 10)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_classify_f<NTC, FAST, STRICT, WIDE, EXACT, TWO, GEO, RL>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_classify_f<NTC, FAST, STRICT, WIDE, EXACT, TWO, GEO, RL, DENSE>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((k_classify_f<NTC, FAST, STRICT, WIDE, EXACT, TWO, GEO, RL>), dim3(grid), dim3(kThreadsF), smem, s, a);
+    hipLaunchKernelGGL((k_classify_f<NTC, FAST, STRICT, WIDE, EXACT, TWO, GEO, RL, DENSE>), dim3(grid), dim3(kThreadsF), smem, s, a);
     return hipGetLastError();
 }
 // the row shape the host computed is the one a kernel with RL compiled in assumes
 static bool rows_are(const ClassifyArgs &a, uint32_t rl, int k, int t) {
-    return a.read_len == rl && a.w64 == (rl + 31) / 32 && a.max_pos == rl - (uint32_t)k + 1 && a.l1_stride == ((rl - (uint32_t)t + 1 + 1 + 3) & ~3u);
+    return a.read_len == rl && a.w64 == (rl + 31) / 32 && a.max_pos == rl - (uint32_t)k + 1 &&
+           a.l1_stride == (a.fg.dense ? 0u : ((rl - (uint32_t)t + 1 + 1 + 3) & ~3u));
 }
 static bool geo_is(const ClassifyArgs &a, int k, int m, int t, int kp) {
     return a.k == k && a.fg.k == k && a.fg.m == m && a.fg.t == t && a.fg.kp == kp && a.fg.g == 4;
@@ -608,6 +626,20 @@ static bool geo_is(const ClassifyArgs &a, int k, int m, int t, int kp) {
 // EXACT implies one sub-bucket per window (TWO = false)
 // variants: bit 0 = instantiations with the geometry compiled in allowed, bit 1 = with the row length too (the context's switches,
 // read from the environment once when it was created)
+// the DENSE instantiations: the geometry rule only files densely where W is a power of two (hast_common.h), the probe's mask
+template <bool STRICT>
+static hipError_t launch_f_dense(const ClassifyArgs &a, int grid, size_t smem, int variants, hipStream_t s) {
+    const bool fast = a.div_magic && a.div_hw;
+    const bool geo_on = (variants & 1) != 0, rl_on = (variants & 2) != 0;
+    if (fast && geo_on && !STRICT && geo_is(a, 21, 14, 6, 21)) {
+        if (rl_on && rows_are(a, 150, 21, 6)) return launch_f_t<4, true, false, false, true, false, 1, 150, true>(a, grid, smem, s);
+        if (rl_on && rows_are(a, 100, 21, 6)) return launch_f_t<4, true, false, false, true, false, 1, 100, true>(a, grid, smem, s);
+        return launch_f_t<4, true, false, false, true, false, 1, 0, true>(a, grid, smem, s);
+    }
+    return fast ? launch_f_t<0, true, STRICT, false, true, false, 0, 0, true>(a, grid, smem, s)
+                : launch_f_t<0, false, STRICT, false, true, false, 0, 0, true>(a, grid, smem, s);
+}
+
 template <bool STRICT, bool EXACT, bool TWO>
 static hipError_t launch_f_s(const ClassifyArgs &a, int grid, size_t smem, int variants, hipStream_t s) {
     const bool fast = a.div_magic && a.div_l1g && a.div_hw;
@@ -637,6 +669,11 @@ static hipError_t launch_f_s(const ClassifyArgs &a, int grid, size_t smem, int v
 
 hipError_t launch_classify_f(const ClassifyArgs &a, int grid, size_t smem, int variants, hipStream_t s) {
     if (a.n_reads == 0) return hipSuccess;
+    if (a.fg.exact && a.fg.dense && !a.wide) {
+        const uint32_t w = filter_w(a.fg);
+        if (a.l1_stride != 0 || (w & (w - 1)) != 0) return hipErrorInvalidValue;      // (the host sized the tile for another kernel)
+        return a.strict ? launch_f_dense<true>(a, grid, smem, variants, s) : launch_f_dense<false>(a, grid, smem, variants, s);
+    }
     if (a.fg.exact && !a.wide) return a.strict ? launch_f_s<true, true, false>(a, grid, smem, variants, s) : launch_f_s<false, true, false>(a, grid, smem, variants, s);
     if (a.fg.choices == 1) return a.strict ? launch_f_s<true, false, false>(a, grid, smem, variants, s) : launch_f_s<false, false, false>(a, grid, smem, variants, s);
     return a.strict ? launch_f_s<true, false, true>(a, grid, smem, variants, s) : launch_f_s<false, false, true>(a, grid, smem, variants, s);

@@ -70,7 +70,7 @@ int         hast_ctx_device(const hast_ctx *);
  * HAST_F_GEO, HAST_F_RL, HAST_TILE_LDS, HAST_MINIMIZER); results never depend on them.  hast_ctx_set_option changes one on a live
  * context: "commit" 0 = by batch size / 1 = one atomic per read / 2 = partitioned; "kernel_geo", "kernel_rl" 0 = the generic
  * k_classify_f instantiations instead of the ones with the BASELINE geometry / row length compiled in; "tile_lds" bytes (0 =
- * default).  hast_ctx_options writes the switches that differ from their defaults as "name=value ..." ("" = none). */
+ * default); "filter_exact_once" 1 = exact filter entries filed once per strand (see hast_ctx_set_filter).  hast_ctx_options writes the switches that differ from their defaults as "name=value ..." ("" = none). */
 hast_status hast_ctx_set_option(hast_ctx *, const char *name, long value);
 hast_status hast_ctx_options(const hast_ctx *, char *out, size_t cap);
 hast_stream hast_ctx_stream(const hast_ctx *);
@@ -157,10 +157,16 @@ hast_status hast_table_info(const hast_ctx *, uint64_t *n_buckets, uint64_t *byt
  * hast_ctx_set_filter: enable = 0 probes the table directly (the round-1 kernel; also HAST_CLASSIFY=exact in the
  * environment), 1 = filter, exact entries where they fit, 2 = filter with prints always (also HAST_FILTER_EXACT=0); m (sampled
  * m-mer, 4^m blocks), t (ordering t-mer), kp (bases of a window the sampling looks at) = 0 picks the geometry from K and
- * the key count.  hast_filter_info: *enabled = 0 off, 1 prints, 2 exact entries (known once the filter is built). */
+ * the key count.  hast_filter_info: *enabled = 0 off, 1 prints, 2 exact entries (known once the filter is built).
+ * Exact entries are filed DENSELY -- under every one of a string's W = K-m+1 m-mers instead of under one sampled m-mer -- where W
+ * is a power of two <= 8 and the sub-buckets then hold <= 3.2 entries on average (K = 21 up to ~430M keys): the probe takes the
+ * m-mer on a fixed grid of the row, ceil(windows / W) blocks per read, no sampling arithmetic.  HAST_FILTER_EXACT=once in the
+ * environment (hast_ctx_set_option "filter_exact_once") keeps exact entries filed once per strand under the sampled m-mer.
+ * hast_filter_dense: *dense = 1 when the filter built for the current table is a dense one.  Same results either way. */
 hast_status hast_ctx_set_filter(hast_ctx *, int enable, int m, int t, int kp);
 hast_status hast_filter_build(hast_ctx *);
 hast_status hast_filter_info(const hast_ctx *, int *enabled, int *m, int *t, int *kp, uint64_t *bytes);
+hast_status hast_filter_dense(const hast_ctx *, int *dense);
 /* Measurement entry (bench.py's roofline): requests per second at which this GPU serves uniformly random 128-B blocks of the
  * context's own filter, read in the probe kernel's access shape with no arithmetic -- the request-rate ceiling of this box
  * over this footprint, against which k_classify_f's own request rate is priced in the same run. */

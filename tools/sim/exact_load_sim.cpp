@@ -1,6 +1,9 @@
 // exact_load_sim.cpp -- design tool, not product code: load of the EXACT-entry filter (hast_common.h) for random and for clustered
 // keys (synth_key, reserved = 1: runs of K windows around variant sites), one slice of the blocks: sub-bucket histogram and the
-// share of random read windows that land in a FULL sub-bucket (those ask the exact table).   exact_load_sim keys_per_hap clustered(0/1)
+// share of random read windows that land in a FULL sub-bucket, and in a MARKED one (a ninth entry came: those ask the exact table).
+//   exact_load_sim keys_per_hap clustered(0/1) [dense(0/1)]
+// dense = 0 models the sampled scheme (a string filed once per strand, under filter_sample_pos; windows probe there), dense = 1 dense
+// filing (a string under each of its W m-mers; a probing window is a random string at a random position of the row's grid).
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
@@ -10,10 +13,12 @@
 using namespace hast;
 int main(int argc, char **argv) {
     const uint64_t n_per_hap = strtoull(argv[1], 0, 10);
-    const int clustered = atoi(argv[2]), threads = 8;
+    const int clustered = atoi(argv[2]), dense = argc > 3 ? atoi(argv[3]) : 0, threads = 8;
     const uint32_t SLICE = 64;
     const int K = 21;
-    FilterGeom g = filter_geom_for(K, 2 * n_per_hap, 0, 0);
+    FilterGeom g = filter_geom_for(K, 2 * n_per_hap, 0, 0, 0, 1);
+    const uint32_t W = filter_w(g);
+    if (dense && (W & (W - 1))) { printf("dense filing needs W a power of two\n"); return 1; }
     SynthParams p{0x4841535401ull, 0x4841535402ull, 0x4841535403ull, n_per_hap, 1000, 150, (uint32_t)K, (uint32_t)(clustered ? 1 : 0)};
     const uint64_t nb = filter_nblocks(g), nslice = nb / SLICE;
     std::vector<std::atomic<uint8_t>> cnt(nslice * 8);
@@ -27,37 +32,43 @@ int main(int argc, char **argv) {
                 for (int o = 0; o < 2; o++) {
                     const uint64_t s = o ? kmer_revcomp(key, K) : key;
                     if (o && s == key) break;
-                    const uint32_t pm = filter_sample_pos(s, g);
-                    const uint32_t b = filter_block_of((uint32_t)(s >> (2 * (K - g.m - (int)pm))) & (uint32_t)kmer_mask(g.m), g.m);
-                    if (b % SLICE) continue;
-                    const uint32_t c17 = filter_exact_code(s, pm, g);
-                    std::atomic<uint8_t> &c = cnt[(uint64_t)(b / SLICE) * 8 + filter_exact_sub(c17)];
-                    // (duplicates -- the same string from both haplotypes -- would be one entry; ignored here)
-                    uint8_t v = c.load();
-                    if (v >= 8) { lost++; continue; }
-                    c++;
-                    filed++;
+                    const uint32_t pm0 = dense ? 0u : filter_sample_pos(s, g), pm1 = dense ? W : pm0 + 1u;
+                    for (uint32_t pm = pm0; pm < pm1; pm++) {
+                        const uint32_t b = filter_block_of((uint32_t)(s >> (2 * (K - g.m - (int)pm))) & (uint32_t)kmer_mask(g.m), g.m);
+                        if (b % SLICE) continue;
+                        const uint32_t c17 = filter_exact_code(s, pm, g);
+                        std::atomic<uint8_t> &c = cnt[(uint64_t)(b / SLICE) * 8 + filter_exact_sub(c17)];
+                        // (duplicates -- the same string from both haplotypes -- would be one entry; ignored here)
+                        // 0 .. 8 entries; 9 = the ninth came: slot 7 becomes the overflow mark, the entry it held is turned away too
+                        uint8_t v = c.load();
+                        while (v < 9 && !c.compare_exchange_weak(v, (uint8_t)(v + 1))) {}
+                        if (v >= 8) lost += v == 8 ? 2 : 1; else filed++;
+                    }
                 }
             }
     });
     for (auto &x : th) x.join();
     uint64_t hist[10] = {0};
-    for (auto &c : cnt) hist[c > 8 ? 8 : (int)c]++;
+    for (auto &c : cnt) hist[(int)c]++;
     // random windows
-    std::atomic<uint64_t> in_slice{0}, full{0};
+    std::atomic<uint64_t> in_slice{0}, full{0}, marked{0};
     th.clear();
     for (int t = 0; t < threads; t++) th.emplace_back([&, t] {
         for (uint64_t i = t; i < 40000000ull; i += threads) {
             const uint64_t s = synth_rand(99, i, 7) & kmer_mask(K);
-            const uint32_t pm = filter_sample_pos(s, g);
+            const uint32_t pm = dense ? filter_dense_pm((uint32_t)synth_rand(98, i, 7), W) : filter_sample_pos(s, g);
             const uint32_t b = filter_block_of((uint32_t)(s >> (2 * (K - g.m - (int)pm))) & (uint32_t)kmer_mask(g.m), g.m);
             if (b % SLICE) continue;
             in_slice++;
-            if (cnt[(uint64_t)(b / SLICE) * 8 + filter_exact_sub(filter_exact_code(s, pm, g))] >= 8) full++;
+            const uint8_t v = cnt[(uint64_t)(b / SLICE) * 8 + filter_exact_sub(filter_exact_code(s, pm, g))];
+            if (v >= 8) full++;
+            if (v >= 9) marked++;
         }
     });
     for (auto &x : th) x.join();
-    printf("clustered=%d m=%d filed/block %.2f lost %.5f hist", clustered, g.m, (double)filed / nslice, (double)lost / (double)(lost + filed));
-    for (int i = 0; i <= 8; i++) printf(" %llu", (unsigned long long)hist[i]);
-    printf("  windows in a full sub-bucket: %.5f = %.2f per 130-window read\n", (double)full / in_slice, 130.0 * full / in_slice);
+    filed -= hist[9];                                                   // (the entry a mark overwrote)
+    printf("clustered=%d dense=%d m=%d filed/block %.2f lost %.5f hist", clustered, dense, g.m, (double)filed / nslice, (double)lost / (double)(lost + filed));
+    for (int i = 0; i <= 9; i++) printf(" %llu", (unsigned long long)hist[i]);
+    printf("  windows in a full sub-bucket: %.5f = %.2f per 130-window read, in a marked one: %.5f = %.2f per read\n", (double)full / in_slice,
+           130.0 * full / in_slice, (double)marked / in_slice, 130.0 * marked / in_slice);
 }

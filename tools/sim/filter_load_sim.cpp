@@ -19,7 +19,7 @@ int main(int argc, char **argv) {
     const uint32_t SLICE = argc > 7 ? atoi(argv[7]) : 256;
     // the sampling scheme only looks at the first kp bases of a window (kp = argv[8], default K)
     const int kp = argc > 8 ? atoi(argv[8]) : K;
-    FilterGeom g = filter_geom_for(kp, 0, m, t);
+    FilterGeom g = filter_geom_for(kp, 0, m, t, 0, 1);          // (exact entries filed once: this tool models the SAMPLED scheme)
     auto block_of = [&](uint64_t s) { return filter_block_of_string(s >> (2 * (K - kp)), g); };
     const uint64_t nb = filter_nblocks(g);
     const uint64_t nslice = nb / SLICE;

@@ -29,7 +29,7 @@ int main(int argc, char **argv) {
     const uint64_t N = strtoull(argv[2], 0, 10);
     const int K = atoi(argv[3]), m = atoi(argv[4]), t = atoi(argv[5]), kp = atoi(argv[6]), exact = atoi(argv[7]), choices = atoi(argv[8]);
     const int threads = argc > 9 ? atoi(argv[9]) : 8;
-    FilterGeom g = filter_geom_for(kp, 0, m, t, 0, exact ? -1 : 0);
+    FilterGeom g = filter_geom_for(kp, 0, m, t, 0, exact ? 1 : 0);       // (1: exact entries filed once -- this tool models the SAMPLED scheme)
     if (exact && !g.exact) { fprintf(stderr, "exact entries do not fit this geometry\n"); return 2; }
     // filter_sample_pos with the order as a parameter (the window's first kp bases only)
     auto sample = [&](uint64_t s) {
