@@ -129,6 +129,11 @@ ABI_SYMBOLS = {
     "hast_names_insert": (C.c_int, [vp, C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.c_size_t]),
     "hast_fq_set_route": (C.c_int, [vp, C.POINTER(vp), C.c_int]),
     "hast_fq_next_routed": (C.c_int, [vp, C.POINTER(FqRouted)]),
+    "hast_fq_set_route_gz": (C.c_int, [vp, C.c_int]),
+    "hast_fq_routed_raw_bytes": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+    "hast_dz_bound": (C.c_size_t, [C.c_size_t]),
+    "hast_dz_compress_device": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), vp]),
+    "hast_dz_compress_device_ex": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_uint, vp]),
     "hast_gz_open": (C.c_int, [vp, C.c_char_p, C.POINTER(vp)]),
     "hast_gz_open_ex": (C.c_int, [vp, C.c_char_p, C.c_size_t, C.c_size_t, C.c_double, C.POINTER(vp)]),
     "hast_gz_open_multi": (C.c_int, [C.POINTER(vp), C.c_int, C.c_char_p, C.POINTER(vp)]),
@@ -500,6 +505,12 @@ class Context:
                                                    n_reads, C.c_void_p(d_votes), stream))
 
     # synthetic
+    def dz_compress_device(self, d_src, n_bytes, d_dst, cap, literals_only=False, stream=None) -> int:
+        """one gzip member for the n_bytes at d_src, written to d_dst (room: cap >= dz_bound(n_bytes)); returns its size"""
+        n = C.c_size_t()
+        _ck(self._lib.hast_dz_compress_device_ex(self._h, C.c_void_p(d_src), n_bytes, C.c_void_p(d_dst), cap, C.byref(n), 1 if literals_only else 0, stream))
+        return n.value
+
     def synth_keys_device(self, p, hap, first, n, d_out, stream=None):
         _ck(self._lib.hast_synth_keys_device(self._h, C.byref(p), hap, first, n, C.c_void_p(d_out), stream))
 
@@ -512,6 +523,11 @@ class Context:
 
 
 # ---- stage 00: parent-unique k-mer sets ---------------------------------------------------------------------
+def dz_bound(n_bytes: int) -> int:
+    """the most bytes Context.dz_compress_device can write for n_bytes of input"""
+    return lib().hast_dz_bound(n_bytes)
+
+
 def kc_find_bounds(histo: np.ndarray):
     """(MIN_INDEX, MAX_INDEX, LOWER_INDEX, UPPER_INDEX) of find_bounds.awk; host arithmetic only"""
     histo = np.ascontiguousarray(histo, dtype=np.uint64)

@@ -78,6 +78,8 @@ void print_usage() {                              // same flags as the reference
           "      --stats-json FILE the same as one JSON object (- = stderr)\n"
           "      --phase-reads     also do the wrapper's steps 10-11: write the three barcode lists and route every record of every\n"
           "                        input to <name>.{paternal,maternal,homozygous,nobarcode}.fastq (HAST_PHASE_READS=1)\n"
+          "      --gz-out          with --phase-reads: the four files are gzip, <name>.<class>.fastq.gz; records routed on the GPU are\n"
+          "                        compressed there and only compressed bytes come back (HAST_PHASE_GZ=1)\n"
           "      --route MODE      device (default): records routed on the GPU; host: parsed again by host threads\n"
           "      --inflate MODE    device (default) | host | zlib: who inflates .gz inputs (HAST_INFLATE)\n"
           "      --gz-ring-bytes N compressed bytes of a .gz input kept on the device at a time (default: whole files up to 2 GB;\n"
@@ -328,6 +330,7 @@ int main(int argc, char **argv) {
         {"gz-ring-bytes", required_argument, NULL, 1012}, {"stats-json", required_argument, NULL, 1013},
         {"park-gb", required_argument, NULL, 1014},     {"name-cache", required_argument, NULL, 1015},
         {"deal", required_argument, NULL, 1016},        {"route", required_argument, NULL, 1017},
+        {"gz-out", no_argument, NULL, 1018},
         {0, 0, 0, 0}};
     static char optstring[] = "p:m:l:r:t:w:u:f:q:h";             // classify.cpp:387
     std::string hap0, hap1, save_table, load_table;
@@ -342,11 +345,13 @@ int main(int argc, char **argv) {
     bool stats = false, host_parse = false;
     // What changes what a production run allocates or writes is a FLAG; the environment variable each one replaces stays as an alias
     // (a flag wins).  The library reads its switches from the environment, once: a flag is put there before the first library call.
-    bool phase_reads = false;
+    bool phase_reads = false, gz_out = false, gz_out_flag = false;
     std::string stats_json, route_mode;
     {
         const char *pr = getenv("HAST_PHASE_READS");
         phase_reads = pr && *pr && strcmp(pr, "0") != 0;
+        const char *pg = getenv("HAST_PHASE_GZ");
+        gz_out = pg && *pg && strcmp(pg, "0") != 0;
     }
     double w0 = 1.0, w1 = 1.0;
     for (;;) {
@@ -386,6 +391,7 @@ int main(int argc, char **argv) {
             if (strcmp(optarg, "host") && strcmp(optarg, "device")) { print_usage(); return -1; }
             route_mode = optarg;
             break;
+        case 1018: gz_out = gz_out_flag = true; break;
         case 1008:
             for (const char *q = optarg; *q;) {
                 char *end;
@@ -404,6 +410,14 @@ int main(int argc, char **argv) {
         print_usage();
         return -1;
     }
+    // --gz-out says how the routed files are written: without --phase-reads there are none (HAST_PHASE_GZ alone is ignored: a wrapper
+    // may export it for every stage)
+    if (gz_out_flag && !phase_reads) {
+        fputs("classify: --gz-out needs --phase-reads\n", stderr);
+        print_usage();
+        return -1;
+    }
+    gz_out = gz_out && phase_reads;
     if (devices.empty()) devices.push_back(device);
     device = devices[0];
     fprintf(stderr, "__START__\n");
@@ -1366,6 +1380,8 @@ int main(int argc, char **argv) {
         // line awk cuts short): the inputs are parsed again by the worker threads, quartering.h.
         const bool route_on_device = !host_parse && route_mode != "host" && !any_sep;
         uint64_t blocks_routed = 0, blocks_host = 0, bytes_routed = 0;
+        struct GzIn { hq::GzOutStats dev, host; };              // --gz-out, per input: into / out of the GPU's encoder and zlib, members written
+        std::vector<GzIn> gz_in(read.size());
         double t_wait_write = 0, t_wait_gpu = 0;
         if (route_on_device) {
             // the table text -> class of every GPU
@@ -1415,7 +1431,10 @@ int main(int argc, char **argv) {
                 bool any_input = false;
                 std::string err_lines;
             };
-            static const char *suffix[4] = {".nobarcode.fastq", ".paternal.fastq", ".maternal.fastq", ".homozygous.fastq"};
+            static const char *suffix_plain[4] = {".nobarcode.fastq", ".paternal.fastq", ".maternal.fastq", ".homozygous.fastq"};
+            static const char *suffix_gz[4] = {".nobarcode.fastq.gz", ".paternal.fastq.gz", ".maternal.fastq.gz", ".homozygous.fastq.gz"};
+            static const char *const *suffix = nullptr;
+            suffix = gz_out ? suffix_gz : suffix_plain;
             const int n_buf = stripe ? std::max(2, (fq_bufs + (int)ctxs.size() - 1) / (int)ctxs.size()) : fq_bufs;
             std::mutex wake_mu;
             std::condition_variable wake_cv;
@@ -1470,6 +1489,7 @@ int main(int argc, char **argv) {
                 if (stripe) lane_tabs = tabs;
                 else lane_tabs.push_back(tabs[next_file % ctxs.size()]);
                 CK(hast_fq_set_route(f->fq, lane_tabs.data(), (int)lane_tabs.size()), "switching the FASTQ stream to routing");
+                CK(hast_fq_set_route_gz(f->fq, gz_out ? 1 : 0), "switching the routed runs to gzip members");
                 next_file++;
                 RFeed *fp = f.get();
                 f->th = std::thread([fp, cap, &wake] {
@@ -1550,7 +1570,17 @@ int main(int argc, char **argv) {
                         j.p[c] = b.run[c];
                         j.n[c] = (size_t)b.run_bytes[c];
                         f.counts[c] += (long long)b.count[c];
-                        bytes_routed += b.run_bytes[c];
+                        if (!gz_out) bytes_routed += b.run_bytes[c];
+                    }
+                    if (gz_out) {
+                        uint64_t raw[4];
+                        CK(hast_fq_routed_raw_bytes(f.fq, raw), "asking for the runs' sizes");
+                        for (int c = 0; c < 4; c++) {
+                            bytes_routed += raw[c];              // (the records' bytes, as without the flag; the members' sizes: __stats_route_gz__)
+                            gz_in[f.file_index].dev.bytes_in += raw[c];
+                            gz_in[f.file_index].dev.bytes_out += b.run_bytes[c];
+                            gz_in[f.file_index].dev.members += b.run_bytes[c] != 0;
+                        }
                     }
                     f.counts[4] += (long long)b.n_records;
                     if (b.n_records) f.any_input = true;
@@ -1570,6 +1600,16 @@ int main(int argc, char **argv) {
                         f.any_input = true;
                         if (c >= 0) { (*j.own)[(size_t)c].append(r0, len); f.counts[c]++; }
                     }
+                    if (gz_out)                                         // the caller's block: its records compressed by zlib, a member per class
+                        for (int c = 0; c < 4; c++) {
+                            std::string &plain = (*j.own)[(size_t)c], z;
+                            if (plain.empty()) continue;
+                            if (!hq::gz_member(plain.data(), plain.size(), z)) die(2, "cannot compress a block of routed records");
+                            gz_in[f.file_index].host.bytes_in += plain.size();
+                            gz_in[f.file_index].host.bytes_out += z.size();
+                            gz_in[f.file_index].host.members++;
+                            plain.swap(z);
+                        }
                     for (int c = 0; c < 4; c++) { j.p[c] = reinterpret_cast<const uint8_t *>((*j.own)[(size_t)c].data()); j.n[c] = (*j.own)[(size_t)c].size(); }
                     blocks_host++;
                 }
@@ -1585,8 +1625,15 @@ int main(int argc, char **argv) {
                     f.counts[4]++;
                     f.any_input = true;
                     if (c >= 0) {
-                        (*j.own)[(size_t)c].append(rest);
-                        if (rest.back() != '\n') (*j.own)[(size_t)c].push_back('\n');
+                        std::string rec(rest);
+                        if (rec.back() != '\n') rec.push_back('\n');
+                        if (gz_out) {                                   // a member of its own behind the block's
+                            const size_t before = (*j.own)[(size_t)c].size();
+                            if (!hq::gz_member(rec.data(), rec.size(), (*j.own)[(size_t)c])) die(2, "cannot compress the last record");
+                            gz_in[f.file_index].host.bytes_in += rec.size();
+                            gz_in[f.file_index].host.bytes_out += (*j.own)[(size_t)c].size() - before;
+                            gz_in[f.file_index].host.members++;
+                        } else (*j.own)[(size_t)c].append(rec);
                         f.counts[c]++;
                     }
                     for (int c2 = 0; c2 < 4; c2++) { j.p[c2] = reinterpret_cast<const uint8_t *>((*j.own)[(size_t)c2].data()); j.n[c2] = (*j.own)[(size_t)c2].size(); }
@@ -1759,12 +1806,12 @@ int main(int argc, char **argv) {
                     src.gz = nullptr;                        // (no room on the device, ...: the host inflates)
                     hast::BlockSource hsrc;
                     if (!hsrc.open(x, 64u << 20)) die(2, ("cannot open " + x).c_str());
-                    rc = hq::route(name, cls_of, hsrc, "-", t_num, "classify");
-                } else rc = hq::route(name, cls_of, src, "-", t_num, "classify");
+                    rc = hq::route(name, cls_of, hsrc, "-", t_num, "classify", gz_out, &gz_in[fi].host);
+                } else rc = hq::route(name, cls_of, src, "-", t_num, "classify", gz_out, &gz_in[fi].host);
             } else {
                 hast::BlockSource hsrc;
                 if (!hsrc.open(x, 64u << 20)) die(2, ("cannot open " + x).c_str());
-                rc = hq::route(name, cls_of, hsrc, gz_name ? "-" : x, t_num, "classify");       // (awk's FILENAME behind `gzip -dc` is "-")
+                rc = hq::route(name, cls_of, hsrc, gz_name ? "-" : x, t_num, "classify", gz_out, &gz_in[fi].host);       // (awk's FILENAME behind `gzip -dc` is "-")
             }
             if (rc) {
                 fprintf(stderr, "classify: ERROR: routing the reads of %s failed\n", x.c_str());
@@ -1783,6 +1830,11 @@ int main(int argc, char **argv) {
                             "bytes_routed_on_device=%llu waiting_for_gpu_s=%.3f idle_s=%.3f\n",
                     now_s() - t_ph0, t_lists - t_ph0, now_s() - t_lists, route_on_device ? "device" : "host", read.size(), (unsigned long long)blocks_routed,
                     (unsigned long long)blocks_host, (unsigned long long)bytes_routed, t_wait_gpu, t_wait_write);
+        if (stats && gz_out)                                    // one line per input, in the order of the inputs
+            for (size_t i = 0; i < read.size(); i++)
+                stat_line("__stats_route_gz__ file=%s device_bytes_in=%llu device_bytes_out=%llu device_members=%llu host_bytes_in=%llu host_bytes_out=%llu host_members=%llu\n",
+                          read[i].c_str(), gz_in[i].dev.bytes_in, gz_in[i].dev.bytes_out, gz_in[i].dev.members, gz_in[i].host.bytes_in, gz_in[i].host.bytes_out,
+                          gz_in[i].host.members);
     }
     if (past_int)
         fprintf(stderr, " WARN : a barcode has more than INT_MAX hits: the reference's `int` counters overflow on this input; the exact counts were printed\n");

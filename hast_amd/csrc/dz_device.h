@@ -1,0 +1,43 @@
+// dz_device.h -- what dz_api.cpp / fq_api.cpp (host) and dz_kernels.hip (device) share: the description of a compression call as
+// it lies in device memory, the workspace's size and the launchers.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "dz_core.h"
+#include "fq_device.h"
+
+namespace hast {
+namespace dz {
+
+constexpr int kMaxRuns = 4;
+// What to compress: up to four runs of bytes inside one device buffer, a gzip member each.  The sizes may be known on the device only
+// (the routed runs of a FASTQ block: launch_job_from_route), so the kernels read them here and the grids are sized by an upper bound.
+struct Job {
+    uint64_t src_off[kMaxRuns], n_bytes[kMaxRuns];
+    uint32_t n_runs;
+    uint32_t emit_empty;        // 1: a run of 0 bytes becomes an empty member (20 bytes); 0: it becomes nothing
+};
+struct Result {
+    uint64_t out_bytes[kMaxRuns];       // bytes of every member; the members lie back to back from d_dst[0] on
+    uint64_t member_off[kMaxRuns];
+    uint32_t flags;                     // 1: the members do not fit cap, 2: more pieces than the workspace holds (nothing is written then)
+    uint32_t reserved;
+};
+constexpr uint32_t kResOverflow = 1, kResPieces = 2;
+
+// pieces a job of n_bytes in all can have at most, whatever its runs are
+inline uint32_t max_pieces(uint64_t n_bytes) { return (uint32_t)(n_bytes / kPiece) + kMaxRuns; }
+// most bytes the members of such a job take
+inline uint64_t max_out_bytes(uint64_t n_bytes) { return n_bytes + 5ull * max_pieces(n_bytes) + (uint64_t)kMaxRuns * (kMemberHead + kMemberTail); }
+size_t workspace_bytes(uint32_t max_pieces);
+
+hipError_t launch_job_one(Job *d_job, uint64_t n_bytes, hipStream_t s);                       // one run from offset 0, empty member for 0 bytes
+hipError_t launch_job_from_route(Job *d_job, const RouteState *d_rs, hipStream_t s);          // the four runs of a routed block, as they lie in its d_out
+// d_src + job.src_off[r] .. -> members from d_dst[0] on, never at or behind d_dst + cap; d_res says how long they are.
+// literals_only: no match search (Huffman coding alone)
+hipError_t launch_compress(const Job *d_job, const uint8_t *d_src, uint32_t max_pieces, void *d_work, uint8_t *d_dst, uint64_t cap, Result *d_res,
+                           int literals_only, hipStream_t s);
+
+}  // namespace dz
+}  // namespace hast

@@ -13,6 +13,7 @@
 
 #include "../../include/hast.h"
 #include "fq_device.h"
+#include "dz_device.h"
 #include "hast_internal.h"
 
 using namespace hast;
@@ -65,6 +66,15 @@ struct Slot {
     uint8_t *d_rcls = nullptr, *d_out = nullptr, *h_out = nullptr;
     RouteState *d_rs = nullptr, *h_rs = nullptr;       // h_rs pinned
     size_t route_rec = 0;                              // record slots the routing arrays hold
+    // ... as gzip members (hast_fq_set_route_gz): the members back to back and their pinned copy, the encoder's workspace, the call's
+    // description and result (dz_device.h) behind it, the result's pinned copy
+    uint8_t *d_gz = nullptr, *h_gz = nullptr;
+    void *d_dzwork = nullptr;
+    dz::Job *d_dzjob = nullptr;
+    dz::Result *d_dzres = nullptr, *h_dzres = nullptr;
+    size_t gz_cap = 0, dzwork_bytes = 0;
+    uint32_t dz_pieces = 0;
+    bool gz = false;                                   // this block's runs were compressed
     std::vector<uint32_t> v_rstart, v_rlen;            // host copies for a block the caller routes itself (rare)
     std::vector<uint8_t> v_rcls, v_tail;
 };
@@ -116,6 +126,7 @@ struct hast_fq {
     // routing (hast_fq_set_route): the blocks are not classified; their records leave the GPU as four runs by barcode class
     bool route = false;
     std::vector<hast_names *> route_tab;                       // per lane (one for a plain stream): barcode text -> class on that GPU
+    bool route_gz = false;                                     // ... and the runs leave the GPU as gzip members (hast_fq_set_route_gz)
 };
 
 // Every per-record array of a slot has ONE capacity, h_cap, and is only ever resized here: h_bc = [pos | len | 4 words of
@@ -161,6 +172,10 @@ static void free_slot(Slot &s) {
         park_device(p, (p == (void *)s.d_buf || p == (void *)s.d_out) ? s.h_buf_bytes : 0, 3);
     park_pinned(s.h_out, s.h_buf_bytes, 3);
     park_pinned(s.h_rs, 64, 3);
+    park_device(s.d_gz, s.gz_cap, 3);
+    park_device(s.d_dzwork, s.dzwork_bytes, 3);
+    park_pinned(s.h_gz, s.gz_cap, 3);
+    park_pinned(s.h_dzres, 64, 3);
     if (s.copied) (void)hipEventDestroy(s.copied);
     if (s.parsed) (void)hipEventDestroy(s.parsed);
     if (s.done) (void)hipEventDestroy(s.done);
@@ -192,10 +207,18 @@ static hast_status enqueue_names_early(Slot &s, hast_names *nm, hipStream_t hs) 
 // Routing streams: behind the framing of a block, on the same stream -- class and extent of every record, prefix sums, the records copied
 // into four runs, the runs and their sizes to pinned host memory (fq_kernels.hip, "routing").  view_bytes bounds what the runs can hold.
 static hast_status enqueue_route(hast_fq *f, Slot &s, hast_names *tab, bool striped, int last, size_t view_bytes, hipStream_t hs) {
-    (void)f;
     FQ_TRY(launch_fq_route(s.d_buf, s.d_st, s.d_nl, striped ? 1 : 0, last, tab ? tab->d_tab : nullptr, tab ? tab->mask : 0, s.d_rstart, s.d_rlen, s.d_rcls, s.d_rtile,
                            (uint32_t)s.route_rec, s.d_rs, s.d_out, hs));
     FQ_TRY(hipMemcpyAsync(s.h_rs, s.d_rs, sizeof(RouteState), hipMemcpyDeviceToHost, hs));
+    s.gz = f->route_gz && s.d_gz;
+    if (s.gz) {
+        // the runs stay in HBM and are compressed there, a gzip member each (dz_kernels.hip); their sizes come back with the block's
+        // state, the members themselves once hast_fq_next_routed knows how long they are
+        FQ_TRY(dz::launch_job_from_route(s.d_dzjob, s.d_rs, hs));
+        FQ_TRY(dz::launch_compress(s.d_dzjob, s.d_out, s.dz_pieces, s.d_dzwork, s.d_gz, s.gz_cap, s.d_dzres, 0, hs));
+        FQ_TRY(hipMemcpyAsync(s.h_dzres, s.d_dzres, sizeof(dz::Result), hipMemcpyDeviceToHost, hs));
+        return HAST_OK;
+    }
     if (view_bytes) FQ_TRY(hipMemcpyAsync(s.h_out, s.d_out, std::min(view_bytes, s.h_buf_bytes), hipMemcpyDeviceToHost, hs));
     return HAST_OK;
 }
@@ -859,6 +882,7 @@ hast_status hast_fq_set_route(hast_fq *f, hast_names *const *tables, int n_table
         if (s.state != Slot::FREE) return set_error(HAST_ERR_INVALID, "hast_fq_set_route: a block is in hand (commit it first)");
     if (!tables) {
         f->route = false;
+        f->route_gz = false;
         f->route_tab.clear();
         return HAST_OK;
     }
@@ -885,6 +909,58 @@ hast_status hast_fq_set_route(hast_fq *f, hast_names *const *tables, int n_table
     // (the next block starts a file: a routing pass reads its inputs from their first byte)
     f->prev_submitted = -1;
     f->carry.clear();
+    return HAST_OK;
+}
+
+// The routed runs compressed on the device (dz_kernels.hip).  Per slot: room for the members of a whole view, the encoder's workspace.
+// WHAT CROSSES PCIe is the members: their sizes are known on the device only, so they come back with the block's state (pinned, in
+// front of the block's `parsed` event) and hast_fq_next_routed then issues ONE copy of exactly that many bytes and waits for it -- a
+// copy that cannot be queued ahead of time as the plain runs' is; it costs the latency of that copy per block (compressed bytes of a
+// block at PCIe speed -- an estimate, ~1 ms for 64 MB of FASTQ; not measured on its own) while the blocks behind go on being framed, routed and compressed on their streams.
+hast_status hast_fq_set_route_gz(hast_fq *f, int on) {
+    if (!f) return set_error(HAST_ERR_INVALID, "null argument");
+    if (!f->route) return set_error(HAST_ERR_INVALID, "hast_fq_set_route_gz: the stream does not route (hast_fq_set_route)");
+    for (const Slot &s : f->slots)
+        if (s.state != Slot::FREE) return set_error(HAST_ERR_INVALID, "hast_fq_set_route_gz: a block is in hand (commit it first)");
+    if (on)
+        for (Slot &s : f->slots) {
+            if (s.d_gz) continue;
+            FQ_TRY(hipSetDevice(dev_of(f, s)));
+            s.dz_pieces = dz::max_pieces(s.h_buf_bytes);
+            s.gz_cap = (size_t)dz::max_out_bytes(s.h_buf_bytes);
+            const size_t work = (dz::workspace_bytes(s.dz_pieces) + 63) & ~(size_t)63;
+            s.dzwork_bytes = work + sizeof(dz::Job) + sizeof(dz::Result);
+            FQ_TRY(dev_malloc(&s.d_gz, s.gz_cap));
+            FQ_TRY(dev_malloc(&s.d_dzwork, s.dzwork_bytes));
+            s.d_dzjob = reinterpret_cast<dz::Job *>(static_cast<uint8_t *>(s.d_dzwork) + work);
+            s.d_dzres = reinterpret_cast<dz::Result *>(s.d_dzjob + 1);
+            FQ_TRY(pinned_malloc(&s.h_gz, s.gz_cap));
+            FQ_TRY(pinned_malloc(&s.h_dzres, sizeof(dz::Result)));
+        }
+    else
+        for (Slot &s : f->slots) {                          // switched off: the members' buffers and the workspace go back (parked, as a closed stream's)
+            if (!s.d_gz) continue;
+            park_device(s.d_gz, s.gz_cap, 3);
+            park_device(s.d_dzwork, s.dzwork_bytes, 3);
+            park_pinned(s.h_gz, s.gz_cap, 3);
+            park_pinned(s.h_dzres, 64, 3);
+            s.d_gz = s.h_gz = nullptr;
+            s.d_dzwork = nullptr;
+            s.d_dzjob = nullptr;
+            s.d_dzres = s.h_dzres = nullptr;
+            s.gz_cap = s.dzwork_bytes = 0;
+            s.gz = false;
+        }
+    f->route_gz = on != 0;
+    return HAST_OK;
+}
+
+hast_status hast_fq_routed_raw_bytes(hast_fq *f, uint64_t out[4]) {
+    if (!f || !out) return set_error(HAST_ERR_INVALID, "null argument");
+    if (!f->route || f->n_opened == 0) return set_error(HAST_ERR_INVALID, "hast_fq_routed_raw_bytes: no open routed block");
+    const Slot &s = f->slots[(f->n_opened - 1) % f->slots.size()];
+    if (s.state != Slot::OPEN) return set_error(HAST_ERR_INVALID, "hast_fq_routed_raw_bytes: no open routed block");
+    for (int c = 0; c < 4; ++c) out[c] = (s.h_rs->flags & 1) ? 0 : s.h_rs->bytes[c];
     return HAST_OK;
 }
 
@@ -916,6 +992,29 @@ hast_status hast_fq_next_routed(hast_fq *f, hast_fq_routed *out) {
         at += rs.bytes[c];
     }
     if (at > s.h_buf_bytes) return set_error(HAST_ERR_INVALID, "routed runs overflow their buffer");
+    if (s.gz) {
+        // gzip members instead of plain runs (a block the caller routes itself has none: its records go by `bytes`)
+        const dz::Result zr = *s.h_dzres;
+        uint64_t total = 0;
+        for (int c = 0; c < 4; ++c) {
+            out->run[c] = nullptr;
+            out->run_bytes[c] = 0;
+        }
+        if (!(rs.flags & 1)) {
+            if (zr.flags) return set_error(HAST_ERR_INVALID, "the compressed runs overflow their buffer (flags %u)", zr.flags);
+            for (int c = 0; c < 4; ++c) {
+                if (!zr.out_bytes[c]) continue;
+                if (zr.member_off[c] != total || total + zr.out_bytes[c] > s.gz_cap) return set_error(HAST_ERR_INVALID, "the compressed runs are not where they should be");
+                out->run[c] = s.h_gz + total;
+                out->run_bytes[c] = zr.out_bytes[c];
+                total += zr.out_bytes[c];
+            }
+            if (total) {
+                FQ_TRY(hipMemcpyAsync(s.h_gz, s.d_gz, total, hipMemcpyDeviceToHost, hs));
+                FQ_TRY(hipStreamSynchronize(hs));
+            }
+        }
+    }
     if (rs.flags & 1) {
         // a record the device could not route: the caller gets the view and every record's extent + class and routes the block itself
         if (!s.h_buf) FQ_TRY(pinned_malloc(&s.h_buf, s.h_buf_bytes));

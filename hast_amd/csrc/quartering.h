@@ -21,10 +21,45 @@
 #include <unordered_map>
 #include <vector>
 
+#include <zlib.h>
+
 #include "ingest.h"
 
 namespace hast {
 namespace quartering {
+
+// --gz-out: what the host routes leaves as gzip members too (<prefix>.<class>.fastq.gz; concatenated members are one gzip file, so the
+// members `classify` gets from the GPU's encoder and the ones made here share a file).  n bytes -> one member appended to out; level 1,
+// as the files are an intermediate that the next stage reads once.  False: zlib failed (out of memory).
+inline bool gz_member(const char *p, size_t n, std::string &out) {
+    z_stream z;
+    memset(&z, 0, sizeof z);
+    if (deflateInit2(&z, 1, Z_DEFLATED, 15 + 16, 8, Z_DEFAULT_STRATEGY) != Z_OK) return false;
+    const size_t at = out.size();
+    out.resize(at + deflateBound(&z, (uLong)n) + 32);
+    size_t done = 0, written = 0;
+    int rc = Z_OK;
+    do {                                                            // (avail_in is 32 bits wide)
+        const size_t take = std::min<size_t>(n - done, 1u << 30);
+        z.next_in = reinterpret_cast<Bytef *>(const_cast<char *>(p + done));
+        z.avail_in = (uInt)take;
+        done += take;
+        do {
+            if (out.size() - at - written < (1u << 16)) out.resize(out.size() + (1u << 20));
+            z.next_out = reinterpret_cast<Bytef *>(&out[at + written]);
+            const size_t room = std::min<size_t>(out.size() - at - written, 1u << 30);
+            z.avail_out = (uInt)room;
+            rc = deflate(&z, done == n ? Z_FINISH : Z_NO_FLUSH);
+            written += room - z.avail_out;
+        } while (rc == Z_OK && z.avail_out == 0);
+    } while (rc == Z_OK && done < n);
+    deflateEnd(&z);
+    out.resize(at + written);
+    return rc == Z_STREAM_END;
+}
+struct GzOutStats {             // --stats: what went into and came out of the encoder, members written
+    unsigned long long bytes_in = 0, bytes_out = 0, members = 0;
+};
 
 inline std::string_view field(std::string_view line, int idx) {      // idx-th field under -F '#|/' (0-based); npos data() if absent
     size_t start = 0;
@@ -61,19 +96,37 @@ inline bool load_list(const std::string &path, uint8_t cls, ClassMap &map) {
 // Routes the records of one input.  src: next() -> a block with kFrontPad bytes of room in front of its data (empty = end of input),
 // recycle(), error().  log_name: what awk's FILENAME would be (the path as given, "-" behind `gzip -dc`).  who: the program's name in
 // messages.  Returns 0, or the exit code of a failure (2: I/O, 3: a record larger than 4 GB).
+// gz_out: the four files are <prefix>.<class>.fastq.gz, every worker's share of a block one gzip member (gz_stats: totals, may be null)
 template <class Source>
-int route(const std::string &prefix, const ClassMap &cls_of, Source &src, const std::string &log_name, int t_num, const char *who) {
+int route(const std::string &prefix, const ClassMap &cls_of, Source &src, const std::string &log_name, int t_num, const char *who, bool gz_out = false,
+          GzOutStats *gz_stats = nullptr) {
     hast::WorkerPool pool(t_num);
     const int T = pool.size();
-    const char *suffix[4] = {".nobarcode.fastq", ".paternal.fastq", ".maternal.fastq", ".homozygous.fastq"};
+    const char *suffix_plain[4] = {".nobarcode.fastq", ".paternal.fastq", ".maternal.fastq", ".homozygous.fastq"};
+    const char *suffix_gz[4] = {".nobarcode.fastq.gz", ".paternal.fastq.gz", ".maternal.fastq.gz", ".homozygous.fastq.gz"};
+    const char *const *suffix = gz_out ? suffix_gz : suffix_plain;
     FILE *out[4] = {nullptr, nullptr, nullptr, nullptr};
     long long counts[5] = {0, 0, 0, 0, 0};                         // no, pa, ma, ho, total
     bool any_input = false;
     std::vector<std::vector<uint32_t>> nl(T);
     std::vector<uint32_t> allnl;
     struct Local {
-        std::string buf[4], err;
+        std::string buf[4], err, zbuf;
         long long n[4] = {0, 0, 0, 0};
+        bool z_failed = false;
+        GzOutStats z;
+    };
+    // a worker's four buffers, each replaced by one gzip member of its bytes
+    auto compress_local = [&](Local &L) {
+        for (int c = 0; c < 4; c++) {
+            if (L.buf[c].empty()) continue;
+            L.zbuf.clear();
+            if (!gz_member(L.buf[c].data(), L.buf[c].size(), L.zbuf)) L.z_failed = true;
+            L.z.bytes_in += L.buf[c].size();
+            L.z.bytes_out += L.zbuf.size();
+            L.z.members++;
+            L.buf[c].swap(L.zbuf);
+        }
     };
     std::vector<Local> loc(T);
 
@@ -90,6 +143,17 @@ int route(const std::string &prefix, const ClassMap &cls_of, Source &src, const 
     auto emit = [&]() {                                             // worker buffers -> files, in input order
         for (int t = 0; t < T; t++) {
             fputs(loc[t].err.c_str(), stderr);
+            if (loc[t].z_failed) {
+                fprintf(stderr, "%s: cannot compress the records of %s\n", who, prefix.c_str());
+                write_failed = true;
+                return;
+            }
+            if (gz_stats) {
+                gz_stats->bytes_in += loc[t].z.bytes_in;
+                gz_stats->bytes_out += loc[t].z.bytes_out;
+                gz_stats->members += loc[t].z.members;
+            }
+            loc[t].z = GzOutStats();
             for (int c = 0; c < 4; c++) {
                 counts[c] += loc[t].n[c];
                 if (loc[t].buf[c].empty()) continue;
@@ -145,6 +209,7 @@ int route(const std::string &prefix, const ClassMap &cls_of, Source &src, const 
                 const int c = classify(std::string_view(data + r0, h1 - r0), L.err);
                 if (c >= 0) { L.buf[c].append(data + r0, r1 - r0); L.n[c]++; }
             }
+            if (gz_out) compress_local(L);
         });
         counts[4] += (long long)n_rec;
         emit();
@@ -164,6 +229,7 @@ int route(const std::string &prefix, const ClassMap &cls_of, Source &src, const 
                     if (rest.back() != '\n') L.buf[c].push_back('\n');
                     L.n[c]++;
                 }
+                if (gz_out) compress_local(L);
                 emit();
             }
             break;

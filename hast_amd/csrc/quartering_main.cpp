@@ -5,7 +5,10 @@
 //   awk -v prefix=NAME -F '#|/' -f quartering_fastq.awk paternal.unique.barcodes maternal.unique.barcodes
 //       homozygous.unique.barcodes READS   (READS may be "-" behind `gzip -dc`)).
 //
-//   quartering_fastq [-t N] --prefix NAME paternal.barcodes maternal.barcodes homozygous.barcodes READS|-|READS.gz
+//   quartering_fastq [-t N] [--gz-out] --prefix NAME paternal.barcodes maternal.barcodes homozygous.barcodes READS|-|READS.gz
+//
+// --gz-out: the four files are written as <prefix>.<class>.fastq.gz (gzip members made by zlib, quartering.h), which is what stage 02
+// compresses them into anyway; `gzip -dc` of each is the plain file byte for byte.
 //
 // (the routing itself: quartering.h, shared with `classify`)
 // Same outputs byte for byte: the four FASTQ files (created only when something is routed to them), the
@@ -21,20 +24,22 @@
 
 int main(int argc, char **argv) {
     static struct option lo[] = {{"prefix", required_argument, NULL, 'p'}, {"thread", required_argument, NULL, 't'},
-                                 {"block-mb", required_argument, NULL, 'b'}, {0, 0, 0, 0}};
+                                 {"block-mb", required_argument, NULL, 'b'}, {"gz-out", no_argument, NULL, 'z'}, {0, 0, 0, 0}};
     std::string prefix;
     int t_num = 8;
     size_t block_mb = 64;
+    bool gz_out = false;
     for (;;) {
         int c = getopt_long(argc, argv, "p:t:b:", lo, NULL);
         if (c < 0) break;
         if (c == 'p') prefix = optarg;
         else if (c == 't') t_num = atoi(optarg);
         else if (c == 'b') block_mb = (size_t)std::max(1L, atol(optarg));
+        else if (c == 'z') gz_out = true;
         else return 2;
     }
     if (argc - optind != 4 || t_num < 1) {
-        fprintf(stderr, "usage: quartering_fastq [-t N] --prefix NAME paternal.barcodes maternal.barcodes homozygous.barcodes READS|-\n");
+        fprintf(stderr, "usage: quartering_fastq [-t N] [--gz-out] --prefix NAME paternal.barcodes maternal.barcodes homozygous.barcodes READS|-\n");
         return 2;
     }
     hast::quartering::ClassMap cls_of;
@@ -49,5 +54,5 @@ int main(int argc, char **argv) {
         fprintf(stderr, "quartering_fastq: cannot open %s\n", reads.c_str());
         return 2;
     }
-    return hast::quartering::route(prefix, cls_of, src, reads, t_num, "quartering_fastq");
+    return hast::quartering::route(prefix, cls_of, src, reads, t_num, "quartering_fastq", gz_out);
 }

@@ -409,6 +409,35 @@ typedef struct {
 } hast_fq_routed;
 hast_status hast_fq_set_route(hast_fq *, hast_names *const *tables, int n_tables);
 hast_status hast_fq_next_routed(hast_fq *, hast_fq_routed *out);
+/* Routed runs that leave the GPU as gzip members (hast_amd/csrc/dz_core.h, dz_kernels.hip).  on != 0: the four run[c] of
+ * hast_fq_next_routed hold one complete gzip member each instead of plain records and run_bytes[c] are the members' sizes; an empty
+ * run stays 0 bytes (no member).  count[] and n_records are as before.  Only the compressed bytes are copied to the host: their sizes
+ * are known on the device only, so hast_fq_next_routed reads them first and then waits for that one copy.  Blocks that come back
+ * with host_block != 0, and the tail, are the caller's and stay plain, as without the switch (such a block is not compressed at all).
+ * Memory while the switch is on, per buffer slot of the stream: about two blocks of device memory (the members' buffer and the
+ * encoder's workspace) and one block of pinned host memory; on = 0 gives them back.  Only between files, like
+ * hast_fq_set_route, and only on a stream that routes.
+ * hast_fq_routed_raw_bytes: the uncompressed bytes of the open block's four runs (what run_bytes[] would have been). */
+hast_status hast_fq_set_route_gz(hast_fq *, int on);
+hast_status hast_fq_routed_raw_bytes(hast_fq *, uint64_t out[4]);
+
+/* ---- deflate on the GPU: device memory -> one gzip member -----------------------------------------------------------------
+ * hast_dz_compress_device writes ONE complete gzip member (RFC 1952: what gzip -dc, zlib and hast_gz read) for the n_bytes at
+ * d_src, n_bytes == 0 included (an empty member), to d_dst, and waits for it; *n_out = its size.  The input is cut into pieces of
+ * 16 KB that a wave each compresses on its own (hashed match search verified byte by byte, greedy parse, dynamic Huffman codes
+ * limited to 15 bits; a piece that would not get smaller is a stored block), every piece ends on a byte boundary with an empty
+ * stored block, CRC-32 is computed on the device.  The bytes written are a function of the input bytes alone.
+ * hast_dz_bound(n): the most bytes a call can write for n bytes of input (host arithmetic).  cap < hast_dz_bound(n_bytes) is
+ * HAST_ERR_INVALID; nothing is ever written at or behind d_dst + cap.
+ * hast_dz_compress_device_ex / HAST_DZ_LITERALS_ONLY are a TEST HOOK, not part of the interface a caller should build on and not
+ * promised to stay: flags = HAST_DZ_LITERALS_ONLY switches the match search off (Huffman coding of the bytes alone), which is how
+ * tests/test_dz_gpu.py gets a block whose symbol histogram is the input's byte histogram (code lengths that have to be limited to
+ * 15 bits); no program of this tree passes it. */
+#define HAST_DZ_LITERALS_ONLY 1u
+size_t      hast_dz_bound(size_t n_bytes);
+hast_status hast_dz_compress_device(hast_ctx *, const uint8_t *d_src, size_t n_bytes, uint8_t *d_dst, size_t cap, size_t *n_out, hast_stream);
+hast_status hast_dz_compress_device_ex(hast_ctx *, const uint8_t *d_src, size_t n_bytes, uint8_t *d_dst, size_t cap, size_t *n_out, unsigned flags,
+                                       hast_stream);
 
 /* ---- gzip input decoded on the device (gzstream.h:47, classify.cpp:245-254: one zlib stream per .gz file) -----------------
  * HAST's real inputs are ordinary .fq.gz files: ONE deflate stream per file, which the reference inflates on the thread that
