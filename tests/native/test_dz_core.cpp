@@ -7,6 +7,9 @@
 //                            (limited: pieces whose literal/length code had to be brought under 15 bits).
 //   test_dz_core -H IN OUT   the same without the match search (what HAST_DZ_LITERALS_ONLY asks of the kernel): the symbol
 //                            histogram is the input's byte histogram, which is how a test gets at a chosen histogram
+//   test_dz_core -v [-H] IN OUT   either of them with a second line of output: the bytes every piece takes in the member, in order (a
+//                            stored piece: its bytes + 5).  The member is 10 bytes of header, these, 10 bytes of trailer: a test that
+//                            compares the member with the kernel's can name the piece a difference lies in.
 //   test_dz_core -s          len_symbol over 3 .. 258 and dist_symbol over 1 .. 32768 against gz_core.h's base / extra-bit tables (what the
 //                            decoder adds up): also the distances no 16-KB piece can hold (codes 28, 29), for the day the piece grows
 //   test_dz_core -P          prints the piece size
@@ -45,6 +48,7 @@ static bool g_literals_only = false;
 
 struct Counters {
     uint64_t pieces = 0, stored = 0, limited = 0;
+    std::vector<uint32_t> sizes;                        // bytes of every piece in the member
 };
 
 // one piece -> its bytes, appended to out
@@ -122,6 +126,7 @@ static void piece(const uint8_t *src, uint32_t n, std::vector<uint8_t> &outb, Co
         const uint8_t h[5] = {0, (uint8_t)n, (uint8_t)(n >> 8), (uint8_t)~n, (uint8_t)(~n >> 8)};
         outb.insert(outb.end(), h, h + 5);
         outb.insert(outb.end(), src, src + n);
+        ct.sizes.push_back(n + 5);
         return;
     }
     memset(out, 0, sizeof out);
@@ -158,6 +163,7 @@ static void piece(const uint8_t *src, uint32_t n, std::vector<uint8_t> &outb, Co
     if (at != cb * 8) fail("the piece is not as long as planned");
     const uint8_t *ob = reinterpret_cast<const uint8_t *>(out);
     outb.insert(outb.end(), ob, ob + cb);
+    ct.sizes.push_back(cb);
 }
 
 int main(int argc, char **argv) {
@@ -205,12 +211,18 @@ int main(int argc, char **argv) {
         printf("%u\n", longest);
         return 0;
     }
+    bool piece_sizes = false;
+    if (argc >= 4 && !strcmp(argv[1], "-v")) {
+        piece_sizes = true;
+        ++argv;
+        --argc;
+    }
     if (argc == 4 && !strcmp(argv[1], "-H")) {
         g_literals_only = true;
         ++argv;
         --argc;
     }
-    if (argc != 3) fail("usage: test_dz_core [-H] IN OUT | -P | -s | -k N");
+    if (argc != 3) fail("usage: test_dz_core [-v] [-H] IN OUT | -P | -s | -k N");
     std::vector<uint8_t> data;
     {
         FILE *f = fopen(argv[1], "rb");
@@ -266,5 +278,9 @@ int main(int argc, char **argv) {
     if (!f || fwrite(gzb.data(), 1, gzb.size(), f) != gzb.size()) fail("cannot write the output");
     fclose(f);
     printf("%llu %llu %llu %llu\n", (unsigned long long)ct.pieces, (unsigned long long)ct.stored, (unsigned long long)gzb.size(), (unsigned long long)ct.limited);
+    if (piece_sizes) {
+        for (size_t i = 0; i < ct.sizes.size(); ++i) printf(i ? " %u" : "%u", ct.sizes[i]);
+        printf("\n");
+    }
     return 0;
 }

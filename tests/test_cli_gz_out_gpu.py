@@ -10,12 +10,14 @@ import os
 import re
 import shutil
 import subprocess
+import zlib
 
 import pytest
 
 import hast_amd
 from tests.conftest import GOLDEN
 from tests.test_cli_gpu import _edge_fastq
+from tests.test_dz_core_cpu import PIECE
 
 pytestmark = pytest.mark.gpu
 
@@ -179,3 +181,38 @@ def test_round_trip_a_routed_gz_file_as_read_input(exe, golden_workdir, tmp_path
     assert p.returncode == 0 and z.returncode == 0, z.stderr.decode()[-1000:]
     assert z.stdout == p.stdout and len(p.stdout) > 100
     assert b"__stats_gz__" in z.stderr                       # (inflated on the device, not by the host decoders)
+
+
+def test_gz_out_at_scale_with_the_default_block_size(exe, golden_workdir, tmp_path):
+    """the production shape: the golden r1.fq tiled to 52 MB (record names repeat) in the default blocks of 16 MB, so a routed run is
+    hundreds of 16-KB pieces and k_dz_scan (256 pieces a lap) goes round more than once.  The command without the flag is the
+    reference, as above; and the members of every .fastq.gz are walked one by one: at least one member THE DEVICE made (its header
+    says XFL = 0; zlib's level-1 members of handed-over blocks and tails say 4) inflates to more than 256 pieces."""
+    tiles = 151
+    with gzip.open(golden_workdir / "rand_k21" / "r1.fq.gz") as f:
+        text = f.read() * tiles
+    assert len(text) >= 50 << 20
+    a, b = tmp_path / "a", tmp_path / "b"
+    for d in (a, b):
+        shutil.copytree(golden_workdir / "rand_k21", d)
+        (d / "big.fq").write_bytes(text)
+    args = ["--hap0", "hap0.mer", "--hap1", "hap1.mer", "--weight0", "1.04", "--read", "big.fq", "--thread", "5", "--phase-reads"]
+    _, _, n_fastq = run_pair(exe, (a, b), args, [])
+    assert n_fastq >= 3
+    device_made, longest = 0, 0
+    for p in sorted(b.iterdir()):
+        if not p.name.endswith(".fastq.gz"):
+            continue
+        rest, sizes = p.read_bytes(), []
+        while rest:
+            d = zlib.decompressobj(31)
+            n = len(d.decompress(rest))
+            assert d.eof
+            if rest[:10] == b"\x1f\x8b\x08\x00\x00\x00\x00\x00\x00\x03":
+                device_made += 1
+                longest = max(longest, n)
+            sizes.append(n)
+            rest = d.unused_data
+        print("%s: %d members, the longest inflates to %d bytes" % (p.name, len(sizes), max(sizes)))
+    assert device_made > 0
+    assert longest > 256 * PIECE, "no device-made member of more than 256 pieces: the longest inflates to %d bytes" % longest

@@ -4,13 +4,17 @@ ISIZE checked: wbits=31), that gz_core.h's decode_chunk reads back to the same b
 against its encoder without zlib in between), whose Huffman codes are complete and within 15 / 7 bits, and that is no longer than
 hast_dz_bound.  The corpus is where deflate encoders break: no distance code in use, a single symbol, lengths over 15, stored
 fallback, matches of 258 at distance 1, the piece's borders.  Built with ASAN + UBSAN.  (tests/test_dz_gpu.py runs the same corpus
-through the kernels.)"""
+through the kernels; tests/test_dz_model_gpu.py holds the kernels to THIS model byte for byte, so what is asserted of the model
+here -- the fuzz, the sizes around the laps of k_dz_scan, the size against zlib level 1 -- is asserted of the kernels too.)"""
+import functools
 import gzip
+import math
 import os
 import random
 import subprocess
 import zlib
 
+import numpy as np
 import pytest
 
 from tests.conftest import ROOT
@@ -75,12 +79,22 @@ def huffman_only(data):
     return c.compress(data) + c.flush()
 
 
+def build_driver(directory, sanitize=True):
+    """tests/native/test_dz_core.cpp compiled into directory: with ASAN + UBSAN, or (for inputs of megabytes) with -O2 alone"""
+    exe = os.path.join(str(directory), "test_dz_core" if sanitize else "test_dz_core_o2")
+    how = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] if sanitize else ["-O2"]
+    subprocess.run(["g++"] + how + ["-std=c++17", "-Wall", "-Wextra", "-Werror", "-o", exe, os.path.join(ROOT, "tests", "native", "test_dz_core.cpp")], check=True)
+    return exe
+
+
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("dzcore") / "test_dz_core"
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-o", str(exe), os.path.join(ROOT, "tests", "native", "test_dz_core.cpp")], check=True)
-    return str(exe)
+    return build_driver(tmp_path_factory.mktemp("dzcore"))
+
+
+@pytest.fixture(scope="module")
+def fast_driver(tmp_path_factory):
+    return build_driver(tmp_path_factory.mktemp("dzcore_o2"), sanitize=False)
 
 
 def compress(driver, tmp_path, data, literals_only=False):
@@ -92,6 +106,109 @@ def compress(driver, tmp_path, data, literals_only=False):
     blob = dst.read_bytes()
     assert size == len(blob)
     return blob, pieces, stored, limited
+
+
+def compress_with_sizes(driver, tmp_path, data, literals_only=False):
+    """the driver's -v: (the member, the bytes each piece takes in it)"""
+    src, dst = tmp_path / "in.bin", tmp_path / "out.gz"
+    src.write_bytes(data)
+    r = subprocess.run([driver, "-v"] + (["-H"] if literals_only else []) + [str(src), str(dst)], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    assert r.returncode == 0, r.stderr[-400:]
+    first, second = r.stdout.split(b"\n")[:2]
+    pieces, _, size, _ = (int(x) for x in first.split())
+    sizes = [int(x) for x in second.split()]
+    blob = dst.read_bytes()
+    assert size == len(blob) == 10 + sum(sizes) + 10 and len(sizes) == pieces == (len(data) + PIECE - 1) // PIECE
+    return blob, sizes
+
+
+# ---- inputs shared with tests/test_dz_model_gpu.py ------------------------------------------------------------------------------
+COPY_DISTANCES = (1, 2, 3, 63, 64, 65, 4095, 4096, 16383, 16384, 16385)     # around a step of 64 positions, the table's 4096 entries, a piece
+FUZZ_MAX = 70_000
+
+
+def _some_length(rng, most):
+    """1 .. most, short lengths as likely as long ones"""
+    return min(most, int(math.exp(rng.uniform(0, math.log(most + 1)))))
+
+
+def fuzz_input(rng):
+    """0 .. 70 000 bytes put together from segments of random length: FASTQ records, bytes over 2, 4 or 20 symbols, incompressible
+    bytes, a run of one byte (1 .. 70 000), a pattern of period 2 .. 300, a copy of what lies a chosen distance back"""
+    edges = (0, 1, 2, 3, 4, 5, 63, 64, 65, PIECE - 1, PIECE, PIECE + 1, 2 * PIECE, 4 * PIECE, 4 * PIECE + 3, FUZZ_MAX)
+    target = rng.choice(edges) if rng.random() < 0.15 else rng.randint(0, FUZZ_MAX)
+    out = bytearray()
+    while len(out) < target:
+        kind = rng.choice(("fastq", "alphabet", "noise", "run", "period", "copy", "copy"))
+        if kind == "fastq":
+            seg = fastq(rng, rng.randint(1, 30))
+            seg = seg[:_some_length(rng, len(seg))]
+        elif kind == "alphabet":
+            symbols = bytes(rng.sample(range(256), rng.choice((2, 4, 20))))
+            seg = bytes(rng.choices(symbols, k=_some_length(rng, 20_000)))
+        elif kind == "noise":
+            n = _some_length(rng, 20_000)
+            seg = rng.getrandbits(8 * n).to_bytes(n, "little")
+        elif kind == "run":
+            seg = bytes([rng.getrandbits(8)]) * _some_length(rng, FUZZ_MAX)
+        elif kind == "period":
+            period = rng.randint(2, 300)
+            pattern = bytes(rng.choices(b"ACGTN\n" if rng.random() < 0.5 else bytes(range(256)), k=period))
+            n = _some_length(rng, 20_000)
+            seg = (pattern * (n // period + 1))[:n]
+        else:
+            near = [d for d in COPY_DISTANCES if d <= len(out)]
+            if not near:
+                continue
+            d = rng.choice(near)
+            n = _some_length(rng, 3000)
+            seg = (bytes(out[-d:]) * (n // d + 1))[:n]      # (as a match does it: longer than its distance, it repeats)
+        out += seg
+    return bytes(out[:target])
+
+
+@functools.lru_cache(maxsize=None)
+def fuzz_inputs():
+    """the fuzz corpus: HAST_FUZZ_SEED (a fixed default), HAST_FUZZ_ITERS inputs (150 at least)"""
+    rng = random.Random(int(os.environ.get("HAST_FUZZ_SEED", "20261017")))
+    return [fuzz_input(rng) for _ in range(max(150, int(os.environ.get("HAST_FUZZ_ITERS", "160"))))]
+
+
+def fastq_150(n_bytes, noisy, seed):
+    """n_bytes of FASTQ with 150-bp records (headers as tests.test_inflate_cpu.fastq writes them), quality lines constant or over
+    the alphabet FFFFF:F,F#; the last record is cut where n_bytes end"""
+    rng = np.random.default_rng(seed)
+    n = n_bytes // 320 + 1
+    bases = rng.choice(np.frombuffer(b"ACGT", np.uint8), (n, 150))
+    qual = rng.choice(np.frombuffer(b"FFFFF:F,F#", np.uint8), (n, 150)) if noisy else np.full((n, 150), ord("F"), np.uint8)
+    data = b"".join(b"@V300R%09d#%d_%d_%d/1\n" % (i, i % 1536, i % 977, i % 3) + bases[i].tobytes() + b"\n+\n" + qual[i].tobytes() + b"\n" for i in range(n))
+    assert len(data) >= n_bytes
+    return data[:n_bytes]
+
+
+def lap_sizes(piece=PIECE):
+    """k_dz_scan places 256 pieces a lap: input sizes around the first and second lap's end, and one of 1227 pieces (five laps)"""
+    return [255 * piece, 256 * piece - 1, 256 * piece, 256 * piece + 1, 257 * piece, 512 * piece + 7, 1227 * piece - 100]
+
+
+@functools.lru_cache(maxsize=None)
+def lap_content(kind):
+    """the content the lap sizes are cut from: generated FASTQ (every piece coded), or the corpus's "mixed" tiled (95 000 bytes of
+    FASTQ, noise, zeros, FASTQ: stored and coded pieces alternate, so the places of the pieces mix n + 5 and coded sizes)"""
+    n = max(lap_sizes())
+    if kind == "fastq":
+        return fastq_150(n, True, 11)
+    assert kind == "mixed_tiled"
+    return (CORPUS["mixed"] * (n // len(CORPUS["mixed"]) + 1))[:n]
+
+
+def zlib_level_1_in_pieces(data):
+    """what zlib level 1 makes of the same pieces without history: raw deflate of every 16 KB, and 20 bytes of header and trailer"""
+    total = 20
+    for off in range(0, len(data), PIECE):
+        c = zlib.compressobj(1, zlib.DEFLATED, -15)
+        total += len(c.compress(data[off:off + PIECE]) + c.flush())
+    return total
 
 
 def test_the_piece_size_is_the_one_the_tests_assume(driver):
@@ -152,3 +269,50 @@ def test_it_compresses(driver, tmp_path):
     assert len(data) == 347531
     blob = compress(driver, tmp_path, data)[0]
     assert len(blob) < len(huffman_only(data))
+
+
+# ---- the model on the inputs tests/test_dz_model_gpu.py compares the kernels on ---------------------------------------------------
+def test_fuzz(driver, tmp_path):
+    """the fuzz corpus through the driver under ASAN + UBSAN (its own checks: complete codes, matches that match, decode_chunk, the
+    CRC by slices), zlib's round trip, the bound"""
+    inputs = fuzz_inputs()
+    assert len(inputs) >= 150 and max(len(d) for d in inputs) <= FUZZ_MAX
+    for k, data in enumerate(inputs):
+        blob, sizes = compress_with_sizes(driver, tmp_path, data)
+        d = zlib.decompressobj(31)
+        assert d.decompress(blob) == data and d.eof and d.unused_data == b"", (k, len(data))
+        assert len(blob) <= bound(len(data)), (k, len(data))
+        assert all(sz <= min(PIECE, len(data) - i * PIECE) + 5 for i, sz in enumerate(sizes)), (k, len(data))
+
+
+@pytest.mark.parametrize("kind", ["fastq", "mixed_tiled"])
+def test_sizes_around_the_laps_of_the_scan(fast_driver, tmp_path, kind):
+    """the model at the sizes where k_dz_scan starts a new lap of 256 pieces (and the CRC terms of megabytes of bytes behind a piece:
+    the driver checks the member's CRC-32 against the bytewise one, zlib checks it again)"""
+    content = lap_content(kind)
+    for n in lap_sizes():
+        data = content[:n]
+        blob, sizes = compress_with_sizes(fast_driver, tmp_path, data)
+        d = zlib.decompressobj(31)
+        assert d.decompress(blob) == data and d.eof and d.unused_data == b"", n
+        assert len(blob) <= bound(n) and len(sizes) == (n + PIECE - 1) // PIECE
+        full = sizes[:n // PIECE]                           # (a last piece of a byte is a stored block in any content)
+        if kind == "fastq":
+            assert all(sz < PIECE for sz in full), n
+        else:
+            assert any(sz == PIECE + 5 for sz in full) and any((a > PIECE) != (b > PIECE) for a, b in zip(full, full[1:])), n
+
+
+@pytest.mark.parametrize("name", ["golden", "generated_constant_quality", "generated_noisy_quality"])
+def test_no_larger_than_zlib_level_1_on_the_same_pieces(fast_driver, tmp_path, name):
+    """the ratio, as a condition on the model (the kernels are held to the model's bytes): on FASTQ of a piece or more the member is
+    no larger than zlib level 1 applied to the same 16-KB pieces one by one (the golden r1.fq: 76 360 against 79 486 bytes; 20 MB of
+    generated FASTQ: 0.967 of it with constant quality lines, 0.979 with noisy ones).  Not for tiny runs: a member of 380 bytes pays
+    a dynamic header."""
+    data = {"golden": golden_fastq, "generated_constant_quality": lambda: fastq_150(2 << 20, False, 12),
+            "generated_noisy_quality": lambda: fastq_150(2 << 20, True, 13)}[name]()
+    assert len(data) >= PIECE
+    blob = compress(fast_driver, tmp_path, data)[0]
+    assert gzip.decompress(blob) == data
+    print("%s: %d -> %d bytes, zlib level 1 in pieces %d" % (name, len(data), len(blob), zlib_level_1_in_pieces(data)))
+    assert len(blob) <= zlib_level_1_in_pieces(data)

@@ -113,10 +113,11 @@ def test_it_compresses(ctx):
 
 
 # ---- routing: the four runs of a block as gzip members --------------------------------------------------------------------------
-def route_gz_through_abi(data, cls_of, block, n_ctx, k=21):
+def route_gz_through_abi(data, cls_of, block, n_ctx, k=21, members=None):
     """tests/test_fq_gpu.py's route_through_abi with hast_fq_set_route_gz on: every run of a block the device routed is ONE gzip member
     (an empty run: nothing), inflated here and appended; blocks the device hands over and the tail are plain and decided by awk's rule.
-    Returns (the four classes' bytes, the dropped field-2 texts, counters)."""
+    Returns (the four classes' bytes, the dropped field-2 texts, counters).  members: a list that gets a (class, member, its inflated
+    bytes) for every device-made member, block after block, the classes of a block rising."""
     import re
     from hast_amd.binding import FqRouted
     lib = hast_amd.lib()
@@ -174,6 +175,8 @@ def route_gz_through_abi(data, cls_of, block, n_ctx, k=21):
                     st["members"] += 1
                     st["raw"] += len(plain)
                     st["compressed"] += len(member)
+                    if members is not None:
+                        members.append((c, member, plain))
             else:
                 st["host_blocks"] += 1
                 for i in range(b.n_slots):
