@@ -85,7 +85,9 @@ void print_usage() {                              // same flags as the reference
           "      --gz-ring-bytes N compressed bytes of a .gz input kept on the device at a time (default: whole files up to 2 GB;\n"
           "                        HAST_GZ_RING_BYTES)\n"
           "      --park-gb X       device memory of closed streams kept for reuse instead of freed (default 32; HAST_PARK_GB)\n"
-          "      --name-cache N    barcodes the device-side dictionary holds (default 16M; HAST_NAME_CACHE)\n"
+          "      --name-cache N    barcodes the device-side dictionary holds (default 16M; HAST_NAME_CACHE); what it cannot hold is\n"
+          "                        numbered by the host\n"
+          "                        (N: digits, optionally followed by K, M or G = 2^10, 2^20, 2^30; X: a decimal number such as 1.5)\n"
           "      --deal MODE       with --devices: blocks (default) | files (HAST_DEAL)\n"
           "  -h, --help            this text\n\n"
           "stdout: barcode <TAB> haplotype(0/1/-1) <TAB> hits_hap0 <TAB> hits_hap1, sorted by barcode\n\n",
@@ -249,6 +251,7 @@ struct Naming {
     std::vector<int> group_of;                     // per context
     std::vector<std::vector<uint32_t>> perm;       // per dictionary but the first: its ids in the first one's numbering, as far as merged
     double merge_s = 0;
+    size_t merged_to_host = 0;                     // texts of another dictionary that the first one had no id left for
 };
 
 inline void add_into(std::vector<uint64_t> &dst, const std::vector<uint64_t> &src, size_t n) {
@@ -256,7 +259,7 @@ inline void add_into(std::vector<uint64_t> &dst, const std::vector<uint64_t> &sr
     for (size_t i = 0; i < n; i++) dst[i] += src[i];       // (64-bit on the device and here: nothing wraps)
 }
 
-void flush_counts(std::vector<hast_ctx *> &ctxs, Counts &acc, Naming &nm, hast::WorkerPool &, size_t n_host, size_t new_cap) {
+void flush_counts(std::vector<hast_ctx *> &ctxs, Counts &acc, Naming &nm, hast::WorkerPool &, hast::BarcodeDict &dict, hast::BarcodeDict::Cache &dict_cache, size_t new_cap) {
     // fold what the devices have counted so far into the host sums, then (re)size the device arrays.  Several GPUs: ONE
     // all-reduce(sum,u64) over RCCL/xGMI leaves the totals on every device (collectBarcodes + data.Add, classify.cpp:226-229,277)
     hast_ctx *ctx = ctxs[0];
@@ -278,15 +281,27 @@ void flush_counts(std::vector<hast_ctx *> &ctxs, Counts &acc, Naming &nm, hast::
                 const size_t have = nm.perm[g].size();
                 if (n_g > have) {
                     nm.perm[g].resize(n_g);
-                    if (hast_names_merge(nm.groups[0], nm.groups[g], have, n_g - have, nm.perm[g].data() + have) != HAST_OK)
-                        die(4, "merging the GPUs' barcode dictionaries (more barcodes than --name-cache allows?)");
+                    const hast_status ms = hast_names_merge(nm.groups[0], nm.groups[g], have, n_g - have, nm.perm[g].data() + have);
+                    if (ms == HAST_ERR_TABLE_FULL) {
+                        // the first dictionary is out of ids: what it could not take (HAST_NAME_NONE, include/hast.h) is the host's, like
+                        // everything a full dictionary leaves to it -- the text by id from the other dictionary, its counters to the host's id
+                        std::vector<uint8_t> txt(16 * (n_g - have));
+                        CK(hast_names_texts(nm.groups[g], have, n_g - have, txt.data()), "reading a dictionary's texts");
+                        for (size_t i = have; i < n_g; i++) {
+                            if (nm.perm[g][i] != HAST_NAME_NONE) continue;
+                            const uint8_t *t = txt.data() + 16 * (i - have);
+                            nm.perm[g][i] = (uint32_t)nm.host_base + dict.get(std::string_view(reinterpret_cast<const char *>(t) + 1, t[0]), dict_cache);
+                            nm.merged_to_host++;
+                        }
+                    } else if (ms != HAST_OK)
+                        die(4, "merging the GPUs' barcode dictionaries");
                 }
             }
             // (the first dictionary may have grown past what the counters were sized for -- they follow the ids of each dictionary's own
             // blocks: every context's counters move into arrays that hold the merged numbering)
             size_t n_merged = 0;
             CK(hast_names_count(nm.groups[0], &n_merged), "asking the dictionary for its size");
-            const size_t need_cap = std::max(acc.device_cap, n_merged);
+            const size_t need_cap = std::max({acc.device_cap, n_merged, dict.size() ? nm.host_base + dict.size() : 0});
             for (size_t i = 0; i < ctxs.size(); i++) {
                 const size_t g = (size_t)nm.group_of[i];
                 if (g == 0 && need_cap == acc.device_cap) continue;
@@ -297,6 +312,7 @@ void flush_counts(std::vector<hast_ctx *> &ctxs, Counts &acc, Naming &nm, hast::
             nm.merge_s += now_s() - t0;
         }
         if (ctxs.size() > 1) CK(hast_counts_allreduce(ctxs.data(), (int)ctxs.size()), "summing the counters of the GPUs");
+        const size_t n_host = dict.size();                                         // (after the merge: it may have named texts)
         if (!nm.device_dict) read_range(0, n_host, acc.c0, acc.c1, acc.neg);      // (only the barcodes that exist: the counters are sized ahead of the dictionary)
         else {
             size_t n_dev = 0;
@@ -307,6 +323,36 @@ void flush_counts(std::vector<hast_ctx *> &ctxs, Counts &acc, Naming &nm, hast::
     }
     for (hast_ctx *c : ctxs) CK(hast_counts_resize(c, new_cap), "allocating counters");
     acc.device_cap = new_cap;
+}
+
+// a count or a size on the command line: decimal digits and at most one of K, M, G behind them (powers of 1024, either case); anything
+// else -- no digits, a sign, a fraction, another suffix, trailing bytes, more than 64 bits hold -- is not a number
+bool parse_count(const char *text, uint64_t *out) {
+    if (!text || *text < '0' || *text > '9') return false;
+    errno = 0;
+    char *end = nullptr;
+    const unsigned long long v = strtoull(text, &end, 10);
+    if (errno || end == text) return false;
+    int shift = 0;
+    switch (*end) {
+    case 'K': case 'k': shift = 10; end++; break;
+    case 'M': case 'm': shift = 20; end++; break;
+    case 'G': case 'g': shift = 30; end++; break;
+    default: break;
+    }
+    if (*end || (shift && v > (~0ull >> shift))) return false;
+    *out = (uint64_t)v << shift;
+    return true;
+}
+// a plain non-negative decimal number, fractions allowed ("1.5"), nothing behind it
+bool parse_amount(const char *text, double *out) {
+    if (!text || !((*text >= '0' && *text <= '9') || *text == '.')) return false;
+    errno = 0;
+    char *end = nullptr;
+    const double v = strtod(text, &end);
+    if (errno || end == text || *end || !(v >= 0) || v > 1e12) return false;
+    *out = v;
+    return true;
 }
 
 }  // namespace
@@ -379,10 +425,25 @@ int main(int argc, char **argv) {
             if (strcmp(optarg, "host") && strcmp(optarg, "device") && strcmp(optarg, "zlib")) { print_usage(); return -1; }
             setenv("HAST_INFLATE", optarg, 1);
             break;
-        case 1012: setenv("HAST_GZ_RING_BYTES", optarg, 1); break;
+        case 1012: {                                     // (the library reads plain decimal digits from the environment: what a suffix meant is spelt out)
+            uint64_t v;
+            if (!parse_count(optarg, &v)) { print_usage(); return -1; }
+            setenv("HAST_GZ_RING_BYTES", std::to_string(v).c_str(), 1);
+            break;
+        }
         case 1013: stats_json = optarg; stats = true; break;
-        case 1014: setenv("HAST_PARK_GB", optarg, 1); break;
-        case 1015: setenv("HAST_NAME_CACHE", optarg, 1); break;
+        case 1014: {
+            double v;
+            if (!parse_amount(optarg, &v)) { print_usage(); return -1; }
+            setenv("HAST_PARK_GB", optarg, 1);
+            break;
+        }
+        case 1015: {
+            uint64_t v;
+            if (!parse_count(optarg, &v)) { print_usage(); return -1; }
+            setenv("HAST_NAME_CACHE", std::to_string(v).c_str(), 1);
+            break;
+        }
         case 1016:
             if (strcmp(optarg, "files") && strcmp(optarg, "blocks")) { print_usage(); return -1; }
             setenv("HAST_DEAL", optarg, 1);
@@ -718,7 +779,7 @@ int main(int argc, char **argv) {
     Counts acc;
     // (a device dictionary hands out ids below host_base; the first id the host has to give lies there: counters for both from the start,
     // unless --initial-barcodes asks for less, tests)
-    flush_counts(ctxs, acc, naming, pool, 0, initial_barcodes == (1u << 24) && naming.device_dict ? naming.host_base + 4096 : initial_barcodes);
+    flush_counts(ctxs, acc, naming, pool, dict, caches[0], initial_barcodes == (1u << 24) && naming.device_dict ? naming.host_base + 4096 : initial_barcodes);
     const int T = pool.size();
     uint64_t total_reads = 0, total_bases = 0;
     std::vector<std::vector<uint32_t>> nl(T);          // per-worker newline positions of the current block
@@ -788,7 +849,7 @@ int main(int argc, char **argv) {
                 _exit(3);                                                                  // it down under them (seen: SIGSEGV instead of status 3)
             }
         }
-        if (dict.size() > acc.device_cap) flush_counts(ctxs, acc, naming, pool, dict.size(), std::max(dict.size() * 2, acc.device_cap * 2));
+        if (dict.size() > acc.device_cap) flush_counts(ctxs, acc, naming, pool, dict, caches[0], std::max(dict.size() * 2, acc.device_cap * 2));
         CK(hast_batch_submit(bctx, n_rec, mx), "classifying a batch");
         total_reads += n_rec;
         total_bases += part_bytes[T];
@@ -1046,7 +1107,7 @@ int main(int argc, char **argv) {
             {
                 const size_t need = std::max<size_t>(naming.device_dict ? (size_t)b.dict_ids : 0, dict.size() ? naming.host_base + dict.size() : 0);
                 if (need > acc.device_cap)
-                    flush_counts(ctxs, acc, naming, pool, dict.size(), std::max(dict.size() ? naming.host_base + 2 * dict.size() + 4096 : 2 * need, acc.device_cap * 2));
+                    flush_counts(ctxs, acc, naming, pool, dict, caches[0], std::max(dict.size() ? naming.host_base + 2 * dict.size() + 4096 : 2 * need, acc.device_cap * 2));
             }
             CK(hast_fq_commit(f.fq), "classifying a block");
             t_commit += now_s() - t2;
@@ -1154,7 +1215,7 @@ int main(int argc, char **argv) {
                     t_idle, t_gpu_wait, t_names, t_commit, t_create, (unsigned long long)total_named);
     }
     const double t_read_done = now_s();
-    flush_counts(ctxs, acc, naming, pool, dict.size(), 1);
+    flush_counts(ctxs, acc, naming, pool, dict, caches[0], 1);
     const double t_classified = now_s();
     // the names by row: the device dictionary's texts by id (read once, now), then what the host named
     std::vector<uint8_t> dev_texts;
@@ -1182,6 +1243,41 @@ int main(int argc, char **argv) {
         acc.h0.resize(n_host_names); acc.h1.resize(n_host_names);
         acc.c0.insert(acc.c0.end(), acc.h0.begin(), acc.h0.end());
         acc.c1.insert(acc.c1.end(), acc.h1.begin(), acc.h1.end());
+    }
+    // One row per TEXT, not per id.  A single dictionary never gives a text both a device id and leaves it to the host (name_claim.h).
+    // Several do: one that has run out hands a text to the host which another, not yet full, numbers in its own blocks (or has numbered
+    // long before), and nothing on the way merges the two ranges by text.  Only a host name of at most 15 bytes can have a device id as
+    // well, and only once a dictionary has run out is there such a host name: then -- and only then -- the device's texts are looked up
+    // among them, the host's row is added to the device's and dropped.
+    size_t n_rows_summed = 0;
+    if (naming.device_dict && n_dev_names && n_host_names) {
+        std::unordered_map<std::string_view, uint32_t> short_host;
+        for (size_t j = 0; j < n_host_names; j++)
+            if (names[n_dev_names + j].size() <= 15) short_host.emplace(names[n_dev_names + j], (uint32_t)j);
+        if (!short_host.empty()) {
+            std::vector<char> drop(n_host_names, 0);
+            for (size_t i = 0; i < n_dev_names; i++) {
+                const auto it = short_host.find(names[i]);
+                if (it == short_host.end()) continue;
+                acc.c0[i] += acc.c0[n_dev_names + it->second];
+                acc.c1[i] += acc.c1[n_dev_names + it->second];
+                drop[it->second] = 1;
+                n_rows_summed++;
+            }
+            if (n_rows_summed) {
+                size_t to = n_dev_names;
+                for (size_t j = 0; j < n_host_names; j++) {
+                    if (drop[j]) continue;
+                    names[to] = names[n_dev_names + j];
+                    acc.c0[to] = acc.c0[n_dev_names + j];
+                    acc.c1[to] = acc.c1[n_dev_names + j];
+                    to++;
+                }
+                names.resize(to);
+                acc.c0.resize(to);
+                acc.c1.resize(to);
+            }
+        }
     }
 
     // ---- printBarcodeInfos (classify.cpp:93-102): byte-wise sorted rows ------------------------
@@ -1846,7 +1942,12 @@ int main(int argc, char **argv) {
                 (unsigned long long)total_bases, names.size(), t_loaded - t_start, dt, dt > 0 ? total_bases / dt / 1e6 : 0.0);
     }
     if (stats && naming.device_dict)
-        stat_line("__stats_dictionary__ on=device dictionaries=%zu ids_from_device=%zu ids_from_host=%zu merge_by_text_s=%.3f\n", naming.groups.size(), n_dev_names, n_host_names, naming.merge_s);
+        stat_line("__stats_dictionary__ on=device dictionaries=%zu ids_limit=%zu ids_from_device=%zu ids_from_host=%zu merge_by_text_s=%.3f texts_merged_to_host=%zu rows_summed_by_text=%zu\n", naming.groups.size(), naming.host_base, n_dev_names, n_host_names, naming.merge_s,
+                  naming.merged_to_host, n_rows_summed);
+    if (stats) {                                   // the sizes as the library reads them: what a flag with a suffix came to
+        const char *nc = getenv("HAST_NAME_CACHE"), *rb = getenv("HAST_GZ_RING_BYTES"), *pg = getenv("HAST_PARK_GB");
+        stat_line("__stats_sizes__ name_cache=%s gz_ring_bytes=%s park_gb=%s\n", nc ? nc : "default", rb ? rb : "default", pg ? pg : "default");
+    }
     if (stats) stat_line("__stats_setup__ waited_for_stream_setup_s=%.3f (inside scrub_sizes_clone_s: .gz inputs opened, FASTQ streams created while the table was built)\n", t_pre_waited);
     // a context that could not get room for its filter probes the table directly (the round-1 kernel: 1.6 x the HBM requests per read):
     // same results, never silently

@@ -1071,6 +1071,11 @@ hast_status hast_fq_commit(hast_fq *f) {
             // read the ids where they are (pinned host memory: a copy would queue up behind the next block's upload)
             const uint32_t nu = s.h_unknown[0];
             hast_names *nm = names_of(f, s);
+            // a dictionary's own ids never pass through the caller: every one of the block lies below what it had handed out when the block
+            // was named (hast_fq_block.dict_ids), and the bookkeeping kernel adds at them unchecked -- the counters must hold them all
+            if (nm && nm->dict && std::min<size_t>(s.h_nids[0], nm->limit) > nbc)
+                return set_error(HAST_ERR_INVALID, "hast_fq_commit: the dictionary had handed out %zu ids when this block was named, the context has %zu counters (hast_counts_resize to dict_ids first)",
+                                 std::min<size_t>(s.h_nids[0], nm->limit), nbc);
             uint32_t np = 0;
             for (uint32_t j = 0; j < nu; ++j) {
                 const uint32_t i = s.h_unknown[1 + j];

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "name_claim.h"
+
 namespace hast {
 
 struct FqState {               // one per buffer slot, in device memory; copied to the host after the framing kernels
@@ -22,20 +24,13 @@ struct FqState {               // one per buffer slot, in device memory; copied 
     uint32_t reserved;
 };
 
-// Device-side cache barcode text -> dense id (the authority stays the host's dictionary, which is one per job): 32-byte
-// entries, open addressing.  key = the 16-byte text record the framer makes (length byte + up to 15 bytes).
-struct NameEntry {
-    uint32_t key[4];
-    uint32_t id;
-    uint32_t state;            // 0 empty, 1 being written, 2 ready
-    uint32_t pad[2];
-};
+// Device-side cache barcode text -> dense id (the authority stays the host's dictionary, which is one per job): NameEntry and the
+// claim protocol of the dictionary variant live in name_claim.h.
 struct NamePub {               // what the host publishes after naming a record the cache did not know
     uint32_t key[4];
     uint32_t id;
     uint32_t pad[3];
 };
-constexpr uint32_t kNameUnknown = 0xFFFFFFFFu;
 
 // ids of the first n records from the cache: d_ids / h_ids get the id or kNameUnknown, h_unknown = [count, index, index, ...]
 hipError_t launch_fq_name(const uint32_t *d_text, uint32_t n, const NameEntry *tab, uint32_t mask, uint32_t *h_ids, uint32_t *h_unknown, hipStream_t s);

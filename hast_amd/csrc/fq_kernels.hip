@@ -241,13 +241,6 @@ __global__ void __launch_bounds__(256) k_fq_begin(uint8_t *buf, FqState *st, con
 }
 
 // ---- device-side name cache ---------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t name_hash(const uint32_t k[4]) {
-    uint32_t h = k[0] * 0x9E3779B1u;
-    h = (h ^ (h >> 15) ^ k[1]) * 0x85EBCA6Bu;
-    h = (h ^ (h >> 13) ^ k[2]) * 0xC2B2AE35u;
-    h = (h ^ (h >> 16) ^ k[3]) * 0x27D4EB2Fu;
-    return h ^ (h >> 15);
-}
 // Runs on the context's stream, after every k_names_insert of earlier blocks: no insert is in flight while it probes.
 __global__ void __launch_bounds__(256) k_fq_name(const uint32_t *text, uint32_t n, const NameEntry *tab, uint32_t mask, uint32_t *h_ids,
                                                  uint32_t *h_unknown) {
@@ -509,12 +502,36 @@ hipError_t launch_fq_route(const uint8_t *d_buf, const FqState *d_st, const uint
 }
 
 
+// the protocol's memory operations (name_claim.h) on the device: atomics at agent scope -- every context of this GPU may be in the table
+struct NameClaimDevice {
+    NameEntry *tab;
+    uint32_t *n_ids;
+    uint4 *text_of_id;
+    __device__ __forceinline__ uint32_t load_state(uint32_t e) { return __hip_atomic_load(&tab[e].state, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT); }
+    __device__ __forceinline__ uint32_t load_counter() { return __hip_atomic_load(n_ids, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT); }
+    __device__ __forceinline__ uint32_t cas_state_0_1(uint32_t e) { return atomicCAS(&tab[e].state, 0u, 1u); }
+    __device__ __forceinline__ uint32_t add_counter() { return __hip_atomic_fetch_add(n_ids, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); }
+    __device__ __forceinline__ void store_state(uint32_t e, uint32_t v) { __hip_atomic_store(&tab[e].state, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); }
+    __device__ __forceinline__ void write_entry(uint32_t e, const uint32_t k[4], uint32_t id) {
+        NameEntry &x = tab[e];
+        x.key[0] = k[0]; x.key[1] = k[1]; x.key[2] = k[2]; x.key[3] = k[3];
+        x.id = id;
+    }
+    __device__ __forceinline__ void write_text(uint32_t id, const uint32_t k[4]) { text_of_id[id] = make_uint4(k[0], k[1], k[2], k[3]); }
+    __device__ __forceinline__ bool key_equals(uint32_t e, const uint32_t k[4]) const {
+        const NameEntry &x = tab[e];
+        return x.key[0] == k[0] && x.key[1] == k[1] && x.key[2] == k[2] && x.key[3] == k[3];
+    }
+    __device__ __forceinline__ uint32_t load_id(uint32_t e) const { return tab[e].id; }
+};
+
 // The DICTIONARY variant (round 6): the table hands out the ids itself.  classify.cpp:52-56 gives a barcode its map entry at its first
 // sighting; until round 5 that first sighting went to the host (a dictionary insert there, the id taught back to this table): a third
 // of a read phase at 10M barcodes.  Here the lane that meets an unknown text claims its slot (compare-and-swap empty -> being written),
 // takes the next id from one counter, writes text and id, files the text under its id for the host (text_of_id: read once, at the
-// end, for printing) and publishes.  The same state machine as k_names_insert, for the same reason: two lanes of one wave may meet the
-// same new barcode.  Left to the host: texts longer than 15 bytes and what arrives once `limit` ids are out (the host names those in an
+// end, for printing) and publishes.  The same kind of state machine as k_names_insert, for the same reason: two lanes of one wave may
+// meet the same new barcode.  The protocol itself, and why a text never gets an id from the device AND is left to the host, is in
+// name_claim.h; tests/native/test_name_claim.cpp enumerates its interleavings.  Left to the host: texts longer than 15 bytes and what arrives once `limit` ids are out (the host names those in an
 // id range of its own, above `limit`).  Streams of several contexts of ONE GPU may run this on one table at the same time.
 __global__ void __launch_bounds__(256) k_fq_name_claim(const uint32_t *text, uint32_t n, const FqState *st, NameEntry *tab, uint32_t mask, uint32_t *n_ids, uint32_t limit,
                                                        uint4 *text_of_id, uint32_t *h_ids, uint32_t *h_unknown, uint32_t *d_ids) {
@@ -528,43 +545,18 @@ __global__ void __launch_bounds__(256) k_fq_name_claim(const uint32_t *text, uin
         uint4 t = make_uint4(0, 0, 0, 0);
         if (busy) t = reinterpret_cast<const uint4 *>(text)[i];
         const uint32_t k[4] = {t.x, t.y, t.z, t.w};
-        uint32_t id = kNameUnknown;
         if (busy && (t.x & 0xFFu) == 0xFFu) busy = false;              // longer than a text record: the host's
         const bool mine = i < n;
-        uint32_t at = busy ? name_hash(k) & mask : 0, probes = 0;
-        while (__any(busy)) {
-            if (busy) {
-                NameEntry *e = &tab[at];
-                uint32_t st = __hip_atomic_load(&e->state, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-                if (st == 0) {
-                    if (__hip_atomic_load(n_ids, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= limit) busy = false;       // every id is out
-                    else {
-                        st = atomicCAS(&e->state, 0u, 1u);
-                        if (st == 0) {                                    // claimed
-                            const uint32_t got = atomicAdd(n_ids, 1u);
-                            if (got >= limit) {                           // (the last ids went while this lane claimed: give the slot back)
-                                __hip_atomic_store(&e->state, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-                            } else {
-                                e->key[0] = k[0]; e->key[1] = k[1]; e->key[2] = k[2]; e->key[3] = k[3];
-                                e->id = got;
-                                text_of_id[got] = t;
-                                __hip_atomic_store(&e->state, 2u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-                                id = got;
-                            }
-                            busy = false;
-                        }
-                    }
-                }
-                if (busy && st == 2) {
-                    if (e->key[0] == k[0] && e->key[1] == k[1] && e->key[2] == k[2] && e->key[3] == k[3]) { id = e->id; busy = false; }
-                    else {
-                        at = (at + 1) & mask;
-                        if (++probes > mask) busy = false;
-                    }
-                }
-                // st == 1: being written by another lane (of this wave, or of another stream's kernel) -- look again next round
-            }
+        NameClaimLane lane;
+        name_claim_begin(lane, k, busy ? name_hash(k) & mask : 0);
+        lane.busy = busy;
+        NameClaimDevice mem{tab, n_ids, text_of_id};
+        // (wave-uniform loop, one step of the state machine per turn: a lane that finds a slot being written -- by a lane of this wave, or
+        // of another stream's kernel -- looks again in the next turn, by when the writer has had its turn to publish)
+        while (__any(lane.busy)) {
+            if (lane.busy) name_claim_step(mem, lane, mask, limit);
         }
+        const uint32_t id = lane.id;
         if (mine) {
             h_ids[i] = id;
             // (the same ids in device memory: a block the dictionary named completely is booked from there -- the bookkeeping kernel reading

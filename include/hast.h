@@ -320,6 +320,13 @@ hast_status hast_names_create(hast_ctx *, size_t max_barcodes, hast_names **out)
  * framer's naming kernel hands out the dense ids itself -- 0 .. hast_names_limit() - 1 in the order in which new texts are met, one atomic
  * counter -- so no first sighting goes through the host.  Left to the caller (hast_fq_block.unknown, as before): texts longer than 15
  * bytes and what arrives once every id is out; the caller names those in an id range of its own at or above hast_names_limit().
+ * AT EXHAUSTION the dictionary gives ONE ANSWER PER TEXT: a text of at most 15 bytes either has a device id -- then every record that
+ * carries it, in this block and in every later one, on whichever context of the GPU, comes back with that id -- or it has none and
+ * never will, and every record that carries it is left to the caller.  No text is ever numbered by both sides, also not in the
+ * block(s) in which the last ids go, so one dictionary plus the caller's range is one numbering without a merge by text.  (That holds
+ * per dictionary: a caller that runs SEVERAL -- one per GPU -- may see a text left to it by one that has run out and numbered by
+ * another that has not, and must sum such rows by text itself.)  Nothing of at most 15 bytes is left to the caller before
+ * hast_fq_block.dict_ids has reached hast_names_limit().
  * hast_names_count: ids handed out so far; hast_names_texts: the text records (16 bytes: length byte + text) of ids [first, first + n),
  * read once at the end for printing.  Dictionaries of different GPUs number independently: their counters are merged by text
  * (hast_names_merge into the first dictionary's numbering, hast_counts_permute, then hast_counts_allreduce). */
@@ -329,7 +336,13 @@ hast_status hast_names_count(hast_names *, size_t *n_ids);
 hast_status hast_names_texts(hast_names *, size_t first, size_t n, uint8_t *out16);
 /* Two dictionaries, one numbering: ids_out[i] = the id that dst has for src's text of id first + i (i < n) -- a text dst does not know
  * yet gets dst's next id there and then.  On the GPU: src's text records are copied to dst's device (peer to peer when that is another
- * GPU) and go through dst's naming kernel; no host map.  HAST_ERR_TABLE_FULL when dst has no id left for a new text. */
+ * GPU) and go through dst's naming kernel; no host map.
+ * HAST_ERR_TABLE_FULL when dst has no id left for some new text.  ids_out is then COMPLETE all the same: the entries of the texts dst
+ * knows or could still take hold their ids (below hast_names_limit(dst), dense as ever), the entries of the texts that did not fit
+ * hold HAST_NAME_NONE.  Nothing is undone and nothing is lost: dst keeps what it took, the same call again returns the same status
+ * and the same ids_out, and the caller numbers the HAST_NAME_NONE texts itself (hast_names_texts(src, ...) has them), as it does
+ * for what a stream leaves to it. */
+#define HAST_NAME_NONE 0xFFFFFFFFu
 hast_status hast_names_merge(hast_names *dst, hast_names *src, size_t first, size_t n, uint32_t *ids_out);
 void        hast_names_destroy(hast_names *);
 /* Entries the caller knows: n text records (16 bytes each: length byte + up to 15 bytes of text, the format of hast_fq_block.bc_text)
@@ -375,6 +388,11 @@ hast_status hast_fq_submit_device(hast_fq *, size_t n_bytes, int last);
 hast_status hast_fq_block_host_bytes(hast_fq *, const uint8_t **bytes);
 int         hast_fq_poll(hast_fq *);      /* 1: hast_fq_next would not have to wait for the framing of the oldest submitted block */
 hast_status hast_fq_next(hast_fq *, hast_fq_block *out);
+/* HAST_ERR_INVALID when an id is outside the context's counters: one the caller filled in, or -- on a stream over a device dictionary --
+ * when the counters are fewer than hast_fq_block.dict_ids (the dictionary's own ids are not looked at one by one: the bound is checked
+ * on the host before anything is queued, so no add outside the counters is ever issued).  Nothing has happened then: the block is
+ * still open, its votes are kept; once the counters are large enough (read them, then hast_counts_resize: it zeroes) or the ids are
+ * corrected, hast_fq_commit may be called again. */
 hast_status hast_fq_commit(hast_fq *);
 
 /* ---- routing: steps 10 and 11 of the wrapper (classify_stlfr_reads.sh:155-190, quartering_fastq.awk:12-61) --------------------

@@ -175,6 +175,12 @@ def test_cli_usage_and_errors(exe, golden_workdir, tmp_path):
         r = subprocess.run([exe, "--hap0", "hap0.mer", "--hap1", "hap1.mer", "--read", str(late), "-t", "8", "--stats"], cwd=d,
                            stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
         assert r.returncode == 3 and b"read shorter than K" in r.stderr, (r.returncode, r.stderr[-300:])
+    # a size that is not a number, or has something behind it, is a usage error like a wrong --inflate or --route, before anything is
+    # read (atol made 16 of "16M" and 0 of "foo"); what a well-formed one comes to: test_cli_names_gpu.py
+    for bad in (["--inflate", "gpu"], ["--route", "both"], ["--name-cache", "foo"], ["--park-gb", "foo"], ["--name-cache", "16Mx"], ["--name-cache", "65536x"],
+                ["--gz-ring-bytes", "2Gx"], ["--park-gb", "1.5x"], ["--name-cache", "-1"], ["--name-cache", ""], ["--gz-ring-bytes", "1.5G"], ["--name-cache", "16T"]):
+        r = subprocess.run([exe, "--hap0", "hap0.mer", "--hap1", "hap1.mer", "--read", "r1.fq"] + bad, cwd=d, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=60)
+        assert r.returncode == 255 and b"--hap0" in r.stderr and r.stdout == b"", (bad, r.returncode, r.stderr[-300:])
 
 
 def _write_case(tmp_path, n_records, seed, gz, long_reads=False):

@@ -66,7 +66,8 @@ def stream_through_framer(ctx, data, lo, hi, cache, rng, n_buffers=3, more_ctxs=
     order, the dictionary, the base count, the per-block short-read flags and how many records the host had to name.
     dict_mode: the table is the DICTIONARY (hast_names_create_dict): the device hands out the ids below hast_names_limit itself, the
     caller names what is left to it (long texts, and what arrives when every id is out) from the limit upwards; checked here: one id
-    per text, dense from 0, below dict_ids, and the texts the dictionary files under its ids are the barcodes.
+    per text, dense from 0, below dict_ids, the texts the dictionary files under its ids are the barcodes, and no text is both numbered
+    by the device and left to the caller (tests/test_names_gpu.py holds the kernel to that at scale).
     more_ctxs: further contexts -> a striped stream (block i on context i % n; n_buffers per context; lo == hi: full blocks);
     eager: open a block as soon as the one behind it has been submitted (else: as late as the buffers allow)"""
     lib = hast_amd.lib()
@@ -114,6 +115,9 @@ def stream_through_framer(ctx, data, lo, hi, cache, rng, n_buffers=3, more_ctxs=
             for i in todo:                           # left to the caller: longer than a text record, or every id was out
                 bc = got[base + i]
                 assert len(bc) > 15 or b.dict_ids >= limit or bc in host_names, (bc, b.dict_ids, limit)
+                # ONE ANSWER PER TEXT: what is left to the caller has no device id -- not from an earlier block, not from this one (its own
+                # ids went into `names` just above).  names.setdefault alone would hand the device's id back and hide a text named twice.
+                assert names.get(bc, limit) >= limit, (bc, names[bc], b.dict_ids, limit)
                 b.ids[i] = names.setdefault(bc, limit + host_names.setdefault(bc, len(host_names)))
             st["host_named"] += len(todo)
             st["n_bases"] += b.n_bases
