@@ -43,6 +43,12 @@ class GzStats(C.Structure):
                [(n, C.c_uint64) for n in ("ring_bytes", "upload_waited_for_ring")] + [("chain_walk_s", C.c_double), ("ring_laps", C.c_uint64)]
 
 
+class SqResult(C.Structure):
+    _fields_ = [("consumed", C.c_uint64), ("out_bytes", C.c_uint64), ("records", C.c_uint64), ("bases", C.c_uint64),
+                ("flags", C.c_uint32), ("first_bad", C.c_uint32)]
+
+
+SQ_NOT_FOUR_LINE, SQ_NO_RECORD = 1, 2
 KC_HISTO_HIGH = 10000
 
 # every symbol include/hast.h declares: name -> (restype, argtypes)
@@ -174,6 +180,17 @@ ABI_SYMBOLS = {
     "hast_kc_selection_keys": (C.c_int, [vp, C.c_int, C.c_size_t, C.c_size_t, vp]),
     "hast_kc_synth_host": (C.c_int, [C.POINTER(KcSynth), C.c_int, C.c_uint64, C.c_size_t, vp]),
     "hast_kc_synth_device": (C.c_int, [vp, C.POINTER(KcSynth), C.c_int, C.c_uint64, C.c_size_t, vp]),
+    # stage 00 ingest on the device: four-line FASTQ in HBM -> the counter's base stream
+    "hast_sq_create": (C.c_int, [vp, C.c_size_t, C.POINTER(vp)]),
+    "hast_sq_frame_device": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(SqResult)]),
+    "hast_sq_destroy": (None, [vp]),
+    "hast_sq_feed_create": (C.c_int, [vp, C.c_size_t, C.POINTER(vp)]),
+    "hast_sq_feed_host_block": (C.c_int, [vp, C.POINTER(vp)]),
+    "hast_sq_feed_device_block": (C.c_int, [vp, C.POINTER(vp)]),
+    "hast_sq_feed_submit": (C.c_int, [vp, C.c_size_t]),
+    "hast_sq_feed_next": (C.c_int, [vp, C.c_int, C.POINTER(SqResult)]),
+    "hast_sq_feed_take_tail": (C.c_int, [vp, vp, C.POINTER(C.c_size_t)]),
+    "hast_sq_feed_destroy": (None, [vp]),
 }
 
 
@@ -685,3 +702,29 @@ class KmerCounter:
 
     def synth_device(self, p: KcSynth, parent, first, n_reads, d_out):
         _ck(self._lib.hast_kc_synth_device(self._h, C.byref(p), parent, first, n_reads, C.c_void_p(d_out)))
+
+
+class SqFramer:
+    """Raw four-line FASTQ in HBM -> the counter's base stream in HBM (hast_sq_*), on the stream of a KmerCounter."""
+
+    def __init__(self, kc: KmerCounter, max_in_bytes):
+        self._lib = lib()
+        h = C.c_void_p()
+        _ck(self._lib.hast_sq_create(kc._h, max_in_bytes, C.byref(h)))
+        self._h = h
+
+    def frame_device(self, d_in, n_in, d_out, cap_out) -> SqResult:
+        res = SqResult()
+        _ck(self._lib.hast_sq_frame_device(self._h, C.c_void_p(d_in), n_in, C.c_void_p(d_out), cap_out, C.byref(res)))
+        return res
+
+    def close(self):
+        if self._h:
+            self._lib.hast_sq_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()

@@ -14,6 +14,7 @@ hast_status classify_framed(hast_ctx *c, const uint8_t *d_buf, size_t buf_bytes,
 hast_status commit_framed(hast_ctx *c, const uint32_t *d_votes, const uint32_t *d_ids, size_t n_reads, hipStream_t hs);
 hipStream_t ctx_stream_of(hast_ctx *c);
 size_t ctx_n_barcodes(const hast_ctx *c);
+int kc_device_of(const hast_kc *c);                                                                  // the count table's device (sq_api.cpp)
 // FREES THAT DO NOT STOP THE DEVICE.  hipFree and hipHostFree wait for every stream of the device and hold the runtime's lock while
 // they do: a stream that is closed while another one still decodes (the reader threads of `classify`, the upload thread of a .gz stream
 // that has sent its last byte) made every HIP call of the process wait 20-50 ms, 0.3 s on some boxes of the pool (tools/hipstall,

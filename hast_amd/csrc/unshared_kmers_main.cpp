@@ -11,9 +11,11 @@
 //
 // Extra options: --device N (repeat it, or --devices a,b,c, to split the key space over several GPUs), --table-gb X (size of the count table per GPU; default: from the input size, at most 85 % of the free HBM), --slices S (process
 // the key space in S passes over the input; doubled automatically when the table overflows), --save-table FILE (the
-// two sets as a binary stage-01 table for `classify --load-table`), --stats.
+// two sets as a binary stage-01 table for `classify --load-table`), --stats, --ingest host|device (HAST_KC_INGEST; device: the files'
+// bytes are inflated and framed on the GPU, see "ingest on the device" below; default host).
 // Exit status: 0 ok / usage; 1 bad arguments, missing or malformed input (the script: exit 1); 4 GPU trouble.
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -48,7 +50,9 @@ void usage(FILE *f) {
           "    --p-lower N / --p-upper N   the same for paternal k-mers (default 9 / 33)\n"
           "    --auto_bounds     derive the four bounds from the count histograms (also writes *.histo, *.bounds.txt)\n"
           "    --device N (repeatable) / --devices a,b,c   GPUs; the k-mer space is split between them\n"
-          "    --table-gb X  --slices S  --save-table FILE  --stats\n",
+          "    --table-gb X  --slices S  --save-table FILE  --stats\n"
+          "    --ingest host|device   device: inflate .gz and frame four-line FASTQ on the GPU (one GPU; anything else\n"
+          "                      is read by the host parser after all); default host, or HAST_KC_INGEST\n",
           f);
 }
 
@@ -62,6 +66,7 @@ struct Options {
     double table_gb = 0;
     long slices = 1;
     std::string save_table;
+    std::string ingest = "host";     // --ingest host|device
 };
 
 // ---- ingest: files -> byte stream of bases -> GPU ---------------------------------------------------------------
@@ -74,6 +79,7 @@ struct Gpu {
     std::vector<std::unique_ptr<std::mutex>> dev_mu;
     std::mutex mu;
     std::string error;               // first failure of a submit
+    hast_ctx *gz_ctx = nullptr;      // --ingest device: the context hast_gz_open wants, on the table's device
     bool ok() {
         std::lock_guard<std::mutex> g(mu);
         return error.empty();
@@ -84,6 +90,8 @@ struct Gpu {
     }
     void destroy() {
         for (hast_kc *k : all) hast_kc_destroy(k);
+        if (gz_ctx) hast_ctx_destroy(gz_ctx);
+        gz_ctx = nullptr;
         all.clear();
         kc = nullptr;
     }
@@ -226,6 +234,209 @@ bool ingest_all(Gpu &gpu, const Options &o, bool &gz_in_order, std::string &err,
     return err.empty();
 }
 
+// ---- ingest on the device (--ingest device, one count table) -------------------------------------------------------------------
+// The host only moves raw bytes: a .gz file is inflated on the GPU straight into the framer's input (hast_gz_*), anything else is
+// read (or, where hast_gz_open passes, inflated by BlockSource) into pinned memory and uploaded; the framer (hast_sq_*, sq_core.h)
+// turns four-line FASTQ into the base stream and hast_kc_count_device counts it.  One feed per parent's input stream, as a thread.
+// The gz files of a parent are read IN ORDER as one stream (`zcat a b`): what file a leaves unframed is carried in front of file
+// b's bytes.  At the end of an input the bytes behind the last complete record go through SeqParser and the ChunkSink, so the
+// unterminated last line and the "ends inside a quality string" error stay the parser's.  Whatever the framer refuses -- a record
+// that is not four lines, a full block without a record, an end the parser does not take -- makes the sweep start over with the
+// host ingest, which then reports errors in its own words.
+struct DeviceIngest {
+    bool on = false;
+    size_t block = 16u << 20;        // HAST_KC_INGEST_BLOCK
+    std::mutex mu;
+    std::string refused;             // first refusal of the sweep
+    uint64_t blocks_framed = 0, gz_on_device = 0;
+    std::string fallback = "none";   // why the host ingest ran after all
+    void refuse(const std::string &why) {
+        std::lock_guard<std::mutex> g(mu);
+        if (refused.empty()) refused = why;
+    }
+    bool is_refused() {
+        std::lock_guard<std::mutex> g(mu);
+        return !refused.empty();
+    }
+};
+
+void ingest_device_stream(Gpu &gpu, DeviceIngest &di, int parent, int k, const std::vector<std::string> &paths, bool gz, IngestResult &res) {
+    std::mutex &table_mu = *gpu.dev_mu[0];
+    hast_sq_feed *feed = nullptr;
+    {
+        std::lock_guard<std::mutex> g(table_mu);
+        if (hast_sq_feed_create(gpu.kc, di.block, &feed) != HAST_OK) {
+            gpu.fail(hast_last_error());
+            return;
+        }
+    }
+    ChunkSink sink(gpu, parent, k);
+    std::vector<uint8_t> tail(di.block);
+    int pending = 0;                 // blocks submitted and not framed yet
+    uint64_t blocks = 0, gz_dev = 0;
+    size_t bases = 0;
+    auto step = [&]() -> bool {      // frame and count the oldest submitted block
+        hast_sq_result r;
+        hast_status st;
+        {
+            std::lock_guard<std::mutex> g(table_mu);
+            st = hast_sq_feed_next(feed, parent, &r);
+            if (st != HAST_OK) gpu.fail(hast_last_error());
+        }
+        --pending;
+        if (st != HAST_OK) return false;
+        if (r.flags & HAST_SQ_NOT_FOUR_LINE) {
+            di.refuse("not four-line FASTQ (record " + std::to_string(res.records + r.first_bad + 1) + " of a " + (parent ? "maternal" : "paternal") + " input)");
+            return false;
+        }
+        if (r.flags & HAST_SQ_TAIL_TOO_LONG) {
+            di.refuse("a full block holds no record");
+            return false;
+        }
+        if (r.records) ++blocks;
+        res.records += r.records;
+        bases += r.bases;
+        return true;
+    };
+    auto submit = [&](size_t n) -> bool {    // ... and keep one block ahead of the framer
+        if (hast_sq_feed_submit(feed, n) != HAST_OK) {
+            gpu.fail(hast_last_error());
+            return false;
+        }
+        res.bytes += n;
+        ++pending;
+        return pending < 2 || step();
+    };
+    auto end_of_input = [&](const std::string &path) -> bool {
+        while (pending)
+            if (!step()) return false;
+        size_t n = 0;
+        {
+            std::lock_guard<std::mutex> g(table_mu);
+            if (hast_sq_feed_take_tail(feed, tail.data(), &n) != HAST_OK) {
+                gpu.fail(hast_last_error());
+                return false;
+            }
+        }
+        hast::SeqParser<ChunkSink> parser(sink);
+        if (!parser.feed(reinterpret_cast<const char *>(tail.data()), n) || !parser.finish()) {
+            di.refuse("the end of " + path + " is the host parser's (" + parser.error() + ")");
+            return false;
+        }
+        res.records += parser.records();
+        sink.flush(true);
+        return true;
+    };
+    auto good = [&] { return res.error.empty() && gpu.ok() && !di.is_refused(); };
+    for (size_t i = 0; i < paths.size() && good(); ++i) {
+        hast_gz *z = nullptr;
+        if (gz && gpu.gz_ctx && hast_gz_open(gpu.gz_ctx, paths[i].c_str(), &z) != HAST_OK) z = nullptr;   // (not for the GPU, or not readable: BlockSource's words)
+        if (z) {
+            ++gz_dev;
+            while (good()) {
+                uint8_t *d = nullptr;
+                size_t n = 0;
+                if (hast_sq_feed_device_block(feed, &d) != HAST_OK) {
+                    gpu.fail(hast_last_error());
+                    break;
+                }
+                if (hast_gz_read_device(z, d, di.block, &n, hast_kc_stream(gpu.kc)) != HAST_OK) {
+                    di.refuse("hast_gz: " + std::string(hast_last_error()));
+                    break;
+                }
+                if (n == 0) break;           // (only a call that returns nothing ends the stream, include/hast.h)
+                if (!submit(n)) break;
+            }
+            while (pending && good())        // before the decoder goes: its kernels wrote the blocks still waiting
+                if (!step()) break;
+            hast_gz_close(z);
+        } else if (gz) {                     // inflated on the host, uploaded
+            hast::BlockSource src;
+            if (!src.open(paths[i], di.block)) {
+                res.error = "cannot open " + paths[i];
+                break;
+            }
+            while (good()) {
+                std::vector<char> b = src.next();
+                if (b.empty()) {
+                    if (!src.error().empty()) res.error = paths[i] + ": " + src.error();
+                    break;
+                }
+                const size_t n = b.size() - hast::BlockSource::kFrontPad;
+                for (size_t at = 0; at < n && good(); at += di.block) {
+                    uint8_t *h = nullptr;
+                    if (hast_sq_feed_host_block(feed, &h) != HAST_OK) {
+                        gpu.fail(hast_last_error());
+                        break;
+                    }
+                    const size_t take = std::min(di.block, n - at);
+                    memcpy(h, b.data() + hast::BlockSource::kFrontPad + at, take);
+                    if (!submit(take)) break;
+                }
+                src.recycle(std::move(b));
+            }
+        } else {                             // a plain file: read into the pinned block, uploaded
+            FILE *fp = fopen(paths[i].c_str(), "rb");
+            if (!fp) {
+                res.error = "cannot open " + paths[i];
+                break;
+            }
+            for (bool first = true; good(); first = false) {
+                uint8_t *h = nullptr;
+                if (hast_sq_feed_host_block(feed, &h) != HAST_OK) {
+                    gpu.fail(hast_last_error());
+                    break;
+                }
+                const size_t n = fread(h, 1, di.block, fp);
+                if (n == 0) break;
+                if (first && h[0] != '@') {
+                    di.refuse(h[0] == '>' ? paths[i] + " is FASTA" : paths[i] + " does not start with '@'");
+                    break;
+                }
+                if (!submit(n)) break;
+            }
+            fclose(fp);
+        }
+        if (good() && (!gz || i + 1 == paths.size()) && !end_of_input(paths[i])) break;
+    }
+    {
+        std::lock_guard<std::mutex> g(table_mu);
+        hast_sq_feed_destroy(feed);          // (waits for what this feed has put on the table's stream)
+    }
+    res.bases = bases + sink.bases();
+    std::lock_guard<std::mutex> g(di.mu);
+    di.blocks_framed += blocks;
+    di.gz_on_device += gz_dev;
+}
+
+// 0 ok, 1 error (err), -3 the device path refused the input (di.refused)
+int ingest_device_all(Gpu &gpu, const Options &o, DeviceIngest &di, std::string &err, ParentTotals tot[2]) {
+    struct Job { int parent; std::vector<std::string> paths; bool gz; IngestResult res; };
+    std::vector<Job> jobs;
+    for (int p = 1; p >= 0; --p) {                                              // maternal first, as the script does
+        std::vector<std::string> order(o.files[p].rbegin(), o.files[p].rend());   // s00:105,109: each new file is put in front
+        jobs.push_back({p, order, ends_gz(order[0]), {}});
+    }
+    di.refused.clear();
+    std::atomic<size_t> next{0};
+    const int nt = (int)std::max<long>(1, std::min<long>(o.cpu, (long)jobs.size()));
+    std::vector<std::thread> th;
+    for (int t = 0; t < nt; ++t)
+        th.emplace_back([&] {
+            for (size_t i; (i = next.fetch_add(1)) < jobs.size();) ingest_device_stream(gpu, di, jobs[i].parent, (int)o.mer, jobs[i].paths, jobs[i].gz, jobs[i].res);
+        });
+    for (auto &t : th) t.join();
+    if (!di.refused.empty()) return -3;
+    for (const auto &j : jobs) {
+        if (!j.res.error.empty() && err.empty()) err = j.res.error;
+        tot[j.parent].bases += j.res.bases;
+        tot[j.parent].records += j.res.records;
+        tot[j.parent].bytes += j.res.bytes;
+    }
+    if (err.empty() && !gpu.ok()) err = gpu.error;
+    return err.empty() ? 0 : 1;
+}
+
 bool write_histo(const char *path, const std::vector<uint64_t> &h) {
     FILE *f = fopen(path, "w");
     if (!f) return false;
@@ -245,6 +456,7 @@ int main(int argc, char **argv) {
     printf("CMD :");
     for (int i = 0; i < argc; ++i) printf(" %s", argv[i]);
     printf("\n");
+    bool ingest_given = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto val = [&]() -> const char * { return i + 1 < argc ? argv[++i] : ""; };
@@ -271,10 +483,17 @@ int main(int argc, char **argv) {
         else if (a == "--slices") o.slices = atol(val());
         else if (a == "--save-table") o.save_table = val();
         else if (a == "--stats") o.stats = true;
+        else if (a == "--ingest") { o.ingest = val(); ingest_given = true; }
         else {                                                                  // s00:113-116: message, then a bare `exit`
             printf("unknown option \"%s\"\n", a.c_str());
             return 0;
         }
+    }
+    if (!ingest_given)
+        if (const char *e = getenv("HAST_KC_INGEST")) o.ingest = e;
+    if (o.ingest != "host" && o.ingest != "device") {
+        printf("ERROR: --ingest %s: host or device\n", o.ingest.c_str());
+        return 1;
     }
     if (o.memory < 1 || o.cpu < 1 || o.files[0].empty() || o.files[1].empty() || o.mer < 11 || o.lower[1] < 1 ||
         o.upper[1] > 100000000 || o.lower[0] < 1 || o.upper[0] > 100000000 || o.slices < 1 || o.slices > 4096) {   // s00:141-152
@@ -341,6 +560,21 @@ int main(int argc, char **argv) {
         gpu.dev_mu.emplace_back(new std::mutex());
     }
     gpu.kc = gpu.all[0];
+    DeviceIngest di;
+    if (o.ingest == "device") {
+        if (n_dev > 1) {
+            fprintf(stderr, "--ingest device works with one count table, there are %ld: using the host ingest\n", n_dev);
+            di.fallback = "several tables";
+        } else {
+            di.on = true;
+            if (const char *e = getenv("HAST_KC_INGEST_BLOCK"))
+                if (atol(e) >= 64) di.block = (size_t)atol(e);
+            bool any_gz = false;
+            for (int p = 0; p < 2; ++p) any_gz = any_gz || ends_gz(o.files[p][0]);
+            // (without a context the .gz files are inflated on the host and uploaded)
+            if (any_gz && hast_ctx_create(o.devices[0], (int)o.mer, &gpu.gz_ctx) != HAST_OK) gpu.gz_ctx = nullptr;
+        }
+    }
     const double t_table = now();
     auto gpu_fail = [&](const char *what) {
         fprintf(stderr, "unshared_kmers: %s: %s\n", what, hast_last_error());
@@ -354,7 +588,8 @@ int main(int argc, char **argv) {
     uint64_t stats_sum[6] = {0, 0, 0, 0, 0, 0};
     size_t bases[2] = {0, 0}, records[2] = {0, 0}, bytes[2] = {0, 0};
     // One sweep = every slice of the key space: count both parents, then take what this sweep is for.
-    // Returns 0 ok, 1 input error, 4 GPU error, -1 table full (caller retries with more slices), -2 read the gz files in order.
+    // Returns 0 ok, 1 input error, 4 GPU error, -1 table full (caller retries with more slices), -2 read the gz files in order,
+    // -3 the device ingest refused the input (caller starts over with the host ingest).
     // the sets of the tables as they stand, appended to the first GPU's selection
     auto select_all = [&]() -> bool {
         for (hast_kc *k : gpu.all) {
@@ -373,6 +608,7 @@ int main(int argc, char **argv) {
             bases[p] = records[p] = bytes[p] = 0;
         }
         for (auto &x : stats_sum) x = 0;
+        di.blocks_framed = di.gz_on_device = 0;
         if (take_sets)                                                          // a sweep that starts over starts from nothing
             for (hast_kc *k : gpu.all)
                 if (hast_kc_selection_clear(k) != HAST_OK) return 4;
@@ -392,8 +628,10 @@ int main(int argc, char **argv) {
                 ParentTotals tot[2];
                 const bool was_in_order = gz_in_order;
                 const double t_in = now();
-                const bool ok = ingest_all(gpu, o, gz_in_order, err, tot);
+                const int dev_rc = di.on ? ingest_device_all(gpu, o, di, err, tot) : 0;
+                const bool ok = di.on ? dev_rc == 0 : ingest_all(gpu, o, gz_in_order, err, tot);
                 t_ingest += now() - t_in;
+                if (dev_rc == -3) return -3;
                 if (!ok) {
                     if (gz_in_order && !was_in_order) return -2;               // a gz file ends inside a record: read them in order
                     const bool gpu_side = !gpu.error.empty();
@@ -429,6 +667,13 @@ int main(int argc, char **argv) {
             const int rc = sweep(take_histo, take_sets);
             if (rc == -2) {
                 fprintf(stderr, "a gz input ends inside a record: reading each parent's gz files in order, as one stream\n");
+                for (hast_kc *k : gpu.all) hast_kc_sync(k);
+                continue;
+            }
+            if (rc == -3) {
+                fprintf(stderr, "--ingest device: %s: starting over with the host ingest\n", di.refused.c_str());
+                di.on = false;
+                di.fallback = di.refused;
                 for (hast_kc *k : gpu.all) hast_kc_sync(k);
                 continue;
             }
@@ -539,6 +784,9 @@ int main(int argc, char **argv) {
         for (int p = 0; p < 2; ++p)
             fprintf(stderr, "[stats] %s: %zu input bytes, %zu records, %zu bases, %llu k-mers counted, %llu distinct, %zu selected\n", pname[p],
                     bytes[p], records[p], bases[p], (unsigned long long)stats_sum[4 + p], (unsigned long long)stats_sum[p], n_sel[p]);
+        if (o.ingest == "device")
+            fprintf(stderr, "[stats] ingest device: blocks_framed=%llu gz_on_device=%llu fallback=%s\n", (unsigned long long)di.blocks_framed,
+                    (unsigned long long)di.gz_on_device, di.fallback.c_str());
         fprintf(stderr, "[stats] table %.3f s, read+parse+count %.3f s, table passes %.3f s, output %.3f s, total %.3f s\n", t_table - t_start, t_ingest,
                 t_count - t_table - t_ingest, t_end - t_count, t_end - t_start);
     }

@@ -638,6 +638,48 @@ typedef struct hast_kc_synth {
 hast_status hast_kc_synth_host(const hast_kc_synth *, int parent, uint64_t first_read, size_t n_reads, uint8_t *out);
 hast_status hast_kc_synth_device(hast_kc *, const hast_kc_synth *, int parent, uint64_t first_read, size_t n_reads, uint8_t *d_out);
 
+/* ---- stage 00 ingest on the device: raw four-line FASTQ in HBM -> the base stream hast_kc_count_device takes --------------------
+ * The stream is what the host parser (hast_amd/csrc/seqstream.h) hands the counter: per record the bytes of the sequence line, the
+ * '\r's of the line break stripped, then one '\n'.  A block is taken only when "a record is four lines" and that parser agree on it
+ * (hast_amd/csrc/sq_core.h: header starts with '@'; a non-empty sequence does not start with '+'; the third line starts with '+';
+ * quality as long as the sequence) and is refused as a whole otherwise: HAST_SQ_NOT_FOUR_LINE, first_bad = index of the first record
+ * that breaks a rule, nothing written, every count 0.  consumed = the byte behind the last 4n-th newline: the caller puts
+ * [consumed, n_in) in front of the next bytes.  A block with fewer than four newlines frames nothing (HAST_SQ_NO_RECORD, consumed 0).
+ * first_bad is 0xFFFFFFFF when no record breaks a rule.
+ * hast_sq_create: on the device and the stream of the count table (hast_kc_stream); scratch for the worst block of max_in_bytes
+ * (< 4 GB; all newlines: ~6 bytes per byte of input).  Destroy it before the table.
+ * hast_sq_frame_device: asynchronous on that stream up to the copy of *res, returns when *res is valid; d_in and d_out at any
+ * alignment; cap_out >= n_in; nothing is written at or behind d_out + out_bytes, nothing read outside [d_in, d_in + n_in). */
+typedef struct hast_sq hast_sq;
+typedef struct { uint64_t consumed, out_bytes, records, bases; uint32_t flags, first_bad; } hast_sq_result;
+#define HAST_SQ_NOT_FOUR_LINE 1u   /* a record breaks a rule: nothing written */
+#define HAST_SQ_NO_RECORD     2u   /* fewer than four newlines in the input */
+hast_status hast_sq_create(hast_kc *, size_t max_in_bytes, hast_sq **out);
+hast_status hast_sq_frame_device(hast_sq *, const uint8_t *d_in, size_t n_in, uint8_t *d_out, size_t cap_out, hast_sq_result *res);
+void        hast_sq_destroy(hast_sq *);
+
+/* The feed of one input stream of `unshared_kmers --ingest device`: two input and two output buffers on the device and two pinned
+ * staging blocks, so that the upload of block n+1 (a stream of the feed's own) overlaps the framing and counting of block n.
+ *   hast_sq_feed_host_block    pinned memory for the next up to block_bytes raw bytes (waits until it is free), uploaded by _submit
+ *   hast_sq_feed_device_block  where the caller's kernels on hast_kc_stream write them instead (hast_gz_read_device), block_bytes of room
+ *   hast_sq_feed_submit        n_bytes > 0 of the block just handed out are valid; at most two blocks are submitted and not yet taken by _next
+ *   hast_sq_feed_next          frames the bytes carried from the block before + the oldest submitted block, counts the stream for
+ *                              `parent` (hast_kc_count_device) and carries [consumed, n) to the front of the next block.  *res as
+ *                              hast_sq_frame_device; nothing is counted when res->flags has HAST_SQ_NOT_FOUR_LINE or
+ *                              HAST_SQ_TAIL_TOO_LONG (more than block_bytes would have to be carried: a full buffer without a record).
+ *                              Calls into the count table: the caller serialises it with the table's other users.
+ *   hast_sq_feed_take_tail     the carried bytes (fewer than four newlines) to dst (block_bytes of room) at the end of an input; the
+ *                              feed then starts the next input with nothing carried. */
+typedef struct hast_sq_feed hast_sq_feed;
+#define HAST_SQ_TAIL_TOO_LONG 4u
+hast_status hast_sq_feed_create(hast_kc *, size_t block_bytes, hast_sq_feed **out);
+hast_status hast_sq_feed_host_block(hast_sq_feed *, uint8_t **h_buf);
+hast_status hast_sq_feed_device_block(hast_sq_feed *, uint8_t **d_buf);
+hast_status hast_sq_feed_submit(hast_sq_feed *, size_t n_bytes);
+hast_status hast_sq_feed_next(hast_sq_feed *, int parent, hast_sq_result *res);
+hast_status hast_sq_feed_take_tail(hast_sq_feed *, uint8_t *dst, size_t *n_bytes);
+void        hast_sq_feed_destroy(hast_sq_feed *);
+
 #ifdef __cplusplus
 }
 #endif
