@@ -48,6 +48,19 @@ class SqResult(C.Structure):
                 ("flags", C.c_uint32), ("first_bad", C.c_uint32)]
 
 
+class TxMapInfo(C.Structure):
+    _fields_ = [("n_keys", C.c_uint64), ("device_ok", C.c_int), ("reason", C.c_char * 60)]
+
+
+class TxState(C.Structure):
+    _fields_ = [("used", C.c_uint64), ("headers", C.c_uint64)]
+
+
+class TxResult(C.Structure):
+    _fields_ = [("consumed1", C.c_uint64), ("consumed2", C.c_uint64), ("pairs", C.c_uint64), ("used", C.c_uint64),
+                ("out_bytes", C.c_uint64 * 2), ("raw_bytes", C.c_uint64 * 2), ("lines", C.c_uint32 * 2)]
+
+
 SQ_NOT_FOUR_LINE, SQ_NO_RECORD = 1, 2
 KC_HISTO_HIGH = 10000
 
@@ -191,6 +204,14 @@ ABI_SYMBOLS = {
     "hast_sq_feed_next": (C.c_int, [vp, C.c_int, C.POINTER(SqResult)]),
     "hast_sq_feed_take_tail": (C.c_int, [vp, vp, C.POINTER(C.c_size_t)]),
     "hast_sq_feed_destroy": (None, [vp]),
+    # stage 02: stLFR pairs -> 10x FASTQ (fake_10x.pl)
+    "hast_tx_map_load": (C.c_int, [C.c_char_p, C.POINTER(vp), C.POINTER(TxMapInfo)]),
+    "hast_tx_map_parse": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(vp), C.POINTER(TxMapInfo)]),
+    "hast_tx_map_destroy": (None, [vp]),
+    "hast_tx_pair_host": (C.c_int, [vp, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_int, C.POINTER(TxState), C.POINTER(vp), C.POINTER(vp),
+                                    C.POINTER(TxResult)]),
+    "hast_tx_free": (None, [vp]),
+    "hast_tx_step_mode": (C.c_int, [C.c_int, C.c_int, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]),
 }
 
 
@@ -219,6 +240,10 @@ def classify_read_exe():
 
 def unshared_kmers_exe():
     return os.path.join(_HERE, "unshared_kmers")
+
+
+def fake_10x_exe():
+    return os.path.join(_HERE, "fake_10x")
 
 
 def build(verbose=False):
@@ -727,4 +752,37 @@ class SqFramer:
         return self
 
     def __exit__(self, *a):
+        self.close()
+
+
+# ---- stage 02: stLFR pairs -> 10x FASTQ ----------------------------------------------------------
+class TxMap:
+    """fake_10x.pl's map file as perl reads it (hast_tx_map_*); host only, no GPU"""
+
+    def __init__(self, text: bytes):
+        self._lib = lib()
+        self._h = C.c_void_p()
+        info = TxMapInfo()
+        _ck(self._lib.hast_tx_map_parse(text, len(text), C.byref(self._h), C.byref(info)))
+        self.n_keys, self.device_ok, self.reason = info.n_keys, bool(info.device_ok), info.reason.decode()
+
+    def pair_host(self, r1: bytes, r2: bytes, final, state: TxState):
+        """the host model over two buffers -> (out1, out2, TxResult); state is updated"""
+        o1, o2, res = C.c_void_p(), C.c_void_p(), TxResult()
+        _ck(self._lib.hast_tx_pair_host(self._h, r1, len(r1), r2, len(r2), int(final), C.byref(state), C.byref(o1), C.byref(o2), C.byref(res)))
+        try:
+            return C.string_at(o1, res.out_bytes[0]), C.string_at(o2, res.out_bytes[1]), res
+        finally:
+            self._lib.hast_tx_free(o1)
+            self._lib.hast_tx_free(o2)
+
+    def close(self):
+        if self._h:
+            self._lib.hast_tx_map_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
         self.close()

@@ -1,0 +1,234 @@
+// fake_10x -- drop-in for HAST's 02.assemble_by_supernova/fake_10x.pl: stLFR read pairs -> 10x FASTQ for Supernova.
+//   fake_10x READ1.gz READ2.gz MERGE.txt [--inflate host|zlib] [--block-mb N] [--plain-out] [--stats]
+// writes SampleName_S1_L001_R1_001.fastq.gz and SampleName_S1_L001_R2_001.fastq.gz into the working directory and prints the
+// script's stdout.  A host program: the inputs come through ingest.h (ordinary gzip inflated by several threads, BGZF, pipes, plain
+// FASTQ), a block of each at a time; the whole pairs of what has been read go through the model of the script
+// (hast_tx_pair_host, include/hast.h "stage 02"), what is left is carried in front of the next block; both outputs leave as one
+// zlib gzip member per step, deflated side by side.  Memory stays at a few blocks whatever the inputs' lengths: when read 2 ends
+// first, the rest of read 1 is still converted block by block, as the script pairs it with nothing.
+// Exit codes: 0 done; 1 usage; 2 an input that cannot be opened, or a .gz that is damaged or fails its CRC; 3 a failing library
+// call or write.
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <zlib.h>
+
+#include <algorithm>
+#include <chrono>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "../../include/hast.h"
+#include "ingest.h"
+
+namespace {
+
+struct Options {
+    std::string in[2], map;
+    bool plain_out = false, stats = false;
+    std::string inflate = "host";
+    size_t block = 16u << 20;
+};
+
+double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+int usage() {
+    fprintf(stderr, "usage: fake_10x READ1.gz READ2.gz MERGE.txt [--inflate host|zlib] [--block-mb N] [--plain-out] [--stats]\n");
+    return 1;
+}
+
+struct Outputs {
+    FILE *f[2] = {nullptr, nullptr};
+    bool plain = false;
+    uint64_t bytes[2] = {0, 0};
+    bool open(bool plain_out) {
+        plain = plain_out;
+        const char *names[2] = {"SampleName_S1_L001_R1_001.fastq", "SampleName_S1_L001_R2_001.fastq"};
+        for (int s = 0; s < 2; ++s) {
+            f[s] = fopen((std::string(names[s]) + (plain ? "" : ".gz")).c_str(), "wb");
+            if (!f[s]) return false;
+        }
+        return true;
+    }
+    bool write(int s, const uint8_t *p, size_t n) {
+        bytes[s] += n;
+        return n == 0 || fwrite(p, 1, n, f[s]) == n;
+    }
+    // a run of converted records: as it is, or as one zlib gzip member (nothing for an empty run); zlib is fed pieces it can count
+    bool write_host(int s, const uint8_t *p, size_t n) {
+        if (plain || n == 0) return write(s, p, n);
+        z_stream z;
+        memset(&z, 0, sizeof z);
+        if (deflateInit2(&z, 6, Z_DEFLATED, 15 + 16, 8, Z_DEFAULT_STRATEGY) != Z_OK) return false;
+        std::vector<uint8_t> out(1u << 20);
+        bool ok = true;
+        for (size_t at = 0; ok;) {
+            const size_t piece = std::min<size_t>(n - at, 1u << 30);
+            z.next_in = const_cast<uint8_t *>(p + at);
+            z.avail_in = (uInt)piece;
+            at += piece;
+            int r;
+            do {
+                z.next_out = out.data();
+                z.avail_out = (uInt)out.size();
+                r = deflate(&z, at == n ? Z_FINISH : Z_NO_FLUSH);
+                ok = r != Z_STREAM_ERROR && write(s, out.data(), out.size() - z.avail_out);
+            } while (ok && z.avail_out == 0);
+            if (at == n) {
+                ok = ok && r == Z_STREAM_END;
+                break;
+            }
+        }
+        deflateEnd(&z);
+        return ok;
+    }
+    // both outputs of a host step, deflated side by side (the script pipes its outputs through two gzip processes)
+    bool write_host_both(uint8_t *const o[2], const uint64_t n[2]) {
+        bool ok1 = true;
+        std::thread side1([&] { ok1 = write_host(1, o[1], (size_t)n[1]); });
+        const bool ok0 = write_host(0, o[0], (size_t)n[0]);
+        side1.join();
+        return ok0 && ok1;
+    }
+    bool close() {
+        bool ok = true;
+        for (int s = 0; s < 2; ++s)
+            if (f[s] && fclose(f[s]) != 0) ok = false;
+        return ok;
+    }
+};
+
+struct Input {
+    std::string path;
+    hast::BlockSource src;
+    bool eof = false;
+};
+
+struct Run {
+    Options o;
+    hast_tx_map *map = nullptr;
+    hast_tx_map_info info{};
+    hast_tx_state st{0, 0};
+    Outputs out;
+    uint64_t steps = 0, plain_in = 0;
+};
+
+void progress(uint64_t before, uint64_t after) {
+    for (uint64_t mb = before / 1000000 + 1; mb * 1000000 <= after; ++mb) printf("process %llu (Mb) pair of reads now  \n", (unsigned long long)mb);
+}
+
+int fail_lib(const char *what) {
+    fprintf(stderr, "fake_10x: %s: %s\n", what, hast_last_error());
+    return 3;
+}
+
+bool has_record(const std::vector<uint8_t> &v) {
+    size_t at = 0;
+    for (int lines = 0; lines < 4; ++lines) {
+        const void *nl = at < v.size() ? memchr(v.data() + at, '\n', v.size() - at) : nullptr;
+        if (!nl) return false;
+        at = (size_t)(static_cast<const uint8_t *>(nl) - v.data()) + 1;
+    }
+    return true;
+}
+
+int run(Run &r) {
+    Input in[2];
+    for (int s = 0; s < 2; ++s) {
+        in[s].path = r.o.in[s];
+        if (!in[s].src.open(in[s].path, r.o.block, false)) {
+            fprintf(stderr, "fake_10x: cannot open %s\n", in[s].path.c_str());
+            return 2;
+        }
+    }
+    std::vector<uint8_t> have[2];            // per side: what the step before left + the block just read
+    std::string trouble;
+    for (int mode = 0; mode != 1;) {
+        // a side that has more than a block waiting, a whole record in it, reads nothing: the other side has to catch up
+        for (int s = 0; s < 2; ++s) {
+            if (in[s].eof || (have[s].size() > r.o.block && has_record(have[s]))) continue;
+            const size_t at = have[s].size();
+            have[s].resize(at + r.o.block);
+            const size_t n = in[s].src.read_into(reinterpret_cast<char *>(have[s].data() + at), r.o.block, trouble);
+            have[s].resize(at + n);
+            r.plain_in += n;
+            if (!trouble.empty()) {
+                fprintf(stderr, "fake_10x: %s: %s\n", in[s].path.c_str(), trouble.c_str());
+                return 2;
+            }
+            if (n < r.o.block) in[s].eof = true;
+        }
+        // 0: the whole pairs; 2: read 2 has ended, the whole records of read 1 pair with nothing; 1: the inputs end here
+        mode = hast_tx_step_mode(in[0].eof, in[1].eof, have[0].data(), have[0].size(), have[1].data(), have[1].size());
+        uint8_t *o[2] = {nullptr, nullptr};
+        hast_tx_result res;
+        const uint64_t before = r.st.headers;
+        if (hast_tx_pair_host(r.map, have[0].data(), have[0].size(), have[1].data(), have[1].size(), mode, &r.st, &o[0], &o[1], &res) != HAST_OK)
+            return fail_lib("the conversion");
+        progress(before, r.st.headers);
+        ++r.steps;
+        const bool ok = r.out.write_host_both(o, res.out_bytes);
+        hast_tx_free(o[0]);
+        hast_tx_free(o[1]);
+        if (!ok) {
+            fprintf(stderr, "fake_10x: cannot write the outputs\n");
+            return 3;
+        }
+        have[0].erase(have[0].begin(), have[0].begin() + (size_t)res.consumed1);
+        have[1].erase(have[1].begin(), have[1].begin() + (size_t)res.consumed2);
+    }
+    return 0;
+}
+
+}  // namespace
+
+int main(int argc, char **argv) {
+    Run r;
+    std::vector<std::string> pos;
+    bool block_given = false;
+    for (int i = 1; i < argc; ++i) {
+        const std::string a = argv[i];
+        auto value = [&]() -> const char * { return i + 1 < argc ? argv[++i] : nullptr; };
+        if (a == "--inflate") { const char *v = value(); if (!v || (strcmp(v, "host") && strcmp(v, "zlib"))) return usage(); r.o.inflate = v; }
+        else if (a == "--block-mb") { const char *v = value(); if (!v || atoi(v) < 1 || atoi(v) > 1024) return usage(); r.o.block = (size_t)atoi(v) << 20; block_given = true; }
+        else if (a == "--plain-out") r.o.plain_out = true;
+        else if (a == "--stats") r.o.stats = true;
+        else if (a.size() > 1 && a[0] == '-' && a[1] == '-') return usage();
+        else pos.push_back(a);
+    }
+    if (pos.size() != 3) return usage();
+    r.o.in[0] = pos[0];
+    r.o.in[1] = pos[1];
+    r.o.map = pos[2];
+    if (const char *e = getenv("HAST_TX_BLOCK"))         // tests: blocks of a few KB
+        if (!block_given && atol(e) >= 64) r.o.block = (size_t)atol(e);
+    if (r.o.inflate == "zlib") setenv("HAST_INFLATE", "zlib", 1);
+    printf("Merge stLFR reads into 10X format !\n read1 :  %s \n. read2 : %s \n map file : %s\n", pos[0].c_str(), pos[1].c_str(), pos[2].c_str());
+    fflush(stdout);
+    if (hast_tx_map_load(r.o.map.c_str(), &r.map, &r.info) != HAST_OK) {
+        fprintf(stderr, "fake_10x: %s\n", hast_last_error());
+        return 2;
+    }
+    if (!r.out.open(r.o.plain_out)) {
+        fprintf(stderr, "fake_10x: cannot create the outputs in the working directory\n");
+        return 3;
+    }
+    const double t0 = now();
+    const int rc = run(r);
+    const bool closed = r.out.close();
+    hast_tx_map_destroy(r.map);
+    if (rc) return rc;
+    if (!closed) {
+        fprintf(stderr, "fake_10x: cannot write the outputs\n");
+        return 3;
+    }
+    printf("Total %llu pair reads and used %llu pairs.\n", (unsigned long long)r.st.headers, (unsigned long long)r.st.used);
+    if (r.o.stats) {
+        fprintf(stderr, "[stats] transform host: steps=%llu pairs_on_device=0 pairs_on_host=%llu fallback=none\n", (unsigned long long)r.steps,
+                (unsigned long long)r.st.headers);
+        fprintf(stderr, "[stats] seconds: read_phase=%.3f plain_in_bytes=%llu out_bytes=%llu+%llu\n", now() - t0, (unsigned long long)r.plain_in,
+                (unsigned long long)r.out.bytes[0], (unsigned long long)r.out.bytes[1]);
+    }
+    return 0;
+}

@@ -680,6 +680,36 @@ hast_status hast_sq_feed_next(hast_sq_feed *, int parent, hast_sq_result *res);
 hast_status hast_sq_feed_take_tail(hast_sq_feed *, uint8_t *dst, size_t *n_bytes);
 void        hast_sq_feed_destroy(hast_sq_feed *);
 
+/* ---- stage 02: stLFR pairs -> 10x FASTQ (02.assemble_by_supernova/fake_10x.pl) ----------------------------------------------
+ * The script's conversion, on the host (no GPU is touched): record i of read 1 goes with record i of read 2; the key in read 1's
+ * header (the text after the first '#' of the header's first tab field, up to the next '#' or '/') is looked up in the map file; a
+ * pair whose key the map lacks is dropped, a pair it holds is numbered (N, from 1) and both records rewritten
+ * (hast_amd/csrc/tx_core.h has the rules, tx_host.h the model).
+ * hast_tx_map_load / hast_tx_map_parse read the map as perl does (split at tabs, a later line wins, no tab: the empty value).
+ * info.device_ok == 0 with info.reason: a device path with 16-byte text records could not take this map (an empty key, a key over 15
+ * bytes, a value over 16).
+ * hast_tx_pair_host converts r1[0, n1) / r2[0, n2) with the running state (*state: N so far, read-1 headers so far; updated).
+ * final == 0: the whole pairs only, res->consumed1/2 = the byte behind them, the caller carries the rest in front of the next bytes.
+ * final == 1: the inputs end here; everything is converted the way the script ends (missing lines are empty, an unterminated line
+ * gets no newline, a partial read-1 record whose key the map holds is numbered).  final == 2: read 2 has ended (r2 is all that is
+ * left of it, less than a record) while read 1 goes on: the whole records of r1, paired with what r2 still has and then with nothing.
+ * *out1 / *out2 are malloc'ed (hast_tx_free), res->raw_bytes = res->out_bytes = their sizes, res->pairs = the read-1 headers
+ * converted, res->used = the pairs kept, res->lines = the newlines of the two inputs.  The script's progress line is due whenever
+ * state->headers passes a multiple of 1 000 000. */
+typedef struct hast_tx_map hast_tx_map;
+typedef struct { uint64_t n_keys; int device_ok; char reason[60]; } hast_tx_map_info;
+typedef struct { uint64_t used, headers; } hast_tx_state;
+typedef struct { uint64_t consumed1, consumed2, pairs, used, out_bytes[2], raw_bytes[2]; uint32_t lines[2]; } hast_tx_result;
+hast_status hast_tx_map_load(const char *path, hast_tx_map **out, hast_tx_map_info *info);
+hast_status hast_tx_map_parse(const uint8_t *text, size_t n_bytes, hast_tx_map **out, hast_tx_map_info *info);
+void        hast_tx_map_destroy(hast_tx_map *);
+hast_status hast_tx_pair_host(const hast_tx_map *, const uint8_t *r1, size_t n1, const uint8_t *r2, size_t n2, int final, hast_tx_state *state,
+                              uint8_t **out1, uint8_t **out2, hast_tx_result *res);
+void        hast_tx_free(void *);
+/* the `final` of the next hast_tx_pair_host call over what a caller has read and not converted yet; eof1 / eof2: that input has been
+ * read to its end.  1 also when read 1 has ended without a whole record and read 2 holds one (the script takes no more than that). */
+int         hast_tx_step_mode(int eof1, int eof2, const uint8_t *r1, size_t n1, const uint8_t *r2, size_t n2);
+
 #ifdef __cplusplus
 }
 #endif
