@@ -12,6 +12,7 @@
 
 #include "dz_core.h"
 #include "dz_device.h"
+#include "scan_device.h"
 
 namespace hast {
 namespace dz {
@@ -56,19 +57,8 @@ __device__ inline uint32_t load_word(const uint8_t *s, uint32_t w) {
     return sa ? (base[0] >> (8 * sa)) | (base[1] << (32 - 8 * sa)) : base[0];
 }
 
-__device__ inline uint32_t wave_sum(uint32_t v) {
-    for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
 __device__ inline uint32_t wave_xor(uint32_t v) {
     for (int d = 32; d; d >>= 1) v ^= __shfl_xor(v, d, 64);
-    return v;
-}
-__device__ inline uint32_t wave_inclusive_sum(uint32_t v, uint32_t lane) {
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t u = __shfl_up(v, d, 64);
-        if (lane >= (uint32_t)d) v += u;
-    }
     return v;
 }
 

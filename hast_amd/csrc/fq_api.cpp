@@ -13,19 +13,13 @@
 
 #include "../../include/hast.h"
 #include "fq_device.h"
+#include "nl_index.h"
 #include "dz_device.h"
 #include "hast_internal.h"
 
 using namespace hast;
 
 namespace {
-#define FQ_TRY(expr)                                                                                          \
-    do {                                                                                                      \
-        hipError_t e_ = (expr);                                                                               \
-        if (e_ != hipSuccess)                                                                                 \
-            return set_error(e_ == hipErrorOutOfMemory ? HAST_ERR_OOM : HAST_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
 struct Slot {
     uint8_t *h_buf = nullptr, *d_buf = nullptr;        // pad + block bytes (+ slack)
     size_t h_buf_bytes = 0;
@@ -143,10 +137,10 @@ static hast_status grow_records(Slot &s, size_t cap) {
     s.h_bc = s.h_ids = s.h_unknown = nullptr;
     s.h_pubs = nullptr;
     s.h_cap = 0;
-    FQ_TRY(pinned_malloc((void **)&s.h_bc, (2 + 4) * cap * sizeof(uint32_t), hipHostMallocDefault));
-    FQ_TRY(pinned_malloc((void **)&s.h_ids, cap * sizeof(uint32_t), hipHostMallocDefault));
-    FQ_TRY(pinned_malloc((void **)&s.h_unknown, (1 + cap) * sizeof(uint32_t), hipHostMallocDefault));
-    FQ_TRY(pinned_malloc((void **)&s.h_pubs, cap * sizeof(NamePub), hipHostMallocDefault));
+    HAST_HIP_TRY(pinned_malloc((void **)&s.h_bc, (2 + 4) * cap * sizeof(uint32_t), hipHostMallocDefault));
+    HAST_HIP_TRY(pinned_malloc((void **)&s.h_ids, cap * sizeof(uint32_t), hipHostMallocDefault));
+    HAST_HIP_TRY(pinned_malloc((void **)&s.h_unknown, (1 + cap) * sizeof(uint32_t), hipHostMallocDefault));
+    HAST_HIP_TRY(pinned_malloc((void **)&s.h_pubs, cap * sizeof(NamePub), hipHostMallocDefault));
     s.h_cap = cap;
     return HAST_OK;
 }
@@ -196,10 +190,10 @@ static hast_status enqueue_names_early(Slot &s, hast_names *nm, hipStream_t hs) 
     s.named_early = false;
     if (!nm || !nm->dict || !nm->name_early || !s.h_cap) return HAST_OK;
     s.h_unknown[0] = 0;
-    FQ_TRY(launch_fq_name_claim_framed(s.d_text, s.d_st, (uint32_t)s.h_cap, nm->d_tab, nm->mask, nm->d_n_ids, (uint32_t)nm->limit, nm->d_text_of_id, s.h_ids, s.h_unknown,
+    HAST_HIP_TRY(launch_fq_name_claim_framed(s.d_text, s.d_st, (uint32_t)s.h_cap, nm->d_tab, nm->mask, nm->d_n_ids, (uint32_t)nm->limit, nm->d_text_of_id, s.h_ids, s.h_unknown,
                                        s.d_ids, hs));
-    FQ_TRY(hipMemcpyAsync(s.h_nids, nm->d_n_ids, sizeof(uint32_t), hipMemcpyDeviceToHost, hs));
-    FQ_TRY(hipEventRecord(s.named, hs));
+    HAST_HIP_TRY(hipMemcpyAsync(s.h_nids, nm->d_n_ids, sizeof(uint32_t), hipMemcpyDeviceToHost, hs));
+    HAST_HIP_TRY(hipEventRecord(s.named, hs));
     s.named_early = true;
     return HAST_OK;
 }
@@ -207,19 +201,19 @@ static hast_status enqueue_names_early(Slot &s, hast_names *nm, hipStream_t hs) 
 // Routing streams: behind the framing of a block, on the same stream -- class and extent of every record, prefix sums, the records copied
 // into four runs, the runs and their sizes to pinned host memory (fq_kernels.hip, "routing").  view_bytes bounds what the runs can hold.
 static hast_status enqueue_route(hast_fq *f, Slot &s, hast_names *tab, bool striped, int last, size_t view_bytes, hipStream_t hs) {
-    FQ_TRY(launch_fq_route(s.d_buf, s.d_st, s.d_nl, striped ? 1 : 0, last, tab ? tab->d_tab : nullptr, tab ? tab->mask : 0, s.d_rstart, s.d_rlen, s.d_rcls, s.d_rtile,
+    HAST_HIP_TRY(launch_fq_route(s.d_buf, s.d_st, s.d_nl, striped ? 1 : 0, last, tab ? tab->d_tab : nullptr, tab ? tab->mask : 0, s.d_rstart, s.d_rlen, s.d_rcls, s.d_rtile,
                            (uint32_t)s.route_rec, s.d_rs, s.d_out, hs));
-    FQ_TRY(hipMemcpyAsync(s.h_rs, s.d_rs, sizeof(RouteState), hipMemcpyDeviceToHost, hs));
+    HAST_HIP_TRY(hipMemcpyAsync(s.h_rs, s.d_rs, sizeof(RouteState), hipMemcpyDeviceToHost, hs));
     s.gz = f->route_gz && s.d_gz;
     if (s.gz) {
         // the runs stay in HBM and are compressed there, a gzip member each (dz_kernels.hip); their sizes come back with the block's
         // state, the members themselves once hast_fq_next_routed knows how long they are
-        FQ_TRY(dz::launch_job_from_route(s.d_dzjob, s.d_rs, hs));
-        FQ_TRY(dz::launch_compress(s.d_dzjob, s.d_out, s.dz_pieces, s.d_dzwork, s.d_gz, s.gz_cap, s.d_dzres, 0, hs));
-        FQ_TRY(hipMemcpyAsync(s.h_dzres, s.d_dzres, sizeof(dz::Result), hipMemcpyDeviceToHost, hs));
+        HAST_HIP_TRY(dz::launch_job_from_route(s.d_dzjob, s.d_rs, hs));
+        HAST_HIP_TRY(dz::launch_compress(s.d_dzjob, s.d_out, s.dz_pieces, s.d_dzwork, s.d_gz, s.gz_cap, s.d_dzres, 0, hs));
+        HAST_HIP_TRY(hipMemcpyAsync(s.h_dzres, s.d_dzres, sizeof(dz::Result), hipMemcpyDeviceToHost, hs));
         return HAST_OK;
     }
-    if (view_bytes) FQ_TRY(hipMemcpyAsync(s.h_out, s.d_out, std::min(view_bytes, s.h_buf_bytes), hipMemcpyDeviceToHost, hs));
+    if (view_bytes) HAST_HIP_TRY(hipMemcpyAsync(s.h_out, s.d_out, std::min(view_bytes, s.h_buf_bytes), hipMemcpyDeviceToHost, hs));
     return HAST_OK;
 }
 
@@ -249,8 +243,8 @@ static hast_status advance_striped_once(hast_fq *f, bool wait, size_t upto) {
         uint64_t nl_before = 0;                       // (f->nl_before moves on only once the framing launch has succeeded)
         if (!s.first_of_file) {
             Slot &pv = f->slots[(j - 1) % f->slots.size()];
-            FQ_TRY(hipSetDevice(dev_of(f, pv)));
-            if (wait) FQ_TRY(hipEventSynchronize(pv.counted));
+            HAST_HIP_TRY(hipSetDevice(dev_of(f, pv)));
+            if (wait) HAST_HIP_TRY(hipEventSynchronize(pv.counted));
             else {
                 const hipError_t q = hipEventQuery(pv.counted);
                 if (q == hipErrorNotReady) break;
@@ -261,16 +255,16 @@ static hast_status advance_striped_once(hast_fq *f, bool wait, size_t upto) {
         }
         phase = (uint32_t)(nl_before & 3);
         FqLane &ln = f->lanes[(size_t)s.lane];
-        FQ_TRY(hipSetDevice(ln.device));
-        if (s.n_over) FQ_TRY(hipStreamWaitEvent(ln.parse_stream, s.over_copied, 0));
-        FQ_TRY(launch_fq_block_striped(s.d_buf, s.d_st, f->pad, s.n_bytes, s.n_over, phase, bol, s.eof_view ? 1 : 0, s.d_tile, s.d_nl, s.d_off, s.d_len,
+        HAST_HIP_TRY(hipSetDevice(ln.device));
+        if (s.n_over) HAST_HIP_TRY(hipStreamWaitEvent(ln.parse_stream, s.over_copied, 0));
+        HAST_HIP_TRY(launch_fq_block_striped(s.d_buf, s.d_st, f->pad, s.n_bytes, s.n_over, phase, bol, s.eof_view ? 1 : 0, s.d_tile, s.d_nl, s.d_off, s.d_len,
                                        s.d_bcpos, s.d_bclen, s.h_bc, s.d_text, (uint32_t)s.h_cap, (uint32_t)f->k, ln.parse_stream));
         s.k_cap = s.h_cap;
-        FQ_TRY(hipMemcpyAsync(s.h_st, s.d_st, sizeof(FqState), hipMemcpyDeviceToHost, ln.parse_stream));
+        HAST_HIP_TRY(hipMemcpyAsync(s.h_st, s.d_st, sizeof(FqState), hipMemcpyDeviceToHost, ln.parse_stream));
         if (f->route) {
             if (hast_status st = enqueue_route(f, s, f->route_tab[(size_t)s.lane], true, s.eof_view ? 1 : 0, f->pad + s.n_bytes + s.n_over, ln.parse_stream)) return st;
         } else if (hast_status st = enqueue_names_early(s, ln.names, ln.parse_stream)) return st;
-        FQ_TRY(hipEventRecord(s.parsed, ln.parse_stream));
+        HAST_HIP_TRY(hipEventRecord(s.parsed, ln.parse_stream));
         f->nl_before = nl_before;
         f->n_framed++;
     }
@@ -287,7 +281,7 @@ static hast_status submit_striped(hast_fq *f, size_t n_bytes, int last, bool dev
         if (hast_status st = advance_striped(f, true, i - S + 2)) return st;
     Slot &s = f->slots[i % S];
     FqLane &ln = f->lanes[(size_t)s.lane];
-    FQ_TRY(hipSetDevice(ln.device));
+    HAST_HIP_TRY(hipSetDevice(ln.device));
     s.n_bytes = n_bytes;
     s.last = last;
     s.n_over = 0;
@@ -298,15 +292,15 @@ static hast_status submit_striped(hast_fq *f, size_t n_bytes, int last, bool dev
     s.host_view = !dev_src;
     if (!dev_src) {
         s.last_byte = n_bytes ? s.h_buf[f->pad + n_bytes - 1] : (uint8_t)'\n';
-        if (n_bytes) FQ_TRY(hipMemcpyAsync(s.d_buf + f->pad, s.h_buf + f->pad, n_bytes, hipMemcpyHostToDevice, ln.copy_stream));
+        if (n_bytes) HAST_HIP_TRY(hipMemcpyAsync(s.d_buf + f->pad, s.h_buf + f->pad, n_bytes, hipMemcpyHostToDevice, ln.copy_stream));
     }
-    FQ_TRY(hipEventRecord(s.copied, ln.copy_stream));      // (a device block: behind the caller's writes, which it put on this stream)
-    FQ_TRY(hipStreamWaitEvent(ln.parse_stream, s.copied, 0));
+    HAST_HIP_TRY(hipEventRecord(s.copied, ln.copy_stream));      // (a device block: behind the caller's writes, which it put on this stream)
+    HAST_HIP_TRY(hipStreamWaitEvent(ln.parse_stream, s.copied, 0));
     // newlines of the block's own bytes, for the blocks behind it
-    FQ_TRY(launch_fq_count_own(s.d_buf, s.d_st, f->pad, n_bytes, s.d_tile, ln.parse_stream));
-    FQ_TRY(hipMemcpyAsync(s.h_cnt, s.d_st, sizeof(FqState), hipMemcpyDeviceToHost, ln.parse_stream));
-    if (dev_src && n_bytes) FQ_TRY(hipMemcpyAsync(s.h_last, s.d_buf + f->pad + n_bytes - 1, 1, hipMemcpyDeviceToHost, ln.parse_stream));
-    FQ_TRY(hipEventRecord(s.counted, ln.parse_stream));
+    HAST_HIP_TRY(launch_fq_count_own(s.d_buf, s.d_st, f->pad, n_bytes, s.d_tile, ln.parse_stream));
+    HAST_HIP_TRY(hipMemcpyAsync(s.h_cnt, s.d_st, sizeof(FqState), hipMemcpyDeviceToHost, ln.parse_stream));
+    if (dev_src && n_bytes) HAST_HIP_TRY(hipMemcpyAsync(s.h_last, s.d_buf + f->pad + n_bytes - 1, 1, hipMemcpyDeviceToHost, ln.parse_stream));
+    HAST_HIP_TRY(hipEventRecord(s.counted, ln.parse_stream));
     if (!s.first_of_file) {
         // the block in front gets the first bytes of this one behind its own: host copy (the barcode extents of its records may
         // point there) + upload on ITS GPU -- or, for blocks filled on the device, a copy from this block's GPU to that one
@@ -329,16 +323,16 @@ static hast_status submit_striped(hast_fq *f, size_t n_bytes, int last, bool dev
         pv.eof_view = last != 0 && ov == n_bytes;  // the whole rest of the file is in its view
         if (ov && !dev_src) {
             memcpy(pv.h_buf + f->pad + pv.n_bytes, s.h_buf + f->pad, ov);
-            FQ_TRY(hipSetDevice(pl.device));
-            FQ_TRY(hipMemcpyAsync(pv.d_buf + f->pad + pv.n_bytes, pv.h_buf + f->pad + pv.n_bytes, ov, hipMemcpyHostToDevice, pl.copy_stream));
-            FQ_TRY(hipEventRecord(pv.over_copied, pl.copy_stream));
+            HAST_HIP_TRY(hipSetDevice(pl.device));
+            HAST_HIP_TRY(hipMemcpyAsync(pv.d_buf + f->pad + pv.n_bytes, pv.h_buf + f->pad + pv.n_bytes, ov, hipMemcpyHostToDevice, pl.copy_stream));
+            HAST_HIP_TRY(hipEventRecord(pv.over_copied, pl.copy_stream));
         } else if (ov) {
-            FQ_TRY(hipSetDevice(pl.device));
-            FQ_TRY(hipStreamWaitEvent(pl.copy_stream, s.copied, 0));
-            if (pl.device == ln.device) FQ_TRY(hipMemcpyAsync(pv.d_buf + f->pad + pv.n_bytes, s.d_buf + f->pad, ov, hipMemcpyDeviceToDevice, pl.copy_stream));
-            else FQ_TRY(hipMemcpyPeerAsync(pv.d_buf + f->pad + pv.n_bytes, pl.device, s.d_buf + f->pad, ln.device, ov, pl.copy_stream));
-            FQ_TRY(hipEventRecord(pv.over_copied, pl.copy_stream));
-            FQ_TRY(hipEventRecord(s.over_read, pl.copy_stream));       // (this buffer's next filling waits for the copy out of it)
+            HAST_HIP_TRY(hipSetDevice(pl.device));
+            HAST_HIP_TRY(hipStreamWaitEvent(pl.copy_stream, s.copied, 0));
+            if (pl.device == ln.device) HAST_HIP_TRY(hipMemcpyAsync(pv.d_buf + f->pad + pv.n_bytes, s.d_buf + f->pad, ov, hipMemcpyDeviceToDevice, pl.copy_stream));
+            else HAST_HIP_TRY(hipMemcpyPeerAsync(pv.d_buf + f->pad + pv.n_bytes, pl.device, s.d_buf + f->pad, ln.device, ov, pl.copy_stream));
+            HAST_HIP_TRY(hipEventRecord(pv.over_copied, pl.copy_stream));
+            HAST_HIP_TRY(hipEventRecord(s.over_read, pl.copy_stream));       // (this buffer's next filling waits for the copy out of it)
             s.over_read_pending = true;
         }
         pv.over_ready = true;
@@ -353,7 +347,7 @@ extern "C" {
 hast_status hast_names_create(hast_ctx *ctx, size_t max_barcodes, hast_names **out) {
     if (!ctx || !out) return set_error(HAST_ERR_INVALID, "null argument");
     *out = nullptr;
-    FQ_TRY(hipSetDevice(hast_ctx_device(ctx)));
+    HAST_HIP_TRY(hipSetDevice(hast_ctx_device(ctx)));
     size_t slots = 64;
     while (slots < 2 * std::max<size_t>(max_barcodes, 1) && slots < (1ull << 31)) slots <<= 1;
     hast_names *nm = new (std::nothrow) hast_names();
@@ -397,9 +391,9 @@ hast_status hast_names_count(hast_names *nm, size_t *n_ids) {
     if (!nm || !n_ids) return set_error(HAST_ERR_INVALID, "null argument");
     *n_ids = 0;
     if (!nm->dict) { *n_ids = nm->count; return HAST_OK; }
-    FQ_TRY(hipSetDevice(nm->device));
+    HAST_HIP_TRY(hipSetDevice(nm->device));
     uint32_t v = 0;
-    FQ_TRY(hipMemcpy(&v, nm->d_n_ids, sizeof(v), hipMemcpyDeviceToHost));
+    HAST_HIP_TRY(hipMemcpy(&v, nm->d_n_ids, sizeof(v), hipMemcpyDeviceToHost));
     *n_ids = std::min<size_t>(v, nm->limit);
     return HAST_OK;
 }
@@ -408,8 +402,8 @@ hast_status hast_names_texts(hast_names *nm, size_t first, size_t n, uint8_t *ou
     if (!nm || (n && !out16)) return set_error(HAST_ERR_INVALID, "null argument");
     if (!nm->dict) return set_error(HAST_ERR_INVALID, "hast_names_texts: not a dictionary (hast_names_create_dict)");
     if (first + n > nm->limit) return set_error(HAST_ERR_INVALID, "hast_names_texts: ids [%zu, %zu) beyond the %zu the dictionary can hand out", first, first + n, nm->limit);
-    FQ_TRY(hipSetDevice(nm->device));
-    if (n) FQ_TRY(hipMemcpy(out16, static_cast<const uint8_t *>(nm->d_text_of_id) + 16 * first, 16 * n, hipMemcpyDeviceToHost));
+    HAST_HIP_TRY(hipSetDevice(nm->device));
+    if (n) HAST_HIP_TRY(hipMemcpy(out16, static_cast<const uint8_t *>(nm->d_text_of_id) + 16 * first, 16 * n, hipMemcpyDeviceToHost));
     return HAST_OK;
 }
 
@@ -419,9 +413,9 @@ hast_status hast_names_merge(hast_names *dst, hast_names *src, size_t first, siz
     if (!dst->dict || !src->dict) return set_error(HAST_ERR_INVALID, "hast_names_merge: both must be dictionaries (hast_names_create_dict)");
     if (first + n > src->limit) return set_error(HAST_ERR_INVALID, "hast_names_merge: ids [%zu, %zu) beyond the source's %zu", first, first + n, src->limit);
     if (!n) return HAST_OK;
-    FQ_TRY(hipSetDevice(src->device));
-    FQ_TRY(hipStreamSynchronize(ctx_stream_of(src->ctx)));                     // (its naming kernels have filed the texts)
-    FQ_TRY(hipSetDevice(dst->device));
+    HAST_HIP_TRY(hipSetDevice(src->device));
+    HAST_HIP_TRY(hipStreamSynchronize(ctx_stream_of(src->ctx)));                     // (its naming kernels have filed the texts)
+    HAST_HIP_TRY(hipSetDevice(dst->device));
     hipStream_t hs = ctx_stream_of(dst->ctx);
     uint8_t *d_text = nullptr;
     uint32_t *d_ids = nullptr, *d_unknown = nullptr;
@@ -463,11 +457,11 @@ void hast_names_destroy(hast_names *nm) {
 hast_status hast_names_insert(hast_names *nm, const uint8_t *text16, const uint32_t *ids, size_t n) {
     if (!nm || (n && (!text16 || !ids))) return set_error(HAST_ERR_INVALID, "null argument");
     if (nm->count + n > nm->limit) return set_error(HAST_ERR_INVALID, "hast_names_insert: %zu entries + %zu do not fit a table made for %zu", nm->count, n, nm->limit);
-    FQ_TRY(hipSetDevice(nm->device));
+    HAST_HIP_TRY(hipSetDevice(nm->device));
     hipStream_t hs = ctx_stream_of(nm->ctx);
     const size_t kPiece = 1u << 20;
     NamePub *h = nullptr, *d = nullptr;
-    FQ_TRY(pinned_malloc((void **)&h, std::min(n, kPiece) * sizeof(NamePub) + 64));
+    HAST_HIP_TRY(pinned_malloc((void **)&h, std::min(n, kPiece) * sizeof(NamePub) + 64));
     if (dev_malloc((void **)&d, std::min(n, kPiece) * sizeof(NamePub) + 64) != hipSuccess) {
         (void)hipHostFree(h);
         return set_error(HAST_ERR_OOM, "hast_names_insert: device allocation failed");
@@ -495,28 +489,28 @@ static hast_status alloc_slot(Slot &s, size_t buf, size_t max_rec, size_t pad, s
     // (a stream of device-side blocks pins no host copy of its blocks: ~0.7 ms per MB, 6 x 17 MB per stream -- the copy is made
     // if and when hast_fq_block_host_bytes asks for one)
     s.h_buf_bytes = buf;
-    if (!device_blocks) FQ_TRY(pinned_malloc((void **)&s.h_buf, buf, hipHostMallocDefault));
-    FQ_TRY(pinned_malloc((void **)&s.h_st, sizeof(FqState), hipHostMallocDefault));
-    FQ_TRY(pinned_malloc((void **)&s.h_nids, 64, hipHostMallocDefault));
+    if (!device_blocks) HAST_HIP_TRY(pinned_malloc((void **)&s.h_buf, buf, hipHostMallocDefault));
+    HAST_HIP_TRY(pinned_malloc((void **)&s.h_st, sizeof(FqState), hipHostMallocDefault));
+    HAST_HIP_TRY(pinned_malloc((void **)&s.h_nids, 64, hipHostMallocDefault));
     s.h_nids[0] = 0;
-    FQ_TRY(dev_malloc((void **)&s.d_buf, buf));
-    FQ_TRY(dev_malloc((void **)&s.d_st, sizeof(FqState)));
-    FQ_TRY(dev_malloc((void **)&s.d_tile, (buf / 4096 + 2) * sizeof(uint32_t)));
-    FQ_TRY(dev_malloc((void **)&s.d_nl, (buf + 16) * sizeof(uint32_t)));
-    FQ_TRY(dev_malloc((void **)&s.d_off, max_rec * sizeof(uint64_t)));
-    for (uint32_t **p : {&s.d_len, &s.d_bcpos, &s.d_bclen, &s.d_ids}) FQ_TRY(dev_malloc((void **)p, max_rec * sizeof(uint32_t)));
-    FQ_TRY(dev_malloc((void **)&s.d_votes, max_rec * 2 * sizeof(uint32_t)));
-    FQ_TRY(dev_malloc((void **)&s.d_text, max_rec * 4 * sizeof(uint32_t)));
+    HAST_HIP_TRY(dev_malloc((void **)&s.d_buf, buf));
+    HAST_HIP_TRY(dev_malloc((void **)&s.d_st, sizeof(FqState)));
+    HAST_HIP_TRY(dev_malloc((void **)&s.d_tile, nl_tiles(buf) * sizeof(uint32_t)));
+    HAST_HIP_TRY(dev_malloc((void **)&s.d_nl, nl_index_words(buf) * sizeof(uint32_t)));
+    HAST_HIP_TRY(dev_malloc((void **)&s.d_off, max_rec * sizeof(uint64_t)));
+    for (uint32_t **p : {&s.d_len, &s.d_bcpos, &s.d_bclen, &s.d_ids}) HAST_HIP_TRY(dev_malloc((void **)p, max_rec * sizeof(uint32_t)));
+    HAST_HIP_TRY(dev_malloc((void **)&s.d_votes, max_rec * 2 * sizeof(uint32_t)));
+    HAST_HIP_TRY(dev_malloc((void **)&s.d_text, max_rec * 4 * sizeof(uint32_t)));
     // records the pinned per-record arrays hold (34 B each: page pinning is ~0.7 ms per MB, six slots a stream): a record of 100-bp
     // reads is ~240 bytes, of 150-bp reads ~340; a block of shorter ones takes the copy path and grows the arrays (hast_fq_next)
     size_t cap = block / 224 + 4096;
     if (const char *e = getenv("HAST_FQ_HOST_RECORDS")) cap = (size_t)std::max(1L, atol(e));           // (tests: force the copy path)
     if (hast_status st = grow_records(s, cap)) return st;
-    for (hipEvent_t *e : {&s.named, &s.copied, &s.parsed, &s.done}) FQ_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    for (hipEvent_t *e : {&s.named, &s.copied, &s.parsed, &s.done}) HAST_HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
     if (striped) {
-        FQ_TRY(pinned_malloc((void **)&s.h_cnt, sizeof(FqState), hipHostMallocDefault));
-        FQ_TRY(pinned_malloc((void **)&s.h_last, 16, hipHostMallocDefault));
-        for (hipEvent_t *e : {&s.counted, &s.over_copied, &s.over_read}) FQ_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
+        HAST_HIP_TRY(pinned_malloc((void **)&s.h_cnt, sizeof(FqState), hipHostMallocDefault));
+        HAST_HIP_TRY(pinned_malloc((void **)&s.h_last, 16, hipHostMallocDefault));
+        for (hipEvent_t *e : {&s.counted, &s.over_copied, &s.over_read}) HAST_HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
     }
     (void)pad;
     return HAST_OK;
@@ -533,7 +527,7 @@ hast_status hast_fq_create_ex(hast_ctx *ctx, size_t block_bytes, int n_buffers, 
     if (names && names->device != hast_ctx_device(ctx)) return set_error(HAST_ERR_INVALID, "the name cache belongs to another device");
     if (block_bytes < 4096 || block_bytes > (1ull << 30)) return set_error(HAST_ERR_INVALID, "block_bytes %zu out of [4 KB, 1 GB]", block_bytes);
     if (n_buffers < 2 || n_buffers > 16) return set_error(HAST_ERR_INVALID, "n_buffers %d out of [2,16]", n_buffers);
-    FQ_TRY(hipSetDevice(hast_ctx_device(ctx)));
+    HAST_HIP_TRY(hipSetDevice(hast_ctx_device(ctx)));
     hast_fq *f = new (std::nothrow) hast_fq();
     if (!f) return set_error(HAST_ERR_OOM, "host allocation failed");
     f->ctx = ctx;
@@ -661,9 +655,9 @@ hast_status hast_fq_acquire(hast_fq *f, uint8_t **host_buf) {
     if (!f || !host_buf) return set_error(HAST_ERR_INVALID, "null argument");
     Slot &s = f->slots[f->n_acquired % f->slots.size()];
     if (s.state != Slot::FREE) return set_error(HAST_ERR_INVALID, "hast_fq_acquire: all %zu buffers are in use (commit the oldest block first)", f->slots.size());
-    FQ_TRY(hipSetDevice(dev_of(f, s)));
+    HAST_HIP_TRY(hipSetDevice(dev_of(f, s)));
     if (s.done_pending) {
-        FQ_TRY(hipEventSynchronize(s.done));
+        HAST_HIP_TRY(hipEventSynchronize(s.done));
         s.done_pending = false;
     }
     s.state = Slot::ACQUIRED;
@@ -688,9 +682,9 @@ hast_status hast_fq_device_block(hast_fq *f, uint8_t **d_block, hast_stream *fil
             return set_error(HAST_ERR_INVALID, "hast_fq_device_block: %zu blocks are in hand and not submitted; a stream of %zu buffers allows %zu", i - f->n_submitted, S, S - 1);
         Slot &s = f->slots[i % S];
         FqLane &ln = f->lanes[(size_t)s.lane];
-        FQ_TRY(hipSetDevice(ln.device));
+        HAST_HIP_TRY(hipSetDevice(ln.device));
         if (s.over_read_pending) {
-            FQ_TRY(hipStreamWaitEvent(ln.copy_stream, s.over_read, 0));
+            HAST_HIP_TRY(hipStreamWaitEvent(ln.copy_stream, s.over_read, 0));
             s.over_read_pending = false;
         }
         f->source = 2;
@@ -711,9 +705,9 @@ hast_status hast_fq_device_block(hast_fq *f, uint8_t **d_block, hast_stream *fil
                          i - f->n_submitted, f->slots.size(), f->slots.size() - 1);
     const int si = (int)(i % f->slots.size());
     Slot &s = f->slots[(size_t)si];
-    FQ_TRY(hipSetDevice(f->device));
+    HAST_HIP_TRY(hipSetDevice(f->device));
     // (as in hast_fq_submit: the successor slot's framing reads this buffer's old tail)
-    if (i >= f->slots.size()) FQ_TRY(hipStreamWaitEvent(f->copy_stream, f->slots[(size_t)(si + 1) % f->slots.size()].parsed, 0));
+    if (i >= f->slots.size()) HAST_HIP_TRY(hipStreamWaitEvent(f->copy_stream, f->slots[(size_t)(si + 1) % f->slots.size()].parsed, 0));
     f->n_device_blocks++;
     *d_block = s.d_buf + f->pad;
     *fill_stream = (hast_stream)f->copy_stream;
@@ -730,7 +724,7 @@ static hast_status submit_block(hast_fq *f, size_t n_bytes, int last, bool dev_s
     if (f->striped) return submit_striped(f, n_bytes, last, dev_src);
     const int si = (int)(f->n_submitted % f->slots.size());
     Slot &s = f->slots[(size_t)si];
-    FQ_TRY(hipSetDevice(f->device));
+    HAST_HIP_TRY(hipSetDevice(f->device));
     hipStream_t hs = f->parse_stream;
     s.n_bytes = n_bytes;
     s.last = last;
@@ -739,20 +733,20 @@ static hast_status submit_block(hast_fq *f, size_t n_bytes, int last, bool dev_s
     // this slot's device buffer held block i - n_buffers, whose unfinished tail the NEXT block's k_fq_begin reads on the parse
     // stream: the upload that overwrites it waits for that kernel (the successor slot's `parsed` event, recorded behind it)
     if (!dev_src) {
-        if (f->n_submitted >= f->slots.size()) FQ_TRY(hipStreamWaitEvent(f->copy_stream, f->slots[(size_t)(si + 1) % f->slots.size()].parsed, 0));
-        if (n_bytes) FQ_TRY(hipMemcpyAsync(s.d_buf + f->pad, s.h_buf + f->pad, n_bytes, hipMemcpyHostToDevice, f->copy_stream));
+        if (f->n_submitted >= f->slots.size()) HAST_HIP_TRY(hipStreamWaitEvent(f->copy_stream, f->slots[(size_t)(si + 1) % f->slots.size()].parsed, 0));
+        if (n_bytes) HAST_HIP_TRY(hipMemcpyAsync(s.d_buf + f->pad, s.h_buf + f->pad, n_bytes, hipMemcpyHostToDevice, f->copy_stream));
     }
-    FQ_TRY(hipEventRecord(s.copied, f->copy_stream));
-    FQ_TRY(hipStreamWaitEvent(hs, s.copied, 0));
+    HAST_HIP_TRY(hipEventRecord(s.copied, f->copy_stream));
+    HAST_HIP_TRY(hipStreamWaitEvent(hs, s.copied, 0));
     const Slot *prev = f->prev_submitted >= 0 ? &f->slots[(size_t)f->prev_submitted] : nullptr;
-    FQ_TRY(launch_fq_block(s.d_buf, s.d_st, prev ? prev->d_buf : nullptr, prev ? prev->d_st : nullptr, f->pad, n_bytes, s.d_tile, s.d_nl, s.d_off,
+    HAST_HIP_TRY(launch_fq_block(s.d_buf, s.d_st, prev ? prev->d_buf : nullptr, prev ? prev->d_st : nullptr, f->pad, n_bytes, s.d_tile, s.d_nl, s.d_off,
                            s.d_len, s.d_bcpos, s.d_bclen, s.h_bc, s.d_text, (uint32_t)s.h_cap, (uint32_t)f->k, last, hs));
     s.k_cap = s.h_cap;
-    FQ_TRY(hipMemcpyAsync(s.h_st, s.d_st, sizeof(FqState), hipMemcpyDeviceToHost, hs));
+    HAST_HIP_TRY(hipMemcpyAsync(s.h_st, s.d_st, sizeof(FqState), hipMemcpyDeviceToHost, hs));
     if (f->route) {
         if (hast_status st = enqueue_route(f, s, f->route_tab[0], false, last, f->pad + n_bytes, hs)) return st;
     } else if (hast_status st = enqueue_names_early(s, f->names, hs)) return st;
-    FQ_TRY(hipEventRecord(s.parsed, hs));
+    HAST_HIP_TRY(hipEventRecord(s.parsed, hs));
     s.state = Slot::SUBMITTED;
     f->n_submitted++;
     f->prev_submitted = last ? -1 : si;                       // the next block starts a new file after `last`
@@ -771,11 +765,11 @@ hast_status hast_fq_block_host_bytes(hast_fq *f, const uint8_t **bytes) {
     Slot &s = f->slots[(f->n_opened - 1) % f->slots.size()];
     if (s.state != Slot::OPEN) return set_error(HAST_ERR_INVALID, "no open block");
     if (!s.host_view) {
-        FQ_TRY(hipSetDevice(dev_of(f, s)));
-        if (!s.h_buf) FQ_TRY(pinned_malloc((void **)&s.h_buf, s.h_buf_bytes, hipHostMallocDefault));
+        HAST_HIP_TRY(hipSetDevice(dev_of(f, s)));
+        if (!s.h_buf) HAST_HIP_TRY(pinned_malloc((void **)&s.h_buf, s.h_buf_bytes, hipHostMallocDefault));
         hipStream_t hs = ctx_stream_of(ctx_of(f, s));
-        FQ_TRY(hipMemcpyAsync(s.h_buf, s.d_buf, f->pad + s.n_bytes + s.n_over, hipMemcpyDeviceToHost, hs));
-        FQ_TRY(hipStreamSynchronize(hs));
+        HAST_HIP_TRY(hipMemcpyAsync(s.h_buf, s.d_buf, f->pad + s.n_bytes + s.n_over, hipMemcpyDeviceToHost, hs));
+        HAST_HIP_TRY(hipStreamSynchronize(hs));
         s.host_view = true;
     }
     *bytes = s.h_buf;
@@ -809,9 +803,9 @@ hast_status hast_fq_next(hast_fq *f, hast_fq_block *out) {
     }
     hast_ctx *const sctx = ctx_of(f, s);
     hast_names *const snames = names_of(f, s);
-    FQ_TRY(hipSetDevice(dev_of(f, s)));
+    HAST_HIP_TRY(hipSetDevice(dev_of(f, s)));
     hipStream_t hs = ctx_stream_of(sctx);
-    FQ_TRY(hipEventSynchronize(s.parsed));
+    HAST_HIP_TRY(hipEventSynchronize(s.parsed));
     const FqState st = *s.h_st;
     if (st.flags & 2) return set_error(HAST_ERR_FORMAT, "a FASTQ record is larger than %zu bytes", f->striped ? f->over_cap : f->pad);
     if (st.n_rec > f->max_rec) return set_error(HAST_ERR_INVALID, "record table overflow");
@@ -820,9 +814,9 @@ hast_status hast_fq_next(hast_fq *f, hast_fq_block *out) {
     if (by_copy) {
         // every per-record array grows together (the slot's next block hands the new h_cap to the records kernel)
         if (hast_status g = grow_records(s, n + n / 4 + 1024)) return g;
-        FQ_TRY(hipMemcpyAsync(s.h_bc, s.d_bcpos, n * sizeof(uint32_t), hipMemcpyDeviceToHost, hs));
-        FQ_TRY(hipMemcpyAsync(s.h_bc + s.h_cap, s.d_bclen, n * sizeof(uint32_t), hipMemcpyDeviceToHost, hs));
-        FQ_TRY(hipEventRecord(s.parsed, hs));
+        HAST_HIP_TRY(hipMemcpyAsync(s.h_bc, s.d_bcpos, n * sizeof(uint32_t), hipMemcpyDeviceToHost, hs));
+        HAST_HIP_TRY(hipMemcpyAsync(s.h_bc + s.h_cap, s.d_bclen, n * sizeof(uint32_t), hipMemcpyDeviceToHost, hs));
+        HAST_HIP_TRY(hipEventRecord(s.parsed, hs));
     }
     // ids from the device-side name cache (after a few blocks nearly every barcode of a block has been seen before)
     s.host_texts = !by_copy;
@@ -833,17 +827,17 @@ hast_status hast_fq_next(hast_fq *f, hast_fq_block *out) {
     } else if (s.use_cache) {
         s.h_unknown[0] = 0;
         if (snames->dict) {
-            FQ_TRY(launch_fq_name_claim(s.d_text, (uint32_t)n, snames->d_tab, snames->mask, snames->d_n_ids, (uint32_t)snames->limit, snames->d_text_of_id, s.h_ids,
+            HAST_HIP_TRY(launch_fq_name_claim(s.d_text, (uint32_t)n, snames->d_tab, snames->mask, snames->d_n_ids, (uint32_t)snames->limit, snames->d_text_of_id, s.h_ids,
                                         s.h_unknown, s.d_ids, hs));
-            FQ_TRY(hipMemcpyAsync(s.h_nids, snames->d_n_ids, sizeof(uint32_t), hipMemcpyDeviceToHost, hs));
-        } else FQ_TRY(launch_fq_name(s.d_text, (uint32_t)n, snames->d_tab, snames->mask, s.h_ids, s.h_unknown, hs));
-        FQ_TRY(hipEventRecord(s.named, hs));
+            HAST_HIP_TRY(hipMemcpyAsync(s.h_nids, snames->d_n_ids, sizeof(uint32_t), hipMemcpyDeviceToHost, hs));
+        } else HAST_HIP_TRY(launch_fq_name(s.d_text, (uint32_t)n, snames->d_tab, snames->mask, s.h_ids, s.h_unknown, hs));
+        HAST_HIP_TRY(hipEventRecord(s.named, hs));
     }
     // the reads are classified where they lie in the raw block WHILE the host names the barcodes
     if (n && !(st.flags & 1))
         if (hast_status c = classify_framed(sctx, s.d_buf, f->pad + s.n_bytes + s.n_over, s.d_off, s.d_len, st.max_len, s.d_votes, n, hs)) return c;
-    if (by_copy) FQ_TRY(hipEventSynchronize(s.parsed));        // (the event sits in front of the kernels)
-    if (s.use_cache) FQ_TRY(hipEventSynchronize(s.named));
+    if (by_copy) HAST_HIP_TRY(hipEventSynchronize(s.parsed));        // (the event sits in front of the kernels)
+    if (s.use_cache) HAST_HIP_TRY(hipEventSynchronize(s.named));
     if (f->striped) {
         // (the host view already holds the first bytes of the next block behind this block's own: submit_striped put them there)
         f->records_per_lane[(size_t)s.lane] += n;
@@ -893,16 +887,16 @@ hast_status hast_fq_set_route(hast_fq *f, hast_names *const *tables, int n_table
             return set_error(HAST_ERR_INVALID, "hast_fq_set_route: table %d is missing or lives on another device", i);
     for (Slot &s : f->slots) {
         if (s.d_out) continue;
-        FQ_TRY(hipSetDevice(dev_of(f, s)));
+        HAST_HIP_TRY(hipSetDevice(dev_of(f, s)));
         s.route_rec = f->max_rec;
-        FQ_TRY(dev_malloc(&s.d_rstart, s.route_rec * sizeof(uint32_t)));
-        FQ_TRY(dev_malloc(&s.d_rlen, s.route_rec * sizeof(uint32_t)));
-        FQ_TRY(dev_malloc(&s.d_rcls, s.route_rec));
-        FQ_TRY(dev_malloc(&s.d_rtile, (s.route_rec / kRouteTile + 2) * 8 * sizeof(uint32_t)));
-        FQ_TRY(dev_malloc(&s.d_rs, sizeof(RouteState)));
-        FQ_TRY(dev_malloc(&s.d_out, s.h_buf_bytes));
-        FQ_TRY(pinned_malloc(&s.h_out, s.h_buf_bytes));
-        FQ_TRY(pinned_malloc(&s.h_rs, sizeof(RouteState)));
+        HAST_HIP_TRY(dev_malloc(&s.d_rstart, s.route_rec * sizeof(uint32_t)));
+        HAST_HIP_TRY(dev_malloc(&s.d_rlen, s.route_rec * sizeof(uint32_t)));
+        HAST_HIP_TRY(dev_malloc(&s.d_rcls, s.route_rec));
+        HAST_HIP_TRY(dev_malloc(&s.d_rtile, (s.route_rec / kRouteTile + 2) * 8 * sizeof(uint32_t)));
+        HAST_HIP_TRY(dev_malloc(&s.d_rs, sizeof(RouteState)));
+        HAST_HIP_TRY(dev_malloc(&s.d_out, s.h_buf_bytes));
+        HAST_HIP_TRY(pinned_malloc(&s.h_out, s.h_buf_bytes));
+        HAST_HIP_TRY(pinned_malloc(&s.h_rs, sizeof(RouteState)));
     }
     f->route_tab.assign(tables, tables + lanes);
     f->route = true;
@@ -925,17 +919,17 @@ hast_status hast_fq_set_route_gz(hast_fq *f, int on) {
     if (on)
         for (Slot &s : f->slots) {
             if (s.d_gz) continue;
-            FQ_TRY(hipSetDevice(dev_of(f, s)));
+            HAST_HIP_TRY(hipSetDevice(dev_of(f, s)));
             s.dz_pieces = dz::max_pieces(s.h_buf_bytes);
             s.gz_cap = (size_t)dz::max_out_bytes(s.h_buf_bytes);
             const size_t work = (dz::workspace_bytes(s.dz_pieces) + 63) & ~(size_t)63;
             s.dzwork_bytes = work + sizeof(dz::Job) + sizeof(dz::Result);
-            FQ_TRY(dev_malloc(&s.d_gz, s.gz_cap));
-            FQ_TRY(dev_malloc(&s.d_dzwork, s.dzwork_bytes));
+            HAST_HIP_TRY(dev_malloc(&s.d_gz, s.gz_cap));
+            HAST_HIP_TRY(dev_malloc(&s.d_dzwork, s.dzwork_bytes));
             s.d_dzjob = reinterpret_cast<dz::Job *>(static_cast<uint8_t *>(s.d_dzwork) + work);
             s.d_dzres = reinterpret_cast<dz::Result *>(s.d_dzjob + 1);
-            FQ_TRY(pinned_malloc(&s.h_gz, s.gz_cap));
-            FQ_TRY(pinned_malloc(&s.h_dzres, sizeof(dz::Result)));
+            HAST_HIP_TRY(pinned_malloc(&s.h_gz, s.gz_cap));
+            HAST_HIP_TRY(pinned_malloc(&s.h_dzres, sizeof(dz::Result)));
         }
     else
         for (Slot &s : f->slots) {                          // switched off: the members' buffers and the workspace go back (parked, as a closed stream's)
@@ -977,8 +971,8 @@ hast_status hast_fq_next_routed(hast_fq *f, hast_fq_routed *out) {
         if (f->n_framed <= f->n_opened)
             return set_error(HAST_ERR_INVALID, "hast_fq_next_routed: a block of a striped stream is framed once the block behind it has been submitted (or it ends the file)");
     }
-    FQ_TRY(hipSetDevice(dev_of(f, s)));
-    FQ_TRY(hipEventSynchronize(s.parsed));
+    HAST_HIP_TRY(hipSetDevice(dev_of(f, s)));
+    HAST_HIP_TRY(hipEventSynchronize(s.parsed));
     const FqState st = *s.h_st;
     const RouteState rs = *s.h_rs;
     if ((st.flags & 2) || (rs.flags & 2)) return set_error(HAST_ERR_FORMAT, "a FASTQ record is larger than %zu bytes", f->striped ? f->over_cap : f->pad);
@@ -1010,25 +1004,25 @@ hast_status hast_fq_next_routed(hast_fq *f, hast_fq_routed *out) {
                 total += zr.out_bytes[c];
             }
             if (total) {
-                FQ_TRY(hipMemcpyAsync(s.h_gz, s.d_gz, total, hipMemcpyDeviceToHost, hs));
-                FQ_TRY(hipStreamSynchronize(hs));
+                HAST_HIP_TRY(hipMemcpyAsync(s.h_gz, s.d_gz, total, hipMemcpyDeviceToHost, hs));
+                HAST_HIP_TRY(hipStreamSynchronize(hs));
             }
         }
     }
     if (rs.flags & 1) {
         // a record the device could not route: the caller gets the view and every record's extent + class and routes the block itself
-        if (!s.h_buf) FQ_TRY(pinned_malloc(&s.h_buf, s.h_buf_bytes));
+        if (!s.h_buf) HAST_HIP_TRY(pinned_malloc(&s.h_buf, s.h_buf_bytes));
         const size_t view = std::min<size_t>(st.parse_hi, s.h_buf_bytes);
         s.v_rstart.resize(rs.n_cand);
         s.v_rlen.resize(rs.n_cand);
         s.v_rcls.resize(rs.n_cand);
-        FQ_TRY(hipMemcpyAsync(s.h_buf, s.d_buf, view, hipMemcpyDeviceToHost, hs));
+        HAST_HIP_TRY(hipMemcpyAsync(s.h_buf, s.d_buf, view, hipMemcpyDeviceToHost, hs));
         if (rs.n_cand) {
-            FQ_TRY(hipMemcpyAsync(s.v_rstart.data(), s.d_rstart, rs.n_cand * sizeof(uint32_t), hipMemcpyDeviceToHost, hs));
-            FQ_TRY(hipMemcpyAsync(s.v_rlen.data(), s.d_rlen, rs.n_cand * sizeof(uint32_t), hipMemcpyDeviceToHost, hs));
-            FQ_TRY(hipMemcpyAsync(s.v_rcls.data(), s.d_rcls, rs.n_cand, hipMemcpyDeviceToHost, hs));
+            HAST_HIP_TRY(hipMemcpyAsync(s.v_rstart.data(), s.d_rstart, rs.n_cand * sizeof(uint32_t), hipMemcpyDeviceToHost, hs));
+            HAST_HIP_TRY(hipMemcpyAsync(s.v_rlen.data(), s.d_rlen, rs.n_cand * sizeof(uint32_t), hipMemcpyDeviceToHost, hs));
+            HAST_HIP_TRY(hipMemcpyAsync(s.v_rcls.data(), s.d_rcls, rs.n_cand, hipMemcpyDeviceToHost, hs));
         }
-        FQ_TRY(hipStreamSynchronize(hs));
+        HAST_HIP_TRY(hipStreamSynchronize(hs));
         s.host_view = true;
         out->host_block = 1;
         out->bytes = s.h_buf;
@@ -1039,8 +1033,8 @@ hast_status hast_fq_next_routed(hast_fq *f, hast_fq_routed *out) {
     }
     if (rs.tail_hi > rs.tail_lo) {                         // the partial record at the end of the file: the caller's, by awk's rules
         s.v_tail.resize(rs.tail_hi - rs.tail_lo);
-        FQ_TRY(hipMemcpyAsync(s.v_tail.data(), s.d_buf + rs.tail_lo, s.v_tail.size(), hipMemcpyDeviceToHost, hs));
-        FQ_TRY(hipStreamSynchronize(hs));
+        HAST_HIP_TRY(hipMemcpyAsync(s.v_tail.data(), s.d_buf + rs.tail_lo, s.v_tail.size(), hipMemcpyDeviceToHost, hs));
+        HAST_HIP_TRY(hipStreamSynchronize(hs));
         out->tail = s.v_tail.data();
         out->tail_bytes = s.v_tail.size();
     }
@@ -1056,7 +1050,7 @@ hast_status hast_fq_commit(hast_fq *f) {
     Slot &s = f->slots[(f->n_opened - 1) % f->slots.size()];
     if (s.state != Slot::OPEN) return set_error(HAST_ERR_INVALID, "hast_fq_commit: no open block");
     hast_ctx *const sctx = ctx_of(f, s);
-    FQ_TRY(hipSetDevice(dev_of(f, s)));
+    HAST_HIP_TRY(hipSetDevice(dev_of(f, s)));
     hipStream_t hs = ctx_stream_of(sctx);
     const size_t n = s.h_st->n_rec;
     if (f->route) {                                        // a routed block: the caller is through with its runs, nothing to book
@@ -1088,7 +1082,7 @@ hast_status hast_fq_commit(hast_fq *f) {
                 p.id = s.h_ids[i];
             }
             if (np) {
-                FQ_TRY(launch_names_insert(s.h_pubs, np, nm->d_tab, nm->mask, hs));
+                HAST_HIP_TRY(launch_names_insert(s.h_pubs, np, nm->d_tab, nm->mask, hs));
                 nm->count += np;                               // (an upper bound: a barcode met twice in one block is counted twice)
             }
             // (a block the dictionary named completely: its ids lie in device memory as well -- the bookkeeping kernel reads them there)
@@ -1098,11 +1092,11 @@ hast_status hast_fq_commit(hast_fq *f) {
         } else {
             for (size_t i = 0; i < n; ++i)
                 if (s.h_ids[i] >= nbc) return set_error(HAST_ERR_INVALID, "barcode id %u of record %zu is outside the %zu counters", s.h_ids[i], i, nbc);
-            FQ_TRY(hipMemcpyAsync(s.d_ids, s.h_ids, n * sizeof(uint32_t), hipMemcpyHostToDevice, hs));
+            HAST_HIP_TRY(hipMemcpyAsync(s.d_ids, s.h_ids, n * sizeof(uint32_t), hipMemcpyHostToDevice, hs));
             if (hast_status c = commit_framed(sctx, s.d_votes, s.d_ids, n, hs)) return c;
         }
     }
-    FQ_TRY(hipEventRecord(s.done, hs));
+    HAST_HIP_TRY(hipEventRecord(s.done, hs));
     s.done_pending = true;
     s.state = Slot::FREE;
     return HAST_OK;

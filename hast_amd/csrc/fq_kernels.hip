@@ -15,89 +15,43 @@
 #include <stdint.h>
 
 #include "fq_device.h"
+#include "nl_index.h"
 
 namespace hast {
 
-constexpr int kFqTile = 4096;                    // bytes per tile = 256 lanes x 16 B
-
-__device__ __forceinline__ uint32_t nl_mask16(const uint8_t *p, const uint8_t *lo, const uint8_t *hi) {
-    // bit i set <=> p[i] == '\n', for the 16 bytes at p (16-B aligned); bytes outside [lo, hi) never count
-    uint32_t m = 0;
-    if (p + 16 <= lo || p >= hi) return 0;
-    const uint4 v = *reinterpret_cast<const uint4 *>(p);
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const uint32_t y = w[i] ^ 0x0A0A0A0Au;
-        const uint32_t z = ~(((y & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | y) & 0x80808080u;     // 0x80 in every zero byte, exact
-        m |= (((z >> 7) * 0x00204081u) >> 21 & 0xFu) << (4 * i);                          // bits 0,8,16,24 -> 4 adjacent bits
-    }
-    if (p < lo) m &= 0xFFFFu << (uint32_t)(lo - p);
-    if (p + 16 > hi) m &= 0xFFFFu >> (uint32_t)(p + 16 - hi);
-    return m & 0xFFFFu;
-}
-
-// tiles are 4-KB aligned pieces of the buffer; `lo`/`hi` bound the bytes that belong to this parse
+// tiles are 4-KB aligned pieces of the buffer (a device allocation: 16-byte aligned); parse_lo / parse_hi bound the bytes that belong
+// to this parse.  The index itself is nl_index.h's, shared with stage 00's framer (sq_kernels.hip).
 __global__ void __launch_bounds__(256) k_fq_count(const uint8_t *buf, const FqState *st, uint32_t *tile_cnt) {
     const uint64_t lo = st->parse_lo, hi = st->parse_hi;
     const uint64_t tile = blockIdx.x;                                                      // tiles cover the buffer from byte 0
-    if (tile * kFqTile >= hi || (tile + 1) * kFqTile <= lo) { if (threadIdx.x == 0) tile_cnt[blockIdx.x] = 0; return; }
-    const uint8_t *p = buf + tile * kFqTile + threadIdx.x * 16;
-    uint32_t c = __popc(nl_mask16(p, buf + lo, buf + hi));
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
-    __shared__ uint32_t s[4];
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = s[0] + s[1] + s[2] + s[3];
+    if (tile * kNlTile >= hi || (tile + 1) * kNlTile <= lo) { if (threadIdx.x == 0) tile_cnt[tile] = 0; return; }
+    const uint32_t c = nl_tile_count(buf, tile, lo, hi);
+    if (threadIdx.x == 0) tile_cnt[tile] = c;
 }
 
 // exclusive scan of n tile counts in place (n <= a few 10^4), total -> st->n_nl; one workgroup of 1024
 __global__ void __launch_bounds__(1024) k_fq_scan(uint32_t *tile_cnt, uint32_t n, FqState *st) {
     __shared__ uint32_t s_part[1024];
-    const uint32_t per = (n + 1023) / 1024, lo = threadIdx.x * per, hi = lo + per < n ? lo + per : n;
-    uint32_t sum = 0;
-    for (uint32_t i = lo; i < hi; ++i) sum += tile_cnt[i];
-    s_part[threadIdx.x] = sum;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024; d <<= 1) {                 // Hillis-Steele inclusive scan
-        const uint32_t v = threadIdx.x >= d ? s_part[threadIdx.x - d] : 0;
-        __syncthreads();
-        s_part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    uint32_t run = threadIdx.x ? s_part[threadIdx.x - 1] : 0;
-    for (uint32_t i = lo; i < hi; ++i) {
-        const uint32_t c = tile_cnt[i];
-        tile_cnt[i] = run;
-        run += c;
-    }
-    if (threadIdx.x == 1023) st->n_nl = s_part[1023];
+    const uint32_t n_nl = block_exclusive_scan_1024(tile_cnt, n, s_part);
+    if (threadIdx.x == 1023) st->n_nl = n_nl;
 }
 
+// nl[j] = offset of the j-th newline of the parse range from the buffer's first byte
 __global__ void __launch_bounds__(256) k_fq_index(const uint8_t *buf, const FqState *st, const uint32_t *tile_base, uint32_t *nl) {
     const uint64_t lo = st->parse_lo, hi = st->parse_hi;
     const uint64_t tile = blockIdx.x;
-    if (tile * kFqTile >= hi || (tile + 1) * kFqTile <= lo) return;
-    const uint64_t at = tile * kFqTile + threadIdx.x * 16;
-    uint32_t m = nl_mask16(buf + at, buf + lo, buf + hi);
-    const uint32_t c = __popc(m);
-    // exclusive prefix of c over the workgroup
-    uint32_t incl = c;
-    const uint32_t lane = threadIdx.x & 63;
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t v = __shfl_up(incl, off, 64);
-        if (lane >= (uint32_t)off) incl += v;
-    }
-    __shared__ uint32_t s[4];
-    if (lane == 63) s[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    uint32_t base = tile_base[blockIdx.x] + incl - c;
-    for (uint32_t w = 0; w < (threadIdx.x >> 6); ++w) base += s[w];
-    while (m) {
-        const uint32_t b = __ffs(m) - 1;
-        nl[base++] = (uint32_t)(at + b);
-        m &= m - 1;
-    }
+    if (tile * kNlTile >= hi || (tile + 1) * kNlTile <= lo) return;
+    nl_tile_index(buf, tile, lo, hi, 0, tile_base, nl);
+}
+
+// the barcode text [start, start + bl) as a text record: length byte + up to 15 bytes; 0xFF: longer, take it from the block
+__device__ __forceinline__ uint4 fq_text_record(const uint8_t *buf, uint64_t start, uint32_t bl) {
+    uint32_t w[4] = {0, 0, 0, 0};
+    if (bl <= 15) {
+        w[0] = bl;
+        for (uint32_t j = 0; j < bl; ++j) w[(j + 1) >> 2] |= (uint32_t)buf[start + j] << (8 * ((j + 1) & 3));
+    } else w[0] = 0xFF;
+    return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
 // record i of a block: header line [h0, h1), bases [h1 + 1, s1)
@@ -118,28 +72,16 @@ __device__ __forceinline__ void fq_emit_record(const uint8_t *buf, FqState *st, 
     const int64_t stop = (e > s && e >= 0) ? e : (int64_t)h1;
     bc_pos[i] = (uint32_t)start;
     bc_len[i] = (uint32_t)(stop - start);
+    const uint4 text = fq_text_record(buf, (uint64_t)start, (uint32_t)(stop - start));
     if (i < h_cap) {
         h_bc[i] = (uint32_t)start;
         h_bc[h_cap + i] = (uint32_t)(stop - start);
-        const uint32_t bl = (uint32_t)(stop - start);
-        uint32_t w[4] = {0, 0, 0, 0};
-        if (bl <= 15) {
-            w[0] = bl;
-            for (uint32_t j = 0; j < bl; ++j) w[(j + 1) >> 2] |= (uint32_t)buf[start + j] << (8 * ((j + 1) & 3));
-        } else w[0] = 0xFF;
-        reinterpret_cast<uint4 *>(h_bc + 2 * (size_t)h_cap)[i] = make_uint4(w[0], w[1], w[2], w[3]);
+        reinterpret_cast<uint4 *>(h_bc + 2 * (size_t)h_cap)[i] = text;
     }
-    {   // the same text record for the naming kernel, for EVERY record of the block (d_text holds the whole record table): the dictionary
-        // must see a barcode whichever block it comes in -- one named by the host in a block with more records than the pinned arrays
-        // hold and by the device in the next block would have two ids
-        const uint32_t bl = (uint32_t)(stop - start);
-        uint32_t w[4] = {0, 0, 0, 0};
-        if (bl <= 15) {
-            w[0] = bl;
-            for (uint32_t j = 0; j < bl; ++j) w[(j + 1) >> 2] |= (uint32_t)buf[start + j] << (8 * ((j + 1) & 3));
-        } else w[0] = 0xFF;
-        reinterpret_cast<uint4 *>(d_text)[i] = make_uint4(w[0], w[1], w[2], w[3]);
-    }
+    // the same text record for the naming kernel, for EVERY record of the block (d_text holds the whole record table): the dictionary
+    // must see a barcode whichever block it comes in -- one named by the host in a block with more records than the pinned arrays
+    // hold and by the device in the next block would have two ids
+    reinterpret_cast<uint4 *>(d_text)[i] = text;
     atomicMax(&st->max_len, len);
     atomicAdd(reinterpret_cast<unsigned long long *>(&st->bases), (unsigned long long)len);
     if (len < k) {                                            // the reference aborts on such a read unless it holds 'N' (kmer.h:171)
@@ -378,8 +320,8 @@ __global__ void __launch_bounds__(kRouteTile) k_route_class(const uint8_t *buf, 
                     const uint32_t fl = (uint32_t)(b - a - 1);
                     if (fl > 15) cls = kRouteHost;
                     else {
-                        uint32_t w[4] = {fl, 0, 0, 0};
-                        for (uint32_t q = 0; q < fl; ++q) w[(q + 1) >> 2] |= (uint32_t)buf[a + 1 + q] << (8 * ((q + 1) & 3));
+                        const uint4 t = fq_text_record(buf, a + 1, fl);
+                        const uint32_t w[4] = {t.x, t.y, t.z, t.w};
                         if (w[0] == 0x305F3005u && w[1] == 0x0000305Fu) cls = 0;       // "0_0_0" (:22): length 5, then the text
                         else {
                             cls = kRouteUnclassified;
@@ -460,13 +402,8 @@ __global__ void __launch_bounds__(kRouteTile) k_route_copy(const uint8_t *buf, c
         const uint32_t len = (c < n_cand && cls < 4) ? r_len[c] : 0;
         uint32_t incl[4];
         for (int k = 0; k < 4; ++k) {
-            uint32_t v = cls == k ? len : 0;
-            for (int off = 1; off < 64; off <<= 1) {
-                const uint32_t u = __shfl_up(v, off, 64);
-                if (lane >= (uint32_t)off) v += u;
-            }
-            incl[k] = v;
-            if (lane == 63) s_wave[wave][k] = v;
+            incl[k] = wave_inclusive_sum(cls == k ? len : 0, lane);
+            if (lane == 63) s_wave[wave][k] = incl[k];
         }
         __syncthreads();
         uint32_t dst = 0;
@@ -619,7 +556,7 @@ hipError_t launch_fq_block(uint8_t *d_buf, FqState *d_st, const uint8_t *d_prev_
     hipError_t e = hipMemsetAsync(d_st, 0, sizeof(FqState), s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_fq_begin, dim3(1), dim3(256), 0, s, d_buf, d_st, d_prev_buf, d_prev_st, pad, n_bytes);
-    const uint32_t n_tiles = (uint32_t)((pad + n_bytes + kFqTile - 1) / kFqTile);
+    const uint32_t n_tiles = (uint32_t)((pad + n_bytes + kNlTile - 1) / kNlTile);
     hipLaunchKernelGGL(k_fq_count, dim3(n_tiles), dim3(256), 0, s, d_buf, d_st, d_tile_cnt);
     hipLaunchKernelGGL(k_fq_scan, dim3(1), dim3(1024), 0, s, d_tile_cnt, n_tiles, d_st);
     hipLaunchKernelGGL(k_fq_index, dim3(n_tiles), dim3(256), 0, s, d_buf, d_st, d_tile_cnt, d_nl);
@@ -631,7 +568,7 @@ hipError_t launch_fq_count_own(const uint8_t *d_buf, FqState *d_st, uint64_t pad
     hipError_t e = hipMemsetAsync(d_st, 0, sizeof(FqState), s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_fq_view, dim3(1), dim3(1), 0, s, d_st, pad, pad + n_bytes, pad + n_bytes, 0u, 0u, 0u);
-    const uint32_t n_tiles = (uint32_t)((pad + n_bytes + kFqTile - 1) / kFqTile);
+    const uint32_t n_tiles = (uint32_t)((pad + n_bytes + kNlTile - 1) / kNlTile);
     hipLaunchKernelGGL(k_fq_count, dim3(n_tiles), dim3(256), 0, s, d_buf, d_st, d_tile_cnt);
     hipLaunchKernelGGL(k_fq_scan, dim3(1), dim3(1024), 0, s, d_tile_cnt, n_tiles, d_st);
     return hipGetLastError();
@@ -643,7 +580,7 @@ hipError_t launch_fq_block_striped(const uint8_t *d_buf, FqState *d_st, uint64_t
     hipError_t e = hipMemsetAsync(d_st, 0, sizeof(FqState), s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_fq_view, dim3(1), dim3(1), 0, s, d_st, pad, pad + n_bytes + n_over, pad + n_bytes, phase, bol ? 1u : 0u, eof ? 1u : 0u);
-    const uint32_t n_tiles = (uint32_t)((pad + n_bytes + n_over + kFqTile - 1) / kFqTile);
+    const uint32_t n_tiles = (uint32_t)((pad + n_bytes + n_over + kNlTile - 1) / kNlTile);
     hipLaunchKernelGGL(k_fq_count, dim3(n_tiles), dim3(256), 0, s, d_buf, d_st, d_tile_cnt);
     hipLaunchKernelGGL(k_fq_scan, dim3(1), dim3(1024), 0, s, d_tile_cnt, n_tiles, d_st);
     hipLaunchKernelGGL(k_fq_index, dim3(n_tiles), dim3(256), 0, s, d_buf, d_st, d_tile_cnt, d_nl);

@@ -35,22 +35,6 @@ namespace {
 
 thread_local char g_err[512] = "";
 
-hast_status fail(hast_status st, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return st;
-}
-
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return fail(e_ == hipErrorOutOfMemory ? HAST_ERR_OOM : HAST_ERR_HIP, "%s: %s", #expr, \
-                        hipGetErrorString(e_));                                                \
-    } while (0)
-
 struct Staging {          // one pinned+device buffer set of hast_classify_batch's double buffer
     uint8_t *h_bases = nullptr, *d_bases = nullptr;
     uint64_t *h_off = nullptr, *d_off = nullptr;
@@ -142,17 +126,17 @@ int default_minimizer(int k) {
 }
 
 hast_status use(hast_ctx *c) {
-    if (!c) return fail(HAST_ERR_INVALID, "null context");
-    HIP_TRY(hipSetDevice(c->device));
+    if (!c) return set_error(HAST_ERR_INVALID, "null context");
+    HAST_HIP_TRY(hipSetDevice(c->device));
     return HAST_OK;
 }
 
 hast_status ensure_scratch(hast_ctx *c, size_t bytes) {
     if (c->scratch_bytes >= bytes) return HAST_OK;
-    if (c->d_scratch) HIP_TRY(hipFree(c->d_scratch));
+    if (c->d_scratch) HAST_HIP_TRY(hipFree(c->d_scratch));
     c->d_scratch = nullptr;
     c->scratch_bytes = 0;
-    HIP_TRY(dev_malloc(&c->d_scratch, bytes));
+    HAST_HIP_TRY(dev_malloc(&c->d_scratch, bytes));
     c->scratch_bytes = bytes;
     return HAST_OK;
 }
@@ -161,12 +145,12 @@ constexpr size_t kChunkBytes = 64u << 20;   // staging granule for table input
 
 hast_status check_err_word(hast_ctx *c, hipStream_t s) {
     uint32_t e = 0;
-    HIP_TRY(hipMemcpyAsync(&e, c->d_err, sizeof(e), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (e) HIP_TRY(hipMemsetAsync(c->d_err, 0, sizeof(uint32_t), s));
-    if (e & 2) return fail(HAST_ERR_FORMAT, "k-mer text: a line is not exactly K=%d bytes", c->k);
-    if (e & 4) return fail(HAST_ERR_FORMAT, "k-mer text: a byte other than upper-case A/C/G/T");
-    if (e & 1) return fail(HAST_ERR_TABLE_FULL, "k-mer table full: reserve more keys");
+    HAST_HIP_TRY(hipMemcpyAsync(&e, c->d_err, sizeof(e), hipMemcpyDeviceToHost, s));
+    HAST_HIP_TRY(hipStreamSynchronize(s));
+    if (e) HAST_HIP_TRY(hipMemsetAsync(c->d_err, 0, sizeof(uint32_t), s));
+    if (e & 2) return set_error(HAST_ERR_FORMAT, "k-mer text: a line is not exactly K=%d bytes", c->k);
+    if (e & 4) return set_error(HAST_ERR_FORMAT, "k-mer text: a byte other than upper-case A/C/G/T");
+    if (e & 1) return set_error(HAST_ERR_TABLE_FULL, "k-mer table full: reserve more keys");
     return HAST_OK;
 }
 
@@ -176,12 +160,12 @@ hast_status check_err_word(hast_ctx *c, hipStream_t s) {
 hast_status check_classify_err(hast_ctx *c, hipStream_t hs) {
     if (!hs) hs = c->stream;
     *c->h_errword = 0;
-    HIP_TRY(hipMemcpyAsync(c->h_errword, c->d_err + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, hs));
-    HIP_TRY(hipStreamSynchronize(hs));
+    HAST_HIP_TRY(hipMemcpyAsync(c->h_errword, c->d_err + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, hs));
+    HAST_HIP_TRY(hipStreamSynchronize(hs));
     if (!*c->h_errword) return HAST_OK;
-    HIP_TRY(hipMemsetAsync(c->d_err + 1, 0, sizeof(uint32_t), hs));
-    HIP_TRY(hipStreamSynchronize(hs));
-    return fail(HAST_ERR_INVALID, "read offsets overlap or are not monotonic (their lengths add up to more than bases_bytes): rows were dropped");
+    HAST_HIP_TRY(hipMemsetAsync(c->d_err + 1, 0, sizeof(uint32_t), hs));
+    HAST_HIP_TRY(hipStreamSynchronize(hs));
+    return set_error(HAST_ERR_INVALID, "read offsets overlap or are not monotonic (their lengths add up to more than bases_bytes): rows were dropped");
 }
 
 SynthParams resolve(const hast_synth_params *p) {
@@ -198,8 +182,8 @@ SynthParams resolve(const hast_synth_params *p) {
 }
 
 hast_status check_synth(const hast_synth_params *p) {
-    if (!p) return fail(HAST_ERR_INVALID, "null synth params");
-    if (p->k < 1 || p->k > 32) return fail(HAST_ERR_INVALID, "synth k=%u out of [1,32]", p->k);
+    if (!p) return set_error(HAST_ERR_INVALID, "null synth params");
+    if (p->k < 1 || p->k > 32) return set_error(HAST_ERR_INVALID, "synth k=%u out of [1,32]", p->k);
     return HAST_OK;
 }
 
@@ -305,9 +289,9 @@ const char *hast_last_error(void) { return g_err; }
 
 // ---------------------------------------------------------------------------------------------
 hast_status hast_ctx_create(int device, int k, hast_ctx **out) {
-    if (!out) return fail(HAST_ERR_INVALID, "out is null");
+    if (!out) return set_error(HAST_ERR_INVALID, "out is null");
     *out = nullptr;
-    if (k < 1 || k > 32) return fail(HAST_ERR_INVALID, "K=%d out of [1,32]", k);
+    if (k < 1 || k > 32) return set_error(HAST_ERR_INVALID, "K=%d out of [1,32]", k);
     // HAST_TRACE_INIT=1: which call of the context's creation a box makes wait (0.07 - 0.26 s from run to run on one box)
     const bool trace = getenv("HAST_TRACE_INIT") != nullptr;
     auto now_s = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -320,12 +304,12 @@ hast_status hast_ctx_create(int device, int k, hast_ctx **out) {
     hipError_t e = hipGetDeviceCount(&n);
     tr("hipGetDeviceCount (loads the runtime)");
     if (e != hipSuccess || n <= 0)
-        return fail(HAST_ERR_NO_DEVICE, "no HIP device (%s); libhast has no CPU path", hipGetErrorString(e));
-    if (device < 0 || device >= n) return fail(HAST_ERR_NO_DEVICE, "device %d not in [0,%d)", device, n);
-    HIP_TRY(hipSetDevice(device));
+        return set_error(HAST_ERR_NO_DEVICE, "no HIP device (%s); libhast has no CPU path", hipGetErrorString(e));
+    if (device < 0 || device >= n) return set_error(HAST_ERR_NO_DEVICE, "device %d not in [0,%d)", device, n);
+    HAST_HIP_TRY(hipSetDevice(device));
     tr("hipSetDevice");
     hast_ctx *c = new (std::nothrow) hast_ctx();
-    if (!c) return fail(HAST_ERR_OOM, "host allocation failed");
+    if (!c) return set_error(HAST_ERR_OOM, "host allocation failed");
     c->device = device;
     c->k = k;
     c->m = default_minimizer(k);
@@ -352,7 +336,7 @@ hast_status hast_ctx_create(int device, int k, hast_ctx **out) {
     tr("hipGetDeviceProperties");
     hast_status st = HAST_OK;
     auto bail = [&](hipError_t he, const char *what) {
-        if (he != hipSuccess && st == HAST_OK) st = fail(HAST_ERR_HIP, "%s: %s", what, hipGetErrorString(he));
+        if (he != hipSuccess && st == HAST_OK) st = set_error(HAST_ERR_HIP, "%s: %s", what, hipGetErrorString(he));
     };
     bail(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking), "hipStreamCreate");
     tr("hipStreamCreate");
@@ -415,9 +399,9 @@ int hast_ctx_k(const hast_ctx *c) { return c ? c->k : 0; }
 int hast_ctx_minimizer(const hast_ctx *c) { return c ? c->m : 0; }
 
 hast_status hast_ctx_set_minimizer(hast_ctx *c, int m) {
-    if (!c) return fail(HAST_ERR_INVALID, "null context");
-    if (m < 1 || m > c->k) return fail(HAST_ERR_INVALID, "minimizer length %d out of [1,%d]", m, c->k);
-    if (c->d_slots) return fail(HAST_ERR_INVALID, "minimizer length is fixed once the table exists");
+    if (!c) return set_error(HAST_ERR_INVALID, "null context");
+    if (m < 1 || m > c->k) return set_error(HAST_ERR_INVALID, "minimizer length %d out of [1,%d]", m, c->k);
+    if (c->d_slots) return set_error(HAST_ERR_INVALID, "minimizer length is fixed once the table exists");
     c->m = m;
     return HAST_OK;
 }
@@ -426,27 +410,27 @@ hast_stream hast_ctx_stream(const hast_ctx *c) { return c ? (hast_stream)c->stre
 
 hast_status hast_stream_sync(hast_ctx *c, hast_stream s) {
     if (hast_status st = use(c)) return st;
-    HIP_TRY(hipStreamSynchronize(s ? (hipStream_t)s : c->stream));
+    HAST_HIP_TRY(hipStreamSynchronize(s ? (hipStream_t)s : c->stream));
     return check_classify_err(c, s ? (hipStream_t)s : c->stream);
 }
 
 // ---------------------------------------------------------------------------------------------
 hast_status hast_dev_alloc(hast_ctx *c, size_t bytes, void **d_out) {
     if (hast_status st = use(c)) return st;
-    if (!d_out) return fail(HAST_ERR_INVALID, "d_out is null");
-    HIP_TRY(dev_malloc(d_out, bytes ? bytes : 1));
+    if (!d_out) return set_error(HAST_ERR_INVALID, "d_out is null");
+    HAST_HIP_TRY(dev_malloc(d_out, bytes ? bytes : 1));
     return HAST_OK;
 }
 hast_status hast_dev_free(hast_ctx *c, void *p) {
     if (hast_status st = use(c)) return st;
-    if (p) HIP_TRY(hipFree(p));
+    if (p) HAST_HIP_TRY(hipFree(p));
     return HAST_OK;
 }
 // free / total memory of the context's device as the runtime sees it, and what the library holds parked (hast_release_parked)
 hast_status hast_dev_mem_info(hast_ctx *c, size_t *free_bytes, size_t *total_bytes, size_t *parked) {
     if (hast_status st = use(c)) return st;
     size_t f = 0, t = 0;
-    HIP_TRY(hipMemGetInfo(&f, &t));
+    HAST_HIP_TRY(hipMemGetInfo(&f, &t));
     if (free_bytes) *free_bytes = f;
     if (total_bytes) *total_bytes = t;
     if (parked) *parked = parked_bytes();
@@ -454,18 +438,18 @@ hast_status hast_dev_mem_info(hast_ctx *c, size_t *free_bytes, size_t *total_byt
 }
 hast_status hast_memcpy_h2d(hast_ctx *c, void *d, const void *s, size_t n) {
     if (hast_status st = use(c)) return st;
-    if (n) HIP_TRY(hipMemcpy(d, s, n, hipMemcpyHostToDevice));
+    if (n) HAST_HIP_TRY(hipMemcpy(d, s, n, hipMemcpyHostToDevice));
     return HAST_OK;
 }
 hast_status hast_memcpy_d2h(hast_ctx *c, void *d, const void *s, size_t n) {
     if (hast_status st = use(c)) return st;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (n) HIP_TRY(hipMemcpy(d, s, n, hipMemcpyDeviceToHost));
+    HAST_HIP_TRY(hipStreamSynchronize(c->stream));
+    if (n) HAST_HIP_TRY(hipMemcpy(d, s, n, hipMemcpyDeviceToHost));
     return HAST_OK;
 }
 hast_status hast_memset_d(hast_ctx *c, void *d, int byte, size_t n, hast_stream s) {
     if (hast_status st = use(c)) return st;
-    if (n) HIP_TRY(hipMemsetAsync(d, byte, n, s ? (hipStream_t)s : c->stream));
+    if (n) HAST_HIP_TRY(hipMemsetAsync(d, byte, n, s ? (hipStream_t)s : c->stream));
     return HAST_OK;
 }
 
@@ -473,22 +457,22 @@ hast_status hast_memset_d(hast_ctx *c, void *d, int byte, size_t n, hast_stream 
 hast_status hast_table_reserve(hast_ctx *c, uint64_t max_keys, double lf) {
     if (hast_status st = use(c)) return st;
     if (lf <= 0) lf = 0.2;
-    if (lf > 0.9) return fail(HAST_ERR_INVALID, "load factor %.3f > 0.9", lf);
+    if (lf > 0.9) return set_error(HAST_ERR_INVALID, "load factor %.3f > 0.9", lf);
     double want = (double)(max_keys ? max_keys : 1) / lf / kSlotsPerBucket;
     uint64_t nb = (uint64_t)want + 1;
     if (nb < 64) nb = 64;
     nb += nb & 1;                                   // even: buckets may be used in pairs
-    if (nb >= (1ull << 32)) return fail(HAST_ERR_INVALID, "table of %llu buckets exceeds 2^32", (unsigned long long)nb);
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->d_slots) HIP_TRY(hipFree(c->d_slots));
+    if (nb >= (1ull << 32)) return set_error(HAST_ERR_INVALID, "table of %llu buckets exceeds 2^32", (unsigned long long)nb);
+    HAST_HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->d_slots) HAST_HIP_TRY(hipFree(c->d_slots));
     c->d_slots = nullptr;
     c->nbuckets = 0;
     c->filter_valid = false;
     // K == 32: two tag-less tables (one per haplotype) back to back, each sized for all the keys
     size_t bytes = (size_t)nb * kSlotsPerBucket * sizeof(uint64_t) * (c->k == 32 ? 2 : 1);
-    HIP_TRY(dev_malloc(&c->d_slots, bytes));
-    HIP_TRY(hipMemsetAsync(c->d_slots, 0xFF, bytes, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HAST_HIP_TRY(dev_malloc(&c->d_slots, bytes));
+    HAST_HIP_TRY(hipMemsetAsync(c->d_slots, 0xFF, bytes, c->stream));
+    HAST_HIP_TRY(hipStreamSynchronize(c->stream));
     c->nbuckets = (uint32_t)nb;
     return HAST_OK;
 }
@@ -499,13 +483,13 @@ static void table_changed(hast_ctx *c) { c->filter_valid = false; }
 
 static hast_status need_table(hast_ctx *c, int hap) {
     if (hast_status st = use(c)) return st;
-    if (!c->d_slots) return fail(HAST_ERR_INVALID, "call hast_table_reserve first");
-    if (hap != 0 && hap != 1) return fail(HAST_ERR_INVALID, "hap must be 0 or 1");
+    if (!c->d_slots) return set_error(HAST_ERR_INVALID, "call hast_table_reserve first");
+    if (hap != 0 && hap != 1) return set_error(HAST_ERR_INVALID, "hap must be 0 or 1");
     return HAST_OK;
 }
 
 hast_status hast_ctx_set_text_check(hast_ctx *c, int acgt_only) {
-    if (!c) return fail(HAST_ERR_INVALID, "null context");
+    if (!c) return set_error(HAST_ERR_INVALID, "null context");
     c->text_acgt_only = acgt_only ? 1 : 0;
     return HAST_OK;
 }
@@ -514,21 +498,21 @@ hast_status hast_table_insert_keys_device(hast_ctx *c, int hap, const uint64_t *
     if (hast_status st = need_table(c, hap)) return st;
     hipStream_t hs = s ? (hipStream_t)s : c->stream;
     table_changed(c);
-    HIP_TRY(launch_insert_keys(c->d_slots, geom(c), d_keys, n, (uint32_t)hap, c->d_err, hs));
+    HAST_HIP_TRY(launch_insert_keys(c->d_slots, geom(c), d_keys, n, (uint32_t)hap, c->d_err, hs));
     return check_err_word(c, hs);
 }
 
 hast_status hast_table_insert_keys(hast_ctx *c, int hap, const uint64_t *keys, size_t n) {
     if (hast_status st = need_table(c, hap)) return st;
-    if (n && !keys) return fail(HAST_ERR_INVALID, "keys is null");
+    if (n && !keys) return set_error(HAST_ERR_INVALID, "keys is null");
     table_changed(c);
     const size_t per = kChunkBytes / sizeof(uint64_t);
     if (hast_status st = ensure_scratch(c, std::min(n, per) * sizeof(uint64_t) + 16)) return st;
     for (size_t i = 0; i < n; i += per) {
         size_t m = std::min(per, n - i);
-        HIP_TRY(hipMemcpyAsync(c->d_scratch, keys + i, m * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(launch_insert_keys(c->d_slots, geom(c), (const uint64_t *)c->d_scratch, m, (uint32_t)hap, c->d_err, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
+        HAST_HIP_TRY(hipMemcpyAsync(c->d_scratch, keys + i, m * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+        HAST_HIP_TRY(launch_insert_keys(c->d_slots, geom(c), (const uint64_t *)c->d_scratch, m, (uint32_t)hap, c->d_err, c->stream));
+        HAST_HIP_TRY(hipStreamSynchronize(c->stream));
     }
     return check_err_word(c, c->stream);
 }
@@ -536,7 +520,7 @@ hast_status hast_table_insert_keys(hast_ctx *c, int hap, const uint64_t *keys, s
 hast_status hast_table_insert_text(hast_ctx *c, int hap, const char *text, size_t nbytes, uint64_t *lines_out) {
     if (hast_status st = need_table(c, hap)) return st;
     if (lines_out) *lines_out = 0;
-    if (nbytes && !text) return fail(HAST_ERR_INVALID, "text is null");
+    if (nbytes && !text) return set_error(HAST_ERR_INVALID, "text is null");
     table_changed(c);
     const size_t stride = (size_t)c->k + 1;
     // classify.cpp:41: pieces are '\n'-terminated lines; a trailing piece without '\n' is dropped.
@@ -545,14 +529,14 @@ hast_status hast_table_insert_text(hast_ctx *c, int hap, const char *text, size_
     size_t n_lines = nbytes / stride;
     size_t rem = nbytes - n_lines * stride;
     // the dropped tail must itself not contain a newline (else lines are ragged)
-    if (rem && memchr(text + n_lines * stride, '\n', rem)) return fail(HAST_ERR_FORMAT, "k-mer text: ragged last line");
+    if (rem && memchr(text + n_lines * stride, '\n', rem)) return set_error(HAST_ERR_FORMAT, "k-mer text: ragged last line");
     const size_t per = (kChunkBytes / stride);
     if (hast_status st = ensure_scratch(c, std::min(n_lines, per) * stride + 16)) return st;
     for (size_t i = 0; i < n_lines; i += per) {
         size_t m = std::min(per, n_lines - i);
-        HIP_TRY(hipMemcpyAsync(c->d_scratch, text + i * stride, m * stride, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(launch_insert_text(c->d_slots, geom(c), (const char *)c->d_scratch, m, (uint32_t)hap, c->text_acgt_only, c->d_err, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
+        HAST_HIP_TRY(hipMemcpyAsync(c->d_scratch, text + i * stride, m * stride, hipMemcpyHostToDevice, c->stream));
+        HAST_HIP_TRY(launch_insert_text(c->d_slots, geom(c), (const char *)c->d_scratch, m, (uint32_t)hap, c->text_acgt_only, c->d_err, c->stream));
+        HAST_HIP_TRY(hipStreamSynchronize(c->stream));
     }
     if (hast_status st = check_err_word(c, c->stream)) return st;
     if (lines_out) *lines_out = n_lines;
@@ -605,8 +589,8 @@ static hast_status stream_file_region(hast_ctx *c, int fd, const char *path, uin
         const hipError_t e2 = hipStreamSynchronize(c->stream);
         if (e == hipSuccess) e = e2;
     }
-    if (e != hipSuccess) return fail(HAST_ERR_HIP, "%s: %s", path, hipGetErrorString(e));
-    if (short_read) return fail(HAST_ERR_IO, "%s is shorter than its size says (truncated, or changed while it was read)", path);
+    if (e != hipSuccess) return set_error(HAST_ERR_HIP, "%s: %s", path, hipGetErrorString(e));
+    if (short_read) return set_error(HAST_ERR_IO, "%s is shorter than its size says (truncated, or changed while it was read)", path);
     return HAST_OK;
 }
 
@@ -616,21 +600,21 @@ static hast_status stream_file_region(hast_ctx *c, int fd, const char *path, uin
 hast_status hast_table_insert_text_file(hast_ctx *c, int hap, const char *path, uint64_t *lines_out) {
     if (hast_status st = need_table(c, hap)) return st;
     if (lines_out) *lines_out = 0;
-    if (!path) return fail(HAST_ERR_INVALID, "path is null");
+    if (!path) return set_error(HAST_ERR_INVALID, "path is null");
     const int fd = open(path, O_RDONLY);
-    if (fd < 0) return fail(HAST_ERR_IO, "cannot read %s", path);
+    if (fd < 0) return set_error(HAST_ERR_IO, "cannot read %s", path);
     struct stat sb;
     if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) {
         // not a regular file (a pipe): no pread -- the caller reads it into memory and uses hast_table_insert_text
         close(fd);
-        return fail(HAST_ERR_IO, "%s is not a regular file", path);
+        return set_error(HAST_ERR_IO, "%s is not a regular file", path);
     }
     const size_t nbytes = (size_t)sb.st_size, stride = (size_t)c->k + 1;
     const size_t n_lines = nbytes / stride, rem = nbytes - n_lines * stride;
     if (rem) {       // classify.cpp:41: a trailing piece without its own newline is dropped -- it must not hold one, though
         char tail[64];
-        if (pread(fd, tail, rem, (off_t)(n_lines * stride)) != (ssize_t)rem) { close(fd); return fail(HAST_ERR_IO, "cannot read %s", path); }
-        if (memchr(tail, '\n', rem)) { close(fd); return fail(HAST_ERR_FORMAT, "k-mer text: ragged last line"); }
+        if (pread(fd, tail, rem, (off_t)(n_lines * stride)) != (ssize_t)rem) { close(fd); return set_error(HAST_ERR_IO, "cannot read %s", path); }
+        if (memchr(tail, '\n', rem)) { close(fd); return set_error(HAST_ERR_FORMAT, "k-mer text: ragged last line"); }
     }
     table_changed(c);
     const hast_status st = stream_file_region(c, fd, path, 0, n_lines, stride, [&](char *d_piece, size_t m, uint64_t) {
@@ -646,19 +630,19 @@ hast_status hast_table_insert_text_file(hast_ctx *c, int hap, const char *path, 
 hast_status hast_table_erase(hast_ctx *c, const uint64_t *keys, size_t n, uint8_t *out_hit) {
     if (hast_status st = need_table(c, 0)) return st;
     if (n == 0) return HAST_OK;
-    if (!keys) return fail(HAST_ERR_INVALID, "keys is null");
+    if (!keys) return set_error(HAST_ERR_INVALID, "keys is null");
     size_t kb = n * sizeof(uint64_t);
     if (hast_status st = ensure_scratch(c, kb + n + 16)) return st;
     uint8_t *d_hit = (uint8_t *)c->d_scratch + kb;
-    HIP_TRY(hipMemcpyAsync(c->d_scratch, keys, kb, hipMemcpyHostToDevice, c->stream));
+    HAST_HIP_TRY(hipMemcpyAsync(c->d_scratch, keys, kb, hipMemcpyHostToDevice, c->stream));
     // one key at a time per launch order is not required: distinct keys touch distinct slots, and a
     // key listed twice reports its tags once (the second atomicAnd sees them already cleared) --
     // the same as the reference's find-then-erase loop (classify.cpp:318-337).
-    HIP_TRY(launch_erase_keys(c->d_slots, geom(c), (const uint64_t *)c->d_scratch, n, d_hit, c->stream));
+    HAST_HIP_TRY(launch_erase_keys(c->d_slots, geom(c), (const uint64_t *)c->d_scratch, n, d_hit, c->stream));
     table_changed(c);          // exact filter entries answer hits on their own: an erased key must leave the filter too
     std::vector<uint8_t> hit(n);
-    HIP_TRY(hipMemcpyAsync(hit.data(), d_hit, n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HAST_HIP_TRY(hipMemcpyAsync(hit.data(), d_hit, n, hipMemcpyDeviceToHost, c->stream));
+    HAST_HIP_TRY(hipStreamSynchronize(c->stream));
     if (out_hit) memcpy(out_hit, hit.data(), n);
     return HAST_OK;
 }
@@ -666,24 +650,24 @@ hast_status hast_table_erase(hast_ctx *c, const uint64_t *keys, size_t n, uint8_
 hast_status hast_table_lookup(hast_ctx *c, const uint64_t *keys, size_t n, uint8_t *out_tags) {
     if (hast_status st = need_table(c, 0)) return st;
     if (n == 0) return HAST_OK;
-    if (!keys || !out_tags) return fail(HAST_ERR_INVALID, "null argument");
+    if (!keys || !out_tags) return set_error(HAST_ERR_INVALID, "null argument");
     size_t kb = n * sizeof(uint64_t);
     if (hast_status st = ensure_scratch(c, kb + n + 16)) return st;
     uint8_t *d_tags = (uint8_t *)c->d_scratch + kb;
-    HIP_TRY(hipMemcpyAsync(c->d_scratch, keys, kb, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(launch_lookup_keys(c->d_slots, geom(c), (const uint64_t *)c->d_scratch, n, d_tags, c->stream));
-    HIP_TRY(hipMemcpyAsync(out_tags, d_tags, n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HAST_HIP_TRY(hipMemcpyAsync(c->d_scratch, keys, kb, hipMemcpyHostToDevice, c->stream));
+    HAST_HIP_TRY(launch_lookup_keys(c->d_slots, geom(c), (const uint64_t *)c->d_scratch, n, d_tags, c->stream));
+    HAST_HIP_TRY(hipMemcpyAsync(out_tags, d_tags, n, hipMemcpyDeviceToHost, c->stream));
+    HAST_HIP_TRY(hipStreamSynchronize(c->stream));
     return HAST_OK;
 }
 
 hast_status hast_table_sizes(hast_ctx *c, uint64_t *n0, uint64_t *n1) {
     if (hast_status st = need_table(c, 0)) return st;
     unsigned long long h[2] = {0, 0};
-    HIP_TRY(hipMemsetAsync(c->d_cnt, 0, sizeof(h), c->stream));
-    HIP_TRY(launch_count_tags(c->d_slots, geom(c), c->d_cnt, c->stream));
-    HIP_TRY(hipMemcpyAsync(h, c->d_cnt, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HAST_HIP_TRY(hipMemsetAsync(c->d_cnt, 0, sizeof(h), c->stream));
+    HAST_HIP_TRY(launch_count_tags(c->d_slots, geom(c), c->d_cnt, c->stream));
+    HAST_HIP_TRY(hipMemcpyAsync(h, c->d_cnt, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HAST_HIP_TRY(hipStreamSynchronize(c->stream));
     if (n0) *n0 = h[0];
     if (n1) *n1 = h[1];
     return HAST_OK;
@@ -701,13 +685,13 @@ struct CacheHeader {
 
 hast_status hast_table_save(hast_ctx *c, const char *path) {
     if (hast_status st = need_table(c, 0)) return st;
-    if (c->k == 32) return fail(HAST_ERR_INVALID, "the key-set cache stores tag bits next to the key: not available for K=32");
-    if (!path) return fail(HAST_ERR_INVALID, "path is null");
+    if (c->k == 32) return set_error(HAST_ERR_INVALID, "the key-set cache stores tag bits next to the key: not available for K=32");
+    if (!path) return set_error(HAST_ERR_INVALID, "path is null");
     uint64_t n0 = 0, n1 = 0;
     if (hast_status st = hast_table_sizes(c, &n0, &n1)) return st;
     const size_t cap = (size_t)(n0 + n1) + 16;                    // distinct live keys <= n0 + n1
     uint64_t *d_out = nullptr;
-    HIP_TRY(dev_malloc((void **)&d_out, cap * sizeof(uint64_t)));
+    HAST_HIP_TRY(dev_malloc((void **)&d_out, cap * sizeof(uint64_t)));
     unsigned long long n = 0;
     hipError_t e = hipMemsetAsync(c->d_cnt, 0, sizeof(unsigned long long), c->stream);
     if (e == hipSuccess) e = launch_export_slots(c->d_slots, (size_t)c->nbuckets * kSlotsPerBucket, d_out, cap, c->d_cnt, c->stream);
@@ -731,10 +715,10 @@ hast_status hast_table_save(hast_ctx *c, const char *path) {
         (void)hipFree(d_tmp);
     }
     (void)hipFree(d_out);
-    if (e != hipSuccess) return fail(HAST_ERR_HIP, "table export: %s", hipGetErrorString(e));
-    if (n > cap) return fail(HAST_ERR_INVALID, "table export overflow");
+    if (e != hipSuccess) return set_error(HAST_ERR_HIP, "table export: %s", hipGetErrorString(e));
+    if (n > cap) return set_error(HAST_ERR_INVALID, "table export overflow");
     FILE *f = fopen(path, "wb");
-    if (!f) return fail(HAST_ERR_IO, "cannot write %s", path);
+    if (!f) return set_error(HAST_ERR_IO, "cannot write %s", path);
     CacheHeader h;
     memcpy(h.magic, "HASTKEYS", 8);
     h.version = 1;
@@ -743,18 +727,18 @@ hast_status hast_table_save(hast_ctx *c, const char *path) {
     h.reserved = 0;
     bool ok = fwrite(&h, sizeof(h), 1, f) == 1 && (n == 0 || fwrite(host.data(), sizeof(uint64_t), (size_t)n, f) == (size_t)n);
     ok = (fclose(f) == 0) && ok;
-    if (!ok) return fail(HAST_ERR_IO, "short write to %s", path);
+    if (!ok) return set_error(HAST_ERR_IO, "short write to %s", path);
     return HAST_OK;
 }
 
 hast_status hast_table_file_info(const char *path, int *k_out, uint64_t *n_keys_out) {
-    if (!path) return fail(HAST_ERR_INVALID, "path is null");
+    if (!path) return set_error(HAST_ERR_INVALID, "path is null");
     FILE *f = fopen(path, "rb");
-    if (!f) return fail(HAST_ERR_IO, "cannot read %s", path);
+    if (!f) return set_error(HAST_ERR_IO, "cannot read %s", path);
     CacheHeader h;
     const bool ok = fread(&h, sizeof(h), 1, f) == 1 && memcmp(h.magic, "HASTKEYS", 8) == 0 && h.version == 1;
     fclose(f);
-    if (!ok) return fail(HAST_ERR_FORMAT, "%s is not a HASTKEYS v1 file", path);
+    if (!ok) return set_error(HAST_ERR_FORMAT, "%s is not a HASTKEYS v1 file", path);
     if (k_out) *k_out = (int)h.k;
     if (n_keys_out) *n_keys_out = h.n_slots;
     return HAST_OK;
@@ -762,17 +746,17 @@ hast_status hast_table_file_info(const char *path, int *k_out, uint64_t *n_keys_
 
 hast_status hast_table_load(hast_ctx *c, const char *path, double load_factor) {
     if (hast_status st = use(c)) return st;
-    if (!path) return fail(HAST_ERR_INVALID, "path is null");
+    if (!path) return set_error(HAST_ERR_INVALID, "path is null");
     FILE *f = fopen(path, "rb");
-    if (!f) return fail(HAST_ERR_IO, "cannot read %s", path);
+    if (!f) return set_error(HAST_ERR_IO, "cannot read %s", path);
     CacheHeader h;
     if (fread(&h, sizeof(h), 1, f) != 1 || memcmp(h.magic, "HASTKEYS", 8) != 0 || h.version != 1) {
         fclose(f);
-        return fail(HAST_ERR_FORMAT, "%s is not a HASTKEYS v1 file", path);
+        return set_error(HAST_ERR_FORMAT, "%s is not a HASTKEYS v1 file", path);
     }
     if (h.k == 32 || (int)h.k != c->k) {
         fclose(f);
-        return fail(HAST_ERR_INVALID, "%s holds %u-mers, the context is K=%d", path, h.k, c->k);
+        return set_error(HAST_ERR_INVALID, "%s holds %u-mers, the context is K=%d", path, h.k, c->k);
     }
     hast_status st = hast_table_reserve(c, h.n_slots + 1, load_factor);
     struct stat sb;
@@ -781,18 +765,18 @@ hast_status hast_table_load(hast_ctx *c, const char *path, double load_factor) {
         st = stream_file_region(c, fileno(f), path, sizeof(CacheHeader), h.n_slots, sizeof(uint64_t), [&](char *d_piece, size_t m, uint64_t) {
             return launch_import_slots(c->d_slots, geom(c), (const uint64_t *)d_piece, m, c->d_err, c->stream);
         });
-        if (st == HAST_ERR_IO) st = fail(HAST_ERR_IO, "%s is truncated", path);
+        if (st == HAST_ERR_IO) st = set_error(HAST_ERR_IO, "%s is truncated", path);
     } else {
         const size_t per = kChunkBytes / sizeof(uint64_t);
         std::vector<uint64_t> buf(std::min<uint64_t>(per, h.n_slots ? h.n_slots : 1));
         if (st == HAST_OK) st = ensure_scratch(c, buf.size() * sizeof(uint64_t) + 16);
         for (uint64_t i = 0; st == HAST_OK && i < h.n_slots; i += per) {
             const size_t m = (size_t)std::min<uint64_t>(per, h.n_slots - i);
-            if (fread(buf.data(), sizeof(uint64_t), m, f) != m) { st = fail(HAST_ERR_IO, "%s is truncated", path); break; }
+            if (fread(buf.data(), sizeof(uint64_t), m, f) != m) { st = set_error(HAST_ERR_IO, "%s is truncated", path); break; }
             hipError_t e = hipMemcpyAsync(c->d_scratch, buf.data(), m * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream);
             if (e == hipSuccess) e = launch_import_slots(c->d_slots, geom(c), (const uint64_t *)c->d_scratch, m, c->d_err, c->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-            if (e != hipSuccess) st = fail(HAST_ERR_HIP, "table import: %s", hipGetErrorString(e));
+            if (e != hipSuccess) st = set_error(HAST_ERR_HIP, "table import: %s", hipGetErrorString(e));
         }
     }
     fclose(f);
@@ -803,30 +787,30 @@ hast_status hast_table_load(hast_ctx *c, const char *path, double load_factor) {
 // Replicate a finished table (and its filter) onto another context's device: one peer copy over xGMI instead of parsing
 // and inserting the k-mer text once per GPU.
 hast_status hast_table_clone(hast_ctx *dst, hast_ctx *src) {
-    if (!dst || !src || dst == src) return fail(HAST_ERR_INVALID, "clone needs two different contexts");
-    if (dst->k != src->k) return fail(HAST_ERR_INVALID, "clone: K differs (%d vs %d)", dst->k, src->k);
+    if (!dst || !src || dst == src) return set_error(HAST_ERR_INVALID, "clone needs two different contexts");
+    if (dst->k != src->k) return set_error(HAST_ERR_INVALID, "clone: K differs (%d vs %d)", dst->k, src->k);
     if (hast_status st = need_table(src, 0)) return st;
     if (src->use_filter)
         if (hast_status st = ensure_filter(src, src->stream)) return st;
-    HIP_TRY(hipStreamSynchronize(src->stream));
+    HAST_HIP_TRY(hipStreamSynchronize(src->stream));
     if (hast_status st = use(dst)) return st;
-    HIP_TRY(hipStreamSynchronize(dst->stream));
-    if (dst->d_slots) HIP_TRY(hipFree(dst->d_slots));
+    HAST_HIP_TRY(hipStreamSynchronize(dst->stream));
+    if (dst->d_slots) HAST_HIP_TRY(hipFree(dst->d_slots));
     dst->d_slots = nullptr;
     dst->nbuckets = 0;
     dst->filter_valid = false;
     dst->m = src->m;
     const size_t bytes = table_slots(src) * sizeof(uint64_t);
-    HIP_TRY(dev_malloc(&dst->d_slots, bytes));
+    HAST_HIP_TRY(dev_malloc(&dst->d_slots, bytes));
     // ON dst's stream, and waited for below: hipMemcpyPeer between two contexts of ONE GPU is a device-to-device copy, which does not
     // wait for the host -- and dst's stream is a non-blocking one, so nothing would order the reads classified on it behind the copy
     // (seen with --devices 0,0,0 HAST_DEAL=files: a context's first blocks probed a table that was still arriving and lost hits; until
     // round 5 a hipHostFree elsewhere in the process happened to stop the device at the right moment)
-    HIP_TRY(hipMemcpyPeerAsync(dst->d_slots, dst->device, src->d_slots, src->device, bytes, dst->stream));
+    HAST_HIP_TRY(hipMemcpyPeerAsync(dst->d_slots, dst->device, src->d_slots, src->device, bytes, dst->stream));
     dst->nbuckets = src->nbuckets;
     if (src->filter_valid && dst->use_filter) {
         if (dst->filter_bytes != src->filter_bytes) {
-            if (dst->d_filter) HIP_TRY(hipFree(dst->d_filter));
+            if (dst->d_filter) HAST_HIP_TRY(hipFree(dst->d_filter));
             dst->d_filter = nullptr;
             dst->filter_bytes = 0;
             if (dst->test_filter_oom || dev_malloc(&dst->d_filter, src->filter_bytes) != hipSuccess) {
@@ -834,12 +818,12 @@ hast_status hast_table_clone(hast_ctx *dst, hast_ctx *src) {
                 dst->d_filter = nullptr;
                 dst->use_filter = false;                   // no room: this device probes the table directly
                 dst->filter_fallback_bytes = src->filter_bytes;
-                HIP_TRY(hipStreamSynchronize(dst->stream));
+                HAST_HIP_TRY(hipStreamSynchronize(dst->stream));
                 return HAST_OK;
             }
             dst->filter_bytes = src->filter_bytes;
         }
-        HIP_TRY(hipMemcpyPeerAsync(dst->d_filter, dst->device, src->d_filter, src->device, src->filter_bytes, dst->stream));
+        HAST_HIP_TRY(hipMemcpyPeerAsync(dst->d_filter, dst->device, src->d_filter, src->device, src->filter_bytes, dst->stream));
         dst->fg = src->fg;
         dst->filter_m = src->filter_m;
         dst->filter_exact = src->filter_exact;
@@ -847,12 +831,12 @@ hast_status hast_table_clone(hast_ctx *dst, hast_ctx *src) {
         dst->filter_kp = src->filter_kp;
         dst->filter_valid = true;
     }
-    HIP_TRY(hipStreamSynchronize(dst->stream));            // (src may change once this returns)
+    HAST_HIP_TRY(hipStreamSynchronize(dst->stream));            // (src may change once this returns)
     return HAST_OK;
 }
 
 hast_status hast_table_info(const hast_ctx *c, uint64_t *n_buckets, uint64_t *bytes) {
-    if (!c) return fail(HAST_ERR_INVALID, "null context");
+    if (!c) return set_error(HAST_ERR_INVALID, "null context");
     if (n_buckets) *n_buckets = c->nbuckets;
     if (bytes) *bytes = (uint64_t)table_slots(c) * sizeof(uint64_t);
     return HAST_OK;
@@ -861,31 +845,31 @@ hast_status hast_table_info(const hast_ctx *c, uint64_t *n_buckets, uint64_t *by
 // ---------------------------------------------------------------------------------------------
 hast_status hast_counts_resize(hast_ctx *c, size_t n) {
     if (hast_status st = use(c)) return st;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->counts_owned && c->d_counts) HIP_TRY(hipFree(c->d_counts));
+    HAST_HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->counts_owned && c->d_counts) HAST_HIP_TRY(hipFree(c->d_counts));
     c->d_counts = nullptr;
     c->n_barcodes = 0;
     c->counts_owned = false;
     size_t bytes = (n ? n : 1) * 4 * sizeof(unsigned long long);
-    HIP_TRY(dev_malloc(reinterpret_cast<void **>(&c->d_counts), bytes));
+    HAST_HIP_TRY(dev_malloc(reinterpret_cast<void **>(&c->d_counts), bytes));
     c->counts_owned = true;
     c->n_barcodes = n;
-    HIP_TRY(hipMemsetAsync(c->d_counts, 0, bytes, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HAST_HIP_TRY(hipMemsetAsync(c->d_counts, 0, bytes, c->stream));
+    HAST_HIP_TRY(hipStreamSynchronize(c->stream));
     return HAST_OK;
 }
 
 hast_status hast_counts_permute(hast_ctx *c, const uint32_t *perm, size_t n_perm, size_t n_new) {
     if (hast_status st = use(c)) return st;
-    if (!c->d_counts || !c->counts_owned) return fail(HAST_ERR_INVALID, "hast_counts_permute: library-owned counters only (hast_counts_resize)");
-    if (n_perm > c->n_barcodes || (n_perm && !perm)) return fail(HAST_ERR_INVALID, "hast_counts_permute: %zu ids > %zu counters", n_perm, c->n_barcodes);
+    if (!c->d_counts || !c->counts_owned) return set_error(HAST_ERR_INVALID, "hast_counts_permute: library-owned counters only (hast_counts_resize)");
+    if (n_perm > c->n_barcodes || (n_perm && !perm)) return set_error(HAST_ERR_INVALID, "hast_counts_permute: %zu ids > %zu counters", n_perm, c->n_barcodes);
     for (size_t i = 0; i < n_perm; i++)
-        if (perm[i] >= n_new && perm[i] != 0xFFFFFFFFu) return fail(HAST_ERR_INVALID, "hast_counts_permute: perm[%zu] = %u is outside the %zu new records", i, perm[i], n_new);
-    HIP_TRY(hipStreamSynchronize(c->stream));
+        if (perm[i] >= n_new && perm[i] != 0xFFFFFFFFu) return set_error(HAST_ERR_INVALID, "hast_counts_permute: perm[%zu] = %u is outside the %zu new records", i, perm[i], n_new);
+    HAST_HIP_TRY(hipStreamSynchronize(c->stream));
     unsigned long long *d_new = nullptr;
     uint32_t *d_perm = nullptr;
     const size_t bytes = (n_new ? n_new : 1) * 4 * sizeof(unsigned long long);
-    HIP_TRY(dev_malloc(reinterpret_cast<void **>(&d_new), bytes));
+    HAST_HIP_TRY(dev_malloc(reinterpret_cast<void **>(&d_new), bytes));
     hipError_t e = dev_malloc(reinterpret_cast<void **>(&d_perm), (n_perm ? n_perm : 1) * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMemsetAsync(d_new, 0, bytes, c->stream);
     if (e == hipSuccess && n_perm) e = hipMemcpyAsync(d_perm, perm, n_perm * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
@@ -894,9 +878,9 @@ hast_status hast_counts_permute(hast_ctx *c, const uint32_t *perm, size_t n_perm
     if (d_perm) (void)hipFree(d_perm);
     if (e != hipSuccess) {
         (void)hipFree(d_new);
-        return fail(e == hipErrorOutOfMemory ? HAST_ERR_OOM : HAST_ERR_HIP, "hast_counts_permute: %s", hipGetErrorString(e));
+        return set_error(e == hipErrorOutOfMemory ? HAST_ERR_OOM : HAST_ERR_HIP, "hast_counts_permute: %s", hipGetErrorString(e));
     }
-    HIP_TRY(hipFree(c->d_counts));
+    HAST_HIP_TRY(hipFree(c->d_counts));
     c->d_counts = d_new;
     c->n_barcodes = n_new;
     return HAST_OK;
@@ -904,10 +888,10 @@ hast_status hast_counts_permute(hast_ctx *c, const uint32_t *perm, size_t n_perm
 
 hast_status hast_counts_bind(hast_ctx *c, uint64_t *d_counts, size_t n) {
     if (hast_status st = use(c)) return st;
-    if (!d_counts) return fail(HAST_ERR_INVALID, "d_counts is null");
-    if ((uintptr_t)d_counts & 31) return fail(HAST_ERR_INVALID, "d_counts must be 32-byte aligned (one record = 4 x u64)");
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->counts_owned && c->d_counts) HIP_TRY(hipFree(c->d_counts));
+    if (!d_counts) return set_error(HAST_ERR_INVALID, "d_counts is null");
+    if ((uintptr_t)d_counts & 31) return set_error(HAST_ERR_INVALID, "d_counts must be 32-byte aligned (one record = 4 x u64)");
+    HAST_HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->counts_owned && c->d_counts) HAST_HIP_TRY(hipFree(c->d_counts));
     c->d_counts = reinterpret_cast<unsigned long long *>(d_counts);
     c->counts_owned = false;
     c->n_barcodes = n;
@@ -916,50 +900,50 @@ hast_status hast_counts_bind(hast_ctx *c, uint64_t *d_counts, size_t n) {
 
 hast_status hast_counts_zero(hast_ctx *c, hast_stream s) {
     if (hast_status st = use(c)) return st;
-    if (!c->d_counts) return fail(HAST_ERR_INVALID, "no counters: call hast_counts_resize/bind");
-    HIP_TRY(hipMemsetAsync(c->d_counts, 0, c->n_barcodes * 4 * sizeof(unsigned long long), s ? (hipStream_t)s : c->stream));
+    if (!c->d_counts) return set_error(HAST_ERR_INVALID, "no counters: call hast_counts_resize/bind");
+    HAST_HIP_TRY(hipMemsetAsync(c->d_counts, 0, c->n_barcodes * 4 * sizeof(unsigned long long), s ? (hipStream_t)s : c->stream));
     return HAST_OK;
 }
 
 static hast_status ensure_pack(hast_ctx *c, size_t n) {
     if (c->pack_words >= 3 * n) return HAST_OK;
-    if (c->d_pack) HIP_TRY(hipFree(c->d_pack));
+    if (c->d_pack) HAST_HIP_TRY(hipFree(c->d_pack));
     c->d_pack = nullptr;
     c->pack_words = 0;
-    HIP_TRY(dev_malloc((void **)&c->d_pack, std::max<size_t>(3 * n, 1) * sizeof(unsigned long long)));
+    HAST_HIP_TRY(dev_malloc((void **)&c->d_pack, std::max<size_t>(3 * n, 1) * sizeof(unsigned long long)));
     c->pack_words = 3 * n;
     return HAST_OK;
 }
 
 hast_status hast_counts_pack(hast_ctx *c, uint64_t *d_packed, size_t n, hast_stream s) {
     if (hast_status st = use(c)) return st;
-    if (!c->d_counts || !d_packed) return fail(HAST_ERR_INVALID, "no counters");
-    if (n > c->n_barcodes) return fail(HAST_ERR_INVALID, "n_barcodes %zu > %zu", n, c->n_barcodes);
-    HIP_TRY(launch_counts_pack(c->d_counts, reinterpret_cast<unsigned long long *>(d_packed), n, s ? (hipStream_t)s : c->stream));
+    if (!c->d_counts || !d_packed) return set_error(HAST_ERR_INVALID, "no counters");
+    if (n > c->n_barcodes) return set_error(HAST_ERR_INVALID, "n_barcodes %zu > %zu", n, c->n_barcodes);
+    HAST_HIP_TRY(launch_counts_pack(c->d_counts, reinterpret_cast<unsigned long long *>(d_packed), n, s ? (hipStream_t)s : c->stream));
     return HAST_OK;
 }
 hast_status hast_counts_unpack(hast_ctx *c, const uint64_t *d_packed, size_t n, hast_stream s) {
     if (hast_status st = use(c)) return st;
-    if (!c->d_counts || !d_packed) return fail(HAST_ERR_INVALID, "no counters");
-    if (n > c->n_barcodes) return fail(HAST_ERR_INVALID, "n_barcodes %zu > %zu", n, c->n_barcodes);
-    HIP_TRY(launch_counts_unpack(c->d_counts, reinterpret_cast<const unsigned long long *>(d_packed), n, s ? (hipStream_t)s : c->stream));
+    if (!c->d_counts || !d_packed) return set_error(HAST_ERR_INVALID, "no counters");
+    if (n > c->n_barcodes) return set_error(HAST_ERR_INVALID, "n_barcodes %zu > %zu", n, c->n_barcodes);
+    HAST_HIP_TRY(launch_counts_unpack(c->d_counts, reinterpret_cast<const unsigned long long *>(d_packed), n, s ? (hipStream_t)s : c->stream));
     return HAST_OK;
 }
 
 hast_status hast_counts_read_range(hast_ctx *c, size_t first, size_t n, uint64_t *c0, uint64_t *c1, uint64_t *neg) {
     if (hast_status st = use(c)) return st;
-    if (!c->d_counts) return fail(HAST_ERR_INVALID, "no counters");
-    if (first > c->n_barcodes || n > c->n_barcodes - first) return fail(HAST_ERR_INVALID, "records [%zu, %zu) of %zu counters", first, first + n, c->n_barcodes);
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (!c->d_counts) return set_error(HAST_ERR_INVALID, "no counters");
+    if (first > c->n_barcodes || n > c->n_barcodes - first) return set_error(HAST_ERR_INVALID, "records [%zu, %zu) of %zu counters", first, first + n, c->n_barcodes);
+    HAST_HIP_TRY(hipStreamSynchronize(c->stream));
     if (hast_status st = check_classify_err(c, c->stream)) return st;
     if (!n) return HAST_OK;
     // the three live words of every record, as three arrays: 24 bytes per barcode over PCIe, each array straight into the caller's
     if (hast_status st = ensure_pack(c, n)) return st;
-    HIP_TRY(launch_counts_pack(c->d_counts + 4 * first, c->d_pack, n, c->stream));
+    HAST_HIP_TRY(launch_counts_pack(c->d_counts + 4 * first, c->d_pack, n, c->stream));
     uint64_t *dst[3] = {c0, c1, neg};
     for (int a = 0; a < 3; a++)
-        if (dst[a]) HIP_TRY(hipMemcpyAsync(dst[a], c->d_pack + (size_t)a * n, n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+        if (dst[a]) HAST_HIP_TRY(hipMemcpyAsync(dst[a], c->d_pack + (size_t)a * n, n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HAST_HIP_TRY(hipStreamSynchronize(c->stream));
     return HAST_OK;
 }
 hast_status hast_counts_read(hast_ctx *c, uint64_t *c0, uint64_t *c1, uint64_t *neg, size_t n) { return hast_counts_read_range(c, 0, n, c0, c1, neg); }
@@ -969,9 +953,9 @@ hast_status hast_counts_read(hast_ctx *c, uint64_t *c0, uint64_t *c1, uint64_t *
 // by a kernel on that GPU into its first context (the leader), the leaders of DISTINCT GPUs then run the one RCCL all-reduce (a
 // communicator has one rank per GPU), and every leader hands the totals back to the contexts behind it.
 hast_status hast_counts_allreduce(hast_ctx *const *ctxs, int n) {
-    if (!ctxs || n < 1) return fail(HAST_ERR_INVALID, "no contexts");
+    if (!ctxs || n < 1) return set_error(HAST_ERR_INVALID, "no contexts");
     for (int i = 0; i < n; i++)
-        if (!ctxs[i] || !ctxs[i]->d_counts || ctxs[i]->n_barcodes != ctxs[0]->n_barcodes) return fail(HAST_ERR_INVALID, "contexts need equal-size counters");
+        if (!ctxs[i] || !ctxs[i]->d_counts || ctxs[i]->n_barcodes != ctxs[0]->n_barcodes) return set_error(HAST_ERR_INVALID, "contexts need equal-size counters");
     const size_t nbc = ctxs[0]->n_barcodes, nw = nbc * 4;
     // leaders: the first context of every device, in the order of the list; members[l] = the contexts behind leader l
     std::vector<hast_ctx *> lead;
@@ -983,8 +967,8 @@ hast_status hast_counts_allreduce(hast_ctx *const *ctxs, int n) {
             lead.push_back(ctxs[i]);
             members.emplace_back();
         } else {
-            for (hast_ctx *m : members[l]) if (m == ctxs[i]) return fail(HAST_ERR_INVALID, "hast_counts_allreduce: a context is named twice");
-            if (lead[l] == ctxs[i]) return fail(HAST_ERR_INVALID, "hast_counts_allreduce: a context is named twice");
+            for (hast_ctx *m : members[l]) if (m == ctxs[i]) return set_error(HAST_ERR_INVALID, "hast_counts_allreduce: a context is named twice");
+            if (lead[l] == ctxs[i]) return set_error(HAST_ERR_INVALID, "hast_counts_allreduce: a context is named twice");
             members[l].push_back(ctxs[i]);
         }
     }
@@ -992,9 +976,9 @@ hast_status hast_counts_allreduce(hast_ctx *const *ctxs, int n) {
     for (size_t l = 0; l < lead.size(); l++) {
         if (members[l].empty()) continue;
         if (hast_status st = use(lead[l])) return st;
-        HIP_TRY(hipStreamSynchronize(lead[l]->stream));
-        for (hast_ctx *m : members[l]) HIP_TRY(hipStreamSynchronize(m->stream));
-        for (hast_ctx *m : members[l]) HIP_TRY(launch_add_u64(lead[l]->d_counts, m->d_counts, nw, lead[l]->stream));
+        HAST_HIP_TRY(hipStreamSynchronize(lead[l]->stream));
+        for (hast_ctx *m : members[l]) HAST_HIP_TRY(hipStreamSynchronize(m->stream));
+        for (hast_ctx *m : members[l]) HAST_HIP_TRY(launch_add_u64(lead[l]->d_counts, m->d_counts, nw, lead[l]->stream));
     }
     // 3. (after the exchange) per device: the totals back to the members
     auto hand_back = [&]() -> hast_status {
@@ -1002,8 +986,8 @@ hast_status hast_counts_allreduce(hast_ctx *const *ctxs, int n) {
             if (members[l].empty()) continue;
             if (hast_status st = use(lead[l])) return st;
             for (hast_ctx *m : members[l])
-                HIP_TRY(hipMemcpyAsync(m->d_counts, lead[l]->d_counts, nw * sizeof(unsigned long long), hipMemcpyDeviceToDevice, lead[l]->stream));
-            HIP_TRY(hipStreamSynchronize(lead[l]->stream));
+                HAST_HIP_TRY(hipMemcpyAsync(m->d_counts, lead[l]->d_counts, nw * sizeof(unsigned long long), hipMemcpyDeviceToDevice, lead[l]->stream));
+            HAST_HIP_TRY(hipStreamSynchronize(lead[l]->stream));
         }
         return HAST_OK;
     };
@@ -1019,13 +1003,13 @@ hast_status hast_counts_allreduce(hast_ctx *const *ctxs, int n) {
     static void *lib = nullptr;
     if (!lib) lib = dlopen("librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
     if (!lib) lib = dlopen("librccl.so", RTLD_NOW | RTLD_GLOBAL);
-    if (!lib) return fail(HAST_ERR_RCCL, "cannot load librccl: %s", dlerror());
+    if (!lib) return set_error(HAST_ERR_RCCL, "cannot load librccl: %s", dlerror());
     auto init_all = (init_all_t)dlsym(lib, "ncclCommInitAll");
     auto allreduce = (allreduce_t)dlsym(lib, "ncclAllReduce");
     auto gstart = (group_t)dlsym(lib, "ncclGroupStart");
     auto gend = (group_t)dlsym(lib, "ncclGroupEnd");
     auto destroy = (destroy_t)dlsym(lib, "ncclCommDestroy");
-    if (!init_all || !allreduce || !gstart || !gend || !destroy) return fail(HAST_ERR_RCCL, "librccl lacks symbols");
+    if (!init_all || !allreduce || !gstart || !gend || !destroy) return set_error(HAST_ERR_RCCL, "librccl lacks symbols");
     std::vector<int> devs(nl);
     for (int i = 0; i < nl; i++) devs[i] = lead[(size_t)i]->device;
     // one communicator clique per device list, kept for the life of the process: ncclCommInitAll costs hundreds of ms on 8
@@ -1036,7 +1020,7 @@ hast_status hast_counts_allreduce(hast_ctx *const *ctxs, int n) {
     auto it = comm_cache.find(devs);
     if (it == comm_cache.end()) {
         std::vector<comm_t> fresh(nl);
-        if (int rc = init_all(fresh.data(), nl, devs.data())) return fail(HAST_ERR_RCCL, "ncclCommInitAll failed (%d)", rc);
+        if (int rc = init_all(fresh.data(), nl, devs.data())) return set_error(HAST_ERR_RCCL, "ncclCommInitAll failed (%d)", rc);
         it = comm_cache.emplace(devs, std::move(fresh)).first;
     }
     const std::vector<comm_t> &comms = it->second;
@@ -1047,7 +1031,7 @@ hast_status hast_counts_allreduce(hast_ctx *const *ctxs, int n) {
         hast_ctx *c = lead[(size_t)i];
         if (hast_status st = use(c)) return st;
         if (hast_status st = ensure_pack(c, nbc)) return st;
-        HIP_TRY(launch_counts_pack(c->d_counts, c->d_pack, nbc, c->stream));
+        HAST_HIP_TRY(launch_counts_pack(c->d_counts, c->d_pack, nbc, c->stream));
     }
     int rc = gstart();
     for (int i = 0; i < nl && !rc; i++) {
@@ -1066,7 +1050,7 @@ hast_status hast_counts_allreduce(hast_ctx *const *ctxs, int n) {
         for (auto cm : comms) destroy(cm);
         comm_cache.erase(it);
     }
-    if (rc || rc2) return fail(HAST_ERR_RCCL, "ncclAllReduce failed (%d/%d)", rc, rc2);
+    if (rc || rc2) return set_error(HAST_ERR_RCCL, "ncclAllReduce failed (%d/%d)", rc, rc2);
     return hand_back();
 }
 
@@ -1075,14 +1059,14 @@ hast_status hast_counts_allreduce(hast_ctx *const *ctxs, int n) {
 static hast_status ensure_filter(hast_ctx *c, hipStream_t hs) {
     if (c->filter_valid) return HAST_OK;
     unsigned long long h[2] = {0, 0};
-    HIP_TRY(hipMemsetAsync(c->d_cnt, 0, sizeof(h), hs));
-    HIP_TRY(launch_count_tags(c->d_slots, geom(c), c->d_cnt, hs));
-    HIP_TRY(hipMemcpyAsync(h, c->d_cnt, sizeof(h), hipMemcpyDeviceToHost, hs));
-    HIP_TRY(hipStreamSynchronize(hs));
+    HAST_HIP_TRY(hipMemsetAsync(c->d_cnt, 0, sizeof(h), hs));
+    HAST_HIP_TRY(launch_count_tags(c->d_slots, geom(c), c->d_cnt, hs));
+    HAST_HIP_TRY(hipMemcpyAsync(h, c->d_cnt, sizeof(h), hipMemcpyDeviceToHost, hs));
+    HAST_HIP_TRY(hipStreamSynchronize(hs));
     FilterGeom fg = filter_geom_for(c->k, h[0] + h[1], c->filter_m, c->filter_t, c->filter_kp, c->k == 32 ? 0 : c->filter_exact);
     size_t bytes = (size_t)filter_nblocks(fg) * 128;
     if (bytes != c->filter_bytes) {
-        if (c->d_filter) HIP_TRY(hipFree(c->d_filter));
+        if (c->d_filter) HAST_HIP_TRY(hipFree(c->d_filter));
         c->d_filter = nullptr;
         c->filter_bytes = 0;
         // (dev_malloc: what closed streams parked is freed and the allocation tried again before anything smaller or slower is taken)
@@ -1106,8 +1090,8 @@ static hast_status ensure_filter(hast_ctx *c, hipStream_t hs) {
         }
         c->filter_bytes = bytes;
     }
-    HIP_TRY(hipMemsetAsync(c->d_filter, 0, bytes, hs));
-    HIP_TRY(launch_filter_build(c->d_slots, geom(c), c->d_filter, fg, hs));
+    HAST_HIP_TRY(hipMemsetAsync(c->d_filter, 0, bytes, hs));
+    HAST_HIP_TRY(launch_filter_build(c->d_slots, geom(c), c->d_filter, fg, hs));
     c->fg = fg;
     c->filter_valid = true;
     return HAST_OK;
@@ -1126,8 +1110,8 @@ static hast_status commit_votes(hast_ctx *c, const uint32_t *d_votes, const uint
     if (mode != 1 && !atomic_only && !c->part_oom && commit_partition_usable(n_reads, c->n_barcodes, max_votes, mode == 2)) {
         const size_t need = commit_partition_scratch_bytes(n_reads, c->n_barcodes, nullptr, nullptr);
         if (c->part_bytes < need) {
-            HIP_TRY(hipStreamSynchronize(hs));
-            if (c->d_part) HIP_TRY(hipFree(c->d_part));
+            HAST_HIP_TRY(hipStreamSynchronize(hs));
+            if (c->d_part) HAST_HIP_TRY(hipFree(c->d_part));
             c->d_part = nullptr;
             c->part_bytes = 0;
             if (dev_malloc(&c->d_part, need + need / 8) == hipSuccess) c->part_bytes = need + need / 8;
@@ -1138,11 +1122,11 @@ static hast_status commit_votes(hast_ctx *c, const uint32_t *d_votes, const uint
             }
         }
         if (c->d_part) {
-            HIP_TRY(launch_commit_partitioned(d_votes, d_ids, c->d_counts, c->n_barcodes, n_reads, c->d_part, hs));
+            HAST_HIP_TRY(launch_commit_partitioned(d_votes, d_ids, c->d_counts, c->n_barcodes, n_reads, c->d_part, hs));
             return HAST_OK;
         }
     }
-    HIP_TRY(launch_commit_votes(d_votes, d_ids, c->d_counts, nullptr, n_reads, hs));
+    HAST_HIP_TRY(launch_commit_votes(d_votes, d_ids, c->d_counts, nullptr, n_reads, hs));
     return HAST_OK;
 }
 
@@ -1152,13 +1136,13 @@ static hast_status classify_rows(hast_ctx *c, const uint8_t *d_bases, size_t bas
                                  const unsigned long long *d_n_rows = nullptr) {
     if (hast_status st = need_table(c, 0)) return st;
     if (n_reads == 0) return HAST_OK;
-    if (!d_bases) return fail(HAST_ERR_INVALID, "d_bases is null");
-    if (d_barcode_ids && !c->d_counts) return fail(HAST_ERR_INVALID, "barcode ids given but no counters bound");
-    if (read_len == 0 || read_len > (1u << 24)) return fail(HAST_ERR_INVALID, "read_len %u out of range", read_len);
+    if (!d_bases) return set_error(HAST_ERR_INVALID, "d_bases is null");
+    if (d_barcode_ids && !c->d_counts) return set_error(HAST_ERR_INVALID, "barcode ids given but no counters bound");
+    if (read_len == 0 || read_len > (1u << 24)) return set_error(HAST_ERR_INVALID, "read_len %u out of range", read_len);
     // (tmer_order keeps a row position in 12 bits: longer rows are cut into segments by the callers)
-    if (read_len > kLongRead && c->use_filter) return fail(HAST_ERR_INVALID, "internal: a row of %u bases reached the filter kernel", read_len);
+    if (read_len > kLongRead && c->use_filter) return set_error(HAST_ERR_INVALID, "internal: a row of %u bases reached the filter kernel", read_len);
     if (!d_offsets && (uint64_t)n_reads * read_len > bases_bytes)
-        return fail(HAST_ERR_INVALID, "bases_bytes too small for %zu reads of %u", n_reads, read_len);
+        return set_error(HAST_ERR_INVALID, "bases_bytes too small for %zu reads of %u", n_reads, read_len);
     ClassifyArgs a;
     a.bases = d_bases;
     a.bases_bytes = bases_bytes;
@@ -1169,16 +1153,16 @@ static hast_status classify_rows(hast_ctx *c, const uint8_t *d_bases, size_t bas
     // The kernel only writes per-read votes; the per-barcode bookkeeping runs as a kernel of its own afterwards (its random
     // read-modify-writes cost 4x as much when they are interleaved with the probes' reads).  Without a votes buffer from
     // the caller the votes go to library scratch.
-    if (reinterpret_cast<uintptr_t>(d_votes) & 7) return fail(HAST_ERR_INVALID, "d_votes must be 8-byte aligned (a row is stored as one 64-bit word)");
+    if (reinterpret_cast<uintptr_t>(d_votes) & 7) return set_error(HAST_ERR_INVALID, "d_votes must be 8-byte aligned (a row is stored as one 64-bit word)");
     uint32_t *votes_buf = d_votes;
     if (d_barcode_ids && !votes_buf) {
         const size_t need = n_reads * 2 * sizeof(uint32_t);
         if (c->votes_bytes < need) {
-            HIP_TRY(hipStreamSynchronize(s ? (hipStream_t)s : c->stream));
-            if (c->d_votes_scratch) HIP_TRY(hipFree(c->d_votes_scratch));
+            HAST_HIP_TRY(hipStreamSynchronize(s ? (hipStream_t)s : c->stream));
+            if (c->d_votes_scratch) HAST_HIP_TRY(hipFree(c->d_votes_scratch));
             c->d_votes_scratch = nullptr;
             c->votes_bytes = 0;
-            HIP_TRY(dev_malloc(reinterpret_cast<void **>(&c->d_votes_scratch), need + need / 8));
+            HAST_HIP_TRY(dev_malloc(reinterpret_cast<void **>(&c->d_votes_scratch), need + need / 8));
             c->votes_bytes = need + need / 8;
         }
         votes_buf = c->d_votes_scratch;
@@ -1234,7 +1218,7 @@ static hast_status classify_rows(hast_ctx *c, const uint8_t *d_bases, size_t bas
     }
     a.tile_reads = tr;
     const size_t smem = per_read * tr + pad;
-    if (smem + (filt ? (size_t)kTmerLevelTableWords * 4 : 0) > (160u << 10)) return fail(HAST_ERR_INVALID, "read_len %u needs %zu B of LDS", read_len, smem);
+    if (smem + (filt ? (size_t)kTmerLevelTableWords * 4 : 0) > (160u << 10)) return set_error(HAST_ERR_INVALID, "read_len %u needs %zu B of LDS", read_len, smem);
     // __umulhi(q, magic) == q / d for every q the kernel forms (exact while q*d < 2^32)
     auto magic = [](uint64_t qmax, uint32_t d) -> uint32_t {
         if (d <= 1 || qmax * d >= (1ull << 32)) return 0;
@@ -1247,18 +1231,18 @@ static hast_status classify_rows(hast_ctx *c, const uint8_t *d_bases, size_t bas
     const uint64_t n_tiles = (n_reads + tr - 1) / tr;
     const int grid = (int)std::min<uint64_t>(n_tiles, (uint64_t)c->n_cu * 8);
     a.tile_queue = c->d_cnt + 3;
-    HIP_TRY(hipMemsetAsync(a.tile_queue, 0, sizeof(unsigned long long), hs));
+    HAST_HIP_TRY(hipMemsetAsync(a.tile_queue, 0, sizeof(unsigned long long), hs));
     hipEvent_t *ev = c->t_slots ? &c->t_ev[3 * (c->t_next % c->t_slots)] : nullptr;
-    if (ev) HIP_TRY(hipEventRecord(ev[0], hs));
-    HIP_TRY(filt ? launch_classify_f(a, grid, smem, (c->kernel_geo ? 1 : 0) | (c->kernel_rl ? 2 : 0), hs) : launch_classify(a, grid, smem, hs));
-    if (ev) HIP_TRY(hipEventRecord(ev[1], hs));
+    if (ev) HAST_HIP_TRY(hipEventRecord(ev[0], hs));
+    HAST_HIP_TRY(filt ? launch_classify_f(a, grid, smem, (c->kernel_geo ? 1 : 0) | (c->kernel_rl ? 2 : 0), hs) : launch_classify(a, grid, smem, hs));
+    if (ev) HAST_HIP_TRY(hipEventRecord(ev[1], hs));
     if (d_barcode_ids) {
         // per-barcode bookkeeping: one atomic per read, or -- large batches over many barcodes -- the pairs partitioned by barcode
         // range and summed in LDS (hast_kernels.hip, "partitioned commit"; HAST_COMMIT=atomic / partition forces either)
         if (hast_status st = commit_votes(c, votes_buf, d_barcode_ids, n_reads, a.max_pos, d_seg_read != nullptr, hs)) return st;
     }
     if (ev) {
-        HIP_TRY(hipEventRecord(ev[2], hs));
+        HAST_HIP_TRY(hipEventRecord(ev[2], hs));
         c->t_next++;
         c->t_count = std::min(c->t_count + 1, c->t_slots);
     }
@@ -1270,10 +1254,10 @@ static hast_status classify_segmented(hast_ctx *c, const uint8_t *d_bases, size_
                                       hipStream_t hs);
 
 hast_status hast_ctx_set_filter(hast_ctx *c, int enable, int m, int t, int kp) {
-    if (!c) return fail(HAST_ERR_INVALID, "null context");
-    if (m < 0 || m > c->k || m > kFilterMaxM) return fail(HAST_ERR_INVALID, "filter m=%d out of [0,%d]", m, std::min(c->k, kFilterMaxM));
-    if (t < 0 || (m && t > m)) return fail(HAST_ERR_INVALID, "filter t=%d out of [0,m]", t);
-    if (kp < 0 || kp > c->k || (kp && m && (kp < m || kp - m >= 32))) return fail(HAST_ERR_INVALID, "filter kp=%d out of [m,K]", kp);
+    if (!c) return set_error(HAST_ERR_INVALID, "null context");
+    if (m < 0 || m > c->k || m > kFilterMaxM) return set_error(HAST_ERR_INVALID, "filter m=%d out of [0,%d]", m, std::min(c->k, kFilterMaxM));
+    if (t < 0 || (m && t > m)) return set_error(HAST_ERR_INVALID, "filter t=%d out of [0,m]", t);
+    if (kp < 0 || kp > c->k || (kp && m && (kp < m || kp - m >= 32))) return set_error(HAST_ERR_INVALID, "filter kp=%d out of [m,K]", kp);
     c->use_filter = enable != 0;
     c->filter_fallback_bytes = 0;
     c->filter_exact = (enable == 2 || c->exact_env_off) ? 0 : (c->exact_env_once || c->filter_exact == 1) ? 1 : -1;
@@ -1286,25 +1270,25 @@ hast_status hast_ctx_set_filter(hast_ctx *c, int enable, int m, int t, int kp) {
 
 // Measurement switches of a live context (the environment is read once, in hast_ctx_create).
 hast_status hast_ctx_set_option(hast_ctx *c, const char *name, long value) {
-    if (!c || !name) return fail(HAST_ERR_INVALID, "null argument");
+    if (!c || !name) return set_error(HAST_ERR_INVALID, "null argument");
     if (!strcmp(name, "commit")) {
-        if (value < 0 || value > 2) return fail(HAST_ERR_INVALID, "commit: 0 = by batch size, 1 = atomic, 2 = partitioned");
+        if (value < 0 || value > 2) return set_error(HAST_ERR_INVALID, "commit: 0 = by batch size, 1 = atomic, 2 = partitioned");
         c->commit_mode = (int)value;
     } else if (!strcmp(name, "kernel_geo")) c->kernel_geo = value != 0;
     else if (!strcmp(name, "kernel_rl")) c->kernel_rl = value != 0;
     else if (!strcmp(name, "tile_lds")) {
-        if (value && (value < 4096 || value > 160 * 1024)) return fail(HAST_ERR_INVALID, "tile_lds %ld out of [4096, 163840]", value);
+        if (value && (value < 4096 || value > 160 * 1024)) return set_error(HAST_ERR_INVALID, "tile_lds %ld out of [4096, 163840]", value);
         c->tile_lds = (size_t)value;
     } else if (!strcmp(name, "filter_exact_once")) {
         // exact entries filed once per strand (the sampled scheme) instead of under every m-mer; prints stay prints
         if (c->filter_exact != 0) c->filter_exact = value ? 1 : (c->exact_env_once ? 1 : -1);
         c->filter_valid = false;
-    } else return fail(HAST_ERR_INVALID, "unknown option %s", name);
+    } else return set_error(HAST_ERR_INVALID, "unknown option %s", name);
     return HAST_OK;
 }
 // the switches that differ from their defaults, as "name=value name=value" ("" when there are none): what --stats prints
 hast_status hast_ctx_options(const hast_ctx *c, char *out, size_t cap) {
-    if (!c || !out || !cap) return fail(HAST_ERR_INVALID, "null argument");
+    if (!c || !out || !cap) return set_error(HAST_ERR_INVALID, "null argument");
     std::string s;
     auto add = [&](const char *n, long v) { s += (s.empty() ? "" : " "); s += n; s += "=" + std::to_string(v); };
     if (!c->use_filter) add("filter", 0);
@@ -1327,12 +1311,12 @@ hast_status hast_filter_build(hast_ctx *c) {
     if (hast_status st = need_table(c, 0)) return st;
     if (!c->use_filter) return HAST_OK;
     if (hast_status st = ensure_filter(c, c->stream)) return st;
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HAST_HIP_TRY(hipStreamSynchronize(c->stream));
     return HAST_OK;
 }
 
 hast_status hast_filter_info(const hast_ctx *c, int *enabled, int *m, int *t, int *kp, uint64_t *bytes) {
-    if (!c) return fail(HAST_ERR_INVALID, "null context");
+    if (!c) return set_error(HAST_ERR_INVALID, "null context");
     if (enabled) *enabled = !c->use_filter ? 0 : (c->filter_valid && c->fg.exact) ? 2 : 1;
     if (m) *m = c->filter_valid ? c->fg.m : 0;
     if (t) *t = c->filter_valid ? c->fg.t : 0;
@@ -1343,7 +1327,7 @@ hast_status hast_filter_info(const hast_ctx *c, int *enabled, int *m, int *t, in
 
 // 1: the filter built for the current table holds exact entries filed under every m-mer (FilterGeom::dense), 0: anything else
 hast_status hast_filter_dense(const hast_ctx *c, int *dense) {
-    if (!c || !dense) return fail(HAST_ERR_INVALID, "null argument");
+    if (!c || !dense) return set_error(HAST_ERR_INVALID, "null argument");
     *dense = (c->use_filter && c->filter_valid && c->fg.dense) ? 1 : 0;
     return HAST_OK;
 }
@@ -1354,10 +1338,10 @@ hast_status hast_filter_dense(const hast_ctx *c, int *dense) {
 // 47.5 G/s over 6 GB, 45.6 over 137 GB, profiles/round3_hbm_randread_footprint.jsonl).
 hast_status hast_filter_request_ceiling(hast_ctx *c, double *requests_per_s) {
     if (hast_status st = need_table(c, 0)) return st;
-    if (!requests_per_s) return fail(HAST_ERR_INVALID, "null argument");
-    if (!c->use_filter) return fail(HAST_ERR_INVALID, "the filter is off");
+    if (!requests_per_s) return set_error(HAST_ERR_INVALID, "null argument");
+    if (!c->use_filter) return set_error(HAST_ERR_INVALID, "the filter is off");
     if (hast_status st = ensure_filter(c, c->stream)) return st;
-    if (!c->use_filter || !c->d_filter) return fail(HAST_ERR_INVALID, "no filter (HBM too small for it)");
+    if (!c->use_filter || !c->d_filter) return set_error(HAST_ERR_INVALID, "no filter (HBM too small for it)");
     const uint64_t nblocks = filter_nblocks(c->fg);
     const int grid = c->n_cu * 8;
     const uint32_t iters = 256;                                    // 2048 x 32 groups x 1024 blocks = 67M requests = 8.6 GB
@@ -1377,7 +1361,7 @@ hast_status hast_filter_request_ceiling(hast_ctx *c, double *requests_per_s) {
     }
     if (e0) (void)hipEventDestroy(e0);                             // (also on the error paths)
     if (e1) (void)hipEventDestroy(e1);
-    if (e != hipSuccess) return fail(HAST_ERR_HIP, "request ceiling: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return set_error(HAST_ERR_HIP, "request ceiling: %s", hipGetErrorString(e));
     *requests_per_s = (double)grid * 32.0 * 4.0 * (double)iters / ((double)best * 1e-3);
     return HAST_OK;
 }
@@ -1389,20 +1373,20 @@ hast_status hast_classify_timing(hast_ctx *c, int n_slots) {
     c->t_slots = c->t_next = c->t_count = 0;
     if (n_slots <= 0) return HAST_OK;
     c->t_ev.resize(3 * (size_t)n_slots);
-    for (hipEvent_t &e : c->t_ev) HIP_TRY(hipEventCreate(&e));
+    for (hipEvent_t &e : c->t_ev) HAST_HIP_TRY(hipEventCreate(&e));
     c->t_slots = (size_t)n_slots;
     return HAST_OK;
 }
 hast_status hast_classify_times(hast_ctx *c, float *classify_ms, float *commit_ms, int max, int *n_out) {
     if (hast_status st = use(c)) return st;
-    if (!n_out || (max > 0 && (!classify_ms || !commit_ms))) return fail(HAST_ERR_INVALID, "null argument");
+    if (!n_out || (max > 0 && (!classify_ms || !commit_ms))) return set_error(HAST_ERR_INVALID, "null argument");
     int n = 0;
     const size_t first = c->t_next - c->t_count;
     for (size_t i = 0; i < c->t_count && n < max; ++i, ++n) {
         hipEvent_t *ev = &c->t_ev[3 * ((first + i) % c->t_slots)];
-        HIP_TRY(hipEventSynchronize(ev[2]));
-        HIP_TRY(hipEventElapsedTime(&classify_ms[n], ev[0], ev[1]));
-        HIP_TRY(hipEventElapsedTime(&commit_ms[n], ev[1], ev[2]));
+        HAST_HIP_TRY(hipEventSynchronize(ev[2]));
+        HAST_HIP_TRY(hipEventElapsedTime(&classify_ms[n], ev[0], ev[1]));
+        HAST_HIP_TRY(hipEventElapsedTime(&commit_ms[n], ev[1], ev[2]));
     }
     *n_out = n;
     c->t_count = 0;
@@ -1415,10 +1399,10 @@ hast_status hast_classify_device(hast_ctx *c, const uint8_t *d_bases, size_t bas
     if (read_len > kLongRead && c && c->d_slots && n_reads) {
         // stage-01 semantics on long reads (with offsets or of one fixed length): whole-read N skip by a pre-pass, windows
         // through segments
-        if (d_barcode_ids && !c->d_counts) return fail(HAST_ERR_INVALID, "barcode ids given but no counters bound");
-        if (!d_bases) return fail(HAST_ERR_INVALID, "d_bases is null");
+        if (d_barcode_ids && !c->d_counts) return set_error(HAST_ERR_INVALID, "barcode ids given but no counters bound");
+        if (!d_bases) return set_error(HAST_ERR_INVALID, "d_bases is null");
         if (!d_offsets && (uint64_t)n_reads * read_len > bases_bytes)
-            return fail(HAST_ERR_INVALID, "bases_bytes too small for %zu reads of %u", n_reads, read_len);
+            return set_error(HAST_ERR_INVALID, "bases_bytes too small for %zu reads of %u", n_reads, read_len);
         if (hast_status st = use(c)) return st;
         return classify_segmented(c, d_bases, bases_bytes, d_offsets, nullptr, read_len, n_reads, 0, d_barcode_ids, d_votes, s ? (hipStream_t)s : c->stream);
     }
@@ -1430,10 +1414,10 @@ hast_status hast_classify_device(hast_ctx *c, const uint8_t *d_bases, size_t bas
 hast_status hast_counts_add_votes(hast_ctx *c, const uint32_t *d_votes, const uint32_t *d_barcode_ids, size_t n_reads, uint32_t max_votes,
                                   hast_stream s) {
     if (hast_status st = use(c)) return st;
-    if (!c->d_counts) return fail(HAST_ERR_INVALID, "no counters: call hast_counts_resize/bind");
+    if (!c->d_counts) return set_error(HAST_ERR_INVALID, "no counters: call hast_counts_resize/bind");
     if (n_reads == 0) return HAST_OK;
-    if (!d_votes || !d_barcode_ids) return fail(HAST_ERR_INVALID, "null argument");
-    if (reinterpret_cast<uintptr_t>(d_votes) & 7) return fail(HAST_ERR_INVALID, "d_votes must be 8-byte aligned");
+    if (!d_votes || !d_barcode_ids) return set_error(HAST_ERR_INVALID, "null argument");
+    if (reinterpret_cast<uintptr_t>(d_votes) & 7) return set_error(HAST_ERR_INVALID, "d_votes must be 8-byte aligned");
     return commit_votes(c, d_votes, d_barcode_ids, n_reads, max_votes, false, s ? (hipStream_t)s : c->stream);
 }
 
@@ -1448,11 +1432,11 @@ static hast_status classify_segmented(hast_ctx *c, const uint8_t *d_bases, size_
     const size_t votes_b = ((n_reads * 2 * sizeof(uint32_t) + 255) & ~(size_t)255), flags_b = ((n_reads + 255) & ~(size_t)255);
     const size_t need = max_seg * (sizeof(uint64_t) + 2 * sizeof(uint32_t)) + votes_b + flags_b + 256;
     if (c->seg_bytes < need) {
-        HIP_TRY(hipStreamSynchronize(hs));
-        if (c->d_seg) HIP_TRY(hipFree(c->d_seg));
+        HAST_HIP_TRY(hipStreamSynchronize(hs));
+        if (c->d_seg) HAST_HIP_TRY(hipFree(c->d_seg));
         c->d_seg = nullptr;
         c->seg_bytes = 0;
-        HIP_TRY(dev_malloc(&c->d_seg, need + need / 4));
+        HAST_HIP_TRY(dev_malloc(&c->d_seg, need + need / 4));
         c->seg_bytes = need + need / 4;
     }
     uint32_t *acc = (uint32_t *)c->d_seg;                                  // per-read vote accumulator
@@ -1464,21 +1448,21 @@ static hast_status classify_segmented(hast_ctx *c, const uint8_t *d_bases, size_
     // strict callers own an output row per read; otherwise accumulate privately and commit afterwards
     uint32_t *target = strict ? d_votes_out : acc;
     unsigned long long *d_nseg = c->d_cnt + 4;                           // (its own word: ensure_filter counts tags in [0..1])
-    HIP_TRY(hipMemsetAsync(d_nseg, 0, sizeof(unsigned long long), hs));
-    HIP_TRY(hipMemsetAsync(target, 0, n_reads * 2 * sizeof(uint32_t), hs));
-    if (!strict) HIP_TRY(launch_scan_n(d_bases, d_offsets, d_lens, fixed_len, n_reads, has_n, hs));
-    HIP_TRY(launch_build_segments(d_offsets, d_lens, fixed_len, n_reads, c->k, kSegWindows, seg_off, seg_len, seg_read, d_nseg,
+    HAST_HIP_TRY(hipMemsetAsync(d_nseg, 0, sizeof(unsigned long long), hs));
+    HAST_HIP_TRY(hipMemsetAsync(target, 0, n_reads * 2 * sizeof(uint32_t), hs));
+    if (!strict) HAST_HIP_TRY(launch_scan_n(d_bases, d_offsets, d_lens, fixed_len, n_reads, has_n, hs));
+    HAST_HIP_TRY(launch_build_segments(d_offsets, d_lens, fixed_len, n_reads, c->k, kSegWindows, seg_off, seg_len, seg_read, d_nseg,
                                   strict ? nullptr : has_n, (uint64_t)max_seg, (uint64_t)bases_bytes, c->d_err + 1, hs));
     // the number of segments stays on the device (no host round trip between the two kernels): the classify kernel reads it
     // from d_nseg and is launched for the most segments there can be -- every read has at least one, every further one
     // covers kSegWindows more bases -- which the table was sized for above
     // (offsets that overlap or run backwards make the lengths add up to more: k_build_segments drops such rows and raises
     // c->d_err[1], which hast_stream_sync / hast_counts_read / the synchronous calls report)
-    if (max_seg > cap) return fail(HAST_ERR_INVALID, "segment table too small (%zu > %zu)", max_seg, cap);
+    if (max_seg > cap) return set_error(HAST_ERR_INVALID, "segment table too small (%zu > %zu)", max_seg, cap);
     if (hast_status st = classify_rows(c, d_bases, bases_bytes, seg_off, seg_len, seg_read, strict, kSegWindows + (uint32_t)c->k - 1,
                                        nullptr, target, max_seg, hs, d_nseg))
         return st;
-    if (!strict) HIP_TRY(launch_commit_votes(acc, d_barcode_ids, c->d_counts, d_votes_out, n_reads, hs));
+    if (!strict) HAST_HIP_TRY(launch_commit_votes(acc, d_barcode_ids, c->d_counts, d_votes_out, n_reads, hs));
     return HAST_OK;
 }
 
@@ -1486,7 +1470,7 @@ hast_status hast_classify_perread_device(hast_ctx *c, const uint8_t *d_bases, si
                                          size_t n_reads, uint32_t *d_votes, hast_stream s) {
     if (hast_status st = need_table(c, 0)) return st;
     if (n_reads == 0) return HAST_OK;
-    if (!d_bases || !d_offsets || !d_votes) return fail(HAST_ERR_INVALID, "null argument");
+    if (!d_bases || !d_offsets || !d_votes) return set_error(HAST_ERR_INVALID, "null argument");
     return classify_segmented(c, d_bases, bases_bytes, d_offsets, nullptr, 0, n_reads, 1, nullptr, d_votes, s ? (hipStream_t)s : c->stream);
 }
 
@@ -1494,7 +1478,7 @@ hast_status hast_classify_perread(hast_ctx *c, const uint8_t *bases, const uint6
                                   uint32_t *votes_out) {
     if (hast_status st = need_table(c, 0)) return st;
     if (n_reads == 0) return HAST_OK;
-    if (!bases || !offsets || !votes_out) return fail(HAST_ERR_INVALID, "null argument");
+    if (!bases || !offsets || !votes_out) return set_error(HAST_ERR_INVALID, "null argument");
     const size_t nbytes = offsets[n_reads] - offsets[0];
     const size_t ob = (n_reads + 1) * sizeof(uint64_t), vb = n_reads * 2 * sizeof(uint32_t);
     const size_t total = ((nbytes + 255) & ~(size_t)255) + ((ob + 255) & ~(size_t)255) + vb + 256;
@@ -1504,40 +1488,40 @@ hast_status hast_classify_perread(hast_ctx *c, const uint8_t *bases, const uint6
     uint32_t *d_v = (uint32_t *)((uint8_t *)d_o + ((ob + 255) & ~(size_t)255));
     std::vector<uint64_t> rel(n_reads + 1);
     for (size_t i = 0; i <= n_reads; i++) rel[i] = offsets[i] - offsets[0];
-    if (nbytes) HIP_TRY(hipMemcpyAsync(d_b, bases + offsets[0], nbytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_o, rel.data(), ob, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));        // rel is a local
+    if (nbytes) HAST_HIP_TRY(hipMemcpyAsync(d_b, bases + offsets[0], nbytes, hipMemcpyHostToDevice, c->stream));
+    HAST_HIP_TRY(hipMemcpyAsync(d_o, rel.data(), ob, hipMemcpyHostToDevice, c->stream));
+    HAST_HIP_TRY(hipStreamSynchronize(c->stream));        // rel is a local
     if (hast_status st = hast_classify_perread_device(c, d_b, nbytes ? nbytes : 1, d_o, n_reads, d_v, c->stream)) return st;
-    HIP_TRY(hipMemcpyAsync(votes_out, d_v, vb, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HAST_HIP_TRY(hipMemcpyAsync(votes_out, d_v, vb, hipMemcpyDeviceToHost, c->stream));
+    HAST_HIP_TRY(hipStreamSynchronize(c->stream));
     return check_classify_err(c, c->stream);
 }
 
 static hast_status stage_reserve(hast_ctx *c, Staging &s, size_t nbytes, size_t nreads) {
     (void)c;
     if (s.cap_bases < nbytes) {
-        if (s.h_bases) HIP_TRY(hipHostFree(s.h_bases));
-        if (s.d_bases) HIP_TRY(hipFree(s.d_bases));
+        if (s.h_bases) HAST_HIP_TRY(hipHostFree(s.h_bases));
+        if (s.d_bases) HAST_HIP_TRY(hipFree(s.d_bases));
         s.h_bases = s.d_bases = nullptr;
         s.cap_bases = 0;
         size_t cap = nbytes + nbytes / 4 + 64;
-        HIP_TRY(pinned_malloc((void **)&s.h_bases, cap, hipHostMallocDefault));
-        HIP_TRY(dev_malloc((void **)&s.d_bases, cap));
+        HAST_HIP_TRY(pinned_malloc((void **)&s.h_bases, cap, hipHostMallocDefault));
+        HAST_HIP_TRY(dev_malloc((void **)&s.d_bases, cap));
         s.cap_bases = cap;
     }
     if (s.cap_reads < nreads) {
-        if (s.h_off) HIP_TRY(hipHostFree(s.h_off));
-        if (s.h_ids) HIP_TRY(hipHostFree(s.h_ids));
-        if (s.d_off) HIP_TRY(hipFree(s.d_off));
-        if (s.d_ids) HIP_TRY(hipFree(s.d_ids));
+        if (s.h_off) HAST_HIP_TRY(hipHostFree(s.h_off));
+        if (s.h_ids) HAST_HIP_TRY(hipHostFree(s.h_ids));
+        if (s.d_off) HAST_HIP_TRY(hipFree(s.d_off));
+        if (s.d_ids) HAST_HIP_TRY(hipFree(s.d_ids));
         s.h_off = s.d_off = nullptr;
         s.h_ids = s.d_ids = nullptr;
         s.cap_reads = 0;
         size_t cap = nreads + nreads / 4 + 16;
-        HIP_TRY(pinned_malloc((void **)&s.h_off, (cap + 1) * sizeof(uint64_t), hipHostMallocDefault));
-        HIP_TRY(pinned_malloc((void **)&s.h_ids, cap * sizeof(uint32_t), hipHostMallocDefault));
-        HIP_TRY(dev_malloc((void **)&s.d_off, (cap + 1) * sizeof(uint64_t)));
-        HIP_TRY(dev_malloc((void **)&s.d_ids, cap * sizeof(uint32_t)));
+        HAST_HIP_TRY(pinned_malloc((void **)&s.h_off, (cap + 1) * sizeof(uint64_t), hipHostMallocDefault));
+        HAST_HIP_TRY(pinned_malloc((void **)&s.h_ids, cap * sizeof(uint32_t), hipHostMallocDefault));
+        HAST_HIP_TRY(dev_malloc((void **)&s.d_off, (cap + 1) * sizeof(uint64_t)));
+        HAST_HIP_TRY(dev_malloc((void **)&s.d_ids, cap * sizeof(uint32_t)));
         s.cap_reads = cap;
     }
     return HAST_OK;
@@ -1546,11 +1530,11 @@ static hast_status stage_reserve(hast_ctx *c, Staging &s, size_t nbytes, size_t 
 hast_status hast_batch_begin(hast_ctx *c, size_t bases_capacity, size_t reads_capacity, uint8_t **bases,
                              uint64_t **offsets, uint32_t **ids) {
     if (hast_status st = need_table(c, 0)) return st;
-    if (!bases || !offsets || !ids) return fail(HAST_ERR_INVALID, "null argument");
-    if (!c->d_counts) return fail(HAST_ERR_INVALID, "no counters bound");
+    if (!bases || !offsets || !ids) return set_error(HAST_ERR_INVALID, "null argument");
+    if (!c->d_counts) return set_error(HAST_ERR_INVALID, "no counters bound");
     Staging &s = c->stage[c->batch_no & 1];
     if (s.in_flight) {
-        HIP_TRY(hipEventSynchronize(s.done));
+        HAST_HIP_TRY(hipEventSynchronize(s.done));
         s.in_flight = false;
     }
     if (hast_status st = stage_reserve(c, s, bases_capacity, reads_capacity)) return st;
@@ -1564,24 +1548,24 @@ hast_status hast_batch_submit(hast_ctx *c, size_t n_reads, uint32_t max_read_len
     if (hast_status st = need_table(c, 0)) return st;
     Staging &s = c->stage[c->batch_no & 1];
     if (n_reads == 0) return HAST_OK;
-    if (n_reads > s.cap_reads) return fail(HAST_ERR_INVALID, "batch of %zu reads exceeds the staged capacity", n_reads);
+    if (n_reads > s.cap_reads) return set_error(HAST_ERR_INVALID, "batch of %zu reads exceeds the staged capacity", n_reads);
     const size_t nbytes = s.h_off[n_reads];
-    if (nbytes > s.cap_bases || s.h_off[0] != 0) return fail(HAST_ERR_INVALID, "bad staged offsets");
+    if (nbytes > s.cap_bases || s.h_off[0] != 0) return set_error(HAST_ERR_INVALID, "bad staged offsets");
     c->batch_no++;
-    if (nbytes) HIP_TRY(hipMemcpyAsync(s.d_bases, s.h_bases, nbytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(s.d_off, s.h_off, (n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(s.d_ids, s.h_ids, n_reads * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    if (nbytes) HAST_HIP_TRY(hipMemcpyAsync(s.d_bases, s.h_bases, nbytes, hipMemcpyHostToDevice, c->stream));
+    HAST_HIP_TRY(hipMemcpyAsync(s.d_off, s.h_off, (n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    HAST_HIP_TRY(hipMemcpyAsync(s.d_ids, s.h_ids, n_reads * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     hast_status st = hast_classify_device(c, s.d_bases, nbytes ? nbytes : 1, s.d_off, max_read_len ? max_read_len : 1, s.d_ids,
                                           nullptr, n_reads, c->stream);
-    HIP_TRY(hipEventRecord(s.done, c->stream));
+    HAST_HIP_TRY(hipEventRecord(s.done, c->stream));
     s.in_flight = true;
     return st;
 }
 
 hast_status hast_classify_batch(hast_ctx *c, const uint8_t *bases, const uint64_t *offsets, const uint32_t *ids,
                                 size_t n_reads, uint32_t max_read_len) {
-    if (n_reads == 0) return c ? HAST_OK : fail(HAST_ERR_INVALID, "null context");
-    if (!bases || !offsets || !ids) return fail(HAST_ERR_INVALID, "null argument");
+    if (n_reads == 0) return c ? HAST_OK : set_error(HAST_ERR_INVALID, "null context");
+    if (!bases || !offsets || !ids) return set_error(HAST_ERR_INVALID, "null argument");
     const size_t nbytes = offsets[n_reads] - offsets[0];
     uint8_t *hb;
     uint64_t *ho;
@@ -1607,8 +1591,8 @@ hast_status classify_framed(hast_ctx *c, const uint8_t *d_buf, size_t buf_bytes,
 }
 hast_status commit_framed(hast_ctx *c, const uint32_t *d_votes, const uint32_t *d_ids, size_t n_reads, hipStream_t hs) {
     if (hast_status st = use(c)) return st;
-    if (!c->d_counts) return fail(HAST_ERR_INVALID, "no counters bound");
-    HIP_TRY(launch_commit_votes(d_votes, d_ids, c->d_counts, nullptr, n_reads, hs));
+    if (!c->d_counts) return set_error(HAST_ERR_INVALID, "no counters bound");
+    HAST_HIP_TRY(launch_commit_votes(d_votes, d_ids, c->d_counts, nullptr, n_reads, hs));
     return HAST_OK;
 }
 hipStream_t ctx_stream_of(hast_ctx *c) { return c->stream; }
@@ -1687,7 +1671,7 @@ hast_status hast_synth_keys_host(const hast_synth_params *p, int hap, uint64_t f
 hast_status hast_synth_reads_host(const hast_synth_params *p, uint64_t first, size_t n, uint8_t *bases, uint32_t *ids) {
     if (hast_status st = check_synth(p)) return st;
     SynthParams sp = resolve(p);
-    if (sp.read_len == 0) return fail(HAST_ERR_INVALID, "read_len is 0");
+    if (sp.read_len == 0) return set_error(HAST_ERR_INVALID, "read_len is 0");
     for (size_t i = 0; i < n; i++) {
         uint32_t bc;
         synth_read(sp, first + i, bases + i * (size_t)sp.read_len, &bc);
@@ -1700,7 +1684,7 @@ hast_status hast_synth_keys_device(hast_ctx *c, const hast_synth_params *p, int 
                                    uint64_t *d_out, hast_stream s) {
     if (hast_status st = use(c)) return st;
     if (hast_status st = check_synth(p)) return st;
-    HIP_TRY(launch_synth_keys(resolve(p), hap, first, n, d_out, s ? (hipStream_t)s : c->stream));
+    HAST_HIP_TRY(launch_synth_keys(resolve(p), hap, first, n, d_out, s ? (hipStream_t)s : c->stream));
     return HAST_OK;
 }
 
@@ -1708,15 +1692,15 @@ hast_status hast_synth_reads_device(hast_ctx *c, const hast_synth_params *p, uin
                                     uint32_t *d_ids, hast_stream s) {
     if (hast_status st = use(c)) return st;
     if (hast_status st = check_synth(p)) return st;
-    if (p->read_len == 0) return fail(HAST_ERR_INVALID, "read_len is 0");
-    HIP_TRY(launch_synth_reads(resolve(p), first, n, d_bases, d_ids, s ? (hipStream_t)s : c->stream));
+    if (p->read_len == 0) return set_error(HAST_ERR_INVALID, "read_len is 0");
+    HAST_HIP_TRY(launch_synth_reads(resolve(p), first, n, d_bases, d_ids, s ? (hipStream_t)s : c->stream));
     return HAST_OK;
 }
 
 hast_status hast_synth_table_build(hast_ctx *c, const hast_synth_params *p) {
     if (hast_status st = need_table(c, 0)) return st;
     if (hast_status st = check_synth(p)) return st;
-    if ((int)p->k != c->k) return fail(HAST_ERR_INVALID, "synth k=%u != context K=%d", p->k, c->k);
+    if ((int)p->k != c->k) return set_error(HAST_ERR_INVALID, "synth k=%u != context K=%d", p->k, c->k);
     table_changed(c);
     SynthParams sp = resolve(p);
     const size_t per = kChunkBytes / sizeof(uint64_t);
@@ -1724,8 +1708,8 @@ hast_status hast_synth_table_build(hast_ctx *c, const hast_synth_params *p) {
     for (int hap = 0; hap < 2; hap++)
         for (uint64_t i = 0; i < sp.n_keys_per_hap; i += per) {
             size_t m = (size_t)std::min<uint64_t>(per, sp.n_keys_per_hap - i);
-            HIP_TRY(launch_synth_keys(sp, hap, i, m, (uint64_t *)c->d_scratch, c->stream));
-            HIP_TRY(launch_insert_keys(c->d_slots, geom(c), (const uint64_t *)c->d_scratch, m, (uint32_t)hap, c->d_err, c->stream));
+            HAST_HIP_TRY(launch_synth_keys(sp, hap, i, m, (uint64_t *)c->d_scratch, c->stream));
+            HAST_HIP_TRY(launch_insert_keys(c->d_slots, geom(c), (const uint64_t *)c->d_scratch, m, (uint32_t)hap, c->d_err, c->stream));
         }
     return check_err_word(c, c->stream);
 }

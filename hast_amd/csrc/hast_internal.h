@@ -6,6 +6,13 @@
 
 namespace hast {
 hast_status set_error(hast_status st, const char *fmt, ...) __attribute__((format(printf, 2, 3)));   // text for hast_last_error()
+// a HIP call that failed ends the ABI function it is in: its text for hast_last_error(), out of memory told apart
+#define HAST_HIP_TRY(expr)                                                                                                              \
+    do {                                                                                                                                \
+        const hipError_t e_ = (expr);                                                                                                   \
+        if (e_ != hipSuccess)                                                                                                           \
+            return hast::set_error(e_ == hipErrorOutOfMemory ? HAST_ERR_OOM : HAST_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));    \
+    } while (0)
 int default_minimizer_for(int k);                                                                    // honours HAST_MINIMIZER
 // reads given as starts + lengths inside one device buffer (FASTQ framed on the GPU, fq_api.cpp): per-read votes only ...
 hast_status classify_framed(hast_ctx *c, const uint8_t *d_buf, size_t buf_bytes, const uint64_t *d_off, const uint32_t *d_len, uint32_t max_len,

@@ -15,14 +15,6 @@
 
 using namespace hast;
 
-#define KC_TRY(expr)                                                                                  \
-    do {                                                                                              \
-        hipError_t e_ = (expr);                                                                       \
-        if (e_ != hipSuccess)                                                                         \
-            return set_error(e_ == hipErrorOutOfMemory ? HAST_ERR_OOM : HAST_ERR_HIP, "%s: %s", #expr, \
-                             hipGetErrorString(e_));                                                  \
-    } while (0)
-
 namespace {
 constexpr size_t kStageBytes = 64u << 20;      // one pinned/device staging buffer of hast_kc_count
 struct KcStage {
@@ -77,7 +69,7 @@ struct hast_kc {
 namespace {
 hast_status use(hast_kc *c) {
     if (!c) return set_error(HAST_ERR_INVALID, "null k-mer count context");
-    KC_TRY(hipSetDevice(c->device));
+    HAST_HIP_TRY(hipSetDevice(c->device));
     return HAST_OK;
 }
 hast_status need_table(hast_kc *c) {
@@ -160,7 +152,7 @@ static void part_setup(hast_kc *c) {
 // a table that is empty by declaration only (c->fresh) is cleared for real
 static hast_status table_real(hast_kc *c) {
     if (!c->fresh) return HAST_OK;
-    KC_TRY(launch_kc_clear(c->d_table, c->nbuckets, c->stream));
+    HAST_HIP_TRY(launch_kc_clear(c->d_table, c->nbuckets, c->stream));
     c->fresh = false;
     return HAST_OK;
 }
@@ -171,7 +163,7 @@ static hast_status table_empty(hast_kc *c) {
     const bool lazy = !(e && !strcmp(e, "0"));
     c->fresh = c->part_on && lazy;
     if (c->fresh) return HAST_OK;
-    KC_TRY(launch_kc_clear(c->d_table, c->nbuckets, c->stream));
+    HAST_HIP_TRY(launch_kc_clear(c->d_table, c->nbuckets, c->stream));
     return HAST_OK;
 }
 
@@ -179,8 +171,8 @@ static hast_status table_empty(hast_kc *c) {
 static hast_status part_flush(hast_kc *c) {
     if (!c->part_on || c->est_records == 0) return table_real(c);
     unsigned long long cur = 0;
-    KC_TRY(hipMemcpyAsync(&cur, c->d_small + kRecCursor, sizeof(cur), hipMemcpyDeviceToHost, c->stream));
-    KC_TRY(hipStreamSynchronize(c->stream));
+    HAST_HIP_TRY(hipMemcpyAsync(&cur, c->d_small + kRecCursor, sizeof(cur), hipMemcpyDeviceToHost, c->stream));
+    HAST_HIP_TRY(hipStreamSynchronize(c->stream));
     const uint64_t n = std::min<uint64_t>(cur, c->rec_cap);
     KcFlushArgs a;
     a.table = c->d_table;
@@ -214,12 +206,12 @@ static hast_status part_flush(hast_kc *c) {
             if (hast_status st = table_real(c)) return st;
         } else a.fresh = 1;
     }
-    KC_TRY(launch_kc_flush(a, c->stream));
+    HAST_HIP_TRY(launch_kc_flush(a, c->stream));
     c->fresh = false;
     unsigned long long sp = 0;
-    KC_TRY(hipMemcpyAsync(&sp, c->d_small + kSpillN, sizeof(sp), hipMemcpyDeviceToHost, c->stream));
-    KC_TRY(hipMemsetAsync(c->d_small + kRecCursor, 0, 2 * sizeof(unsigned long long), c->stream));      // cursor and spill count
-    KC_TRY(hipStreamSynchronize(c->stream));
+    HAST_HIP_TRY(hipMemcpyAsync(&sp, c->d_small + kSpillN, sizeof(sp), hipMemcpyDeviceToHost, c->stream));
+    HAST_HIP_TRY(hipMemsetAsync(c->d_small + kRecCursor, 0, 2 * sizeof(unsigned long long), c->stream));      // cursor and spill count
+    HAST_HIP_TRY(hipStreamSynchronize(c->stream));
     c->est_records = c->est_after = 0;
     c->cur_pending = false;                        // (the stream has been waited for: a copy of the old cursor is history)
     c->n_flushes++;
@@ -238,7 +230,7 @@ hast_status hast_kc_create_ex(int device, int k, size_t table_bytes, uint64_t ex
     if (e != hipSuccess || n <= 0)
         return set_error(HAST_ERR_NO_DEVICE, "no HIP device (%s); libhast has no CPU path", hipGetErrorString(e));
     if (device < 0 || device >= n) return set_error(HAST_ERR_NO_DEVICE, "device %d not in [0,%d)", device, n);
-    KC_TRY(hipSetDevice(device));
+    HAST_HIP_TRY(hipSetDevice(device));
     hast_kc *c = new (std::nothrow) hast_kc();
     if (!c) return set_error(HAST_ERR_OOM, "host allocation failed");
     c->device = device;
@@ -327,16 +319,16 @@ hast_status hast_kc_set_slice(hast_kc *c, uint32_t slice, uint32_t n_slices) {
     c->slice = slice;
     c->n_slices = n_slices;
     if (hast_status st = table_empty(c)) return st;
-    KC_TRY(hipMemsetAsync(c->d_small, 0, kSmallWords * sizeof(unsigned long long), c->stream));
-    KC_TRY(hipMemsetAsync(c->d_err, 0, 4 * sizeof(uint32_t), c->stream));
+    HAST_HIP_TRY(hipMemsetAsync(c->d_small, 0, kSmallWords * sizeof(unsigned long long), c->stream));
+    HAST_HIP_TRY(hipMemsetAsync(c->d_err, 0, 4 * sizeof(uint32_t), c->stream));
     if (c->err_pending) {                          // a copy of the old word may still be in flight
-        KC_TRY(hipEventSynchronize(c->err_ev));
+        HAST_HIP_TRY(hipEventSynchronize(c->err_ev));
         c->err_pending = false;
     }
     *c->h_err = 0;
     c->est_records = c->est_after = 0;             // (records of the old slice are void with its table; the cursor words were zeroed above)
     if (c->cur_pending) {
-        KC_TRY(hipEventSynchronize(c->cur_ev));
+        HAST_HIP_TRY(hipEventSynchronize(c->cur_ev));
         c->cur_pending = false;
     }
     return HAST_OK;
@@ -385,8 +377,8 @@ static hast_status count_launch(hast_kc *c, int parent, const uint8_t *d_bytes, 
         }
         if (c->est_records + worst > c->rec_cap) {     // before the table is swept: what does the device say, now?  (a flush waits for
             // everything launched so far as well)
-            KC_TRY(hipMemcpyAsync(c->h_cursor, c->d_small + kRecCursor, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-            KC_TRY(hipStreamSynchronize(c->stream));
+            HAST_HIP_TRY(hipMemcpyAsync(c->h_cursor, c->d_small + kRecCursor, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+            HAST_HIP_TRY(hipStreamSynchronize(c->stream));
             c->est_records = std::min<uint64_t>(c->est_records, (uint64_t)*c->h_cursor);
             c->cur_pending = false;
             c->est_after = 0;
@@ -404,12 +396,12 @@ static hast_status count_launch(hast_kc *c, int parent, const uint8_t *d_bytes, 
     }
     const size_t n_tiles = (n_starts + a.tile_bases - 1) / a.tile_bases;
     const unsigned grid = (unsigned)std::min<size_t>(n_tiles, (size_t)c->n_cu * (c->part_on ? 4 : 8));
-    KC_TRY(hipMemsetAsync(c->d_small + kQueue, 0, sizeof(unsigned long long), c->stream));
-    KC_TRY(launch_kc_count(a, grid, c->stream));
+    HAST_HIP_TRY(hipMemsetAsync(c->d_small + kQueue, 0, sizeof(unsigned long long), c->stream));
+    HAST_HIP_TRY(launch_kc_count(a, grid, c->stream));
     if (c->part_on) {
         if (!c->cur_pending) {
-            KC_TRY(hipMemcpyAsync(c->h_cursor, c->d_small + kRecCursor, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-            KC_TRY(hipEventRecord(c->cur_ev, c->stream));
+            HAST_HIP_TRY(hipMemcpyAsync(c->h_cursor, c->d_small + kRecCursor, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+            HAST_HIP_TRY(hipEventRecord(c->cur_ev, c->stream));
             c->cur_pending = true;
             c->est_after = 0;
         } else c->est_after += n_starts / 2 + 1 + (uint64_t)c->n_cu * 4 * a.rec_chunk;
@@ -438,24 +430,24 @@ hast_status hast_kc_count(hast_kc *c, int parent, const uint8_t *bytes, size_t n
     for (size_t at = 0; at < n_bytes; at += chunk) {
         KcStage &s = c->stage[c->turn++ & 1];
         if (!s.h) {
-            KC_TRY(pinned_malloc(reinterpret_cast<void **>(&s.h), kStageBytes, hipHostMallocDefault));
-            KC_TRY(dev_malloc(reinterpret_cast<void **>(&s.d), kStageBytes));
+            HAST_HIP_TRY(pinned_malloc(reinterpret_cast<void **>(&s.h), kStageBytes, hipHostMallocDefault));
+            HAST_HIP_TRY(dev_malloc(reinterpret_cast<void **>(&s.d), kStageBytes));
         }
         if (s.busy) {
-            KC_TRY(hipEventSynchronize(s.done));
+            HAST_HIP_TRY(hipEventSynchronize(s.done));
             s.busy = false;
         }
         const size_t starts = std::min(chunk, n_bytes - at);
         const size_t avail = std::min(starts + overlap, n_bytes - at);       // windows near the cut need the next K-1 bytes
         memcpy(s.h, bytes + at, avail);
-        KC_TRY(hipMemcpyAsync(s.d, s.h, avail, hipMemcpyHostToDevice, c->stream));
+        HAST_HIP_TRY(hipMemcpyAsync(s.d, s.h, avail, hipMemcpyHostToDevice, c->stream));
         if (hast_status st = count_launch(c, parent, s.d, avail, starts)) return st;
-        KC_TRY(hipEventRecord(s.done, c->stream));
+        HAST_HIP_TRY(hipEventRecord(s.done, c->stream));
         s.busy = true;
     }
     if (!c->err_pending && (c->turn & 7) == 0) {
-        KC_TRY(hipMemcpyAsync(c->h_err, c->d_err, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        KC_TRY(hipEventRecord(c->err_ev, c->stream));
+        HAST_HIP_TRY(hipMemcpyAsync(c->h_err, c->d_err, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HAST_HIP_TRY(hipEventRecord(c->err_ev, c->stream));
         c->err_pending = true;
     }
     return HAST_OK;
@@ -466,8 +458,8 @@ hast_status hast_kc_sync(hast_kc *c) {
     if (c->d_table)
         if (hast_status st = part_flush(c)) return st;
     uint32_t e = 0;
-    KC_TRY(hipMemcpyAsync(&e, c->d_err, sizeof(e), hipMemcpyDeviceToHost, c->stream));
-    KC_TRY(hipStreamSynchronize(c->stream));
+    HAST_HIP_TRY(hipMemcpyAsync(&e, c->d_err, sizeof(e), hipMemcpyDeviceToHost, c->stream));
+    HAST_HIP_TRY(hipStreamSynchronize(c->stream));
     for (auto &s : c->stage) s.busy = false;
     c->err_pending = false;
     if (e & 1) return set_error(HAST_ERR_TABLE_FULL, "k-mer count table full (%u buckets of %d keys, slice %u of %u): use more slices",
@@ -480,10 +472,10 @@ hast_status hast_kc_stats(hast_kc *c, uint64_t out[6]) {
     if (!out) return set_error(HAST_ERR_INVALID, "out is null");
     if (hast_status st = part_flush(c)) return st;
     unsigned long long h[kSmallWords];
-    KC_TRY(hipMemsetAsync(c->d_small + kStats, 0, 3 * sizeof(unsigned long long), c->stream));
-    KC_TRY(launch_kc_stats(c->d_table, c->nbuckets, c->d_small + kStats, c->stream));
-    KC_TRY(hipMemcpyAsync(h, c->d_small, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-    KC_TRY(hipStreamSynchronize(c->stream));
+    HAST_HIP_TRY(hipMemsetAsync(c->d_small + kStats, 0, 3 * sizeof(unsigned long long), c->stream));
+    HAST_HIP_TRY(launch_kc_stats(c->d_table, c->nbuckets, c->d_small + kStats, c->stream));
+    HAST_HIP_TRY(hipMemcpyAsync(h, c->d_small, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HAST_HIP_TRY(hipStreamSynchronize(c->stream));
     out[0] = h[kStats];
     out[1] = h[kStats + 1];
     out[2] = h[kStats + 2];
@@ -500,10 +492,10 @@ hast_status hast_kc_histo(hast_kc *c, int parent, uint64_t *histo) {
     if (hast_status st = part_flush(c)) return st;
     const size_t n = HAST_KC_HISTO_HIGH + 2;
     std::vector<unsigned long long> h(n);
-    KC_TRY(hipMemsetAsync(c->d_histo, 0, n * sizeof(unsigned long long), c->stream));
-    KC_TRY(launch_kc_histo(c->d_table, c->nbuckets, (uint32_t)parent, c->d_histo, c->stream));
-    KC_TRY(hipMemcpyAsync(h.data(), c->d_histo, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    KC_TRY(hipStreamSynchronize(c->stream));
+    HAST_HIP_TRY(hipMemsetAsync(c->d_histo, 0, n * sizeof(unsigned long long), c->stream));
+    HAST_HIP_TRY(launch_kc_histo(c->d_table, c->nbuckets, (uint32_t)parent, c->d_histo, c->stream));
+    HAST_HIP_TRY(hipMemcpyAsync(h.data(), c->d_histo, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HAST_HIP_TRY(hipStreamSynchronize(c->stream));
     for (size_t i = 0; i < n; ++i) histo[i] += h[i];
     return HAST_OK;
 }
@@ -541,13 +533,13 @@ hast_status hast_kc_select(hast_kc *c, int parent, uint32_t lower, uint32_t uppe
     if (hast_status st = part_flush(c)) return st;
     unsigned long long n = 0;
     unsigned long long *cur = c->d_small + kCursor;
-    KC_TRY(hipMemsetAsync(cur, 0, sizeof(unsigned long long), c->stream));
-    KC_TRY(launch_kc_select(c->d_table, c->nbuckets, (uint32_t)parent, lower, upper, c->k, nullptr, 0, cur, c->stream));
-    KC_TRY(hipMemcpyAsync(&n, cur, sizeof(n), hipMemcpyDeviceToHost, c->stream));
-    KC_TRY(hipStreamSynchronize(c->stream));
+    HAST_HIP_TRY(hipMemsetAsync(cur, 0, sizeof(unsigned long long), c->stream));
+    HAST_HIP_TRY(launch_kc_select(c->d_table, c->nbuckets, (uint32_t)parent, lower, upper, c->k, nullptr, 0, cur, c->stream));
+    HAST_HIP_TRY(hipMemcpyAsync(&n, cur, sizeof(n), hipMemcpyDeviceToHost, c->stream));
+    HAST_HIP_TRY(hipStreamSynchronize(c->stream));
     if (n == 0) return HAST_OK;
     unsigned long long *d_out = nullptr;
-    KC_TRY(dev_malloc(reinterpret_cast<void **>(&d_out), n * sizeof(unsigned long long)));
+    HAST_HIP_TRY(dev_malloc(reinterpret_cast<void **>(&d_out), n * sizeof(unsigned long long)));
     hast_status st = HAST_OK;
     auto step = [&](hipError_t e, const char *what) {
         if (e != hipSuccess && st == HAST_OK) st = set_error(HAST_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
@@ -574,7 +566,7 @@ hast_status hast_kc_selection_clear(hast_kc *c) {
     if (hast_status st = use(c)) return st;
     for (int p = 0; p < 2; ++p) {
         std::vector<uint64_t>().swap(c->sel[p]);
-        if (c->d_sorted[p]) KC_TRY(hipFree(c->d_sorted[p]));
+        if (c->d_sorted[p]) HAST_HIP_TRY(hipFree(c->d_sorted[p]));
         c->d_sorted[p] = nullptr;
         c->n_sorted[p] = 0;
     }
@@ -605,18 +597,18 @@ hast_status hast_kc_partition_info(hast_kc *c, uint64_t out[5]) {
 
 hast_status hast_kc_release_table(hast_kc *c) {
     if (hast_status st = use(c)) return st;
-    KC_TRY(hipStreamSynchronize(c->stream));
-    if (c->d_table) KC_TRY(hipFree(c->d_table));
+    HAST_HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->d_table) HAST_HIP_TRY(hipFree(c->d_table));
     c->d_table = nullptr;
     for (void *p : {(void *)c->d_rec, (void *)c->d_l1, (void *)c->d_spill, (void *)c->d_fills})
-        if (p) KC_TRY(hipFree(p));
+        if (p) HAST_HIP_TRY(hipFree(p));
     c->d_rec = c->d_l1 = c->d_spill = nullptr;
     c->d_fills = nullptr;
     c->part_on = false;
     for (auto &s : c->stage) {
-        if (s.d) KC_TRY(hipFree(s.d));
+        if (s.d) HAST_HIP_TRY(hipFree(s.d));
         s.d = nullptr;
-        if (s.h) KC_TRY(hipHostFree(s.h));
+        if (s.h) HAST_HIP_TRY(hipHostFree(s.h));
         s.h = nullptr;
     }
     return HAST_OK;
@@ -627,7 +619,7 @@ hast_status hast_kc_selection_sort(hast_kc *c, int parent, size_t *n_out) {
     if (hast_status st = check_parent(parent)) return st;
     std::vector<uint64_t> &v = c->sel[parent];
     if (c->d_sorted[parent]) {
-        KC_TRY(hipFree(c->d_sorted[parent]));
+        HAST_HIP_TRY(hipFree(c->d_sorted[parent]));
         c->d_sorted[parent] = nullptr;
         c->n_sorted[parent] = 0;
     }
@@ -675,7 +667,7 @@ hast_status hast_kc_selection_text(hast_kc *c, int parent, size_t first, size_t 
     if (!out) return set_error(HAST_ERR_INVALID, "out is null");
     const size_t bytes = count * (size_t)(c->k + 1);
     char *d_text = nullptr;
-    KC_TRY(dev_malloc(reinterpret_cast<void **>(&d_text), bytes));
+    HAST_HIP_TRY(dev_malloc(reinterpret_cast<void **>(&d_text), bytes));
     hipError_t e = launch_kc_format(c->d_sorted[parent] + first, count, c->k, d_text, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_text, bytes, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -689,7 +681,7 @@ hast_status hast_kc_selection_keys(hast_kc *c, int parent, size_t first, size_t 
     if (count == 0) return HAST_OK;
     if (!out) return set_error(HAST_ERR_INVALID, "out is null");
     unsigned long long *d_keys = nullptr;
-    KC_TRY(dev_malloc(reinterpret_cast<void **>(&d_keys), count * sizeof(unsigned long long)));
+    HAST_HIP_TRY(dev_malloc(reinterpret_cast<void **>(&d_keys), count * sizeof(unsigned long long)));
     hipError_t e = launch_kc_to_table_keys(c->d_sorted[parent] + first, count, c->k, d_keys, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_keys, count * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -714,6 +706,6 @@ hast_status hast_kc_synth_device(hast_kc *c, const hast_kc_synth *p, int parent,
     if (hast_status st = check_synth(p)) return st;
     if (hast_status st = check_parent(parent)) return st;
     if (n_reads && !d_out) return set_error(HAST_ERR_INVALID, "d_out is null");
-    KC_TRY(launch_kc_synth(resolve(p), parent, first_read, n_reads * ((size_t)p->read_len + 1), d_out, c->stream));
+    HAST_HIP_TRY(launch_kc_synth(resolve(p), parent, first_read, n_reads * ((size_t)p->read_len + 1), d_out, c->stream));
     return HAST_OK;
 }

@@ -12,13 +12,6 @@ using namespace hast;
 static_assert(HAST_SQ_NOT_FOUR_LINE == SQ_NOT_FOUR_LINE && HAST_SQ_NO_RECORD == SQ_NO_RECORD, "hast.h and sq_core.h name the same flags");
 static_assert(sizeof(hast_sq_result) == 40 && sizeof(hast_sq_result) <= sizeof(SqState), "hast_sq_result is the head of SqState");
 
-#define SQ_TRY(expr)                                                                                  \
-    do {                                                                                              \
-        const hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess)                                                                         \
-            return set_error(e_ == hipErrorOutOfMemory ? HAST_ERR_OOM : HAST_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
 struct hast_sq {
     int device = 0;
     hipStream_t stream = nullptr;            // the count table's: a framed block is counted behind its framing without an event
@@ -53,7 +46,7 @@ extern "C" {
 hast_status hast_sq_create(hast_kc *kc, size_t max_in_bytes, hast_sq **out) {
     if (!kc || !out) return set_error(HAST_ERR_INVALID, "null argument");
     *out = nullptr;
-    if (max_in_bytes < 1 || max_in_bytes >= (1ull << 32) - 2 * kSqTile)
+    if (max_in_bytes < 1 || max_in_bytes >= (1ull << 32) - 2 * kNlTile)
         return set_error(HAST_ERR_INVALID, "hast_sq_create: %zu bytes a block; offsets inside a block are 32 bits wide", max_in_bytes);
     hast_sq *q = new (std::nothrow) hast_sq;
     if (!q) return set_error(HAST_ERR_OOM, "hast_sq_create");
@@ -77,10 +70,10 @@ hast_status hast_sq_frame_device(hast_sq *q, const uint8_t *d_in, size_t n_in, u
     if (!q || !res || (n_in && (!d_in || !d_out))) return set_error(HAST_ERR_INVALID, "null argument");
     if (n_in > q->max_in) return set_error(HAST_ERR_INVALID, "hast_sq_frame_device: %zu bytes, the framer was created for %zu", n_in, q->max_in);
     if (cap_out < n_in) return set_error(HAST_ERR_INVALID, "hast_sq_frame_device: %zu bytes of room for a block of %zu", cap_out, n_in);
-    SQ_TRY(hipSetDevice(q->device));
-    SQ_TRY(launch_sq_frame(d_in, n_in, d_out, q->d_scratch, q->plan, q->stream));
-    SQ_TRY(hipMemcpyAsync(q->h_st, q->d_scratch + q->plan.state, sizeof(SqState), hipMemcpyDeviceToHost, q->stream));
-    SQ_TRY(hipStreamSynchronize(q->stream));
+    HAST_HIP_TRY(hipSetDevice(q->device));
+    HAST_HIP_TRY(launch_sq_frame(d_in, n_in, d_out, q->d_scratch, q->plan, q->stream));
+    HAST_HIP_TRY(hipMemcpyAsync(q->h_st, q->d_scratch + q->plan.state, sizeof(SqState), hipMemcpyDeviceToHost, q->stream));
+    HAST_HIP_TRY(hipStreamSynchronize(q->stream));
     const SqState &s = *q->h_st;
     res->consumed = s.consumed;
     res->out_bytes = s.out_bytes;
@@ -136,7 +129,7 @@ static hast_status feed_slot(hast_sq_feed *f, int *slot) {
     if (!f) return set_error(HAST_ERR_INVALID, "null feed");
     if (f->n_submitted - f->n_done >= 2) return set_error(HAST_ERR_INVALID, "hast_sq_feed: two blocks are waiting for hast_sq_feed_next");
     *slot = (int)(f->n_submitted & 1);
-    SQ_TRY(hipSetDevice(f->device));
+    HAST_HIP_TRY(hipSetDevice(f->device));
     return HAST_OK;
 }
 
@@ -145,7 +138,7 @@ hast_status hast_sq_feed_host_block(hast_sq_feed *f, uint8_t **h_buf) {
     if (hast_status st = feed_slot(f, &slot)) return st;
     if (!h_buf) return set_error(HAST_ERR_INVALID, "null argument");
     if (f->up_pending[slot]) {                       // the upload out of this staging block, two blocks ago
-        SQ_TRY(hipEventSynchronize(f->up_ev[slot]));
+        HAST_HIP_TRY(hipEventSynchronize(f->up_ev[slot]));
         f->up_pending[slot] = false;
     }
     f->handed = 1;
@@ -169,9 +162,9 @@ hast_status hast_sq_feed_submit(hast_sq_feed *f, size_t n_bytes) {
     f->on_device[slot] = f->handed == 2;
     if (f->handed == 1) {
         // this buffer held block n-2: its framing has been waited for, the copy of what it left to block n-1 may still run
-        if (f->tail_pending) SQ_TRY(hipStreamWaitEvent(f->up_stream, f->tail_ev, 0));
-        SQ_TRY(hipMemcpyAsync(f->d_in[slot] + f->block, f->h_in[slot], n_bytes, hipMemcpyHostToDevice, f->up_stream));
-        SQ_TRY(hipEventRecord(f->up_ev[slot], f->up_stream));
+        if (f->tail_pending) HAST_HIP_TRY(hipStreamWaitEvent(f->up_stream, f->tail_ev, 0));
+        HAST_HIP_TRY(hipMemcpyAsync(f->d_in[slot] + f->block, f->h_in[slot], n_bytes, hipMemcpyHostToDevice, f->up_stream));
+        HAST_HIP_TRY(hipEventRecord(f->up_ev[slot], f->up_stream));
         f->up_pending[slot] = true;
     }
     f->n_new[slot] = n_bytes;
@@ -184,8 +177,8 @@ hast_status hast_sq_feed_next(hast_sq_feed *f, int parent, hast_sq_result *res) 
     if (!f || !res) return set_error(HAST_ERR_INVALID, "null argument");
     if (f->n_done == f->n_submitted) return set_error(HAST_ERR_INVALID, "hast_sq_feed_next: no block submitted");
     const int slot = (int)(f->n_done & 1);
-    SQ_TRY(hipSetDevice(f->device));
-    if (!f->on_device[slot]) SQ_TRY(hipStreamWaitEvent(f->table_stream, f->up_ev[slot], 0));
+    HAST_HIP_TRY(hipSetDevice(f->device));
+    if (!f->on_device[slot]) HAST_HIP_TRY(hipStreamWaitEvent(f->table_stream, f->up_ev[slot], 0));
     const uint8_t *d_view = f->d_in[slot] + f->block - f->tail;
     const size_t n = f->tail + f->n_new[slot];
     if (hast_status st = hast_sq_frame_device(f->sq, d_view, n, f->d_out[slot], 2 * f->block + 64, res)) return st;
@@ -197,8 +190,8 @@ hast_status hast_sq_feed_next(hast_sq_feed *f, int parent, hast_sq_result *res) 
     }
     if (res->out_bytes)
         if (hast_status st = hast_kc_count_device(f->kc, parent, f->d_out[slot], (size_t)res->out_bytes)) return st;
-    if (left) SQ_TRY(hipMemcpyAsync(f->d_in[slot ^ 1] + f->block - left, d_view + res->consumed, left, hipMemcpyDeviceToDevice, f->table_stream));
-    SQ_TRY(hipEventRecord(f->tail_ev, f->table_stream));
+    if (left) HAST_HIP_TRY(hipMemcpyAsync(f->d_in[slot ^ 1] + f->block - left, d_view + res->consumed, left, hipMemcpyDeviceToDevice, f->table_stream));
+    HAST_HIP_TRY(hipEventRecord(f->tail_ev, f->table_stream));
     f->tail_pending = true;
     f->tail = left;
     ++f->n_done;
@@ -208,11 +201,11 @@ hast_status hast_sq_feed_next(hast_sq_feed *f, int parent, hast_sq_result *res) 
 hast_status hast_sq_feed_take_tail(hast_sq_feed *f, uint8_t *dst, size_t *n_bytes) {
     if (!f || !dst || !n_bytes) return set_error(HAST_ERR_INVALID, "null argument");
     if (f->n_done != f->n_submitted) return set_error(HAST_ERR_INVALID, "hast_sq_feed_take_tail: a submitted block has not been framed");
-    SQ_TRY(hipSetDevice(f->device));
+    HAST_HIP_TRY(hipSetDevice(f->device));
     *n_bytes = f->tail;
     if (f->tail) {
-        SQ_TRY(hipMemcpyAsync(dst, f->d_in[f->n_done & 1] + f->block - f->tail, f->tail, hipMemcpyDeviceToHost, f->table_stream));
-        SQ_TRY(hipStreamSynchronize(f->table_stream));
+        HAST_HIP_TRY(hipMemcpyAsync(dst, f->d_in[f->n_done & 1] + f->block - f->tail, f->tail, hipMemcpyDeviceToHost, f->table_stream));
+        HAST_HIP_TRY(hipStreamSynchronize(f->table_stream));
     }
     f->tail = 0;
     return HAST_OK;

@@ -4,6 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "nl_index.h"
 #include "sq_core.h"
 
 namespace hast {
@@ -14,7 +15,6 @@ struct SqState {               // device memory; its first 40 bytes are hast_sq_
     uint32_t n_nl, n_rec;      // newlines of the block, records framed (n_nl / 4)
 };
 
-constexpr uint32_t kSqTile = 4096;       // input bytes per tile of the newline index = 256 lanes x 16 B
 constexpr uint32_t kSqRecTile = 256;     // records per tile of the prefix sum of the output lengths
 
 // the scratch a block of up to max_in bytes needs in the worst case, a block that is all newlines
@@ -23,11 +23,11 @@ struct SqScratchPlan {
 };
 inline SqScratchPlan sq_scratch_plan(size_t max_in) {
     auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t n_tiles = (max_in + 15) / kSqTile + 2, max_rec = max_in / 4 + 1, rec_tiles = max_rec / kSqRecTile + 2;
+    const size_t n_tiles = nl_tiles(max_in), max_rec = max_in / 4 + 1, rec_tiles = max_rec / kSqRecTile + 2;
     SqScratchPlan p;
     size_t at = 0;
     p.tile_cnt = at; at += up(n_tiles * 4);
-    p.nl = at;       at += up((max_in + 1) * 4);
+    p.nl = at;       at += up(nl_index_words(max_in) * 4);
     p.r_src = at;    at += up(max_rec * 4);
     p.r_len = at;    at += up(max_rec * 4);
     p.r_tile = at;   at += up(rec_tiles * 4);

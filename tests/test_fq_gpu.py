@@ -61,7 +61,7 @@ def make_fastq(rng, n, k, keys, tail):
     return text.encode()
 
 
-def stream_through_framer(ctx, data, lo, hi, cache, rng, n_buffers=3, more_ctxs=(), eager=False, dict_mode=False, keep_names=None):
+def stream_through_framer(ctx, data, lo, hi, cache, rng, n_buffers=3, more_ctxs=(), eager=False, dict_mode=False, keep_names=None, sizes=None):
     """feed `data` to hast_fq_* in pieces of lo..hi bytes, name the records the way the CLI does; returns the barcodes in record
     order, the dictionary, the base count, the per-block short-read flags and how many records the host had to name.
     dict_mode: the table is the DICTIONARY (hast_names_create_dict): the device hands out the ids below hast_names_limit itself, the
@@ -69,7 +69,8 @@ def stream_through_framer(ctx, data, lo, hi, cache, rng, n_buffers=3, more_ctxs=
     per text, dense from 0, below dict_ids, the texts the dictionary files under its ids are the barcodes, and no text is both numbered
     by the device and left to the caller (tests/test_names_gpu.py holds the kernel to that at scale).
     more_ctxs: further contexts -> a striped stream (block i on context i % n; n_buffers per context; lo == hi: full blocks);
-    eager: open a block as soon as the one behind it has been submitted (else: as late as the buffers allow)"""
+    eager: open a block as soon as the one behind it has been submitted (else: as late as the buffers allow);
+    sizes: the pieces' sizes, in order, instead of random ones (every one in 1..hi, their sum len(data))"""
     lib = hast_amd.lib()
     fq, nm = C.c_void_p(), C.c_void_p()
     ctxs = [ctx] + list(more_ctxs)
@@ -94,6 +95,8 @@ def stream_through_framer(ctx, data, lo, hi, cache, rng, n_buffers=3, more_ctxs=
     short = []
     limit = lib.hast_names_limit(nms[0] if nms else nm) if dict_mode else 0
     host_names = {}
+    sizes = list(sizes) if sizes is not None else None
+    assert sizes is None or (sum(sizes) == len(data) and all(0 < n <= hi for n in sizes))
 
     def drain():
         b = FqBlock()
@@ -140,7 +143,7 @@ def stream_through_framer(ctx, data, lo, hi, cache, rng, n_buffers=3, more_ctxs=
         assert lib.hast_fq_commit(fq) == 0, lib.hast_last_error()
 
     while True:
-        n = min(len(data) - pos, rng.randint(lo, hi))
+        n = sizes.pop(0) if sizes is not None else min(len(data) - pos, rng.randint(lo, hi))
         buf = C.POINTER(C.c_uint8)()
         assert lib.hast_fq_acquire(fq, C.byref(buf)) == 0, lib.hast_last_error()
         C.memmove(buf, data[pos:pos + n], n)
@@ -241,6 +244,34 @@ def test_fq_framing_and_counts(oracle_lib, tail, chunk, cache):
     for a, b in zip(counts, e):
         assert np.array_equal(a, b)
     assert int(e[0].sum()) + int(e[1].sum()) > 100
+
+
+@pytest.mark.parametrize("tail", ["plain", "no_final_newline"])
+def test_fq_framing_at_every_cut_of_a_small_input(oracle_lib, tail):
+    """Three records, about a hundred bytes, cut in two at EVERY byte: [0, s) is the first block, the rest the last one (s = 0 and
+    s = len: the whole input as one block).  The second block is parsed from pad - s (the first block's bytes are all tail when it
+    holds no complete record) or from pad - (what follows its last record) up to pad + len - s: both ends of the parse range take every
+    residue mod 16, the edges at which the newline index (nl_index.h) reads byte by byte and must neither miss a newline nor count one
+    outside the range.  Records, barcodes and base counts == the reference's reader, as in test_fq_framing_and_counts."""
+    k = 7
+    recs = [("@a#1_2_3/1", "ACGTTGC"), ("@b#0_0_0/2", "TTGCAACG"), ("@c/x#lib7_4", "GATTACAGA")]
+    data = "".join("%s\n%s\n+\n%s\n" % (h, s, "I" * len(s)) for h, s in recs).encode()
+    if tail == "no_final_newline":
+        data = data[:-1]
+    assert 80 <= len(data) <= 130 and all(len(s) >= k for _, s in recs)
+    want = reference_framing(data, oracle_lib)
+    assert len(want) == 3
+    rng = random.Random(5)                                     # (not drawn from: every size is given)
+    with hast_amd.Context(k) as ctx:
+        ctx.table_reserve(100)
+        ctx.table_insert_keys(0, np.array([hast_amd.canon_kmer(b"ACGTTGC")], dtype=np.uint64))
+        ctx.counts_resize(4096)
+        for s in range(len(data) + 1):
+            sizes = [len(data)] if s in (0, len(data)) else [s, len(data) - s]
+            got, names, n_bases, short, host_named = stream_through_framer(ctx, data, 4096, 4096, 0, rng, sizes=sizes)
+            assert got == [bc for bc, _ in want], (s, got)
+            assert n_bases == sum(len(x) for _, x in want) and not any(short), (s, n_bases, short)
+            assert len(short) == len(sizes) and host_named == len(want), s
 
 
 def stream_device_blocks(ctx, gz_path, block, cache, n_buffers, lag, gz_chunk=4096, gz_pass=7, more_ctxs=()):

@@ -109,3 +109,14 @@ def test_multi_line_golden_is_flagged(driver, work):
     shutil.copyfile(os.path.join(GOLDEN, "s00_edge_k31", "p.fq"), p)
     row = run_driver(driver, 1 << 24, [p])[0]
     assert row["status"] == "flagged" and row["first_bad"] != 0xFFFFFFFF, row["line"]
+
+
+@pytest.mark.parametrize("sanitize", [False, True])
+def test_newline_bits_of_a_word_equal_a_byte_loop(work, sanitize):
+    """nl_bits4 (hast_amd/csrc/nl_index.h), the step of the newline index that the framers of `classify` and of this ingest share:
+    tests/native/test_nl_index.cpp holds it to a byte loop on every word over the neighbours of '\\n'"""
+    out = os.path.join(str(work), "test_nl_index_san" if sanitize else "test_nl_index")
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra"] + (["-fsanitize=address,undefined"] if sanitize else []) +
+                   ["-o", out, os.path.join(sc.ROOT, "tests", "native", "test_nl_index.cpp")], check=True)
+    r = subprocess.run([out], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    assert r.returncode == 0 and r.stdout.startswith(b"ok 65536 words") and r.stderr == b"", (r.stdout, r.stderr)
