@@ -14,6 +14,10 @@
 // two sets as a binary stage-01 table for `classify --load-table`), --stats, --ingest host|device (HAST_KC_INGEST; device: the files'
 // bytes are inflated and framed on the GPU, see "ingest on the device" below; default host).
 // Exit status: 0 ok / usage; 1 bad arguments, missing or malformed input (the script: exit 1); 4 GPU trouble.
+//
+// Layout: main(), at the end, is the list of the run's phases; each phase is a function above it, in that order.  What the command
+// line asked for is an Options, what one phase leaves to the next is a Run.  Above the phases: the two ingests (the host parser's and
+// the device framer's), which share the job list, the worker threads and the folding of their results, and one sweep over the inputs.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -55,6 +59,8 @@ void usage(FILE *f) {
           "                      is read by the host parser after all); default host, or HAST_KC_INGEST\n",
           f);
 }
+
+const char *const kParentName[2] = {"paternal", "maternal"};
 
 bool ends_gz(const std::string &s) { return s.size() >= 3 && s.compare(s.size() - 3, 3, ".gz") == 0; }   // s00:169
 
@@ -153,77 +159,61 @@ struct IngestResult {
     char first = 0;                  // its first byte
 };
 
-// one input stream of the counter: the files one after the other, either as separate inputs (plain) or as one
-// concatenated stream (gz: `zcat files | ...`, s00:187-188)
-void ingest_stream(Gpu &gpu, int parent, int k, const std::vector<std::string> &paths, bool concatenated, IngestResult &res) {
-    ChunkSink sink(gpu, parent, k);
-    hast::SeqParser<ChunkSink> parser(sink);
-    for (size_t i = 0; i < paths.size() && res.error.empty(); ++i) {
-        hast::BlockSource src;
-        if (!src.open(paths[i], 16u << 20)) {
-            res.error = "cannot open " + paths[i];
-            break;
-        }
-        for (;;) {
-            std::vector<char> b = src.next();
-            if (b.empty()) {
-                if (!src.error().empty()) res.error = paths[i] + ": " + src.error();
-                break;
-            }
-            const size_t n = b.size() - hast::BlockSource::kFrontPad;
-            res.bytes += n;
-            if (!parser.feed(b.data() + hast::BlockSource::kFrontPad, n)) res.error = paths[i] + ": " + parser.error();
-            src.recycle(std::move(b));
-            if (!res.error.empty() || !gpu.ok()) break;
-        }
-        if (res.error.empty() && (!concatenated || i + 1 == paths.size())) {
-            res.clean_end = parser.at_record_boundary();
-            res.first = parser.first_byte();
-            if (!parser.finish()) res.error = paths[i] + ": " + parser.error();
-        }
-    }
-    sink.flush(true);
-    res.bases = sink.bases();
-    res.records = parser.records();
-}
-
-// Both parents' files, read and parsed by up to --thread workers at once.  Plain files are independent inputs of the
-// counter (s00:190).  The gz files of a parent are ONE concatenated stream in the reference (s00:187-188); they are
-// still read in parallel, which gives the same result whenever every file ends exactly between two records and all
-// start with the same byte -- if not (gz_in_order comes back true), the caller starts over and reads them in order.
 struct ParentTotals { size_t bases = 0, records = 0, bytes = 0; };
-bool ingest_all(Gpu &gpu, const Options &o, bool &gz_in_order, std::string &err, ParentTotals tot[2]) {
-    struct Job { int parent; std::vector<std::string> paths; bool concatenated, check; IngestResult res; };
+
+// How a sweep over the inputs, or its ingest, ended.  The three in the middle make count() start over.
+enum class Sweep {
+    Ok,
+    InputError,      // reported on stdout as the script would: exit status 1
+    TableFull,       // start over with twice the slices
+    GzInOrder,       // a gz file ends inside a record: start over and read each parent's gz files in order, as one stream
+    DeviceRefused,   // the device framer does not take the input (DeviceIngest::refused): start over with the host ingest
+    GpuError,        // exit status 4
+};
+
+// ---- one driver for both ingests -------------------------------------------------------------------------------------------------
+// Both parents' files, read by up to --thread workers at once.  Plain files are independent inputs of the counter (s00:190).  The gz
+// files of a parent are ONE concatenated stream in the reference (`zcat files | ...`, s00:187-188).  The host ingest still reads them
+// in parallel, which gives the same result whenever every file ends exactly between two records and all start with the same byte --
+// if not (gz_files_are_one_stream), the caller starts over and reads them in order.  The device ingest reads a parent's files in
+// order from the start, plain ones too: one feed per parent.
+struct Job {
+    int parent;
+    std::vector<std::string> paths;  // read one after the other
+    bool gz;
+    bool one_stream;                 // the files are one input: only the end of the last one is an end of input
+    bool check;                      // a gz file read on its own although it is part of a stream: how it starts and ends matters
+    IngestResult res;
+};
+
+std::vector<Job> build_jobs(const Options &o, bool device, bool gz_in_order) {
     std::vector<Job> jobs;
     for (int p = 1; p >= 0; --p) {                                              // maternal first, as the script does
         std::vector<std::string> order(o.files[p].rbegin(), o.files[p].rend());   // s00:105,109: each new file is put in front
         const bool gz = ends_gz(order[0]);
-        if (gz && gz_in_order) jobs.push_back({p, order, true, false, {}});
+        if (device || (gz && gz_in_order)) jobs.push_back({p, order, gz, gz, false, {}});
         else
-            for (size_t i = 0; i < order.size(); ++i) jobs.push_back({p, {order[i]}, false, gz && order.size() > 1, {}});
+            for (size_t i = 0; i < order.size(); ++i) jobs.push_back({p, {order[i]}, gz, false, gz && order.size() > 1, {}});
     }
+    return jobs;
+}
+
+template <class Worker>
+void run_jobs(std::vector<Job> &jobs, long threads, Worker work) {
     std::atomic<size_t> next{0};
-    const int nt = (int)std::max<long>(1, std::min<long>(o.cpu, (long)jobs.size()));
+    const int nt = (int)std::max<long>(1, std::min<long>(threads, (long)jobs.size()));
     std::vector<std::thread> th;
     for (int t = 0; t < nt; ++t)
         th.emplace_back([&] {
-            for (size_t i; (i = next.fetch_add(1)) < jobs.size();) ingest_stream(gpu, jobs[i].parent, (int)o.mer, jobs[i].paths, jobs[i].concatenated, jobs[i].res);
+            for (size_t i; (i = next.fetch_add(1)) < jobs.size();) work(jobs[i]);
         });
     for (auto &t : th) t.join();
-    bool redo = false;
-    for (size_t i = 0; i < jobs.size(); ++i) {
-        const Job &j = jobs[i];
-        if (j.check) {
-            const bool last = i + 1 == jobs.size() || jobs[i + 1].parent != j.parent;
-            const bool first = i == 0 || jobs[i - 1].parent != j.parent;
-            if ((!last && !j.res.clean_end) || (!first && j.res.first != jobs[i - 1].res.first && j.res.first && jobs[i - 1].res.first)) redo = true;
-            if (!j.res.error.empty() && !first) redo = true;                    // may parse differently as part of the whole stream
-        }
-    }
-    if (redo && !gz_in_order) {
-        gz_in_order = true;
-        return false;
-    }
+}
+
+// the jobs' totals per parent (of this pass over the files alone), and what went wrong: the first input's error before the GPU's
+std::string fold_jobs(const std::vector<Job> &jobs, Gpu &gpu, ParentTotals tot[2]) {
+    std::string err;
+    tot[0] = tot[1] = ParentTotals();
     for (const auto &j : jobs) {
         if (!j.res.error.empty() && err.empty()) err = j.res.error;
         tot[j.parent].bases += j.res.bases;
@@ -231,7 +221,65 @@ bool ingest_all(Gpu &gpu, const Options &o, bool &gz_in_order, std::string &err,
         tot[j.parent].bytes += j.res.bytes;
     }
     if (err.empty() && !gpu.ok()) err = gpu.error;
-    return err.empty();
+    return err;
+}
+
+// Every block of a file as BlockSource delivers it (a .gz file inflated), its payload handed to use(bytes, n); use returns false to
+// stop early.  What keeps the file from being read to its end is left in err.
+template <class Use>
+void for_each_block(const std::string &path, size_t block_bytes, std::string &err, Use use) {
+    hast::BlockSource src;
+    if (!src.open(path, block_bytes)) {
+        err = "cannot open " + path;
+        return;
+    }
+    for (;;) {
+        std::vector<char> b = src.next();
+        if (b.empty()) {
+            if (!src.error().empty()) err = path + ": " + src.error();
+            return;
+        }
+        const bool go_on = use(b.data() + hast::BlockSource::kFrontPad, b.size() - hast::BlockSource::kFrontPad);
+        src.recycle(std::move(b));
+        if (!go_on) return;
+    }
+}
+
+// ---- the host ingest: files -> SeqParser -> chunks of bases -> GPU ------------------------------------------------------------------
+void ingest_stream(Gpu &gpu, int k, Job &job) {
+    IngestResult &res = job.res;
+    ChunkSink sink(gpu, job.parent, k);
+    hast::SeqParser<ChunkSink> parser(sink);
+    for (size_t i = 0; i < job.paths.size() && res.error.empty(); ++i) {
+        const std::string &path = job.paths[i];
+        for_each_block(path, 16u << 20, res.error, [&](const char *p, size_t n) {
+            res.bytes += n;
+            if (!parser.feed(p, n)) res.error = path + ": " + parser.error();
+            return res.error.empty() && gpu.ok();
+        });
+        if (res.error.empty() && (!job.one_stream || i + 1 == job.paths.size())) {
+            res.clean_end = parser.at_record_boundary();
+            res.first = parser.first_byte();
+            if (!parser.finish()) res.error = path + ": " + parser.error();
+        }
+    }
+    sink.flush(true);
+    res.bases = sink.bases();
+    res.records = parser.records();
+}
+
+// the gz files of a parent, each read on its own: did that give what reading them as one stream gives?
+bool gz_files_are_one_stream(const std::vector<Job> &jobs) {
+    bool same = true;
+    for (size_t i = 0; i < jobs.size(); ++i) {
+        const Job &j = jobs[i];
+        if (!j.check) continue;
+        const bool last = i + 1 == jobs.size() || jobs[i + 1].parent != j.parent;
+        const bool first = i == 0 || jobs[i - 1].parent != j.parent;
+        if ((!last && !j.res.clean_end) || (!first && j.res.first != jobs[i - 1].res.first && j.res.first && jobs[i - 1].res.first)) same = false;
+        if (!j.res.error.empty() && !first) same = false;                       // may parse differently as part of the whole stream
+    }
+    return same;
 }
 
 // ---- ingest on the device (--ingest device, one count table) -------------------------------------------------------------------
@@ -260,33 +308,43 @@ struct DeviceIngest {
     }
 };
 
-void ingest_device_stream(Gpu &gpu, DeviceIngest &di, int parent, int k, const std::vector<std::string> &paths, bool gz, IngestResult &res) {
-    std::mutex &table_mu = *gpu.dev_mu[0];
-    hast_sq_feed *feed = nullptr;
-    {
-        std::lock_guard<std::mutex> g(table_mu);
-        if (hast_sq_feed_create(gpu.kc, di.block, &feed) != HAST_OK) {
-            gpu.fail(hast_last_error());
-            return;
-        }
-    }
-    ChunkSink sink(gpu, parent, k);
-    std::vector<uint8_t> tail(di.block);
+// One job on its way through the framer.  At most one block is ahead of the framer (submit), every block a file has submitted is framed
+// before its decoder is closed (from_gz_on_device), and the tail goes to the parser only at the end of an input (end_of_input).
+// Locks: hast_sq_feed_create, _next, _take_tail and _destroy are called under the table's mutex (dev_mu[0], which hast_kc_count inside
+// ChunkSink::flush holds too: "the caller serialises it with the table's other users", include/hast.h); hast_sq_feed_submit,
+// _device_block, _host_block and hast_gz_open / _read_device / _close are called without it, so that one parent's thread reads, inflates
+// and uploads while the other's block is framed and counted.
+struct DeviceStream {
+    DeviceStream(Gpu &g, DeviceIngest &d, int k, Job &j, hast_sq_feed *f)
+        : gpu(g), di(d), job(j), res(j.res), table_mu(*g.dev_mu[0]), feed(f), sink(g, j.parent, k), tail(d.block) {}
+    Gpu &gpu;
+    DeviceIngest &di;
+    const Job &job;
+    IngestResult &res;
+    std::mutex &table_mu;
+    hast_sq_feed *feed;              // ours: run() destroys it
+    ChunkSink sink;
+    std::vector<uint8_t> tail;
     int pending = 0;                 // blocks submitted and not framed yet
     uint64_t blocks = 0, gz_dev = 0;
     size_t bases = 0;
-    auto step = [&]() -> bool {      // frame and count the oldest submitted block
+
+    bool good() { return res.error.empty() && gpu.ok() && !di.is_refused(); }
+    bool ck(hast_status st) {        // a call of the library's that failed is the GPU's failure
+        if (st != HAST_OK) gpu.fail(hast_last_error());
+        return st == HAST_OK;
+    }
+    bool step() {                    // frame and count the oldest submitted block
         hast_sq_result r;
-        hast_status st;
+        bool framed;
         {
             std::lock_guard<std::mutex> g(table_mu);
-            st = hast_sq_feed_next(feed, parent, &r);
-            if (st != HAST_OK) gpu.fail(hast_last_error());
+            framed = ck(hast_sq_feed_next(feed, job.parent, &r));
         }
         --pending;
-        if (st != HAST_OK) return false;
+        if (!framed) return false;
         if (r.flags & HAST_SQ_NOT_FOUR_LINE) {
-            di.refuse("not four-line FASTQ (record " + std::to_string(res.records + r.first_bad + 1) + " of a " + (parent ? "maternal" : "paternal") + " input)");
+            di.refuse("not four-line FASTQ (record " + std::to_string(res.records + r.first_bad + 1) + " of a " + kParentName[job.parent] + " input)");
             return false;
         }
         if (r.flags & HAST_SQ_TAIL_TOO_LONG) {
@@ -297,26 +355,20 @@ void ingest_device_stream(Gpu &gpu, DeviceIngest &di, int parent, int k, const s
         res.records += r.records;
         bases += r.bases;
         return true;
-    };
-    auto submit = [&](size_t n) -> bool {    // ... and keep one block ahead of the framer
-        if (hast_sq_feed_submit(feed, n) != HAST_OK) {
-            gpu.fail(hast_last_error());
-            return false;
-        }
+    }
+    bool submit(size_t n) {          // ... and keep one block ahead of the framer
+        if (!ck(hast_sq_feed_submit(feed, n))) return false;
         res.bytes += n;
         ++pending;
         return pending < 2 || step();
-    };
-    auto end_of_input = [&](const std::string &path) -> bool {
+    }
+    bool end_of_input(const std::string &path) {
         while (pending)
             if (!step()) return false;
         size_t n = 0;
         {
             std::lock_guard<std::mutex> g(table_mu);
-            if (hast_sq_feed_take_tail(feed, tail.data(), &n) != HAST_OK) {
-                gpu.fail(hast_last_error());
-                return false;
-            }
+            if (!ck(hast_sq_feed_take_tail(feed, tail.data(), &n))) return false;
         }
         hast::SeqParser<ChunkSink> parser(sink);
         if (!parser.feed(reinterpret_cast<const char *>(tail.data()), n) || !parser.finish()) {
@@ -326,115 +378,94 @@ void ingest_device_stream(Gpu &gpu, DeviceIngest &di, int parent, int k, const s
         res.records += parser.records();
         sink.flush(true);
         return true;
-    };
-    auto good = [&] { return res.error.empty() && gpu.ok() && !di.is_refused(); };
-    for (size_t i = 0; i < paths.size() && good(); ++i) {
-        hast_gz *z = nullptr;
-        if (gz && gpu.gz_ctx && hast_gz_open(gpu.gz_ctx, paths[i].c_str(), &z) != HAST_OK) z = nullptr;   // (not for the GPU, or not readable: BlockSource's words)
-        if (z) {
-            ++gz_dev;
-            while (good()) {
-                uint8_t *d = nullptr;
-                size_t n = 0;
-                if (hast_sq_feed_device_block(feed, &d) != HAST_OK) {
-                    gpu.fail(hast_last_error());
-                    break;
-                }
-                if (hast_gz_read_device(z, d, di.block, &n, hast_kc_stream(gpu.kc)) != HAST_OK) {
-                    di.refuse("hast_gz: " + std::string(hast_last_error()));
-                    break;
-                }
-                if (n == 0) break;           // (only a call that returns nothing ends the stream, include/hast.h)
-                if (!submit(n)) break;
-            }
-            while (pending && good())        // before the decoder goes: its kernels wrote the blocks still waiting
-                if (!step()) break;
-            hast_gz_close(z);
-        } else if (gz) {                     // inflated on the host, uploaded
-            hast::BlockSource src;
-            if (!src.open(paths[i], di.block)) {
-                res.error = "cannot open " + paths[i];
-                break;
-            }
-            while (good()) {
-                std::vector<char> b = src.next();
-                if (b.empty()) {
-                    if (!src.error().empty()) res.error = paths[i] + ": " + src.error();
-                    break;
-                }
-                const size_t n = b.size() - hast::BlockSource::kFrontPad;
-                for (size_t at = 0; at < n && good(); at += di.block) {
-                    uint8_t *h = nullptr;
-                    if (hast_sq_feed_host_block(feed, &h) != HAST_OK) {
-                        gpu.fail(hast_last_error());
-                        break;
-                    }
-                    const size_t take = std::min(di.block, n - at);
-                    memcpy(h, b.data() + hast::BlockSource::kFrontPad + at, take);
-                    if (!submit(take)) break;
-                }
-                src.recycle(std::move(b));
-            }
-        } else {                             // a plain file: read into the pinned block, uploaded
-            FILE *fp = fopen(paths[i].c_str(), "rb");
-            if (!fp) {
-                res.error = "cannot open " + paths[i];
-                break;
-            }
-            for (bool first = true; good(); first = false) {
-                uint8_t *h = nullptr;
-                if (hast_sq_feed_host_block(feed, &h) != HAST_OK) {
-                    gpu.fail(hast_last_error());
-                    break;
-                }
-                const size_t n = fread(h, 1, di.block, fp);
-                if (n == 0) break;
-                if (first && h[0] != '@') {
-                    di.refuse(h[0] == '>' ? paths[i] + " is FASTA" : paths[i] + " does not start with '@'");
-                    break;
-                }
-                if (!submit(n)) break;
-            }
-            fclose(fp);
-        }
-        if (good() && (!gz || i + 1 == paths.size()) && !end_of_input(paths[i])) break;
     }
-    {
-        std::lock_guard<std::mutex> g(table_mu);
-        hast_sq_feed_destroy(feed);          // (waits for what this feed has put on the table's stream)
+    uint8_t *host_block() {          // the pinned block the next upload is written to
+        uint8_t *h = nullptr;
+        return ck(hast_sq_feed_host_block(feed, &h)) ? h : nullptr;
     }
-    res.bases = bases + sink.bases();
-    std::lock_guard<std::mutex> g(di.mu);
-    di.blocks_framed += blocks;
-    di.gz_on_device += gz_dev;
-}
 
-// 0 ok, 1 error (err), -3 the device path refused the input (di.refused)
-int ingest_device_all(Gpu &gpu, const Options &o, DeviceIngest &di, std::string &err, ParentTotals tot[2]) {
-    struct Job { int parent; std::vector<std::string> paths; bool gz; IngestResult res; };
-    std::vector<Job> jobs;
-    for (int p = 1; p >= 0; --p) {                                              // maternal first, as the script does
-        std::vector<std::string> order(o.files[p].rbegin(), o.files[p].rend());   // s00:105,109: each new file is put in front
-        jobs.push_back({p, order, ends_gz(order[0]), {}});
+    void from_gz_on_device(hast_gz *z) {
+        ++gz_dev;
+        while (good()) {
+            uint8_t *d = nullptr;
+            size_t n = 0;
+            if (!ck(hast_sq_feed_device_block(feed, &d))) break;
+            if (hast_gz_read_device(z, d, di.block, &n, hast_kc_stream(gpu.kc)) != HAST_OK) {
+                di.refuse("hast_gz: " + std::string(hast_last_error()));
+                break;
+            }
+            if (n == 0) break;               // (only a call that returns nothing ends the stream, include/hast.h)
+            if (!submit(n)) break;
+        }
+        while (pending && good())            // before the decoder goes: its kernels wrote the blocks still waiting
+            if (!step()) break;
+        hast_gz_close(z);
     }
-    di.refused.clear();
-    std::atomic<size_t> next{0};
-    const int nt = (int)std::max<long>(1, std::min<long>(o.cpu, (long)jobs.size()));
-    std::vector<std::thread> th;
-    for (int t = 0; t < nt; ++t)
-        th.emplace_back([&] {
-            for (size_t i; (i = next.fetch_add(1)) < jobs.size();) ingest_device_stream(gpu, di, jobs[i].parent, (int)o.mer, jobs[i].paths, jobs[i].gz, jobs[i].res);
-        });
-    for (auto &t : th) t.join();
-    if (!di.refused.empty()) return -3;
-    for (const auto &j : jobs) {
-        if (!j.res.error.empty() && err.empty()) err = j.res.error;
-        tot[j.parent].bases += j.res.bases;
-        tot[j.parent].records += j.res.records;
-        tot[j.parent].bytes += j.res.bytes;
+    bool upload(const char *p, size_t n) {   // inflated on the host: through the pinned block, a feed's block at a time
+        for (size_t at = 0; at < n && good(); at += di.block) {
+            uint8_t *h = host_block();
+            if (!h) break;
+            const size_t take = std::min(di.block, n - at);
+            memcpy(h, p + at, take);
+            if (!submit(take)) break;
+        }
+        return good();
     }
-    if (err.empty() && !gpu.ok()) err = gpu.error;
-    return err.empty() ? 0 : 1;
+    void from_gz_on_host(const std::string &path) {
+        for_each_block(path, di.block, res.error, [&](const char *p, size_t n) { return upload(p, n); });
+    }
+    void from_plain_file(const std::string &path) {   // read into the pinned block
+        FILE *fp = fopen(path.c_str(), "rb");
+        if (!fp) {
+            res.error = "cannot open " + path;
+            return;
+        }
+        for (bool first = true; good(); first = false) {
+            uint8_t *h = host_block();
+            if (!h) break;
+            const size_t n = fread(h, 1, di.block, fp);
+            if (n == 0) break;
+            if (first && h[0] != '@') {
+                di.refuse(h[0] == '>' ? path + " is FASTA" : path + " does not start with '@'");
+                break;
+            }
+            if (!submit(n)) break;
+        }
+        fclose(fp);
+    }
+
+    void run() {
+        for (size_t i = 0; i < job.paths.size() && good(); ++i) {
+            const std::string &path = job.paths[i];
+            hast_gz *z = nullptr;
+            if (job.gz && gpu.gz_ctx && hast_gz_open(gpu.gz_ctx, path.c_str(), &z) != HAST_OK) z = nullptr;   // (not for the GPU, or not readable: BlockSource's words)
+            if (z) from_gz_on_device(z);
+            else if (job.gz) from_gz_on_host(path);
+            else from_plain_file(path);
+            if (good() && (!job.one_stream || i + 1 == job.paths.size())) end_of_input(path);
+        }
+        {
+            std::lock_guard<std::mutex> g(table_mu);
+            hast_sq_feed_destroy(feed);          // (waits for what this feed has put on the table's stream)
+        }
+        res.bases = bases + sink.bases();
+        std::lock_guard<std::mutex> g(di.mu);
+        di.blocks_framed += blocks;
+        di.gz_on_device += gz_dev;
+    }
+};
+
+// the feed first: without one there is no stream, and nothing else is allocated for it
+void ingest_device_stream(Gpu &gpu, DeviceIngest &di, int k, Job &job) {
+    hast_sq_feed *feed = nullptr;
+    {
+        std::lock_guard<std::mutex> g(*gpu.dev_mu[0]);
+        if (hast_sq_feed_create(gpu.kc, di.block, &feed) != HAST_OK) {
+            gpu.fail(hast_last_error());
+            return;
+        }
+    }
+    DeviceStream(gpu, di, k, job, feed).run();
 }
 
 bool write_histo(const char *path, const std::vector<uint64_t> &h) {
@@ -445,13 +476,41 @@ bool write_histo(const char *path, const std::vector<uint64_t> &h) {
     return fclose(f) == 0;
 }
 
-}  // namespace
-
-int main(int argc, char **argv) {
+// ---- the run ---------------------------------------------------------------------------------------------------------------------
+// What a run holds from one phase of main() to the next.
+struct Run {
     Options o;
+    Gpu gpu;
+    DeviceIngest di;
+    double windows = 0;              // an upper bound on the input's k-mer windows
+    size_t table_bytes = 0;
+    long slices = 1;                 // of the key space: --slices, doubled whenever a table overflows
+    bool gz_in_order = false;        // the host ingest reads each parent's gz files in order, as one stream
+    std::vector<uint64_t> histo[2];
+    ParentTotals tot[2];             // of the last slice read
+    uint64_t stats_sum[6] = {0, 0, 0, 0, 0, 0};
+    size_t n_sel[2] = {0, 0};
+    double t_start = 0, t_table = 0, t_ingest = 0, t_count = 0, t_end = 0;
+};
+
+// the only way out once a Run exists
+int leave(Run &r, int status) {
+    r.gpu.destroy();
+    return status;
+}
+
+// the exit status of GPU trouble, said on stderr
+int gpu_trouble(const char *what) {
+    fprintf(stderr, "unshared_kmers: %s: %s\n", what, hast_last_error());
+    return 4;
+}
+
+// false: leave with `status`
+bool parse_command_line(int argc, char **argv, Options &o, int &status) {
+    status = 0;
     if (argc == 1) {                                                            // s00:57-60
         usage(stdout);
-        return 0;
+        return false;
     }
     printf("CMD :");
     for (int i = 0; i < argc; ++i) printf(" %s", argv[i]);
@@ -460,7 +519,7 @@ int main(int argc, char **argv) {
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto val = [&]() -> const char * { return i + 1 < argc ? argv[++i] : ""; };
-        if (a == "-h" || a == "--help") { usage(stdout); return 0; }
+        if (a == "-h" || a == "--help") { usage(stdout); return false; }
         else if (a == "--memory") o.memory = atol(val());
         else if (a == "--thread") o.cpu = atol(val());
         else if (a == "--m-lower") o.lower[1] = atol(val());
@@ -486,310 +545,349 @@ int main(int argc, char **argv) {
         else if (a == "--ingest") { o.ingest = val(); ingest_given = true; }
         else {                                                                  // s00:113-116: message, then a bare `exit`
             printf("unknown option \"%s\"\n", a.c_str());
-            return 0;
+            return false;
         }
     }
     if (!ingest_given)
         if (const char *e = getenv("HAST_KC_INGEST")) o.ingest = e;
     if (o.ingest != "host" && o.ingest != "device") {
         printf("ERROR: --ingest %s: host or device\n", o.ingest.c_str());
-        return 1;
+        status = 1;
+        return false;
     }
+    return true;
+}
+
+// false: said why on stdout, the exit status is 1
+bool check_arguments(const Options &o) {
     if (o.memory < 1 || o.cpu < 1 || o.files[0].empty() || o.files[1].empty() || o.mer < 11 || o.lower[1] < 1 ||
         o.upper[1] > 100000000 || o.lower[0] < 1 || o.upper[0] > 100000000 || o.slices < 1 || o.slices > 4096) {   // s00:141-152
         printf("ERROR: invalid arguments\n");
-        return 1;
+        return false;
     }
     if (o.mer > 32) {
         printf("ERROR: --mer %ld: this build handles k-mers up to 32 bases\n", o.mer);
-        return 1;
+        return false;
     }
     for (int p = 1; p >= 0; --p)                                                // s00:153-158
         for (const auto &f : o.files[p])
             if (access(f.c_str(), F_OK) != 0) {
                 printf("ERROR: input file \"%s\" does not exist\n", f.c_str());
-                return 1;
+                return false;
             }
     for (int p = 1; p >= 0; --p)                                                // s00:166-185, 197-216
         for (const auto &f : o.files[p])
             if (ends_gz(f) != ends_gz(o.files[p][0])) {
                 printf("ERROR: gz and plain inputs mixed for one parent\n");
-                return 1;
+                return false;
             }
-    const char *pname[2] = {"paternal", "maternal"};
-    const double t_start = now();
-    double t_ingest = 0;
+    return true;
+}
 
-    // Table size when not given: from the input -- an upper bound on its windows from the file sizes (about half the bytes of a
-    // FASTQ are bases, a gz file holds at most ~3 bases per byte) and a slot (16 B) per window: every window a different k-mer would
-    // fill the table to the brim, sequencing data (30 x coverage, 15 % error k-mers) fills a quarter to a third of it.  Round 4 took
-    // twice that, and the record buffers "what is left of the device": 100 GB for a 20-Mbp job, which a box that had just freed
-    // them took 6 s to hand out (profiles/round4_measure.txt).  Too small a guess only costs a restart with more slices; capped by
-    // the library at 85 % of the free HBM.
-    size_t table_bytes = (size_t)(o.table_gb * (double)(1ull << 30));
-    double windows = 0;
-    {
-        for (int p = 0; p < 2; ++p)
-            for (const auto &f : o.files[p]) {
-                struct stat sb;
-                if (stat(f.c_str(), &sb) != 0) continue;
-                bool fasta = false;
-                if (!ends_gz(f)) {
-                    if (FILE *fp = fopen(f.c_str(), "rb")) {
-                        fasta = fgetc(fp) == '>';
-                        fclose(fp);
-                    }
+// Table size when not given: from the input -- an upper bound on its windows from the file sizes (about half the bytes of a
+// FASTQ are bases, a gz file holds at most ~3 bases per byte) and a slot (16 B) per window: every window a different k-mer would
+// fill the table to the brim, sequencing data (30 x coverage, 15 % error k-mers) fills a quarter to a third of it.  Round 4 took
+// twice that, and the record buffers "what is left of the device": 100 GB for a 20-Mbp job, which a box that had just freed
+// them took 6 s to hand out (profiles/round4_measure.txt).  Too small a guess only costs a restart with more slices; capped by
+// the library at 85 % of the free HBM.
+void estimate_windows_and_size_table(Run &r) {
+    const Options &o = r.o;
+    r.table_bytes = (size_t)(o.table_gb * (double)(1ull << 30));
+    for (int p = 0; p < 2; ++p)
+        for (const auto &f : o.files[p]) {
+            struct stat sb;
+            if (stat(f.c_str(), &sb) != 0) continue;
+            bool fasta = false;
+            if (!ends_gz(f)) {
+                if (FILE *fp = fopen(f.c_str(), "rb")) {
+                    fasta = fgetc(fp) == '>';
+                    fclose(fp);
                 }
-                windows += ends_gz(f) ? 3.0 * (double)sb.st_size : fasta ? (double)sb.st_size : 0.55 * (double)sb.st_size;
             }
-        if (table_bytes == 0) table_bytes = (size_t)std::max(256.0 * (1 << 20), windows * 16.0);
-    }
+            r.windows += ends_gz(f) ? 3.0 * (double)sb.st_size : fasta ? (double)sb.st_size : 0.55 * (double)sb.st_size;
+        }
+    if (r.table_bytes == 0) r.table_bytes = (size_t)std::max(256.0 * (1 << 20), r.windows * 16.0);
+}
+
+// one count table per --device; 0, or the exit status
+int create_tables(Run &r) {
+    Options &o = r.o;
     if (o.devices.empty()) o.devices.push_back(0);
-    const long n_dev = (long)o.devices.size();
-    Gpu gpu;
+    const size_t n_dev = o.devices.size();
     for (int dev : o.devices) {
         hast_kc *k = nullptr;
         // --table-gb is per GPU; the automatic size is for the whole key space, i.e. divided between the GPUs
-        const size_t per_dev = o.table_gb > 0 ? table_bytes : table_bytes / (size_t)n_dev + 1;
-        if (hast_kc_create_ex(dev, (int)o.mer, per_dev, (uint64_t)(windows / (double)n_dev * 1.1) + 1, &k) != HAST_OK) {
-            fprintf(stderr, "unshared_kmers: device %d: %s\n", dev, hast_last_error());
-            gpu.destroy();
-            return 4;
-        }
-        gpu.all.push_back(k);
-        gpu.dev_mu.emplace_back(new std::mutex());
+        const size_t per_dev = o.table_gb > 0 ? r.table_bytes : r.table_bytes / n_dev + 1;
+        if (hast_kc_create_ex(dev, (int)o.mer, per_dev, (uint64_t)(r.windows / (double)n_dev * 1.1) + 1, &k) != HAST_OK)
+            return gpu_trouble(("device " + std::to_string(dev)).c_str());
+        r.gpu.all.push_back(k);
+        r.gpu.dev_mu.emplace_back(new std::mutex());
     }
-    gpu.kc = gpu.all[0];
-    DeviceIngest di;
-    if (o.ingest == "device") {
-        if (n_dev > 1) {
-            fprintf(stderr, "--ingest device works with one count table, there are %ld: using the host ingest\n", n_dev);
-            di.fallback = "several tables";
-        } else {
-            di.on = true;
-            if (const char *e = getenv("HAST_KC_INGEST_BLOCK"))
-                if (atol(e) >= 64) di.block = (size_t)atol(e);
-            bool any_gz = false;
-            for (int p = 0; p < 2; ++p) any_gz = any_gz || ends_gz(o.files[p][0]);
-            // (without a context the .gz files are inflated on the host and uploaded)
-            if (any_gz && hast_ctx_create(o.devices[0], (int)o.mer, &gpu.gz_ctx) != HAST_OK) gpu.gz_ctx = nullptr;
-        }
-    }
-    const double t_table = now();
-    auto gpu_fail = [&](const char *what) {
-        fprintf(stderr, "unshared_kmers: %s: %s\n", what, hast_last_error());
-        gpu.destroy();
-        return 4;
-    };
-
-    std::vector<uint64_t> histo[2];
-    long slices = o.slices;
-    bool gz_in_order = false;
-    uint64_t stats_sum[6] = {0, 0, 0, 0, 0, 0};
-    size_t bases[2] = {0, 0}, records[2] = {0, 0}, bytes[2] = {0, 0};
-    // One sweep = every slice of the key space: count both parents, then take what this sweep is for.
-    // Returns 0 ok, 1 input error, 4 GPU error, -1 table full (caller retries with more slices), -2 read the gz files in order,
-    // -3 the device ingest refused the input (caller starts over with the host ingest).
-    // the sets of the tables as they stand, appended to the first GPU's selection
-    auto select_all = [&]() -> bool {
-        for (hast_kc *k : gpu.all) {
-            for (int p = 0; p < 2; ++p) {
-                // a bound pair that selects nothing (upper < lower, e.g. from an empty histogram) is an empty set
-                if (o.upper[p] < o.lower[p] || o.upper[p] < 1) continue;
-                if (hast_kc_select(k, p, (uint32_t)o.lower[p], (uint32_t)std::min<long>(o.upper[p], 0xFFFFFFFFl), nullptr) != HAST_OK) return false;
-            }
-            if (k != gpu.kc && hast_kc_selection_adopt(gpu.kc, k) != HAST_OK) return false;
-        }
-        return true;
-    };
-    auto sweep = [&](bool take_histo, bool take_sets) -> int {
-        for (int p = 0; p < 2; ++p) {
-            if (take_histo) histo[p].assign(HAST_KC_HISTO_HIGH + 2, 0);
-            bases[p] = records[p] = bytes[p] = 0;
-        }
-        for (auto &x : stats_sum) x = 0;
-        di.blocks_framed = di.gz_on_device = 0;
-        if (take_sets)                                                          // a sweep that starts over starts from nothing
-            for (hast_kc *k : gpu.all)
-                if (hast_kc_selection_clear(k) != HAST_OK) return 4;
-        for (long s = 0; s < slices; ++s) {
-            for (long d = 0; d < n_dev; ++d)
-                if (hast_kc_set_slice(gpu.all[d], (uint32_t)(s * n_dev + d), (uint32_t)(slices * n_dev)) != HAST_OK) return 4;
-            auto sync_all = [&]() -> hast_status {                              // table-full on any device wins
-                hast_status worst = HAST_OK;
-                for (hast_kc *k : gpu.all) {
-                    const hast_status st = hast_kc_sync(k);
-                    if (st == HAST_ERR_TABLE_FULL || (st != HAST_OK && worst == HAST_OK)) worst = st;
-                }
-                return worst;
-            };
-            {
-                std::string err;
-                ParentTotals tot[2];
-                const bool was_in_order = gz_in_order;
-                const double t_in = now();
-                const int dev_rc = di.on ? ingest_device_all(gpu, o, di, err, tot) : 0;
-                const bool ok = di.on ? dev_rc == 0 : ingest_all(gpu, o, gz_in_order, err, tot);
-                t_ingest += now() - t_in;
-                if (dev_rc == -3) return -3;
-                if (!ok) {
-                    if (gz_in_order && !was_in_order) return -2;               // a gz file ends inside a record: read them in order
-                    const bool gpu_side = !gpu.error.empty();
-                    if (gpu_side && sync_all() == HAST_ERR_TABLE_FULL) return -1;
-                    fprintf(gpu_side ? stderr : stdout, "ERROR: %s\n", err.c_str());
-                    return gpu_side ? 4 : 1;
-                }
-                for (int p = 0; p < 2; ++p) {
-                    bases[p] = tot[p].bases;
-                    records[p] = tot[p].records;
-                    bytes[p] = tot[p].bytes;
-                }
-            }
-            const hast_status st = sync_all();
-            if (st == HAST_ERR_TABLE_FULL) return -1;
-            if (st != HAST_OK) return 4;
-            stats_sum[3] = 0;
-            for (hast_kc *k : gpu.all) {
-                uint64_t stt[6];
-                if (hast_kc_stats(k, stt) != HAST_OK) return 4;
-                for (int i = 0; i < 6; ++i) stats_sum[i] += stt[i];
-                if (take_histo)
-                    for (int p = 0; p < 2; ++p)
-                        if (hast_kc_histo(k, p, histo[p].data()) != HAST_OK) return 4;
-            }
-            if (take_sets && !select_all()) return 4;
-        }
-        return 0;
-    };
-    auto run = [&](bool take_histo, bool take_sets) -> int {
-        for (;;) {
-            gpu.error.clear();
-            const int rc = sweep(take_histo, take_sets);
-            if (rc == -2) {
-                fprintf(stderr, "a gz input ends inside a record: reading each parent's gz files in order, as one stream\n");
-                for (hast_kc *k : gpu.all) hast_kc_sync(k);
-                continue;
-            }
-            if (rc == -3) {
-                fprintf(stderr, "--ingest device: %s: starting over with the host ingest\n", di.refused.c_str());
-                di.on = false;
-                di.fallback = di.refused;
-                for (hast_kc *k : gpu.all) hast_kc_sync(k);
-                continue;
-            }
-            if (rc != -1) return rc;
-            if (slices >= 4096) {
-                fprintf(stderr, "unshared_kmers: the count table is too small even with %ld slices\n", slices);
-                return 4;
-            }
-            slices *= 2;
-            fprintf(stderr, "count table full: starting over with %ld slices of the key space\n", slices);
-        }
-    };
-
-    // Everything in one sweep when the bounds are known up front or the table holds the whole key space (1 slice:
-    // histogram, bounds and sets all come out of the resident table); otherwise histograms first, sets in a second sweep.
-    int rc;
-    if (!o.auto_bounds) rc = run(false, true);
-    else {
-        rc = run(true, false);
-        if (rc == 0) {
-            for (int p = 1; p >= 0; --p) {                                      // analysis_kmercount.sh:7-13
-                long b[4];
-                hast_kc_find_bounds(histo[p].data(), b);
-                o.lower[p] = b[2];
-                o.upper[p] = b[3];
-                const std::string hp = std::string(pname[p]) + ".histo", bp = std::string(pname[p]) + ".bounds.txt";
-                FILE *f = write_histo(hp.c_str(), histo[p]) ? fopen(bp.c_str(), "w") : nullptr;
-                if (!f) {
-                    printf("ERROR: cannot write %s / %s\n", hp.c_str(), bp.c_str());
-                    gpu.destroy();
-                    return 1;
-                }
-                fprintf(f, "MIN_INDEX=%ld\nMAX_INDEX=%ld\nLOWER_INDEX=%ld\nUPPER_INDEX=%ld\n", b[0], b[1], b[2], b[3]);   // find_bounds.awk:31
-                fclose(f);
-            }
-            if (slices == 1) {                                                  // the tables still hold everything
-                if (!select_all()) rc = 4;
-            } else rc = run(false, true);
-        }
-    }
-    if (rc == 4) return gpu_fail("counting");
-    if (rc != 0) {
-        gpu.destroy();
-        return rc;
-    }
-    const double t_count = now();
-    printf("bounds used for maternal: [%ld, %ld]\n", o.lower[1], o.upper[1]);   // s00:254-255
-    printf("bounds used for paternal: [%ld, %ld]\n", o.lower[0], o.upper[0]);
-
-    for (hast_kc *k : gpu.all)
-        if (hast_kc_release_table(k) != HAST_OK) return gpu_fail("releasing the table");
-    size_t n_sel[2] = {0, 0};
-    for (int p = 0; p < 2; ++p) {
-        if (hast_kc_selection_sort(gpu.kc, p, &n_sel[p]) != HAST_OK) return gpu_fail("sorting the selection");
-        const std::string path = std::string(pname[p]) + ".unique.filter.mer";
-        FILE *f = fopen(path.c_str(), "w");
-        if (!f) {
-            printf("ERROR: cannot write %s\n", path.c_str());
-            gpu.destroy();
-            return 1;
-        }
-        const size_t rows = 4u << 20, width = (size_t)o.mer + 1;
-        std::vector<char> text(std::min(rows, std::max<size_t>(n_sel[p], 1)) * width);
-        for (size_t at = 0; at < n_sel[p]; at += rows) {
-            const size_t n = std::min(rows, n_sel[p] - at);
-            if (hast_kc_selection_text(gpu.kc, p, at, n, text.data()) != HAST_OK) {
-                fclose(f);
-                return gpu_fail("formatting the selection");
-            }
-            if (fwrite(text.data(), 1, n * width, f) != n * width) {
-                printf("ERROR: short write to %s\n", path.c_str());
-                fclose(f);
-                gpu.destroy();
-                return 1;
-            }
-        }
-        if (fclose(f) != 0) {
-            printf("ERROR: cannot write %s\n", path.c_str());
-            gpu.destroy();
-            return 1;
-        }
-    }
-    if (!o.save_table.empty()) {                                                // hap 0 = paternal, hap 1 = maternal (classify -p / -m)
-        hast_ctx *ctx = nullptr;
-        if (hast_ctx_create(o.devices[0], (int)o.mer, &ctx) != HAST_OK) return gpu_fail("--save-table");
-        bool ok = hast_table_reserve(ctx, n_sel[0] + n_sel[1] + 64, 0.0) == HAST_OK;
-        std::vector<uint64_t> keys;
-        for (int p = 0; p < 2 && ok; ++p)
-            for (size_t at = 0; at < n_sel[p] && ok; at += 8u << 20) {
-                const size_t n = std::min<size_t>(8u << 20, n_sel[p] - at);
-                keys.resize(n);
-                ok = hast_kc_selection_keys(gpu.kc, p, at, n, keys.data()) == HAST_OK && hast_table_insert_keys(ctx, p, keys.data(), n) == HAST_OK;
-            }
-        ok = ok && hast_table_save(ctx, o.save_table.c_str()) == HAST_OK;
-        if (!ok) fprintf(stderr, "unshared_kmers: --save-table: %s\n", hast_last_error());
-        hast_ctx_destroy(ctx);
-        if (!ok) {
-            gpu.destroy();
-            return 4;
-        }
-    }
-    printf("paternal-unique k-mers kept: %zu (paternal.unique.filter.mer)\n", n_sel[0]);      // s00:300-303 (wc -l of the products)
-    printf("maternal-unique k-mers kept: %zu (maternal.unique.filter.mer)\n", n_sel[1]);
-    const double t_end = now();
-    if (o.stats) {
-        fprintf(stderr, "[stats] K=%ld gpus=%ld slices=%ld table_slots=%llu keys_in_table=%llu\n", o.mer, n_dev, slices * n_dev,
-                (unsigned long long)stats_sum[3], (unsigned long long)stats_sum[2]);
-        for (int p = 0; p < 2; ++p)
-            fprintf(stderr, "[stats] %s: %zu input bytes, %zu records, %zu bases, %llu k-mers counted, %llu distinct, %zu selected\n", pname[p],
-                    bytes[p], records[p], bases[p], (unsigned long long)stats_sum[4 + p], (unsigned long long)stats_sum[p], n_sel[p]);
-        if (o.ingest == "device")
-            fprintf(stderr, "[stats] ingest device: blocks_framed=%llu gz_on_device=%llu fallback=%s\n", (unsigned long long)di.blocks_framed,
-                    (unsigned long long)di.gz_on_device, di.fallback.c_str());
-        fprintf(stderr, "[stats] table %.3f s, read+parse+count %.3f s, table passes %.3f s, output %.3f s, total %.3f s\n", t_table - t_start, t_ingest,
-                t_count - t_table - t_ingest, t_end - t_count, t_end - t_start);
-    }
-    gpu.destroy();
+    r.gpu.kc = r.gpu.all[0];
     return 0;
+}
+
+void set_up_device_ingest(Run &r) {
+    const Options &o = r.o;
+    if (o.ingest != "device") return;
+    if (r.gpu.all.size() > 1) {
+        fprintf(stderr, "--ingest device works with one count table, there are %zu: using the host ingest\n", r.gpu.all.size());
+        r.di.fallback = "several tables";
+        return;
+    }
+    r.di.on = true;
+    if (const char *e = getenv("HAST_KC_INGEST_BLOCK"))
+        if (atol(e) >= 64) r.di.block = (size_t)atol(e);
+    bool any_gz = false;
+    for (int p = 0; p < 2; ++p) any_gz = any_gz || ends_gz(o.files[p][0]);
+    // (without a context the .gz files are inflated on the host and uploaded)
+    if (any_gz && hast_ctx_create(o.devices[0], (int)o.mer, &r.gpu.gz_ctx) != HAST_OK) r.gpu.gz_ctx = nullptr;
+}
+
+// ---- counting --------------------------------------------------------------------------------------------------------------------
+// the sets of the tables as they stand, appended to the first GPU's selection
+bool select_all(Run &r) {
+    const Options &o = r.o;
+    for (hast_kc *k : r.gpu.all) {
+        for (int p = 0; p < 2; ++p) {
+            // a bound pair that selects nothing (upper < lower, e.g. from an empty histogram) is an empty set
+            if (o.upper[p] < o.lower[p] || o.upper[p] < 1) continue;
+            if (hast_kc_select(k, p, (uint32_t)o.lower[p], (uint32_t)std::min<long>(o.upper[p], 0xFFFFFFFFl), nullptr) != HAST_OK) return false;
+        }
+        if (k != r.gpu.kc && hast_kc_selection_adopt(r.gpu.kc, k) != HAST_OK) return false;
+    }
+    return true;
+}
+
+hast_status sync_all(Gpu &gpu) {                                                // table-full on any device wins
+    hast_status worst = HAST_OK;
+    for (hast_kc *k : gpu.all) {
+        const hast_status st = hast_kc_sync(k);
+        if (st == HAST_ERR_TABLE_FULL || (st != HAST_OK && worst == HAST_OK)) worst = st;
+    }
+    return worst;
+}
+
+// Both parents' files into the tables' current slice, by the device framer or the host parser.  Ok (r.tot: this slice's totals),
+// GzInOrder, DeviceRefused, or InputError for any failure: err says what, whose it is the caller finds out.
+Sweep ingest(Run &r, std::string &err) {
+    std::vector<Job> jobs = build_jobs(r.o, r.di.on, r.gz_in_order);
+    const int k = (int)r.o.mer;
+    if (r.di.on) {
+        r.di.refused.clear();
+        run_jobs(jobs, r.o.cpu, [&](Job &j) { ingest_device_stream(r.gpu, r.di, k, j); });
+        if (!r.di.refused.empty()) return Sweep::DeviceRefused;
+    } else {
+        run_jobs(jobs, r.o.cpu, [&](Job &j) { ingest_stream(r.gpu, k, j); });
+        if (!r.gz_in_order && !gz_files_are_one_stream(jobs)) return Sweep::GzInOrder;
+    }
+    err = fold_jobs(jobs, r.gpu, r.tot);
+    return err.empty() ? Sweep::Ok : Sweep::InputError;
+}
+
+// the tables' statistics summed (table_slots: of this slice), their histograms added up
+bool collect_slice(Run &r, bool take_histo) {
+    r.stats_sum[3] = 0;
+    for (hast_kc *k : r.gpu.all) {
+        uint64_t stt[6];
+        if (hast_kc_stats(k, stt) != HAST_OK) return false;
+        for (int i = 0; i < 6; ++i) r.stats_sum[i] += stt[i];
+        if (take_histo)
+            for (int p = 0; p < 2; ++p)
+                if (hast_kc_histo(k, p, r.histo[p].data()) != HAST_OK) return false;
+    }
+    return true;
+}
+
+// One sweep = every slice of the key space: count both parents, then take what this sweep is for.
+Sweep sweep(Run &r, bool take_histo, bool take_sets) {
+    Gpu &gpu = r.gpu;
+    const long n_dev = (long)gpu.all.size();
+    for (int p = 0; p < 2 && take_histo; ++p) r.histo[p].assign(HAST_KC_HISTO_HIGH + 2, 0);
+    for (auto &x : r.stats_sum) x = 0;
+    r.di.blocks_framed = r.di.gz_on_device = 0;
+    if (take_sets)                                                              // a sweep that starts over starts from nothing
+        for (hast_kc *k : gpu.all)
+            if (hast_kc_selection_clear(k) != HAST_OK) return Sweep::GpuError;
+    for (long s = 0; s < r.slices; ++s) {
+        for (long d = 0; d < n_dev; ++d)
+            if (hast_kc_set_slice(gpu.all[d], (uint32_t)(s * n_dev + d), (uint32_t)(r.slices * n_dev)) != HAST_OK) return Sweep::GpuError;
+        std::string err;
+        const double t_in = now();
+        const Sweep in = ingest(r, err);
+        r.t_ingest += now() - t_in;
+        if (in == Sweep::InputError) {
+            // A count the table refused leaves gpu.error, and then the tables decide: one of them full is a reason to start over,
+            // whatever an input said meanwhile; anything else of the GPU's goes to stderr, an input's error to stdout.
+            const bool gpu_side = !gpu.error.empty();
+            if (gpu_side && sync_all(gpu) == HAST_ERR_TABLE_FULL) return Sweep::TableFull;
+            fprintf(gpu_side ? stderr : stdout, "ERROR: %s\n", err.c_str());
+            return gpu_side ? Sweep::GpuError : Sweep::InputError;
+        }
+        if (in != Sweep::Ok) return in;
+        const hast_status st = sync_all(gpu);
+        if (st == HAST_ERR_TABLE_FULL) return Sweep::TableFull;
+        if (st != HAST_OK || !collect_slice(r, take_histo)) return Sweep::GpuError;
+        if (take_sets && !select_all(r)) return Sweep::GpuError;
+    }
+    return Sweep::Ok;
+}
+
+// A sweep, started over for as long as it asks to be.  Ok, InputError or GpuError.
+Sweep count(Run &r, bool take_histo, bool take_sets) {
+    for (;;) {
+        r.gpu.error.clear();
+        const Sweep s = sweep(r, take_histo, take_sets);
+        if (s == Sweep::GzInOrder) {
+            fprintf(stderr, "a gz input ends inside a record: reading each parent's gz files in order, as one stream\n");
+            r.gz_in_order = true;
+            for (hast_kc *k : r.gpu.all) hast_kc_sync(k);
+        } else if (s == Sweep::DeviceRefused) {
+            fprintf(stderr, "--ingest device: %s: starting over with the host ingest\n", r.di.refused.c_str());
+            r.di.on = false;
+            r.di.fallback = r.di.refused;
+            for (hast_kc *k : r.gpu.all) hast_kc_sync(k);
+        } else if (s == Sweep::TableFull) {
+            if (r.slices >= 4096) {
+                fprintf(stderr, "unshared_kmers: the count table is too small even with %ld slices\n", r.slices);
+                return Sweep::GpuError;
+            }
+            r.slices *= 2;
+            fprintf(stderr, "count table full: starting over with %ld slices of the key space\n", r.slices);
+        } else return s;
+    }
+}
+
+// the process's exit status after count(), the one place that turns a Sweep into one; what is the GPU's is said here ("counting")
+int exit_status(Sweep s) { return s == Sweep::Ok ? 0 : s == Sweep::InputError ? 1 : gpu_trouble("counting"); }
+
+// --auto_bounds: the four bounds out of the histograms, which go to *.histo and *.bounds.txt (analysis_kmercount.sh:7-13); 0, or the exit status
+int write_histograms_and_bounds(Run &r) {
+    for (int p = 1; p >= 0; --p) {
+        long b[4];
+        hast_kc_find_bounds(r.histo[p].data(), b);
+        r.o.lower[p] = b[2];
+        r.o.upper[p] = b[3];
+        const std::string hp = std::string(kParentName[p]) + ".histo", bp = std::string(kParentName[p]) + ".bounds.txt";
+        FILE *f = write_histo(hp.c_str(), r.histo[p]) ? fopen(bp.c_str(), "w") : nullptr;
+        if (!f) {
+            printf("ERROR: cannot write %s / %s\n", hp.c_str(), bp.c_str());
+            return 1;
+        }
+        fprintf(f, "MIN_INDEX=%ld\nMAX_INDEX=%ld\nLOWER_INDEX=%ld\nUPPER_INDEX=%ld\n", b[0], b[1], b[2], b[3]);   // find_bounds.awk:31
+        fclose(f);
+    }
+    return 0;
+}
+
+// Everything in one sweep when the bounds are known up front or the table holds the whole key space (1 slice:
+// histogram, bounds and sets all come out of the resident table); otherwise histograms first, sets in a second sweep.
+// 0, or the exit status
+int count_and_select(Run &r) {
+    if (!r.o.auto_bounds) return exit_status(count(r, false, true));
+    if (int st = exit_status(count(r, true, false))) return st;
+    if (int st = write_histograms_and_bounds(r)) return st;
+    if (r.slices == 1) return select_all(r) ? 0 : gpu_trouble("counting");      // the tables still hold everything
+    return exit_status(count(r, false, true));
+}
+
+// ---- the products ----------------------------------------------------------------------------------------------------------------
+// a parent's sorted selection as text, one k-mer per line; 0, or the exit status
+int write_mer_file(Run &r, int p) {
+    hast_kc *kc = r.gpu.kc;
+    if (hast_kc_selection_sort(kc, p, &r.n_sel[p]) != HAST_OK) return gpu_trouble("sorting the selection");
+    const std::string path = std::string(kParentName[p]) + ".unique.filter.mer";
+    FILE *f = fopen(path.c_str(), "w");
+    if (!f) {
+        printf("ERROR: cannot write %s\n", path.c_str());
+        return 1;
+    }
+    const size_t rows = 4u << 20, width = (size_t)r.o.mer + 1, n_sel = r.n_sel[p];
+    std::vector<char> text(std::min(rows, std::max<size_t>(n_sel, 1)) * width);
+    for (size_t at = 0; at < n_sel; at += rows) {
+        const size_t n = std::min(rows, n_sel - at);
+        if (hast_kc_selection_text(kc, p, at, n, text.data()) != HAST_OK) {
+            fclose(f);
+            return gpu_trouble("formatting the selection");
+        }
+        if (fwrite(text.data(), 1, n * width, f) != n * width) {
+            printf("ERROR: short write to %s\n", path.c_str());
+            fclose(f);
+            return 1;
+        }
+    }
+    if (fclose(f) != 0) {
+        printf("ERROR: cannot write %s\n", path.c_str());
+        return 1;
+    }
+    return 0;
+}
+
+int sort_and_write_mer_files(Run &r) {
+    for (hast_kc *k : r.gpu.all)
+        if (hast_kc_release_table(k) != HAST_OK) return gpu_trouble("releasing the table");
+    for (int p = 0; p < 2; ++p)
+        if (int st = write_mer_file(r, p)) return st;
+    return 0;
+}
+
+// --save-table: the two sets as a stage-01 table; hap 0 = paternal, hap 1 = maternal (classify -p / -m).  0, or the exit status
+int save_table(Run &r) {
+    const Options &o = r.o;
+    if (o.save_table.empty()) return 0;
+    hast_ctx *ctx = nullptr;
+    if (hast_ctx_create(o.devices[0], (int)o.mer, &ctx) != HAST_OK) return gpu_trouble("--save-table");
+    bool ok = hast_table_reserve(ctx, r.n_sel[0] + r.n_sel[1] + 64, 0.0) == HAST_OK;
+    std::vector<uint64_t> keys;
+    for (int p = 0; p < 2 && ok; ++p)
+        for (size_t at = 0; at < r.n_sel[p] && ok; at += 8u << 20) {
+            const size_t n = std::min<size_t>(8u << 20, r.n_sel[p] - at);
+            keys.resize(n);
+            ok = hast_kc_selection_keys(r.gpu.kc, p, at, n, keys.data()) == HAST_OK && hast_table_insert_keys(ctx, p, keys.data(), n) == HAST_OK;
+        }
+    ok = ok && hast_table_save(ctx, o.save_table.c_str()) == HAST_OK;
+    const int status = ok ? 0 : gpu_trouble("--save-table");
+    hast_ctx_destroy(ctx);
+    return status;
+}
+
+void print_stats(const Run &r) {
+    const Options &o = r.o;
+    const long n_dev = (long)o.devices.size();
+    fprintf(stderr, "[stats] K=%ld gpus=%ld slices=%ld table_slots=%llu keys_in_table=%llu\n", o.mer, n_dev, r.slices * n_dev,
+            (unsigned long long)r.stats_sum[3], (unsigned long long)r.stats_sum[2]);
+    for (int p = 0; p < 2; ++p)
+        fprintf(stderr, "[stats] %s: %zu input bytes, %zu records, %zu bases, %llu k-mers counted, %llu distinct, %zu selected\n", kParentName[p],
+                r.tot[p].bytes, r.tot[p].records, r.tot[p].bases, (unsigned long long)r.stats_sum[4 + p], (unsigned long long)r.stats_sum[p], r.n_sel[p]);
+    if (o.ingest == "device")
+        fprintf(stderr, "[stats] ingest device: blocks_framed=%llu gz_on_device=%llu fallback=%s\n", (unsigned long long)r.di.blocks_framed,
+                (unsigned long long)r.di.gz_on_device, r.di.fallback.c_str());
+    fprintf(stderr, "[stats] table %.3f s, read+parse+count %.3f s, table passes %.3f s, output %.3f s, total %.3f s\n", r.t_table - r.t_start, r.t_ingest,
+            r.t_count - r.t_table - r.t_ingest, r.t_end - r.t_count, r.t_end - r.t_start);
+}
+
+}  // namespace
+
+int main(int argc, char **argv) {
+    Run r;
+    int status = 0;
+    if (!parse_command_line(argc, argv, r.o, status)) return leave(r, status);
+    if (!check_arguments(r.o)) return leave(r, 1);
+    r.slices = r.o.slices;
+    r.t_start = now();
+    estimate_windows_and_size_table(r);
+    if ((status = create_tables(r))) return leave(r, status);
+    set_up_device_ingest(r);
+    r.t_table = now();
+    if ((status = count_and_select(r))) return leave(r, status);
+    r.t_count = now();
+    printf("bounds used for maternal: [%ld, %ld]\n", r.o.lower[1], r.o.upper[1]);   // s00:254-255
+    printf("bounds used for paternal: [%ld, %ld]\n", r.o.lower[0], r.o.upper[0]);
+    if ((status = sort_and_write_mer_files(r))) return leave(r, status);
+    if ((status = save_table(r))) return leave(r, status);
+    printf("paternal-unique k-mers kept: %zu (paternal.unique.filter.mer)\n", r.n_sel[0]);      // s00:300-303 (wc -l of the products)
+    printf("maternal-unique k-mers kept: %zu (maternal.unique.filter.mer)\n", r.n_sel[1]);
+    r.t_end = now();
+    if (r.o.stats) print_stats(r);
+    return leave(r, 0);
 }

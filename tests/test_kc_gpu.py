@@ -10,7 +10,7 @@ import pytest
 
 import hast_amd
 from hast_amd import KcSynth, KmerCounter
-from tests.conftest import golden_cases, run_s00_case
+from tests.conftest import golden_cases, load_case, run_s00_case
 
 pytestmark = pytest.mark.gpu
 U64P = C.POINTER(C.c_uint64)
@@ -362,6 +362,29 @@ def test_kmers_piled_on_one_minimizer(built, oracle_lib):
 def test_unshared_kmers_matches_reference_script_golden(built, golden_workdir, tmp_path, case, run):
     res = run_s00_case(hast_amd.unshared_kmers_exe(), golden_workdir, tmp_path, case, run, extra_args=["--table-gb", "0.25", "--stats"])
     assert b"[stats]" in res.stderr
+
+
+@pytest.mark.parametrize("run", ["default_bounds", "auto"])
+def test_unshared_kmers_stdout_line_by_line(built, golden_workdir, tmp_path, run):
+    """what a successful run prints on stdout, and nothing else: the command line, the bounds (maternal first,
+    build_unshared_kmers.sh:254-255), the sizes of the two products (:300-303)"""
+    case, exe, extra = "s00_trio_k21", hast_amd.unshared_kmers_exe(), ["--table-gb", "0.25"]
+    res = run_s00_case(exe, golden_workdir, tmp_path, case, run, extra_args=extra)
+    meta = load_case(case)["runs"][run]
+    work = tmp_path / ("%s_%s" % (case, run))
+    bounds = {"paternal": (9, 33), "maternal": (9, 33)}                          # the defaults (:44-55)
+    if run == "auto":
+        for name in bounds:
+            rows = dict(l.split("=") for l in open(work / (name + ".bounds.txt")).read().split())
+            bounds[name] = (int(rows["LOWER_INDEX"]), int(rows["UPPER_INDEX"]))
+    expected = ["CMD : " + " ".join([exe] + meta["argv"] + extra)]
+    expected += ["bounds used for %s: [%d, %d]" % ((name,) + bounds[name]) for name in ("maternal", "paternal")]
+    for name in ("paternal", "maternal"):
+        prod = name + ".unique.filter.mer"
+        n = len(open(work / prod, "rb").read().splitlines())
+        assert n == meta["products"][prod]["lines"]
+        expected.append("%s-unique k-mers kept: %d (%s)" % (name, n, prod))
+    assert res.stdout.decode() == "".join(l + "\n" for l in expected)
 
 
 def test_unshared_kmers_default_table_size(built, golden_workdir, tmp_path):

@@ -1,4 +1,4 @@
-# stage 00: `unshared_kmers --ingest device` against `--ingest host` of the same tree and against another commit's binary (OLD=dir
+# stage 00: `unshared_kmers --ingest device` against `--ingest host` of the same tree and against another commit's binary run both ways (OLD=dir
 # with that commit's libhast.so + unshared_kmers, built by hand, not committed; left out when there is none), on one box, alternating,
 # 5 s apart (back-to-back processes lie).  Inputs: a tools/gen_trio trio of GENOME x COVERAGE bases per parent (default
 # 50 Mbp x 40 = 2 Gbp) as plain FASTQ and as ONE gzip member per file (tools/pgzip1).  Every run has its own time limit and the chain
@@ -33,7 +33,10 @@ one() {   # name, exe, input suffix, extra args...
 }
 for suf in fq fq.gz; do
   for i in $(seq $RUNS); do
-    if [ -n "$OLD" ]; then one old $OLD/unshared_kmers $suf || exit 1; fi
+    if [ -n "$OLD" ]; then
+      one old-host $OLD/unshared_kmers $suf --ingest host || exit 1
+      one old-device $OLD/unshared_kmers $suf --ingest device || exit 1
+    fi
     one host $ROOT/hast_amd/unshared_kmers $suf --ingest host || exit 1
     one device $ROOT/hast_amd/unshared_kmers $suf --ingest device || exit 1
   done
