@@ -61,6 +61,10 @@ class TxResult(C.Structure):
                 ("out_bytes", C.c_uint64 * 2), ("raw_bytes", C.c_uint64 * 2), ("lines", C.c_uint32 * 2)]
 
 
+class TxTimes(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("upload_s", "kernel_s", "deflate_s", "download_s")]
+
+
 SQ_NOT_FOUR_LINE, SQ_NO_RECORD = 1, 2
 KC_HISTO_HIGH = 10000
 
@@ -212,6 +216,11 @@ ABI_SYMBOLS = {
                                     C.POINTER(TxResult)]),
     "hast_tx_free": (None, [vp]),
     "hast_tx_step_mode": (C.c_int, [C.c_int, C.c_int, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]),
+    "hast_tx_create": (C.c_int, [vp, vp, C.c_size_t, C.POINTER(vp)]),
+    "hast_tx_pair_device": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(TxState), vp, C.c_size_t, vp, C.c_size_t, C.POINTER(TxResult), vp]),
+    "hast_tx_destroy": (None, [vp]),
+    "hast_tx_pair_staged": (C.c_int, [vp, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(TxState), C.c_int, C.POINTER(vp), C.POINTER(vp),
+                                      C.POINTER(TxResult), C.POINTER(TxTimes)]),
 }
 
 
@@ -779,6 +788,46 @@ class TxMap:
     def close(self):
         if self._h:
             self._lib.hast_tx_map_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class TxConverter:
+    """The conversion over device memory (hast_tx_create / hast_tx_pair_device): the map as a table in HBM and the scratch of the worst
+    step of max_in_bytes a side, on a Context's device and stream.  A map that is not device_ok raises HastError(UNSUPPORTED)."""
+
+    def __init__(self, ctx: Context, tx_map: TxMap, max_in_bytes):
+        self._lib = lib()
+        self._h = C.c_void_p()
+        _ck(self._lib.hast_tx_create(ctx._h, tx_map._h, max_in_bytes, C.byref(self._h)))
+
+    def pair_device(self, d_r1, n1, d_r2, n2, state: TxState, d_out1, cap1, d_out2, cap2, stream=None) -> TxResult:
+        """TxMap.pair_host(..., False, state) over d_r1[0, n1) / d_r2[0, n2) into d_out1 / d_out2; state is updated.  An output larger
+        than its room raises HastError(UNSUPPORTED) whose .result holds the sizes needed; state is then unchanged."""
+        res = TxResult()
+        st = self._lib.hast_tx_pair_device(self._h, C.c_void_p(d_r1), n1, C.c_void_p(d_r2), n2, C.byref(state), C.c_void_p(d_out1), cap1, C.c_void_p(d_out2), cap2,
+                                           C.byref(res), stream)
+        if st != 0:
+            err = HastError(st, self._lib.hast_last_error().decode())
+            err.result = res
+            raise err
+        return res
+
+    def pair_staged(self, r1: bytes, r2: bytes, state: TxState, gz, times: TxTimes = None):
+        """a step from host bytes to host bytes (hast_tx_pair_staged) -> (out1, out2, TxResult); gz: each run as one gzip member"""
+        o1, o2, res = C.c_void_p(), C.c_void_p(), TxResult()
+        times = TxTimes() if times is None else times
+        _ck(self._lib.hast_tx_pair_staged(self._h, r1, len(r1), r2, len(r2), C.byref(state), int(gz), C.byref(o1), C.byref(o2), C.byref(res), C.byref(times)))
+        return C.string_at(o1, res.out_bytes[0]), C.string_at(o2, res.out_bytes[1]), res
+
+    def close(self):
+        if self._h:
+            self._lib.hast_tx_destroy(self._h)
             self._h = C.c_void_p()
 
     def __enter__(self):

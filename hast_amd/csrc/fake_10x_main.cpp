@@ -1,13 +1,19 @@
 // fake_10x -- drop-in for HAST's 02.assemble_by_supernova/fake_10x.pl: stLFR read pairs -> 10x FASTQ for Supernova.
 //   fake_10x READ1.gz READ2.gz MERGE.txt [--inflate host|zlib] [--block-mb N] [--plain-out] [--stats]
+//            [--convert host|device] [--deflate host|device]
 // writes SampleName_S1_L001_R1_001.fastq.gz and SampleName_S1_L001_R2_001.fastq.gz into the working directory and prints the
 // script's stdout.  A host program: the inputs come through ingest.h (ordinary gzip inflated by several threads, BGZF, pipes, plain
 // FASTQ), a block of each at a time; the whole pairs of what has been read go through the model of the script
 // (hast_tx_pair_host, include/hast.h "stage 02"), what is left is carried in front of the next block; both outputs leave as one
 // zlib gzip member per step, deflated side by side.  Memory stays at a few blocks whatever the inputs' lengths: when read 2 ends
 // first, the rest of read 1 is still converted block by block, as the script pairs it with nothing.
+// --convert device: the steps over whole pairs go to the GPU (hast_tx_pair_staged: upload through pinned staging, the kernels of
+// tx_kernels.hip, with --deflate device -- the default then -- one gzip member per side and step from the GPU's encoder, download);
+// one writer thread per output file writes step n beside step n + 1 (and deflates it, with --deflate host).  The steps at the end of
+// the inputs, a step larger than the converter was created for and one whose outputs outgrow their room are the host model's.  A
+// map the device cannot take (hast_tx_map_info.device_ok == 0) sends the whole run the host way, with one WARN line.
 // Exit codes: 0 done; 1 usage; 2 an input that cannot be opened, or a .gz that is damaged or fails its CRC; 3 a failing library
-// call or write.
+// call or write; 4 --convert device without a usable GPU, or a failing GPU call.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -15,6 +21,8 @@
 
 #include <algorithm>
 #include <chrono>
+#include <condition_variable>
+#include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
@@ -27,14 +35,15 @@ namespace {
 struct Options {
     std::string in[2], map;
     bool plain_out = false, stats = false;
-    std::string inflate = "host";
+    std::string inflate = "host", convert = "host", deflate;      // deflate: "" = host, or device with --convert device
     size_t block = 16u << 20;
 };
 
 double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 int usage() {
-    fprintf(stderr, "usage: fake_10x READ1.gz READ2.gz MERGE.txt [--inflate host|zlib] [--block-mb N] [--plain-out] [--stats]\n");
+    fprintf(stderr, "usage: fake_10x READ1.gz READ2.gz MERGE.txt [--inflate host|zlib] [--block-mb N] [--plain-out] [--stats]\n"
+                    "                [--convert host|device] [--deflate host|device]\n");
     return 1;
 }
 
@@ -99,6 +108,70 @@ struct Outputs {
     }
 };
 
+// The writer of one output file (--convert device): takes one run at a time and writes it while the next step is converted.  submit
+// waits until the run before has been written, so the memory of run n is free again once run n + 1 has been handed over.
+struct Writer {
+    struct Job {
+        const uint8_t *p = nullptr;
+        size_t n = 0;
+        bool deflate = false;      // through zlib first (write_host), or as it is
+        void *free_me = nullptr;   // a host step's output: hast_tx_free once written
+    };
+    Outputs *out = nullptr;
+    int side = 0;
+    std::thread th;
+    std::mutex mu;
+    std::condition_variable cv;
+    Job job;
+    bool have = false, quit = false, ok = true;
+    double busy = 0;
+    void start(Outputs *o, int s) {
+        out = o;
+        side = s;
+        th = std::thread([this] {
+            std::unique_lock<std::mutex> lk(mu);
+            for (;;) {
+                cv.wait(lk, [this] { return have || quit; });
+                if (!have) return;
+                const Job j = job;
+                lk.unlock();
+                const double t0 = now();
+                const bool good = j.deflate ? out->write_host(side, j.p, j.n) : out->write(side, j.p, j.n);
+                if (j.free_me) hast_tx_free(j.free_me);
+                lk.lock();
+                busy += now() - t0;
+                ok = ok && good;
+                have = false;
+                cv.notify_all();
+            }
+        });
+    }
+    // false: a run before this one could not be written; this one is dropped (and freed), the run ends
+    bool submit(const Job &j) {
+        std::unique_lock<std::mutex> lk(mu);
+        cv.wait(lk, [this] { return !have; });
+        if (!ok) {
+            if (j.free_me) hast_tx_free(j.free_me);
+            return false;
+        }
+        job = j;
+        have = true;
+        cv.notify_all();
+        return true;
+    }
+    bool stop() {                  // everything handed over has been written
+        if (!th.joinable()) return ok;
+        {
+            std::unique_lock<std::mutex> lk(mu);
+            cv.wait(lk, [this] { return !have; });
+            quit = true;
+            cv.notify_all();
+        }
+        th.join();
+        return ok;
+    }
+};
+
 struct Input {
     std::string path;
     hast::BlockSource src;
@@ -112,6 +185,14 @@ struct Run {
     hast_tx_state st{0, 0};
     Outputs out;
     uint64_t steps = 0, plain_in = 0;
+    // --convert device
+    hast_ctx *ctx = nullptr;
+    hast_tx *tx = nullptr;         // null: every step is the host model's
+    std::string fallback = "none";
+    hast_tx_times times{0, 0, 0, 0};
+    uint64_t pairs_device = 0, pairs_host = 0;
+    Writer writer[2];
+    double write_s = 0;
 };
 
 void progress(uint64_t before, uint64_t after) {
@@ -164,13 +245,49 @@ int run(Run &r) {
         uint8_t *o[2] = {nullptr, nullptr};
         hast_tx_result res;
         const uint64_t before = r.st.headers;
-        if (hast_tx_pair_host(r.map, have[0].data(), have[0].size(), have[1].data(), have[1].size(), mode, &r.st, &o[0], &o[1], &res) != HAST_OK)
+        bool on_device = false;
+        if (r.tx && mode == 0) {
+            const bool gz = !r.o.plain_out && r.o.deflate == "device";
+            const uint8_t *p[2];
+            const hast_status st = hast_tx_pair_staged(r.tx, have[0].data(), have[0].size(), have[1].data(), have[1].size(), &r.st, gz, &p[0], &p[1], &res, &r.times);
+            if (st == HAST_OK) {
+                on_device = true;
+                for (int s = 0; s < 2; ++s) {
+                    Writer::Job j;
+                    j.p = p[s];
+                    j.n = (size_t)res.out_bytes[s];
+                    j.deflate = !r.o.plain_out && !gz;
+                    if (!r.writer[s].submit(j)) {
+                        fprintf(stderr, "fake_10x: cannot write the outputs\n");
+                        return 3;
+                    }
+                }
+            } else if (st != HAST_ERR_UNSUPPORTED) {
+                fprintf(stderr, "fake_10x: the conversion on the device: %s\n", hast_last_error());
+                return 4;
+            }
+        }
+        if (!on_device && hast_tx_pair_host(r.map, have[0].data(), have[0].size(), have[1].data(), have[1].size(), mode, &r.st, &o[0], &o[1], &res) != HAST_OK)
             return fail_lib("the conversion");
         progress(before, r.st.headers);
         ++r.steps;
-        const bool ok = r.out.write_host_both(o, res.out_bytes);
-        hast_tx_free(o[0]);
-        hast_tx_free(o[1]);
+        (on_device ? r.pairs_device : r.pairs_host) += res.pairs;
+        bool ok = true;
+        if (on_device) {
+        } else if (r.tx) {                                         // behind the runs the writers still hold, in order
+            for (int s = 0; s < 2; ++s) {
+                Writer::Job j;
+                j.p = o[s];
+                j.n = (size_t)res.out_bytes[s];
+                j.deflate = !r.o.plain_out;
+                j.free_me = o[s];
+                if (!r.writer[s].submit(j)) ok = false;          // (the other side's run is still handed over, or freed there)
+            }
+        } else {
+            ok = r.out.write_host_both(o, res.out_bytes);
+            hast_tx_free(o[0]);
+            hast_tx_free(o[1]);
+        }
         if (!ok) {
             fprintf(stderr, "fake_10x: cannot write the outputs\n");
             return 3;
@@ -192,12 +309,16 @@ int main(int argc, char **argv) {
         auto value = [&]() -> const char * { return i + 1 < argc ? argv[++i] : nullptr; };
         if (a == "--inflate") { const char *v = value(); if (!v || (strcmp(v, "host") && strcmp(v, "zlib"))) return usage(); r.o.inflate = v; }
         else if (a == "--block-mb") { const char *v = value(); if (!v || atoi(v) < 1 || atoi(v) > 1024) return usage(); r.o.block = (size_t)atoi(v) << 20; block_given = true; }
+        else if (a == "--convert") { const char *v = value(); if (!v || (strcmp(v, "host") && strcmp(v, "device"))) return usage(); r.o.convert = v; }
+        else if (a == "--deflate") { const char *v = value(); if (!v || (strcmp(v, "host") && strcmp(v, "device"))) return usage(); r.o.deflate = v; }
         else if (a == "--plain-out") r.o.plain_out = true;
         else if (a == "--stats") r.o.stats = true;
         else if (a.size() > 1 && a[0] == '-' && a[1] == '-') return usage();
         else pos.push_back(a);
     }
     if (pos.size() != 3) return usage();
+    if (r.o.deflate == "device" && r.o.convert != "device") return usage();      // (the encoder takes device memory)
+    if (r.o.deflate.empty()) r.o.deflate = r.o.convert;
     r.o.in[0] = pos[0];
     r.o.in[1] = pos[1];
     r.o.map = pos[2];
@@ -210,13 +331,37 @@ int main(int argc, char **argv) {
         fprintf(stderr, "fake_10x: %s\n", hast_last_error());
         return 2;
     }
+    if (r.o.convert == "device" && !r.info.device_ok) {
+        fprintf(stderr, "WARN: fake_10x: the map cannot go to the device (%s): converting on the host\n", r.info.reason);
+        r.fallback = r.info.reason;
+        std::replace(r.fallback.begin(), r.fallback.end(), ' ', '_');
+    } else if (r.o.convert == "device") {
+        // a step holds what the step before left and a block: two blocks in all but odd cases; at least 1 MB, so that records far
+        // larger than a small block still go to the device; at most what 32-bit offsets allow
+        const size_t max_in = std::min<size_t>(std::max<size_t>(2 * r.o.block + 4096, 1u << 20), 128u << 20);
+        if (hast_ctx_create(0, 21, &r.ctx) != HAST_OK || hast_tx_create(r.ctx, r.map, max_in, &r.tx) != HAST_OK) {
+            fprintf(stderr, "fake_10x: --convert device: %s\n", hast_last_error());
+            return 4;
+        }
+    }
     if (!r.out.open(r.o.plain_out)) {
         fprintf(stderr, "fake_10x: cannot create the outputs in the working directory\n");
         return 3;
     }
     const double t0 = now();
-    const int rc = run(r);
+    if (r.tx)
+        for (int s = 0; s < 2; ++s) r.writer[s].start(&r.out, s);
+    int rc = run(r);
+    for (int s = 0; s < 2; ++s) {
+        if (!r.writer[s].stop() && !rc) {
+            fprintf(stderr, "fake_10x: cannot write the outputs\n");
+            rc = 3;
+        }
+        r.write_s += r.writer[s].busy;
+    }
     const bool closed = r.out.close();
+    hast_tx_destroy(r.tx);
+    if (r.ctx) hast_ctx_destroy(r.ctx);
     hast_tx_map_destroy(r.map);
     if (rc) return rc;
     if (!closed) {
@@ -224,7 +369,13 @@ int main(int argc, char **argv) {
         return 3;
     }
     printf("Total %llu pair reads and used %llu pairs.\n", (unsigned long long)r.st.headers, (unsigned long long)r.st.used);
-    if (r.o.stats) {
+    if (r.o.stats && r.o.convert == "device") {
+        fprintf(stderr, "[stats] transform device: steps=%llu pairs_on_device=%llu pairs_on_host=%llu fallback=%s\n", (unsigned long long)r.steps,
+                (unsigned long long)r.pairs_device, (unsigned long long)r.pairs_host, r.fallback.c_str());
+        fprintf(stderr, "[stats] seconds: upload=%.3f kernels=%.3f deflate=%.3f download=%.3f write=%.3f read_phase=%.3f plain_in_bytes=%llu out_bytes=%llu+%llu\n",
+                r.times.upload_s, r.times.kernel_s, r.times.deflate_s, r.times.download_s, r.write_s, now() - t0, (unsigned long long)r.plain_in,
+                (unsigned long long)r.out.bytes[0], (unsigned long long)r.out.bytes[1]);
+    } else if (r.o.stats) {
         fprintf(stderr, "[stats] transform host: steps=%llu pairs_on_device=0 pairs_on_host=%llu fallback=none\n", (unsigned long long)r.steps,
                 (unsigned long long)r.st.headers);
         fprintf(stderr, "[stats] seconds: read_phase=%.3f plain_in_bytes=%llu out_bytes=%llu+%llu\n", now() - t0, (unsigned long long)r.plain_in,

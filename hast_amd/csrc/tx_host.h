@@ -7,8 +7,10 @@
 
 #include <string>
 #include <unordered_map>
+#include <vector>
 
 #include "tx_core.h"
+#include "tx_plan.h"
 
 namespace hast {
 namespace tx {
@@ -44,6 +46,22 @@ inline void map_parse(const uint8_t *text, size_t n, Map &m) {
     }
     m.device_ok = !(empty_key || long_key || long_value);
     m.reason = empty_key ? "empty key" : long_key ? "key longer than 15 bytes" : long_value ? "value longer than 16 bytes" : "none";
+}
+
+// the map as the table of tx_plan.h (device_ok maps only: keys of 1 .. 15 bytes, values of 0 .. 16); what a device step uploads
+inline void table_build(const Map &m, std::vector<TableSlot> &table) {
+    table.assign((size_t)table_slots_for(m.kv.size()), TableSlot{});
+    const uint32_t mask = (uint32_t)table.size() - 1;
+    for (const auto &e : m.kv) {
+        uint32_t k[4];
+        pack_key(reinterpret_cast<const uint8_t *>(e.first.data()), (uint32_t)e.first.size(), k);
+        uint32_t at = name_hash(k) & mask;
+        while (table[at].key[0]) at = (at + 1) & mask;
+        TableSlot &s = table[at];
+        memcpy(s.key, k, sizeof k);
+        memcpy(s.value, e.second.data(), e.second.size());
+        s.v = (uint32_t)e.second.size();
+    }
 }
 
 struct State {

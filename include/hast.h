@@ -681,7 +681,8 @@ hast_status hast_sq_feed_take_tail(hast_sq_feed *, uint8_t *dst, size_t *n_bytes
 void        hast_sq_feed_destroy(hast_sq_feed *);
 
 /* ---- stage 02: stLFR pairs -> 10x FASTQ (02.assemble_by_supernova/fake_10x.pl) ----------------------------------------------
- * The script's conversion, on the host (no GPU is touched): record i of read 1 goes with record i of read 2; the key in read 1's
+ * The script's conversion, on the host (hast_tx_pair_host: no GPU is touched) and over device memory (hast_tx_pair_device):
+ * record i of read 1 goes with record i of read 2; the key in read 1's
  * header (the text after the first '#' of the header's first tab field, up to the next '#' or '/') is looked up in the map file; a
  * pair whose key the map lacks is dropped, a pair it holds is numbered (N, from 1) and both records rewritten
  * (hast_amd/csrc/tx_core.h has the rules, tx_host.h the model).
@@ -709,6 +710,31 @@ void        hast_tx_free(void *);
 /* the `final` of the next hast_tx_pair_host call over what a caller has read and not converted yet; eof1 / eof2: that input has been
  * read to its end.  1 also when read 1 has ended without a whole record and read 2 holds one (the script takes no more than that). */
 int         hast_tx_step_mode(int eof1, int eof2, const uint8_t *r1, size_t n1, const uint8_t *r2, size_t n2);
+/* The same conversion over device memory (hast_amd/csrc/tx_kernels.hip; what is decided per record: tx_plan.h).
+ * hast_tx_create uploads the map as a read-only table and allocates, once, the scratch of the worst step of max_in_bytes a side
+ * (at most 128 MB: offsets inside a step are 32 bits wide; more is HAST_ERR_INVALID).  A map with info.device_ok == 0 is
+ * HAST_ERR_UNSUPPORTED, with info.reason in hast_last_error().
+ * hast_tx_pair_device is hast_tx_pair_host with final == 0 over d_r1[0, n1) / d_r2[0, n2), which may lie at any address: every field
+ * of *res, the updated *state and every byte written to d_out1 / d_out2 equal the host call's.  It runs on the given stream (NULL: the
+ * context's), allocates nothing, and returns when *res is valid and the outputs are written.  n1 or n2 above max_in_bytes:
+ * HAST_ERR_INVALID.  An output larger than its room (cap1, cap2): HAST_ERR_UNSUPPORTED, res->out_bytes = what would have been
+ * needed, *state unchanged, not one byte written -- the caller converts this step another way.  No whole pair: HAST_OK, *res all zeros
+ * but lines, nothing written.  The end-of-input modes (final 1 and 2: a few records per run) stay with hast_tx_pair_host. */
+typedef struct hast_tx hast_tx;
+hast_status hast_tx_create(hast_ctx *, const hast_tx_map *, size_t max_in_bytes, hast_tx **out);
+hast_status hast_tx_pair_device(hast_tx *, const uint8_t *d_r1, size_t n1, const uint8_t *d_r2, size_t n2, hast_tx_state *state,
+                                uint8_t *d_out1, size_t cap1, uint8_t *d_out2, size_t cap2, hast_tx_result *res, hast_stream);
+void        hast_tx_destroy(hast_tx *);
+/* A step from host memory to host memory, as `fake_10x --convert device` takes it: r1 / r2 go through pinned staging to the device,
+ * are converted there (hast_tx_pair_device with room for 2 x the bytes given + 4 KB a side), each run is, with gz != 0, made one gzip
+ * member by hast_dz_compress_device (an empty run: no member), and what results comes back to pinned memory: *out1 / *out2, the
+ * library's, res->out_bytes[] bytes, valid until the next call BUT ONE returns -- whoever writes them out may do so beside the next
+ * step.  res->raw_bytes[] = the runs' sizes before deflate.  The buffers are allocated at the first call.  Inputs larger than the
+ * converter was created for, or outputs larger than that room: HAST_ERR_UNSUPPORTED, *state unchanged, the caller takes
+ * hast_tx_pair_host.  *times is ADDED to: seconds of upload, of the kernels (a hipEvent pair around them), of deflate, of download. */
+typedef struct { double upload_s, kernel_s, deflate_s, download_s; } hast_tx_times;
+hast_status hast_tx_pair_staged(hast_tx *, const uint8_t *r1, size_t n1, const uint8_t *r2, size_t n2, hast_tx_state *state, int gz,
+                                const uint8_t **out1, const uint8_t **out2, hast_tx_result *res, hast_tx_times *times);
 
 #ifdef __cplusplus
 }
