@@ -79,8 +79,7 @@ struct hast_ctx {
     uint32_t *d_votes_scratch = nullptr;
     size_t votes_bytes = 0;
     // scratch of the partitioned commit (bins of compressed records + overflow list)
-    void *d_part = nullptr;
-    size_t part_bytes = 0;
+    CommitScratch part;
     // stream_file_region: two pinned pieces, their device twins, "piece is on the device" events
     char *sf_h[2] = {nullptr, nullptr}, *sf_d[2] = {nullptr, nullptr};
     hipEvent_t sf_done[2] = {nullptr, nullptr};
@@ -105,6 +104,7 @@ struct hast_ctx {
     int commit_mode = 0;                             // HAST_COMMIT: 0 by batch size, 1 = one atomic per read, 2 = partitioned
     int kernel_geo = 1, kernel_rl = 1;               // HAST_F_GEO / HAST_F_RL = 0: the generic k_classify_f instantiations
     size_t tile_lds = 0;                             // HAST_TILE_LDS: LDS budget of a tile (0 = default)
+    uint32_t part_span = 0;                          // HAST_PART_SPAN: barcodes per bin of the partitioned commit, as bits (0 = by barcode count)
     bool part_oom = false;                           // the partitioned commit's scratch did not fit once: atomics from then on
 };
 
@@ -325,6 +325,7 @@ hast_status hast_ctx_create(int device, int k, hast_ctx **out) {
     if (c->exact_env_off) c->filter_exact = 0;
     else if (c->exact_env_once) c->filter_exact = 1;
     if (const char *e = getenv("HAST_COMMIT")) c->commit_mode = !strcmp(e, "atomic") ? 1 : !strcmp(e, "partition") ? 2 : 0;
+    if (const char *e = getenv("HAST_PART_SPAN")) c->part_span = (uint32_t)atoi(e);      // (out of commit_plan.h's range: ignored)
     if (const char *e = getenv("HAST_F_GEO")) c->kernel_geo = e[0] != '0';
     if (const char *e = getenv("HAST_F_RL")) c->kernel_rl = e[0] != '0';
     if (const char *e = getenv("HAST_TILE_LDS")) {
@@ -383,7 +384,7 @@ void hast_ctx_destroy(hast_ctx *c) {
     if (c->d_scratch) (void)hipFree(c->d_scratch);
     if (c->d_seg) (void)hipFree(c->d_seg);
     if (c->d_votes_scratch) (void)hipFree(c->d_votes_scratch);
-    if (c->d_part) (void)hipFree(c->d_part);
+    if (c->part.d) (void)hipFree(c->part.d);
     for (int i = 0; i < 2; ++i) {
         if (c->sf_done[i]) (void)hipEventDestroy(c->sf_done[i]);
         if (c->sf_d[i]) (void)hipFree(c->sf_d[i]);
@@ -1104,30 +1105,40 @@ static constexpr uint32_t kLongRead = 4096;      // longer reads go through the 
 // partitioned by barcode range and summed in LDS (hast_kernels.hip, "partitioned commit"; hast_ctx_set_option "commit" / HAST_COMMIT
 // force either).  The partitioned path needs ~19 B of scratch per read: when HBM has no room for that the atomic path does the same
 // sums (an optional speed-up must not turn a run that fits into an error), and the context does not ask again.
-static hast_status commit_votes(hast_ctx *c, const uint32_t *d_votes, const uint32_t *d_ids, size_t n_reads, uint32_t max_votes,
-                                bool atomic_only, hipStream_t hs) {
+// commit_prepare decides (before anything is launched: a scratch that grows waits for the stream and frees); commit_run launches.
+static hast_status commit_prepare(hast_ctx *c, size_t n_reads, uint32_t max_votes, bool atomic_only, hipStream_t hs, commit::Plan *pl, bool *partitioned) {
+    *partitioned = false;
     const int mode = c->commit_mode;
-    if (mode != 1 && !atomic_only && !c->part_oom && commit_partition_usable(n_reads, c->n_barcodes, max_votes, mode == 2)) {
-        const size_t need = commit_partition_scratch_bytes(n_reads, c->n_barcodes, nullptr, nullptr);
-        if (c->part_bytes < need) {
-            HAST_HIP_TRY(hipStreamSynchronize(hs));
-            if (c->d_part) HAST_HIP_TRY(hipFree(c->d_part));
-            c->d_part = nullptr;
-            c->part_bytes = 0;
-            if (dev_malloc(&c->d_part, need + need / 8) == hipSuccess) c->part_bytes = need + need / 8;
-            else {
-                (void)hipGetLastError();
-                c->d_part = nullptr;
-                c->part_oom = true;
-            }
-        }
-        if (c->d_part) {
-            HAST_HIP_TRY(launch_commit_partitioned(d_votes, d_ids, c->d_counts, c->n_barcodes, n_reads, c->d_part, hs));
-            return HAST_OK;
+    if (mode == 1 || atomic_only || c->part_oom) return HAST_OK;
+    *pl = commit::plan_for(n_reads, c->n_barcodes, c->part_span);
+    if (!commit::usable(*pl, n_reads, max_votes, mode == 2)) return HAST_OK;
+    if (c->part.bytes < pl->bytes) {
+        HAST_HIP_TRY(hipStreamSynchronize(hs));
+        if (c->part.d) HAST_HIP_TRY(hipFree(c->part.d));
+        c->part = CommitScratch{};
+        if (dev_malloc(&c->part.d, pl->bytes + pl->bytes / 8) == hipSuccess) c->part.bytes = pl->bytes + pl->bytes / 8;
+        else {
+            (void)hipGetLastError();
+            c->part.d = nullptr;
+            c->part_oom = true;
         }
     }
-    HAST_HIP_TRY(launch_commit_votes(d_votes, d_ids, c->d_counts, nullptr, n_reads, hs));
+    *partitioned = c->part.d != nullptr;
     return HAST_OK;
+}
+static hast_status commit_run(hast_ctx *c, const void *d_votes, bool votes16, const uint32_t *d_ids, size_t n_reads, const commit::Plan &pl, bool partitioned,
+                              hipStream_t hs) {
+    if (partitioned) HAST_HIP_TRY(launch_commit_partitioned(d_votes, votes16, d_ids, c->d_counts, c->n_barcodes, n_reads, pl, c->part, hs));
+    else if (votes16) return set_error(HAST_ERR_INVALID, "internal: compact votes reached the atomic commit");
+    else HAST_HIP_TRY(launch_commit_votes(reinterpret_cast<const uint32_t *>(d_votes), d_ids, c->d_counts, nullptr, n_reads, hs));
+    return HAST_OK;
+}
+static hast_status commit_votes(hast_ctx *c, const uint32_t *d_votes, const uint32_t *d_ids, size_t n_reads, uint32_t max_votes,
+                                bool atomic_only, hipStream_t hs) {
+    commit::Plan pl{};
+    bool partitioned = false;
+    if (hast_status st = commit_prepare(c, n_reads, max_votes, atomic_only, hs, &pl, &partitioned)) return st;
+    return commit_run(c, d_votes, false, d_ids, n_reads, pl, partitioned, hs);
 }
 
 static hast_status classify_rows(hast_ctx *c, const uint8_t *d_bases, size_t bases_bytes, const uint64_t *d_offsets,
@@ -1154,11 +1165,21 @@ static hast_status classify_rows(hast_ctx *c, const uint8_t *d_bases, size_t bas
     // read-modify-writes cost 4x as much when they are interleaved with the probes' reads).  Without a votes buffer from
     // the caller the votes go to library scratch.
     if (reinterpret_cast<uintptr_t>(d_votes) & 7) return set_error(HAST_ERR_INVALID, "d_votes must be 8-byte aligned (a row is stored as one 64-bit word)");
+    hipStream_t hs = s ? (hipStream_t)s : c->stream;
+    const uint32_t max_pos = read_len >= (uint32_t)c->k ? read_len - c->k + 1 : 0;
+    // How the votes will be committed is decided here, in front of the probe launch: whatever scratch has to grow does so before
+    // the first kernel, never between the two.  When the partitioned commit is the rows' only reader (ids given, no buffer of the
+    // caller's, rows are reads) they cross HBM as the 8 + 8 bits it keeps of them: max_pos <= 255 is commit::usable's condition.
+    commit::Plan pl{};
+    bool partitioned = false;
+    if (d_barcode_ids)
+        if (hast_status st = commit_prepare(c, n_reads, max_pos, d_seg_read != nullptr, hs, &pl, &partitioned)) return st;
+    const bool votes16 = partitioned && !d_votes && !d_seg_read && max_pos <= commit::kMaxVotes;
     uint32_t *votes_buf = d_votes;
     if (d_barcode_ids && !votes_buf) {
-        const size_t need = n_reads * 2 * sizeof(uint32_t);
+        const size_t need = n_reads * (votes16 ? sizeof(uint16_t) : 2 * sizeof(uint32_t));
         if (c->votes_bytes < need) {
-            HAST_HIP_TRY(hipStreamSynchronize(s ? (hipStream_t)s : c->stream));
+            HAST_HIP_TRY(hipStreamSynchronize(hs));
             if (c->d_votes_scratch) HAST_HIP_TRY(hipFree(c->d_votes_scratch));
             c->d_votes_scratch = nullptr;
             c->votes_bytes = 0;
@@ -1167,7 +1188,8 @@ static hast_status classify_rows(hast_ctx *c, const uint8_t *d_bases, size_t bas
         }
         votes_buf = c->d_votes_scratch;
     }
-    a.votes = votes_buf;
+    a.votes = votes16 ? nullptr : votes_buf;
+    a.votes16 = votes16 ? reinterpret_cast<uint16_t *>(votes_buf) : nullptr;
     a.slots = c->d_slots;
     a.n_reads = n_reads;
     a.n_rows_ptr = d_n_rows;                   // (n_reads is then the most rows there can be)
@@ -1176,13 +1198,12 @@ static hast_status classify_rows(hast_ctx *c, const uint8_t *d_bases, size_t bas
     a.k = c->k;
     a.wide = c->k == 32;
     a.m = c->m;
-    a.max_pos = read_len >= (uint32_t)c->k ? read_len - c->k + 1 : 0;
+    a.max_pos = max_pos;
     a.mh_stride = read_len >= (uint32_t)c->m ? read_len - c->m + 1 : 0;
     a.w64 = (read_len + 31) / 32;
     // Reads per tile: at most what fits the LDS budget of a workgroup and at most 64; among the
     // candidates take the one whose windows fill the waves' 64-window blocks best (a workgroup walks
     // 4 waves x 2 blocks per iteration: 150-bp reads => 31 reads = 4030 windows = 63 of 64 block slots).
-    hipStream_t hs = s ? (hipStream_t)s : c->stream;
     if (c->use_filter)
         if (hast_status st = ensure_filter(c, hs)) return st;        // (may switch the filter off when HBM is short)
     const bool filt = c->use_filter;
@@ -1239,7 +1260,7 @@ static hast_status classify_rows(hast_ctx *c, const uint8_t *d_bases, size_t bas
     if (d_barcode_ids) {
         // per-barcode bookkeeping: one atomic per read, or -- large batches over many barcodes -- the pairs partitioned by barcode
         // range and summed in LDS (hast_kernels.hip, "partitioned commit"; HAST_COMMIT=atomic / partition forces either)
-        if (hast_status st = commit_votes(c, votes_buf, d_barcode_ids, n_reads, a.max_pos, d_seg_read != nullptr, hs)) return st;
+        if (hast_status st = commit_run(c, votes_buf, votes16, d_barcode_ids, n_reads, pl, partitioned, hs)) return st;
     }
     if (ev) {
         HAST_HIP_TRY(hipEventRecord(ev[2], hs));
@@ -1274,6 +1295,9 @@ hast_status hast_ctx_set_option(hast_ctx *c, const char *name, long value) {
     if (!strcmp(name, "commit")) {
         if (value < 0 || value > 2) return set_error(HAST_ERR_INVALID, "commit: 0 = by batch size, 1 = atomic, 2 = partitioned");
         c->commit_mode = (int)value;
+    } else if (!strcmp(name, "part_span")) {
+        if (value && (value < (long)commit::kMinSpanBits || value > (long)commit::kMaxSpanBits)) return set_error(HAST_ERR_INVALID, "part_span %ld out of [8, 13]", value);
+        c->part_span = (uint32_t)value;
     } else if (!strcmp(name, "kernel_geo")) c->kernel_geo = value != 0;
     else if (!strcmp(name, "kernel_rl")) c->kernel_rl = value != 0;
     else if (!strcmp(name, "tile_lds")) {
@@ -1299,6 +1323,7 @@ hast_status hast_ctx_options(const hast_ctx *c, char *out, size_t cap) {
     if (c->filter_t) add("filter_t", c->filter_t);
     if (c->filter_kp) add("filter_kp", c->filter_kp);
     if (c->commit_mode) add("commit", c->commit_mode);
+    if (c->part_span) add("part_span", (long)c->part_span);
     if (!c->kernel_geo) add("kernel_geo", 0);
     if (!c->kernel_rl) add("kernel_rl", 0);
     if (c->tile_lds) add("tile_lds", (long)c->tile_lds);

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include "commit_plan.h"
 #include "hast_common.h"
 
 namespace hast {
@@ -21,6 +22,8 @@ struct ClassifyArgs {
     const uint32_t *lens;        // per-row length (rows = segments of long reads) or nullptr
     const uint32_t *seg_read;    // row -> output read index (votes are atomically added) or nullptr
     uint32_t *votes;             // [n_reads][2] or nullptr
+    uint16_t *votes16;           // not nullptr: a row's votes go here instead, as vote0 | vote1 << 8 (rows are reads, max_pos <= 255:
+                                 // what the partitioned commit keeps of a row anyway)
     unsigned long long *tile_queue; // zeroed before the launch: next tile index (dynamic load balance)
     const uint64_t *slots;       // table
     uint64_t n_reads;
@@ -71,10 +74,16 @@ hipError_t launch_commit_votes(const uint32_t *d_votes, const uint32_t *d_barcod
                                size_t n_reads, hipStream_t s);
 // the same bookkeeping without one atomic per read (large batches over many barcodes): pairs partitioned by barcode range in
 // LDS, bins summed in LDS, plain read-modify-writes of the counters; max_votes = the most votes a read can have (<= 255)
-bool commit_partition_usable(size_t n_reads, size_t n_barcodes, uint32_t max_votes, bool forced);
-size_t commit_partition_scratch_bytes(size_t n_reads, size_t n_barcodes, uint32_t *n_bins_out, uint32_t *cap_out);
-hipError_t launch_commit_partitioned(const uint32_t *d_votes, const uint32_t *d_barcode_ids, unsigned long long *d_counts, size_t n_barcodes, size_t n_reads,
-                                     void *d_scratch, hipStream_t s);
+// (the plan of a batch -- bins, capacity, scratch layout -- is commit_plan.h's).  votes16: d_votes are ClassifyArgs::votes16 rows.
+// The scratch cleans itself (commit_plan.h); it is filled only when it was laid out for another (n_bins, cap).
+struct CommitScratch {
+    void *d = nullptr;
+    size_t bytes = 0;
+    uint32_t n_bins = 0, cap = 0;      // what its lines were last initialised for (0: never)
+    uint32_t parity = 0;               // which overflow length the next launch counts in
+};
+hipError_t launch_commit_partitioned(const void *d_votes, bool votes16, const uint32_t *d_barcode_ids, unsigned long long *d_counts, size_t n_barcodes,
+                                     size_t n_reads, const commit::Plan &pl, CommitScratch &sc, hipStream_t s);
 hipError_t launch_add_u64(unsigned long long *d_dst, const unsigned long long *d_src, size_t n, hipStream_t s);          // dst[i] += src[i]
 // counts[n][4] -> packed = c0[n] | c1[n] | neg[n] and back (the reserved word stays where it is)
 hipError_t launch_counts_pack(const unsigned long long *d_counts, unsigned long long *d_packed, size_t n, hipStream_t s);

@@ -561,7 +561,9 @@ __global__ void __launch_bounds__(kThreadsF, DENSE ? HAST_F_MINWAVES_DENSE : HAS
         // ---- C: the read's votes out (the per-barcode bookkeeping is k_commit_votes' job) ----------------
         if (tid < tra) {
             const unsigned long long v = s_vote[tid];
-            if (a.votes) {
+            if (a.votes16) {                      // (wave-uniform) the partitioned commit is this row's only reader: 8 + 8 bits
+                a.votes16[r0 + tid] = (uint16_t)((uint32_t)v | (uint32_t)(v >> 32) << 8);
+            } else if (a.votes) {
                 if (a.seg_read) {                 // rows are segments of long reads: add into the read's (zeroed) row
                     uint32_t *row = a.votes + 2 * (size_t)a.seg_read[r0 + tid];
                     if ((uint32_t)v) atomicAdd(row, (uint32_t)v);

@@ -16,6 +16,8 @@
 #include "hast_device.h"
 #include "hast_devutil.h"
 
+#include <atomic>
+
 namespace hast {
 
 // ------------------------------------------------------------------------------------------
@@ -513,7 +515,9 @@ __global__ void __launch_bounds__(kThreads, HAST_MINWAVES) k_classify(ClassifyAr
         // ---- C: the read's votes out (the per-barcode bookkeeping is k_commit_votes' job) ----------------
         if (tid < tra) {
             const unsigned long long v = s_vote[tid];
-            if (a.votes) {
+            if (a.votes16) {                      // (wave-uniform) the partitioned commit is this row's only reader: 8 + 8 bits
+                a.votes16[r0 + tid] = (uint16_t)((uint32_t)v | (uint32_t)(v >> 32) << 8);
+            } else if (a.votes) {
                 if (a.seg_read) {                 // rows are segments of long reads: add into the read's (zeroed) row
                     uint32_t *row = a.votes + 2 * (size_t)a.seg_read[r0 + tid];
                     if ((uint32_t)v) atomicAdd(row, (uint32_t)v);
@@ -780,13 +784,16 @@ __global__ void __launch_bounds__(256) k_commit_votes(const uint32_t *votes, con
 // workgroup of a bin is the only one that touches those counters.  No atomic leaves the chip except one reservation per
 // (workgroup, bin).  Bins have a fixed capacity; what does not fit (a barcode that owns a large share of the reads) goes to an
 // overflow list that k_commit_pairs adds with atomics afterwards.  Same integer sums, any order.
+// The plan (bins, capacity, the scratch's layout and how it cleans itself) is commit_plan.h's.
 // ------------------------------------------------------------------------------------------
-constexpr uint32_t kPartMaxSpanBits = 13;                                        // at most 8192 barcodes per bin (13 + 8 + 8 bits per record)
-constexpr uint32_t kPartRecs = 16384;                                            // records a workgroup partitions at a time
+constexpr uint32_t kPartRecs = commit::kGroupRecs;                               // records a workgroup partitions at a time
 constexpr int kPartThreads = 1024;
-constexpr uint32_t kPartMaxBins = 4096;
-__global__ void __launch_bounds__(kPartThreads) k_commit_partition(const unsigned long long *votes, const uint32_t *ids, size_t n, uint32_t n_bins,
-                                                                  uint32_t span_bits, uint32_t cap, uint32_t *bin_fill, uint32_t *bin_valid, uint32_t *bin_recs,
+constexpr uint32_t kPartLineWords = (uint32_t)commit::kLineWords;                // a bin's {bin_fill, bin_valid} open a 128-B line of their own
+static_assert(commit::kMaxBins == 4 * kPartThreads, "the scan of k_commit_partition takes 4 bins per thread");
+// V16: the votes are the probe kernel's compact rows (vote0 | vote1 << 8, one u16 per read), else {vote0, vote1} as one u64
+template <bool V16>
+__global__ void __launch_bounds__(kPartThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) k_commit_partition(const void *votes_in, const uint32_t *ids, size_t n, uint32_t n_bins,
+                                                                  uint32_t span_bits, uint32_t cap, uint32_t *bin_lines, uint32_t *bin_recs,
                                                                   unsigned long long *over_n, uint32_t *over_ids, unsigned long long *over_votes) {
     extern __shared__ __align__(16) unsigned char smem[];
     uint32_t *s_cnt = reinterpret_cast<uint32_t *>(smem);                       // [n_bins] records of this span per bin
@@ -801,31 +808,48 @@ __global__ void __launch_bounds__(kPartThreads) k_commit_partition(const unsigne
     for (uint32_t b = tid; b < n_bins; b += kPartThreads) s_cnt[b] = 0;
     __syncthreads();
     constexpr int PER = kPartRecs / kPartThreads;                                // 16 records per thread
-    uint32_t rec[PER], rank[PER];                                                // rec: bin << 29-bit payload is not stored: bin is id >> 13
-    uint32_t bin_of[PER];
+    // a record's bin (12 bits: n_bins <= 4096) and its rank inside the bin's run (14 bits: < kPartRecs) in one word, kNoRec: no record.
+    // 32 registers of state per thread, not 48: the kernel stays under 64 VGPRs, so that two workgroups share a CU (the LDS of two
+    // fits: commit_plan.h) and one's barriers and global latencies are covered by the other's work
+    constexpr uint32_t kRankBits = 14, kNoRec = 0xFFFFFFFFu;
+    static_assert(kPartRecs <= (1u << kRankBits) && commit::kMaxBins <= (1u << (32 - kRankBits - 1)), "bin and rank share a word");
+    uint32_t rec[PER], slot[PER];
 #pragma unroll
     for (int q = 0; q < PER; ++q) {
         const uint32_t i = (uint32_t)q * kPartThreads + tid;                     // coalesced
-        bin_of[q] = 0xFFFFFFFFu;
+        slot[q] = kNoRec;
         if (i < nr) {
             const uint32_t id = ids[r0 + i];
-            const unsigned long long v = votes[r0 + i];
-            bin_of[q] = id >> kPartSpanBits;
-            if (bin_of[q] >= n_bins) { bin_of[q] = 0xFFFFFFFFu; continue; }       // an id outside the counters (the caller's contract): dropped
-            rec[q] = (id & (kPartSpan - 1)) | ((uint32_t)v & 0xFFu) << 13 | ((uint32_t)(v >> 32) & 0xFFu) << 21;
-            rank[q] = atomicAdd(&s_cnt[bin_of[q]], 1u);
+            uint32_t v0, v1;
+            if (V16) {
+                const uint32_t v = reinterpret_cast<const uint16_t *>(votes_in)[r0 + i];
+                v0 = v & 0xFFu;
+                v1 = v >> 8;
+            } else {
+                const unsigned long long v = reinterpret_cast<const unsigned long long *>(votes_in)[r0 + i];
+                v0 = (uint32_t)v & 0xFFu;
+                v1 = (uint32_t)(v >> 32) & 0xFFu;
+            }
+            const uint32_t bin = id >> kPartSpanBits;
+            if (bin >= n_bins) continue;                                         // an id outside the counters (the caller's contract): dropped
+            rec[q] = (id & (kPartSpan - 1)) | v0 << 13 | v1 << 21;
+            slot[q] = bin << kRankBits | atomicAdd(&s_cnt[bin], 1u);
         }
     }
     __syncthreads();
     // exclusive scan of s_cnt over the bins (n_bins <= 4096 = 4 per thread)
     {
-        uint32_t c[4], sum = 0;
+        uint32_t c[4], g[4], sum = 0;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const uint32_t b = tid * 4 + q;
             c[q] = b < n_bins ? s_cnt[b] : 0;
             sum += c[q];
         }
+        // one reservation per (workgroup, bin): a run of c[q] records in the bin.  The thread's four are issued before the scan, whose
+        // barrier they then wait behind together, not one after the other
+#pragma unroll
+        for (int q = 0; q < 4; ++q) g[q] = c[q] ? atomicAdd(&bin_lines[(size_t)(tid * 4 + q) * kPartLineWords], c[q]) : 0;
         uint32_t incl = sum;
         const uint32_t lane = tid & 63;
         for (int off = 1; off < 64; off <<= 1) {
@@ -842,13 +866,11 @@ __global__ void __launch_bounds__(kPartThreads) k_commit_partition(const unsigne
             if (b < n_bins) {
                 s_off[b] = base;
                 base += c[q];
-                // one reservation per (workgroup, bin): a run of c[q] records in the bin, or -- when the bin is full -- in the overflow list
                 uint32_t dst = 0;
                 if (c[q]) {
-                    const uint32_t g = atomicAdd(&bin_fill[b], c[q]);
-                    if (g + c[q] <= cap) dst = g;
-                    else {
-                        atomicMin(&bin_valid[b], g);                             // records [0, first failed reservation) of a bin are real
+                    if (g[q] + c[q] <= cap) dst = g[q];
+                    else {                                                       // the bin is full: the run goes to the overflow list
+                        atomicMin(&bin_lines[(size_t)b * kPartLineWords + 1], g[q]);   // records [0, first failed reservation) of a bin are real
                         dst = 0x80000000u | (uint32_t)atomicAdd(over_n, (unsigned long long)c[q]);
                     }
                 }
@@ -859,7 +881,7 @@ __global__ void __launch_bounds__(kPartThreads) k_commit_partition(const unsigne
     __syncthreads();
 #pragma unroll
     for (int q = 0; q < PER; ++q)
-        if (bin_of[q] != 0xFFFFFFFFu) s_rec[s_off[bin_of[q]] + rank[q]] = rec[q] | 0u;
+        if (slot[q] != kNoRec) s_rec[s_off[slot[q] >> kRankBits] + (slot[q] & ((1u << kRankBits) - 1))] = rec[q];
     __syncthreads();
     // runs out: a quarter of a wave per bin (a run holds ~13 records: 16384 records over ~1200 bins), 16 lanes over the run
     const uint32_t grp = tid >> 4, gl = tid & 15;
@@ -881,106 +903,135 @@ __global__ void __launch_bounds__(kPartThreads) k_commit_partition(const unsigne
     }
 }
 
-// one workgroup per bin: sum its records in LDS, then add the sums to the bin's counters (nobody else touches them in this kernel)
-constexpr int kBinThreads = 1024;
-__global__ void __launch_bounds__(kBinThreads) k_commit_bins(const uint32_t *bin_recs, const uint32_t *bin_fill, const uint32_t *bin_valid, uint32_t cap,
+// one workgroup per bin: sum its records in LDS, then add the sums to the bin's counters (nobody else touches them in this kernel).
+// 96 KB of LDS at 8192 barcodes per bin leave one workgroup per CU with nothing beside it, so the workgroup covers its own
+// latencies: the records are read kBinBatch at a time before their LDS atomics, and the counters of kBinCounters barcodes are all read
+// before the first is written (a store to `counts` in between would pin every later load behind it).
+// It is the last reader of the bin's line and leaves it as the next launch's k_commit_partition needs it; bin 0's also zeroes the
+// overflow length the NEXT launch counts in (this launch's is still to be read by the overflow pass behind this kernel).
+constexpr int kBinThreads = 1024, kBinBatch = 8, kBinCounters = 4;             // (the kernel stays under 64 VGPRs: small bins run two workgroups per CU)
+__global__ void __launch_bounds__(kBinThreads) k_commit_bins(const uint32_t *__restrict__ bin_recs, uint32_t *bin_lines, unsigned long long *over_n_next, uint32_t cap,
                                                      uint32_t span_bits, unsigned long long *counts, size_t n_barcodes) {
     extern __shared__ __align__(16) unsigned char smem[];
     const uint32_t kPartSpanBits = span_bits, kPartSpan = 1u << span_bits;
-    unsigned long long *s_vote = reinterpret_cast<unsigned long long *>(smem);   // [kPartSpan] {c0, c1}: a bin holds <= cap records of <= 255 votes, cap * 255 < 2^32 (commit_partition_usable)
+    unsigned long long *s_vote = reinterpret_cast<unsigned long long *>(smem);   // [kPartSpan] {c0, c1}: a bin holds <= cap records of <= 255 votes, cap * 255 < 2^32 (commit::usable)
     uint32_t *s_neg = reinterpret_cast<uint32_t *>(s_vote + kPartSpan);          // [kPartSpan]
     const uint32_t b = blockIdx.x, tid = threadIdx.x;
-    const uint32_t fill = bin_fill[b], valid = bin_valid[b];
+    uint32_t *line = bin_lines + (size_t)b * kPartLineWords;
+    const uint32_t fill = line[0], valid = line[1];
     const uint32_t n = fill < valid ? (fill < cap ? fill : cap) : valid;
-    if (n == 0) return;
     for (uint32_t j = tid; j < kPartSpan; j += kBinThreads) {
         s_vote[j] = 0;
         s_neg[j] = 0;
     }
-    __syncthreads();
+    __syncthreads();                                                             // (every thread has read the line)
+    if (tid == 0) {
+        line[0] = 0;
+        line[1] = 0xFFFFFFFFu;
+        if (b == 0) *over_n_next = 0;
+    }
+    if (n == 0) return;
     const uint32_t *recs = bin_recs + (size_t)b * cap;
-    for (uint32_t i = tid; i < n; i += kBinThreads) {
-        const uint32_t r = recs[i];
-        const uint32_t id = r & (kPartSpan - 1), v0 = (r >> 13) & 0xFFu, v1 = (r >> 21) & 0xFFu;
-        if (v0 | v1) atomicAdd(&s_vote[id], (unsigned long long)v0 | ((unsigned long long)v1 << 32));
-        else atomicAdd(&s_neg[id], 1u);
+    constexpr uint32_t kNoRec = 0xFFFFFFFFu;                                     // (a record's three top bits are 0)
+    for (uint32_t i0 = 0; i0 < n; i0 += kBinBatch * kBinThreads) {
+        uint32_t r[kBinBatch];
+#pragma unroll
+        for (int u = 0; u < kBinBatch; ++u) {
+            const uint32_t i = i0 + (uint32_t)u * kBinThreads + tid;
+            r[u] = i < n ? recs[i] : kNoRec;
+        }
+#pragma unroll
+        for (int u = 0; u < kBinBatch; ++u) {
+            if (r[u] == kNoRec) continue;
+            const uint32_t id = r[u] & (kPartSpan - 1), v0 = (r[u] >> 13) & 0xFFu, v1 = (r[u] >> 21) & 0xFFu;
+            if (v0 | v1) atomicAdd(&s_vote[id], (unsigned long long)v0 | ((unsigned long long)v1 << 32));
+            else atomicAdd(&s_neg[id], 1u);
+        }
     }
     __syncthreads();
     const size_t first = (size_t)b << kPartSpanBits;
-    for (uint32_t j = tid; j < kPartSpan && first + j < n_barcodes; j += kBinThreads) {
-        const unsigned long long v = s_vote[j];
-        const uint32_t g = s_neg[j];
-        if (v | g) {                                                             // 64-bit counters: no wrap, no carry between them
-            unsigned long long *rec = counts + 4 * (first + j);
-            if (v) {
-                ulonglong2 c = *reinterpret_cast<ulonglong2 *>(rec);
-                c.x += (uint32_t)v;
-                c.y += v >> 32;
-                *reinterpret_cast<ulonglong2 *>(rec) = c;
+    for (uint32_t j0 = 0; j0 < kPartSpan; j0 += kBinCounters * kBinThreads) {
+        unsigned long long v[kBinCounters], neg[kBinCounters];
+        uint32_t g[kBinCounters];
+        ulonglong2 c[kBinCounters];
+#pragma unroll
+        for (int u = 0; u < kBinCounters; ++u) {
+            const uint32_t j = j0 + (uint32_t)u * kBinThreads + tid;
+            const bool in = j < kPartSpan && first + j < n_barcodes;
+            v[u] = in ? s_vote[j] : 0;
+            g[u] = in ? s_neg[j] : 0;
+            const unsigned long long *rec = counts + 4 * (first + j);
+            if (v[u]) c[u] = *reinterpret_cast<const ulonglong2 *>(rec);
+            if (g[u]) neg[u] = rec[2];
+        }
+#pragma unroll
+        for (int u = 0; u < kBinCounters; ++u) {                                    // 64-bit counters: no wrap, no carry between them
+            unsigned long long *rec = counts + 4 * (first + j0 + (uint32_t)u * kBinThreads + tid);
+            if (v[u]) {
+                c[u].x += (uint32_t)v[u];
+                c[u].y += v[u] >> 32;
+                *reinterpret_cast<ulonglong2 *>(rec) = c[u];
             }
-            if (g) rec[2] += g;
+            if (g[u]) rec[2] = neg[u] + g[u];
         }
     }
 }
+// a scratch that was just laid out: every line {0, 0xFFFFFFFF}, both overflow lengths 0
+__global__ void __launch_bounds__(256) k_commit_scratch_init(uint32_t *bin_lines, uint32_t n_bins, unsigned long long *over_n) {
+    const uint32_t b = blockIdx.x * 256 + threadIdx.x;
+    if (b < n_bins) {
+        bin_lines[(size_t)b * kPartLineWords] = 0;
+        bin_lines[(size_t)b * kPartLineWords + 1] = 0xFFFFFFFFu;
+    }
+    if (b < 2) over_n[b] = 0;
+}
 
-static uint32_t part_span_bits(size_t n_barcodes) {               // ~1000 bins where the barcodes allow it, 256 .. 8192 barcodes per bin
-    uint32_t lg = 0;
-    while (((size_t)1 << lg) < n_barcodes) ++lg;
-    const uint32_t want = lg > 10 ? lg - 10 : 0;
-    return want < 8 ? 8u : (want > kPartMaxSpanBits ? kPartMaxSpanBits : want);
+// the kernels' dynamic LDS may pass 64 KB: their attribute is raised to the most a plan can ask for, once per device
+static hipError_t commit_lds_attributes() {
+    static std::atomic<uint64_t> done{0};
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    const uint64_t bit = 1ull << (dev & 63);
+    if (done.load(std::memory_order_acquire) & bit) return hipSuccess;
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_commit_partition<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)commit::kMaxLdsPartition);
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_commit_partition<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)commit::kMaxLdsPartition);
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_commit_bins), hipFuncAttributeMaxDynamicSharedMemorySize, (int)commit::kMaxLdsBins);
+    if (e != hipSuccess) return e;
+    done.fetch_or(bit, std::memory_order_release);
+    return hipSuccess;
 }
-size_t commit_partition_scratch_bytes(size_t n_reads, size_t n_barcodes, uint32_t *n_bins_out, uint32_t *cap_out) {
-    const uint32_t sb = part_span_bits(n_barcodes);
-    const uint32_t n_bins = (uint32_t)((n_barcodes + ((size_t)1 << sb) - 1) >> sb);
-    const uint64_t mean = n_bins ? (n_reads + n_bins - 1) / n_bins : 0;
-    const uint32_t cap = (uint32_t)std::min<uint64_t>(0x7FFFFFFFull, mean + mean / 2 + 2048);
-    if (n_bins_out) *n_bins_out = n_bins;
-    if (cap_out) *cap_out = cap;
-    // [over_n u64 | pad][bin_fill][bin_valid][bin_recs n_bins x cap][over_ids n][over_votes n]
-    return 256 + (size_t)n_bins * 8 + 256 + (size_t)n_bins * cap * 4 + 256 + n_reads * 4 + 256 + n_reads * 8;
-}
-// worth it (and possible) for large batches over many barcodes: enough bins to fill the GPU, votes that fit a byte
-bool commit_partition_usable(size_t n_reads, size_t n_barcodes, uint32_t max_votes, bool forced) {
-    uint32_t n_bins, cap;
-    (void)commit_partition_scratch_bytes(n_reads, n_barcodes, &n_bins, &cap);
-    if (max_votes > 255 || n_bins < 1 || n_bins > kPartMaxBins || n_reads < 1 || n_reads >= (1ull << 31)) return false;
-    if ((uint64_t)cap * 255u >= (1ull << 32)) return false;                  // a bin's sums are 32 + 32 bits in LDS
-    return forced || (n_bins >= 128 && n_reads >= (1u << 21));
-}
-hipError_t launch_commit_partitioned(const uint32_t *d_votes, const uint32_t *d_barcode_ids, unsigned long long *d_counts, size_t n_barcodes, size_t n_reads,
-                                     void *d_scratch, hipStream_t s) {
-    uint32_t n_bins, cap;
-    (void)commit_partition_scratch_bytes(n_reads, n_barcodes, &n_bins, &cap);
-    const uint32_t sb = part_span_bits(n_barcodes);
-    unsigned char *p = reinterpret_cast<unsigned char *>(d_scratch);
-    unsigned long long *over_n = reinterpret_cast<unsigned long long *>(p);
-    uint32_t *bin_fill = reinterpret_cast<uint32_t *>(p + 256);
-    uint32_t *bin_valid = bin_fill + n_bins;
-    size_t at = 256 + (size_t)n_bins * 8;
-    at = (at + 255) & ~(size_t)255;
-    uint32_t *bin_recs = reinterpret_cast<uint32_t *>(p + at);
-    at += (size_t)n_bins * cap * 4;
-    at = (at + 255) & ~(size_t)255;
-    uint32_t *over_ids = reinterpret_cast<uint32_t *>(p + at);
-    at += n_reads * 4;
-    at = (at + 255) & ~(size_t)255;
-    unsigned long long *over_votes = reinterpret_cast<unsigned long long *>(p + at);
-    hipError_t e = hipMemsetAsync(p, 0, 256 + (size_t)n_bins * 4, s);                        // over_n, bin_fill
+hipError_t launch_commit_partitioned(const void *d_votes, bool votes16, const uint32_t *d_barcode_ids, unsigned long long *d_counts, size_t n_barcodes,
+                                     size_t n_reads, const commit::Plan &pl, CommitScratch &sc, hipStream_t s) {
+    unsigned char *p = reinterpret_cast<unsigned char *>(sc.d);
+    unsigned long long *over_n = reinterpret_cast<unsigned long long *>(p + pl.over_n_at);
+    uint32_t *bin_lines = reinterpret_cast<uint32_t *>(p + pl.lines_at);
+    uint32_t *bin_recs = reinterpret_cast<uint32_t *>(p + pl.recs_at);
+    uint32_t *over_ids = reinterpret_cast<uint32_t *>(p + pl.over_ids_at);
+    unsigned long long *over_votes = reinterpret_cast<unsigned long long *>(p + pl.over_votes_at);
+    hipError_t e = commit_lds_attributes();
     if (e != hipSuccess) return e;
-    e = hipMemsetAsync(bin_valid, 0xFF, (size_t)n_bins * 4, s);
-    if (e != hipSuccess) return e;
-    const size_t lds1 = (size_t)n_bins * 12 + (size_t)kPartRecs * 4, lds2 = ((size_t)12 << sb);
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_commit_partition), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_commit_bins), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_commit_partition, dim3((unsigned)((n_reads + kPartRecs - 1) / kPartRecs)), dim3(kPartThreads), lds1, s,
-                       reinterpret_cast<const unsigned long long *>(d_votes), d_barcode_ids, n_reads, n_bins, sb, cap, bin_fill, bin_valid, bin_recs,
-                       over_n, over_ids, over_votes);
-    hipLaunchKernelGGL(k_commit_bins, dim3(n_bins), dim3(kBinThreads), lds2, s, bin_recs, bin_fill, bin_valid, cap, sb, d_counts, n_barcodes);
+    if (sc.n_bins != pl.n_bins || sc.cap != pl.cap) {                                       // laid out anew: the only fill this scratch sees
+        hipLaunchKernelGGL(k_commit_scratch_init, dim3((pl.n_bins + 255) / 256), dim3(256), 0, s, bin_lines, pl.n_bins, over_n);
+        sc.n_bins = pl.n_bins;
+        sc.cap = pl.cap;
+        sc.parity = 0;
+    }
+    unsigned long long *over_now = over_n + sc.parity, *over_next = over_n + (sc.parity ^ 1u);
+    sc.parity ^= 1u;
+    const dim3 grid1((unsigned)((n_reads + kPartRecs - 1) / kPartRecs));
+    if (votes16)
+        hipLaunchKernelGGL(k_commit_partition<true>, grid1, dim3(kPartThreads), pl.lds_partition, s, d_votes, d_barcode_ids, n_reads, pl.n_bins, pl.span_bits,
+                           pl.cap, bin_lines, bin_recs, over_now, over_ids, over_votes);
+    else
+        hipLaunchKernelGGL(k_commit_partition<false>, grid1, dim3(kPartThreads), pl.lds_partition, s, d_votes, d_barcode_ids, n_reads, pl.n_bins, pl.span_bits,
+                           pl.cap, bin_lines, bin_recs, over_now, over_ids, over_votes);
+    hipLaunchKernelGGL(k_commit_bins, dim3(pl.n_bins), dim3(kBinThreads), pl.lds_bins, s, bin_recs, bin_lines, over_next, pl.cap, pl.span_bits, d_counts, n_barcodes);
     // what found no room in its bin (a barcode that owns a large share of the reads): the atomic kernel with its LDS cache for such barcodes
     hipLaunchKernelGGL(k_commit_votes, dim3((unsigned)((n_reads + kCommitSpan - 1) / kCommitSpan)), dim3(256), 0, s,
-                       reinterpret_cast<const uint32_t *>(over_votes), over_ids, d_counts, (uint32_t *)nullptr, (size_t)0, over_n);
+                       reinterpret_cast<const uint32_t *>(over_votes), over_ids, d_counts, (uint32_t *)nullptr, (size_t)0, over_now);
     return hipGetLastError();
 }
 

@@ -67,8 +67,9 @@ int         hast_ctx_minimizer(const hast_ctx *);
 hast_status hast_ctx_set_minimizer(hast_ctx *, int m);
 int         hast_ctx_device(const hast_ctx *);
 /* Measurement switches.  The environment is read ONCE, when a context is created (HAST_CLASSIFY, HAST_FILTER_*, HAST_COMMIT,
- * HAST_F_GEO, HAST_F_RL, HAST_TILE_LDS, HAST_MINIMIZER); results never depend on them.  hast_ctx_set_option changes one on a live
- * context: "commit" 0 = by batch size / 1 = one atomic per read / 2 = partitioned; "kernel_geo", "kernel_rl" 0 = the generic
+ * HAST_PART_SPAN, HAST_F_GEO, HAST_F_RL, HAST_TILE_LDS, HAST_MINIMIZER); results never depend on them.  hast_ctx_set_option changes one on a live
+ * context: "commit" 0 = by batch size / 1 = one atomic per read / 2 = partitioned; "part_span" 8 .. 13 = barcodes per bin of the
+ * partitioned commit as a power of two (0 = by barcode count); "kernel_geo", "kernel_rl" 0 = the generic
  * k_classify_f instantiations instead of the ones with the BASELINE geometry / row length compiled in; "tile_lds" bytes (0 =
  * default); "filter_exact_once" 1 = exact filter entries filed once per strand (see hast_ctx_set_filter).  hast_ctx_options writes the switches that differ from their defaults as "name=value ..." ("" = none). */
 hast_status hast_ctx_set_option(hast_ctx *, const char *name, long value);
