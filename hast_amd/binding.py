@@ -37,6 +37,12 @@ class FqRouted(C.Structure):
                 ("rec_class", C.POINTER(C.c_uint8)), ("n_slots", C.c_uint64), ("tail", C.POINTER(C.c_uint8)), ("tail_bytes", C.c_uint64)]
 
 
+class FqTallied(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_counted", C.c_uint64), ("n_nofield", C.c_uint64), ("n_left", C.c_uint64),
+                ("left_pos", C.POINTER(C.c_uint32)), ("left_len", C.POINTER(C.c_uint32)), ("bytes", C.POINTER(C.c_uint8)),
+                ("tail", C.POINTER(C.c_uint8)), ("tail_bytes", C.c_uint64)]
+
+
 class GzStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("compressed_bytes", "out_bytes", "chunks", "accepted", "followup_jobs", "followup_rounds", "followup_accepted", "members")] + \
                [(n, C.c_double) for n in ("decode_s", "windows_crc_s", "wait_upload_s", "wait_consumer_s", "wait_decode_s", "open_s")] + \
@@ -154,6 +160,14 @@ ABI_SYMBOLS = {
     "hast_fq_next_routed": (C.c_int, [vp, C.POINTER(FqRouted)]),
     "hast_fq_set_route_gz": (C.c_int, [vp, C.c_int]),
     "hast_fq_routed_raw_bytes": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+    # stage 02: per-barcode read counts (barcode_freq.txt)
+    "hast_tally_create": (C.c_int, [vp, C.c_size_t, C.POINTER(vp)]),
+    "hast_tally_limit": (C.c_size_t, [vp]),
+    "hast_tally_size": (C.c_int, [vp, C.POINTER(C.c_size_t)]),
+    "hast_tally_read": (C.c_int, [vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint8), u64p]),
+    "hast_tally_destroy": (None, [vp]),
+    "hast_fq_set_tally": (C.c_int, [vp, C.POINTER(vp), C.c_int]),
+    "hast_fq_next_tallied": (C.c_int, [vp, C.POINTER(FqTallied)]),
     "hast_dz_bound": (C.c_size_t, [C.c_size_t]),
     "hast_dz_compress_device": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), vp]),
     "hast_dz_compress_device_ex": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_uint, vp]),
@@ -253,6 +267,10 @@ def unshared_kmers_exe():
 
 def fake_10x_exe():
     return os.path.join(_HERE, "fake_10x")
+
+
+def barcode_freq_exe():
+    return os.path.join(_HERE, "barcode_freq")
 
 
 def build(verbose=False):
@@ -828,6 +846,42 @@ class TxConverter:
     def close(self):
         if self._h:
             self._lib.hast_tx_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class Tally:
+    """A device dictionary of exactly max_texts ids with a 64-bit counter per id (hast_tally_*): what a FASTQ stream in tally mode
+    (hast_fq_set_tally / hast_fq_next_tallied) counts the keys of its header lines into."""
+
+    def __init__(self, ctx: Context, max_texts):
+        self._h = C.c_void_p()
+        _ck(lib().hast_tally_create(ctx._h, max_texts, C.byref(self._h)))
+
+    def limit(self) -> int:
+        return lib().hast_tally_limit(self._h)
+
+    def size(self) -> int:
+        n = C.c_size_t()
+        _ck(lib().hast_tally_size(self._h, C.byref(n)))
+        return n.value
+
+    def read(self):
+        """{key: count} of every id handed out"""
+        n = self.size()
+        text = np.zeros((max(n, 1), 16), np.uint8)
+        counts = np.zeros(max(n, 1), np.uint64)
+        _ck(lib().hast_tally_read(self._h, 0, n, text.ctypes.data_as(C.POINTER(C.c_uint8)), counts.ctypes.data_as(u64p)))
+        return {bytes(text[i, 1:1 + text[i, 0]]): int(counts[i]) for i in range(n)}
+
+    def close(self):
+        if self._h:
+            lib().hast_tally_destroy(self._h)
             self._h = C.c_void_p()
 
     def __enter__(self):

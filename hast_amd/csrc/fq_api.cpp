@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/hast.h"
+#include "bf_core.h"
 #include "fq_device.h"
 #include "nl_index.h"
 #include "dz_device.h"
@@ -71,6 +72,9 @@ struct Slot {
     bool gz = false;                                   // this block's runs were compressed
     std::vector<uint32_t> v_rstart, v_rlen;            // host copies for a block the caller routes itself (rare)
     std::vector<uint8_t> v_rcls, v_tail;
+    // tally streams (hast_fq_set_tally): what k_fq_field2 and k_tally_add report; v_rstart / v_rlen then hold the extents of the
+    // records left to the caller
+    TallyState *d_ts = nullptr, *h_ts = nullptr;       // h_ts pinned
 };
 }  // namespace
 
@@ -85,6 +89,12 @@ struct hast_names {            // device-side cache barcode text -> id of one GP
     bool name_early = false;                           // HAST_NAME_EARLY=1 (measurements): the naming kernel behind the framing kernels, on their stream (below)
     uint32_t *d_n_ids = nullptr;
     void *d_text_of_id = nullptr;                      // [limit][16]
+};
+
+struct hast_tally {            // a device dictionary and a counter per id it can hand out
+    hast_names *names = nullptr;
+    unsigned long long *d_counts = nullptr;            // [limit]
+    int device = 0;
 };
 
 struct FqLane {                // what a striped stream keeps per context: its GPU's streams and name cache
@@ -121,6 +131,9 @@ struct hast_fq {
     bool route = false;
     std::vector<hast_names *> route_tab;                       // per lane (one for a plain stream): barcode text -> class on that GPU
     bool route_gz = false;                                     // ... and the runs leave the GPU as gzip members (hast_fq_set_route_gz)
+    // tallies (hast_fq_set_tally): the blocks are not classified; field 2 of their header lines is counted per key
+    bool tally = false;
+    std::vector<hast_tally *> tallies;                         // per lane (one for a plain stream)
 };
 
 // Every per-record array of a slot has ONE capacity, h_cap, and is only ever resized here: h_bc = [pos | len | 4 words of
@@ -166,6 +179,8 @@ static void free_slot(Slot &s) {
         park_device(p, (p == (void *)s.d_buf || p == (void *)s.d_out) ? s.h_buf_bytes : 0, 3);
     park_pinned(s.h_out, s.h_buf_bytes, 3);
     park_pinned(s.h_rs, 64, 3);
+    park_device(s.d_ts, 0, 3);
+    park_pinned(s.h_ts, 64, 3);
     park_device(s.d_gz, s.gz_cap, 3);
     park_device(s.d_dzwork, s.dzwork_bytes, 3);
     park_pinned(s.h_gz, s.gz_cap, 3);
@@ -217,6 +232,15 @@ static hast_status enqueue_route(hast_fq *f, Slot &s, hast_names *tab, bool stri
     return HAST_OK;
 }
 
+// Tally streams: behind the framing of a block, on the same stream -- field 2 of every header line as a text record (and its extent, for
+// the records the caller will be left with); the naming and the adds follow in hast_fq_next_tallied, which knows how many there are.
+static hast_status enqueue_tally(hast_fq *f, Slot &s, bool striped, int last, hipStream_t hs) {
+    HAST_HIP_TRY(launch_fq_field2(s.d_buf, s.d_st, s.d_nl, striped ? 1 : 0, last, s.d_text, s.d_bcpos, s.d_bclen, s.h_bc, (uint32_t)s.h_cap, (uint32_t)f->max_rec,
+                                  f->pad + s.n_bytes + s.n_over, s.d_ts, hs));
+    HAST_HIP_TRY(hipMemcpyAsync(s.h_ts, s.d_ts, sizeof(TallyState), hipMemcpyDeviceToHost, hs));
+    return HAST_OK;
+}
+
 // Striped streams: launch the framing of every block that can be framed now, in order.  Block j needs (a) the bytes of block
 // j + 1 that its records may reach into (there once j + 1 has been submitted, or j ends its file) and (b) the number of
 // newlines in front of it: the count of block j - 1's own bytes (a kernel of its own, queued right behind that block's
@@ -263,6 +287,8 @@ static hast_status advance_striped_once(hast_fq *f, bool wait, size_t upto) {
         HAST_HIP_TRY(hipMemcpyAsync(s.h_st, s.d_st, sizeof(FqState), hipMemcpyDeviceToHost, ln.parse_stream));
         if (f->route) {
             if (hast_status st = enqueue_route(f, s, f->route_tab[(size_t)s.lane], true, s.eof_view ? 1 : 0, f->pad + s.n_bytes + s.n_over, ln.parse_stream)) return st;
+        } else if (f->tally) {
+            if (hast_status st = enqueue_tally(f, s, true, s.eof_view ? 1 : 0, ln.parse_stream)) return st;
         } else if (hast_status st = enqueue_names_early(s, ln.names, ln.parse_stream)) return st;
         HAST_HIP_TRY(hipEventRecord(s.parsed, ln.parse_stream));
         f->nl_before = nl_before;
@@ -745,6 +771,8 @@ static hast_status submit_block(hast_fq *f, size_t n_bytes, int last, bool dev_s
     HAST_HIP_TRY(hipMemcpyAsync(s.h_st, s.d_st, sizeof(FqState), hipMemcpyDeviceToHost, hs));
     if (f->route) {
         if (hast_status st = enqueue_route(f, s, f->route_tab[0], false, last, f->pad + n_bytes, hs)) return st;
+    } else if (f->tally) {
+        if (hast_status st = enqueue_tally(f, s, false, last, hs)) return st;
     } else if (hast_status st = enqueue_names_early(s, f->names, hs)) return st;
     HAST_HIP_TRY(hipEventRecord(s.parsed, hs));
     s.state = Slot::SUBMITTED;
@@ -792,6 +820,7 @@ hast_status hast_fq_next(hast_fq *f, hast_fq_block *out) {
     if (!f || !out) return set_error(HAST_ERR_INVALID, "null argument");
     memset(out, 0, sizeof(*out));
     if (f->route) return set_error(HAST_ERR_INVALID, "hast_fq_next: the stream routes (hast_fq_next_routed)");
+    if (f->tally) return set_error(HAST_ERR_INVALID, "hast_fq_next: the stream tallies (hast_fq_next_tallied)");
     if (f->n_opened >= f->n_submitted) return set_error(HAST_ERR_INVALID, "hast_fq_next: no submitted block");
     Slot &s = f->slots[f->n_opened % f->slots.size()];
     if (s.state != Slot::SUBMITTED || (f->n_opened && f->slots[(f->n_opened - 1) % f->slots.size()].state == Slot::OPEN))
@@ -874,6 +903,7 @@ hast_status hast_fq_set_route(hast_fq *f, hast_names *const *tables, int n_table
     if (!f) return set_error(HAST_ERR_INVALID, "null argument");
     for (const Slot &s : f->slots)
         if (s.state != Slot::FREE) return set_error(HAST_ERR_INVALID, "hast_fq_set_route: a block is in hand (commit it first)");
+    if (f->tally && tables) return set_error(HAST_ERR_INVALID, "hast_fq_set_route: the stream tallies (hast_fq_set_tally with NULL first)");
     if (!tables) {
         f->route = false;
         f->route_gz = false;
@@ -1044,6 +1074,170 @@ hast_status hast_fq_next_routed(hast_fq *f, hast_fq_routed *out) {
     return HAST_OK;
 }
 
+// ---- tallies: stage 02's per-barcode read count (bf_core.h has the rule, fq_kernels.hip "tallies" the kernels) ---------------------
+// A tally = the device dictionary of hast_names_create_dict with exactly max_texts ids + a 64-bit counter per id.
+hast_status hast_tally_create(hast_ctx *ctx, size_t max_texts, hast_tally **out) {
+    if (!ctx || !out) return set_error(HAST_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (max_texts < 1 || max_texts > (1ull << 30)) return set_error(HAST_ERR_INVALID, "hast_tally_create: max_texts %zu out of [1, 2^30]", max_texts);
+    hast_tally *t = new (std::nothrow) hast_tally();
+    if (!t) return set_error(HAST_ERR_OOM, "host allocation failed");
+    if (hast_status st = hast_names_create_dict(ctx, max_texts, &t->names)) {
+        delete t;
+        return st;
+    }
+    t->names->limit = max_texts;                           // (the table has at least twice as many slots; text_of_id room for more)
+    t->device = t->names->device;
+    hipStream_t hs = ctx_stream_of(ctx);
+    hipError_t e = dev_malloc((void **)&t->d_counts, max_texts * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemsetAsync(t->d_counts, 0, max_texts * sizeof(unsigned long long), hs);
+    if (e == hipSuccess) e = hipStreamSynchronize(hs);
+    if (e != hipSuccess) {
+        hast_tally_destroy(t);
+        return set_error(e == hipErrorOutOfMemory ? HAST_ERR_OOM : HAST_ERR_HIP, "hast_tally_create: %s", hipGetErrorString(e));
+    }
+    *out = t;
+    return HAST_OK;
+}
+size_t hast_tally_limit(const hast_tally *t) { return t ? t->names->limit : 0; }
+// (hast_fq_next_tallied returns once a block's adds are done: nothing of an opened block is in flight here)
+hast_status hast_tally_size(hast_tally *t, size_t *n_ids) {
+    if (!t || !n_ids) return set_error(HAST_ERR_INVALID, "null argument");
+    return hast_names_count(t->names, n_ids);
+}
+hast_status hast_tally_read(hast_tally *t, size_t first, size_t n, uint8_t *text16, uint64_t *counts) {
+    if (!t || (n && (!text16 || !counts))) return set_error(HAST_ERR_INVALID, "null argument");
+    if (first + n > t->names->limit) return set_error(HAST_ERR_INVALID, "hast_tally_read: ids [%zu, %zu) beyond the tally's %zu", first, first + n, t->names->limit);
+    if (hast_status st = hast_names_texts(t->names, first, n, text16)) return st;
+    if (n) HAST_HIP_TRY(hipMemcpy(counts, t->d_counts + first, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return HAST_OK;
+}
+void hast_tally_destroy(hast_tally *t) {
+    if (!t) return;
+    if (t->names) {
+        (void)hipSetDevice(t->device);
+        (void)hipStreamSynchronize(ctx_stream_of(t->names->ctx));
+        if (t->d_counts) (void)hipFree(t->d_counts);
+        hast_names_destroy(t->names);
+    }
+    delete t;
+}
+
+// From here on the stream TALLIES: its blocks are framed as before, nothing is classified (no k-mer table is needed, read lengths
+// are not looked at); hast_fq_next_tallied hands out what the device counted and what it left.  One tally per lane (contexts of one
+// GPU, and several streams, may share one).  Only between files; tallies == NULL: back to classifying.
+hast_status hast_fq_set_tally(hast_fq *f, hast_tally *const *tallies, int n_tallies) {
+    if (!f) return set_error(HAST_ERR_INVALID, "null argument");
+    for (const Slot &s : f->slots)
+        if (s.state != Slot::FREE) return set_error(HAST_ERR_INVALID, "hast_fq_set_tally: a block is in hand (commit it first)");
+    if (!tallies) {
+        f->tally = false;
+        f->tallies.clear();
+        return HAST_OK;
+    }
+    if (f->route) return set_error(HAST_ERR_INVALID, "hast_fq_set_tally: the stream routes (hast_fq_set_route with NULL first)");
+    const int lanes = f->striped ? (int)f->lanes.size() : 1;
+    if (n_tallies != lanes) return set_error(HAST_ERR_INVALID, "hast_fq_set_tally: %d tallies for a stream of %d lanes", n_tallies, lanes);
+    for (int i = 0; i < lanes; ++i)
+        if (!tallies[i] || tallies[i]->device != (f->striped ? f->lanes[(size_t)i].device : f->device))
+            return set_error(HAST_ERR_INVALID, "hast_fq_set_tally: tally %d is missing or lives on another device", i);
+    for (Slot &s : f->slots) {
+        if (s.d_ts) continue;
+        HAST_HIP_TRY(hipSetDevice(dev_of(f, s)));
+        HAST_HIP_TRY(dev_malloc(&s.d_ts, sizeof(TallyState)));
+        HAST_HIP_TRY(pinned_malloc(&s.h_ts, sizeof(TallyState)));
+    }
+    f->tallies.assign(tallies, tallies + lanes);
+    f->tally = true;
+    f->prev_submitted = -1;                                // (the next block starts a file)
+    f->carry.clear();
+    return HAST_OK;
+}
+
+hast_status hast_fq_next_tallied(hast_fq *f, hast_fq_tallied *out) {
+    if (!f || !out) return set_error(HAST_ERR_INVALID, "null argument");
+    memset(out, 0, sizeof(*out));
+    if (!f->tally) return set_error(HAST_ERR_INVALID, "hast_fq_next_tallied: the stream does not tally (hast_fq_set_tally)");
+    if (f->n_opened >= f->n_submitted) return set_error(HAST_ERR_INVALID, "hast_fq_next_tallied: no submitted block");
+    Slot &s = f->slots[f->n_opened % f->slots.size()];
+    if (s.state != Slot::SUBMITTED || (f->n_opened && f->slots[(f->n_opened - 1) % f->slots.size()].state == Slot::OPEN))
+        return set_error(HAST_ERR_INVALID, "hast_fq_next_tallied: commit the previous block first");
+    if (f->striped) {
+        if (hast_status a = advance_striped(f, true, f->n_opened + 1)) return a;
+        if (f->n_framed <= f->n_opened)
+            return set_error(HAST_ERR_INVALID, "hast_fq_next_tallied: a block of a striped stream is framed once the block behind it has been submitted (or it ends the file)");
+    }
+    HAST_HIP_TRY(hipSetDevice(dev_of(f, s)));
+    HAST_HIP_TRY(hipEventSynchronize(s.parsed));
+    const FqState st = *s.h_st;
+    const TallyState ts = *s.h_ts;
+    if ((st.flags & 2) || (ts.flags & 2)) return set_error(HAST_ERR_FORMAT, "a FASTQ record is larger than %zu bytes", f->striped ? f->over_cap : f->pad);
+    if (ts.n_rec > ts.n_cand || ts.n_cand > f->max_rec) return set_error(HAST_ERR_INVALID, "record table overflow");
+    hast_tally *const tl = f->tallies[f->striped ? (size_t)s.lane : 0];
+    hast_names *const nm = tl->names;
+    hipStream_t hs = ctx_stream_of(ctx_of(f, s));
+    const size_t n = ts.n_rec;
+    if (n > s.k_cap) {
+        // more (short) records than the pinned arrays held when the block was framed: they grow, the extents come by copy
+        if (n > s.h_cap)
+            if (hast_status g = grow_records(s, n + n / 4 + 1024)) return g;
+        HAST_HIP_TRY(hipMemcpyAsync(s.h_bc, s.d_bcpos, n * sizeof(uint32_t), hipMemcpyDeviceToHost, hs));
+        HAST_HIP_TRY(hipMemcpyAsync(s.h_bc + s.h_cap, s.d_bclen, n * sizeof(uint32_t), hipMemcpyDeviceToHost, hs));
+    }
+    s.h_unknown[0] = 0;
+    if (n) {
+        // texts -> ids of this tally's dictionary (k_fq_name_claim as it is; what it cannot number lands in the pinned list), ids -> counters
+        HAST_HIP_TRY(launch_fq_name_claim(s.d_text, (uint32_t)n, nm->d_tab, nm->mask, nm->d_n_ids, (uint32_t)nm->limit, nm->d_text_of_id, s.h_ids, s.h_unknown, s.d_ids, hs));
+        HAST_HIP_TRY(launch_tally_add(s.d_ids, (uint32_t)n, tl->d_counts, (uint32_t)nm->limit, s.d_ts, hs));
+        HAST_HIP_TRY(hipMemcpyAsync(s.h_ts, s.d_ts, sizeof(TallyState), hipMemcpyDeviceToHost, hs));
+    }
+    if (ts.tail_hi > ts.tail_lo) {                         // the partial record at the end of the file: the caller's
+        s.v_tail.resize(ts.tail_hi - ts.tail_lo);
+        HAST_HIP_TRY(hipMemcpyAsync(s.v_tail.data(), s.d_buf + ts.tail_lo, s.v_tail.size(), hipMemcpyDeviceToHost, hs));
+    }
+    HAST_HIP_TRY(hipStreamSynchronize(hs));
+    const TallyState done = *s.h_ts;
+    if (done.flags & 4) return set_error(HAST_ERR_INVALID, "hast_fq_next_tallied: the dictionary handed out an id at or above its limit");
+    // the unknown list holds the records without an id: lines without a field 2 (nobody's) and the records left to the caller
+    const uint32_t nu = s.h_unknown[0];
+    if (nu > n) return set_error(HAST_ERR_INVALID, "hast_fq_next_tallied: %u unnamed records of %zu", nu, n);
+    s.v_rstart.clear();
+    s.v_rlen.clear();
+    uint64_t nofield = 0;
+    for (uint32_t j = 0; j < nu; ++j) {
+        const uint32_t i = s.h_unknown[1 + j];
+        if (i >= n) return set_error(HAST_ERR_INVALID, "hast_fq_next_tallied: unnamed record %u of %zu", i, n);
+        const uint32_t len = s.h_bc[s.h_cap + i];
+        if (len == bf::kNoFieldLen) { ++nofield; continue; }
+        s.v_rstart.push_back(s.h_bc[i]);
+        s.v_rlen.push_back(len);
+    }
+    const uint64_t n_left = s.v_rstart.size();
+    if (nofield != ts.n_nofield || (uint64_t)done.n_counted + n_left + nofield != n)
+        return set_error(HAST_ERR_INVALID, "hast_fq_next_tallied: %u counted + %llu left + %llu (%u) without a field are not the block's %zu header lines", done.n_counted,
+                         (unsigned long long)n_left, (unsigned long long)nofield, ts.n_nofield, n);
+    if (n_left && !s.dev_src && !f->striped && st.tail_in) {
+        // the host view of a plain stream's block lacks the bytes carried over from the block in front: they lie on the device only
+        HAST_HIP_TRY(hipMemcpyAsync(s.h_buf + f->pad - st.tail_in, s.d_buf + f->pad - st.tail_in, st.tail_in, hipMemcpyDeviceToHost, hs));
+        HAST_HIP_TRY(hipStreamSynchronize(hs));
+    }
+    out->n_records = n;
+    out->n_counted = done.n_counted;
+    out->n_nofield = nofield;
+    out->n_left = n_left;
+    out->left_pos = s.v_rstart.data();
+    out->left_len = s.v_rlen.data();
+    out->bytes = s.dev_src ? nullptr : s.h_buf;
+    if (ts.tail_hi > ts.tail_lo) {
+        out->tail = s.v_tail.data();
+        out->tail_bytes = s.v_tail.size();
+    }
+    if (f->striped) f->records_per_lane[(size_t)s.lane] += n;
+    s.state = Slot::OPEN;
+    f->n_opened++;
+    return HAST_OK;
+}
+
 hast_status hast_fq_commit(hast_fq *f) {
     if (!f) return set_error(HAST_ERR_INVALID, "null argument");
     if (f->n_opened == 0) return set_error(HAST_ERR_INVALID, "hast_fq_commit without hast_fq_next");
@@ -1053,7 +1247,7 @@ hast_status hast_fq_commit(hast_fq *f) {
     HAST_HIP_TRY(hipSetDevice(dev_of(f, s)));
     hipStream_t hs = ctx_stream_of(sctx);
     const size_t n = s.h_st->n_rec;
-    if (f->route) {                                        // a routed block: the caller is through with its runs, nothing to book
+    if (f->route || f->tally) {                            // a routed or tallied block: the caller is through with it, nothing to book
         s.done_pending = false;
         s.state = Slot::FREE;
         return HAST_OK;

@@ -69,6 +69,23 @@ hipError_t launch_fq_route(const uint8_t *d_buf, const FqState *d_st, const uint
                            uint32_t *d_rstart, uint32_t *d_rlen, uint8_t *d_rcls, uint32_t *d_rtile, uint32_t max_rec, RouteState *d_rs, uint8_t *d_out,
                            hipStream_t s);
 
+// ---- tallies (stage 02's per-barcode read count, bf_core.h) -------------------------------------------------------------------------
+struct TallyState {            // one per buffer slot, device + a pinned host copy
+    uint64_t tail_lo, tail_hi; // the partial record at the end of the FILE (fewer than four newlines): the caller's, as for routing
+    uint32_t n_cand;           // record slots k_fq_field2 walked
+    uint32_t n_rec;            // header lines this block owns: candidates 0 .. n_rec - 1
+    uint32_t n_nofield;        // ... of them without a field 2
+    uint32_t n_counted;        // ... counted by k_tally_add
+    uint32_t flags;            // 2: a record that does not end inside the view; 4: an id at or above the dictionary's limit (cannot be)
+    uint32_t reserved[3];
+};
+// field 2 of every candidate's header line: text record -> d_text, extent -> d_fpos / d_flen and, for the first h_cap, pinned h_f =
+// [pos x h_cap | len x h_cap] (len bf::kNoFieldLen: no field 2); view_bytes (what the view holds at most) sizes the grid
+hipError_t launch_fq_field2(const uint8_t *d_buf, const FqState *d_st, const uint32_t *d_nl, int striped, int last, uint32_t *d_text, uint32_t *d_fpos, uint32_t *d_flen,
+                            uint32_t *h_f, uint32_t h_cap, uint32_t max_rec, uint64_t view_bytes, TallyState *d_ts, hipStream_t s);
+// d_counts[d_ids[i]] += 1 for the i < n with an id below limit
+hipError_t launch_tally_add(const uint32_t *d_ids, uint32_t n, unsigned long long *d_counts, uint32_t limit, TallyState *d_ts, hipStream_t s);
+
 // ---- striped streams: a block is framed on its own, from the number of newlines in front of it ----------------------------
 // newlines of the block's own bytes [pad, pad + n_bytes) -> d_st->n_nl (the host adds them up over the blocks of the file)
 hipError_t launch_fq_count_own(const uint8_t *d_buf, FqState *d_st, uint64_t pad, uint64_t n_bytes, uint32_t *d_tile_cnt, hipStream_t s);

@@ -14,6 +14,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+
+#include "bf_core.h"
 #include "fq_device.h"
 #include "nl_index.h"
 
@@ -249,9 +252,9 @@ __global__ void __launch_bounds__(256) k_names_insert(const NamePub *pubs, uint3
 // longer than 15 bytes, a barcode in no list (awk prints an ERROR line with its text and drops the record) -- flags the BLOCK for the
 // host, which then routes that block itself from the same bytes; every other block leaves the GPU as four runs of whole records in
 // input order.
-template <bool STRIPED>
+template <bool STRIPED, class State>            // State: RouteState, or the TallyState of a tally stream (tail_lo, tail_hi, flags)
 __device__ __forceinline__ bool route_extent(const FqState *st, const uint32_t *nl, uint32_t c, uint32_t n_cand, int last, uint64_t &h0, uint64_t &h1, uint64_t &end,
-                                             RouteState *rs) {
+                                             State *rs) {
     const uint64_t lo = st->parse_lo, hi = st->parse_hi;
     const uint32_t n_nl = st->n_nl;
     if (!STRIPED) {                                         // records are lines 4c .. 4c+3 of the parse range (it starts at a record boundary)
@@ -526,6 +529,102 @@ hipError_t launch_fq_name(const uint32_t *d_text, uint32_t n, const NameEntry *t
 hipError_t launch_names_insert(const NamePub *pubs, uint32_t n, NameEntry *tab, uint32_t mask, hipStream_t s) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(k_names_insert, dim3((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024), dim3(256), 0, s, pubs, n, tab, mask);
+    return hipGetLastError();
+}
+
+// ---- tallies: stage 02's per-barcode read count (bf_core.h has the rule) ---------------------------------------------------------
+// A tally stream frames its blocks as every stream does and classifies nothing.  Behind the framing a lane per record candidate --
+// the candidates and extents of the routing kernels above -- writes awk's field 2 of the header line as a text record into the
+// slot's text array; k_fq_name_claim, unchanged, then turns the texts into dense ids of the tally's dictionary, and k_tally_add adds
+// one per id to the tally's counters.  What has no id afterwards is the caller's: keys longer than a text record and keys that came
+// once every id was out (name_claim.h: one answer per text, so a key is the device's in every block or the caller's in every block).
+template <bool STRIPED>
+__global__ void __launch_bounds__(256) k_fq_field2(const uint8_t *buf, const FqState *st, const uint32_t *nl, int last, uint32_t *d_text, uint32_t *d_fpos,
+                                                   uint32_t *d_flen, uint32_t *h_f, uint32_t h_cap, uint32_t max_rec, TallyState *ts) {
+    uint32_t n_cand = route_candidates(st, STRIPED);
+    if (n_cand > max_rec) n_cand = max_rec;                 // (cannot be, as in k_route_class)
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        ts->n_cand = n_cand;
+        if (!STRIPED && last && n_cand == 0 && st->parse_lo < st->parse_hi) { ts->tail_lo = st->parse_lo; ts->tail_hi = st->parse_hi; }
+    }
+    const uint32_t lane = threadIdx.x & 63u;
+    // (the loop's bound is the same for every lane of a wave: the ballots below see whole waves)
+    for (uint32_t base = blockIdx.x * blockDim.x; base < n_cand; base += gridDim.x * blockDim.x) {
+        const uint32_t c = base + threadIdx.x;
+        uint64_t h0 = 0, h1 = 0, end = 0;
+        const bool owned = c < n_cand && route_extent<STRIPED>(st, nl, c, n_cand, last, h0, h1, end, ts);
+        uint32_t w[4], pos = 0, len = bf::kNotOwnedLen;
+        bf::nofield_record(w);
+        bool nofield = false;
+        if (owned) {
+            uint64_t fs = 0, fl = 0;
+            if (!bf::field2(buf + h0, h1 - h0, fs, fl)) { nofield = true; len = bf::kNoFieldLen; }
+            else {
+                pos = (uint32_t)(h0 + fs);
+                len = (uint32_t)fl;                          // (a line lies inside a view of less than 4 GB)
+                if (fl > bf::kMaxText) bf::long_record(w);
+                else bf::text_record(buf + h0 + fs, (uint32_t)fl, w);
+            }
+        }
+        // the header lines of a block are a prefix of its candidates: their number is where the naming kernel stops
+        const unsigned long long m_owned = __ballot(owned), m_nofield = __ballot(nofield);
+        if (lane == 0) {
+            if (m_owned) atomicAdd(&ts->n_rec, (uint32_t)__popcll(m_owned));
+            if (m_nofield) atomicAdd(&ts->n_nofield, (uint32_t)__popcll(m_nofield));
+        }
+        if (c < n_cand) {
+            reinterpret_cast<uint4 *>(d_text)[c] = make_uint4(w[0], w[1], w[2], w[3]);
+            d_fpos[c] = pos;
+            d_flen[c] = len;
+            if (c < h_cap) { h_f[c] = pos; h_f[h_cap + c] = len; }       // (pinned host memory, as k_fq_records writes its extents)
+        }
+    }
+}
+
+// counts[id] += 1 for every record with an id.  One barcode owns 10-20 % of real stLFR reads and files keep input order, so whole
+// waves carry one id; atomics execute at the memory side, and 64 of them on one address would queue up there.  So a wave first
+// takes the id of its first pending lane, counts the lanes that hold the same one (ballot + popcount) and sends ONE add of that
+// many; kTallyRounds such rounds peel the heavy ids, whatever is still pending goes as single adds -- a wave of 64 different ids
+// takes kTallyRounds rounds, not 64.  The adds return nothing.
+constexpr int kTallyRounds = 4;
+__global__ void __launch_bounds__(256) k_tally_add(const uint32_t *ids, uint32_t n, unsigned long long *counts, uint32_t limit, TallyState *ts) {
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint32_t base = blockIdx.x * blockDim.x; base < n; base += gridDim.x * blockDim.x) {
+        const uint32_t i = base + threadIdx.x;
+        const uint32_t id = i < n ? ids[i] : kNameUnknown;
+        bool pending = id < limit;                                   // (kNameUnknown is above every limit)
+        if (id != kNameUnknown && id >= limit) atomicOr(&ts->flags, 4u);     // (an id the dictionary cannot have given: nothing is added)
+        const unsigned long long m_valid = __ballot(pending);
+        if (lane == 0 && m_valid) atomicAdd(&ts->n_counted, (uint32_t)__popcll(m_valid));
+        for (int r = 0; r < kTallyRounds; ++r) {
+            const unsigned long long m = __ballot(pending);
+            if (!m) break;
+            const int leader = __ffsll((long long)m) - 1;
+            const uint32_t lid = __shfl(id, leader);
+            const bool same = pending && id == lid;
+            const unsigned long long g = __ballot(same);
+            if (lane == (uint32_t)leader) (void)__hip_atomic_fetch_add(&counts[lid], (unsigned long long)__popcll(g), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            pending = pending && !same;
+        }
+        if (pending) (void)__hip_atomic_fetch_add(&counts[id], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+hipError_t launch_fq_field2(const uint8_t *d_buf, const FqState *d_st, const uint32_t *d_nl, int striped, int last, uint32_t *d_text, uint32_t *d_fpos, uint32_t *d_flen,
+                            uint32_t *h_f, uint32_t h_cap, uint32_t max_rec, uint64_t view_bytes, TallyState *d_ts, hipStream_t s) {
+    hipError_t e = hipMemsetAsync(d_ts, 0, sizeof(TallyState), s);
+    if (e != hipSuccess) return e;
+    // (the candidates are counted on the device; a record holds four newlines, so a view of view_bytes has at most view_bytes / 4 + 2:
+    // a small block gets a small grid, the kernel strides over whatever there is)
+    const uint64_t most = std::min<uint64_t>(view_bytes / 4 + 2, max_rec);
+    const dim3 grid((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(1024, (most + 255) / 256)));
+    if (striped) hipLaunchKernelGGL(k_fq_field2<true>, grid, dim3(256), 0, s, d_buf, d_st, d_nl, last, d_text, d_fpos, d_flen, h_f, h_cap, max_rec, d_ts);
+    else hipLaunchKernelGGL(k_fq_field2<false>, grid, dim3(256), 0, s, d_buf, d_st, d_nl, last, d_text, d_fpos, d_flen, h_f, h_cap, max_rec, d_ts);
+    return hipGetLastError();
+}
+hipError_t launch_tally_add(const uint32_t *d_ids, uint32_t n, unsigned long long *d_counts, uint32_t limit, TallyState *d_ts, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_tally_add, dim3((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024), dim3(256), 0, s, d_ids, n, d_counts, limit, d_ts);
     return hipGetLastError();
 }
 

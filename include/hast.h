@@ -440,6 +440,45 @@ hast_status hast_fq_next_routed(hast_fq *, hast_fq_routed *out);
 hast_status hast_fq_set_route_gz(hast_fq *, int on);
 hast_status hast_fq_routed_raw_bytes(hast_fq *, uint64_t out[4]);
 
+/* ---- tallies: stage 02's per-barcode read count (assemble_by_supernova.sh, the awk line that writes barcode_freq.txt) -----------
+ * Lines are numbered from 1; of every line 4i + 1 (nothing is validated) the header is split at every '#' and '/', and a line with
+ * at least one separator counts one for its second field: the bytes between the first separator and the next, or the line's end
+ * (possibly empty; any byte but the separators and '\n' belongs to it; hast_amd/csrc/bf_core.h).  A hast_tally is a device dictionary
+ * (as hast_names_create_dict makes) of exactly max_texts ids with a 64-bit counter per id.  A stream put into tally mode frames its
+ * blocks as before (plain or striped, host or device blocks), classifies nothing -- no k-mer table is needed, read lengths are not
+ * looked at -- and counts the keys of a block's header lines on the GPU:
+ *     hast_fq_set_tally     one tally per lane of the stream (contexts of one GPU, and several streams, may share one).  Between
+ *                           files only.  NULL: classify again.
+ *     hast_fq_acquire / _submit / _device_block / _submit_device     as before
+ *     hast_fq_next_tallied  oldest submitted block: returns once its keys are counted
+ *     hast_fq_commit        the caller is through with the block: the buffer is free again
+ * hast_fq_next and hast_fq_next_routed fail with HAST_ERR_INVALID on such a stream, hast_fq_next_tallied on any other; nothing
+ * happens then.  Left to the caller, exactly: keys longer than 15 bytes, keys that arrive once the tally has handed out its last id
+ * (one answer per text, as for hast_names_create_dict: a key is counted on the device in every block or left in every block, per
+ * tally), and the partial record at the end of a file (`tail`: it starts at a record boundary).  For every block
+ * n_counted + n_left + n_nofield == n_records.
+ * hast_tally_size: ids handed out; hast_tally_read: text records (16 bytes: length byte + text) and counts of ids [first, first + n). */
+typedef struct hast_tally hast_tally;
+typedef struct {
+    uint64_t n_records;            /* header lines this block owns */
+    uint64_t n_counted;            /* ... counted on the device */
+    uint64_t n_nofield;            /* ... without a separator: counted by nobody */
+    uint64_t n_left;               /* ... left to the caller */
+    const uint32_t *left_pos;      /* [n_left] where their keys start in the block's view */
+    const uint32_t *left_len;      /* [n_left] and how long they are */
+    const uint8_t *bytes;          /* the view; NULL for a block submitted with hast_fq_submit_device: hast_fq_block_host_bytes
+                                      fetches it (needed only when n_left > 0) */
+    const uint8_t *tail;           /* the partial record at the end of the file, or NULL */
+    uint64_t tail_bytes;
+} hast_fq_tallied;
+hast_status hast_tally_create(hast_ctx *, size_t max_texts, hast_tally **out);
+size_t      hast_tally_limit(const hast_tally *);
+hast_status hast_tally_size(hast_tally *, size_t *n_ids);
+hast_status hast_tally_read(hast_tally *, size_t first, size_t n, uint8_t *text16, uint64_t *counts);
+void        hast_tally_destroy(hast_tally *);
+hast_status hast_fq_set_tally(hast_fq *, hast_tally *const *tallies, int n_tallies);
+hast_status hast_fq_next_tallied(hast_fq *, hast_fq_tallied *out);
+
 /* ---- deflate on the GPU: device memory -> one gzip member -----------------------------------------------------------------
  * hast_dz_compress_device writes ONE complete gzip member (RFC 1952: what gzip -dc, zlib and hast_gz read) for the n_bytes at
  * d_src, n_bytes == 0 included (an empty member), to d_dst, and waits for it; *n_out = its size.  The input is cut into pieces of
