@@ -235,6 +235,17 @@ ABI_SYMBOLS = {
     "hast_tx_destroy": (None, [vp]),
     "hast_tx_pair_staged": (C.c_int, [vp, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(TxState), C.c_int, C.POINTER(vp), C.POINTER(vp),
                                       C.POINTER(TxResult), C.POINTER(TxTimes)]),
+    "hast_tx_feed_create": (C.c_int, [vp, C.c_size_t, C.c_int, C.POINTER(vp)]),
+    "hast_tx_feed_wants": (C.c_int, [vp, C.c_int]),
+    "hast_tx_feed_room": (C.c_size_t, [vp]),
+    "hast_tx_feed_device_block": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(vp)]),
+    "hast_tx_feed_host_block": (C.c_int, [vp, C.c_int, C.POINTER(vp)]),
+    "hast_tx_feed_submit": (C.c_int, [vp, C.c_int, C.c_size_t]),
+    "hast_tx_feed_step": (C.c_int, [vp, C.POINTER(TxState), C.POINTER(TxResult), C.POINTER(C.c_int)]),
+    "hast_tx_feed_collect": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint64 * 2), C.POINTER(C.c_uint64 * 2)]),
+    "hast_tx_feed_take_tail": (C.c_int, [vp, C.c_int, vp, C.POINTER(C.c_size_t)]),
+    "hast_tx_feed_times": (C.c_int, [vp, C.POINTER(TxTimes), C.POINTER(C.c_double)]),
+    "hast_tx_feed_destroy": (None, [vp]),
 }
 
 
@@ -846,6 +857,76 @@ class TxConverter:
     def close(self):
         if self._h:
             self._lib.hast_tx_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+TX_ON_HOST, TX_TAIL_TOO_LONG, TX_ENDS = 1, 4, 8
+
+
+class TxFeed:
+    """The paired, pipelined device route of one fake_10x run over a TxConverter (hast_tx_feed_*): per side, bytes are written in HBM
+    (device_block: the address and the stream to fill it on) or handed over from the host (submit_host), step() converts the whole
+    pairs and enqueues the runs' deflate (gz_out) on a second stream, collect() returns the oldest step's outputs.  At most two steps
+    wait for collect()."""
+
+    def __init__(self, conv: TxConverter, block_bytes, gz_out):
+        self._lib = lib()
+        self._h = C.c_void_p()
+        self.block = block_bytes
+        _ck(self._lib.hast_tx_feed_create(conv._h, block_bytes, int(bool(gz_out)), C.byref(self._h)))
+        self.room = self._lib.hast_tx_feed_room(self._h)
+
+    def wants(self, side) -> bool:
+        return bool(self._lib.hast_tx_feed_wants(self._h, side))
+
+    def device_block(self, side):
+        """-> (device address of the side's next block, the stream its bytes must be written on)"""
+        d, stream = C.c_void_p(), C.c_void_p()
+        _ck(self._lib.hast_tx_feed_device_block(self._h, side, C.byref(d), C.byref(stream)))
+        return d.value, stream
+
+    def submit(self, side, n_bytes):
+        _ck(self._lib.hast_tx_feed_submit(self._h, side, n_bytes))
+
+    def submit_host(self, side, data: bytes):
+        """the side's next block from host bytes (at most block_bytes; fewer: the side's end)"""
+        h = C.c_void_p()
+        _ck(self._lib.hast_tx_feed_host_block(self._h, side, C.byref(h)))
+        C.memmove(h, data, len(data))
+        self.submit(side, len(data))
+
+    def step(self, state: TxState):
+        """-> (TxResult, flags: TX_ON_HOST | TX_TAIL_TOO_LONG | TX_ENDS); state is updated"""
+        res, flags = TxResult(), C.c_int(0)
+        _ck(self._lib.hast_tx_feed_step(self._h, C.byref(state), C.byref(res), C.byref(flags)))
+        return res, flags.value
+
+    def collect(self):
+        """the oldest step not yet collected -> (out1, out2, raw_bytes): copies of what the feed's pinned slots hold"""
+        o1, o2, n_out, n_raw = C.c_void_p(), C.c_void_p(), (C.c_uint64 * 2)(), (C.c_uint64 * 2)()
+        _ck(self._lib.hast_tx_feed_collect(self._h, C.byref(o1), C.byref(o2), C.byref(n_out), C.byref(n_raw)))
+        return C.string_at(o1, n_out[0]) if n_out[0] else b"", C.string_at(o2, n_out[1]) if n_out[1] else b"", (n_raw[0], n_raw[1])
+
+    def take_tail(self, side) -> bytes:
+        buf, n = C.create_string_buffer(max(self.room, 1)), C.c_size_t(0)
+        _ck(self._lib.hast_tx_feed_take_tail(self._h, side, buf, C.byref(n)))
+        return buf.raw[:n.value]
+
+    def times(self):
+        """-> (TxTimes, seconds spent waiting in collect)"""
+        t, w = TxTimes(), C.c_double(0)
+        _ck(self._lib.hast_tx_feed_times(self._h, C.byref(t), C.byref(w)))
+        return t, w.value
+
+    def close(self):
+        if self._h:
+            self._lib.hast_tx_feed_destroy(self._h)
             self._h = C.c_void_p()
 
     def __enter__(self):

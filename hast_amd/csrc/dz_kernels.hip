@@ -87,6 +87,19 @@ __global__ void k_dz_job_from_route(Job *job, const RouteState *rs) {
     job->n_runs = kMaxRuns;
     job->emit_empty = 0;
 }
+// the two runs of a converted step (tx_kernels.hip): run 0 from the buffer's first byte, run 1 from second_off on, their sizes where
+// k_tx_scan_out left them (TxDevState.out_bytes); an empty run becomes nothing
+__global__ void k_dz_job_from_tx(Job *job, const uint64_t *run_bytes, uint64_t second_off) {
+    const uint64_t n0 = run_bytes[0], n1 = run_bytes[1];
+    job->src_off[0] = 0;
+    job->n_bytes[0] = n0;
+    job->src_off[1] = second_off;
+    job->n_bytes[1] = n1;
+    job->src_off[2] = job->n_bytes[2] = 0;
+    job->src_off[3] = job->n_bytes[3] = 0;
+    job->n_runs = 2;
+    job->emit_empty = 0;
+}
 
 __global__ void __launch_bounds__(64) k_dz_piece(const Job *d_job, const uint8_t *src, uint32_t max_pieces, void *d_work, int literals_only) {
     __shared__ uint32_t s_in[kPiece / 4 + 2];
@@ -353,6 +366,10 @@ hipError_t launch_job_one(Job *d_job, uint64_t n_bytes, hipStream_t s) {
 }
 hipError_t launch_job_from_route(Job *d_job, const RouteState *d_rs, hipStream_t s) {
     hipLaunchKernelGGL(k_dz_job_from_route, dim3(1), dim3(1), 0, s, d_job, d_rs);
+    return hipGetLastError();
+}
+hipError_t launch_job_from_tx(Job *d_job, const uint64_t *d_run_bytes, uint64_t second_off, hipStream_t s) {
+    hipLaunchKernelGGL(k_dz_job_from_tx, dim3(1), dim3(1), 0, s, d_job, d_run_bytes, second_off);
     return hipGetLastError();
 }
 hipError_t launch_compress(const Job *d_job, const uint8_t *d_src, uint32_t max_pieces, void *d_work, uint8_t *d_dst, uint64_t cap, Result *d_res,

@@ -1,5 +1,5 @@
 // fake_10x -- drop-in for HAST's 02.assemble_by_supernova/fake_10x.pl: stLFR read pairs -> 10x FASTQ for Supernova.
-//   fake_10x READ1.gz READ2.gz MERGE.txt [--inflate host|zlib] [--block-mb N] [--plain-out] [--stats]
+//   fake_10x READ1.gz READ2.gz MERGE.txt [--inflate host|zlib|device] [--block-mb N] [--plain-out] [--stats]
 //            [--convert host|device] [--deflate host|device]
 // writes SampleName_S1_L001_R1_001.fastq.gz and SampleName_S1_L001_R2_001.fastq.gz into the working directory and prints the
 // script's stdout.  A host program: the inputs come through ingest.h (ordinary gzip inflated by several threads, BGZF, pipes, plain
@@ -12,6 +12,12 @@
 // one writer thread per output file writes step n beside step n + 1 (and deflates it, with --deflate host).  The steps at the end of
 // the inputs, a step larger than the converter was created for and one whose outputs outgrow their room are the host model's.  A
 // map the device cannot take (hast_tx_map_info.device_ok == 0) sends the whole run the host way, with one WARN line.
+// --convert device --inflate device: the inputs do not pass through host memory at all (hast_tx_feed_*, include/hast.h): a .gz input is
+// inflated on the GPU (hast_gz_read_device) straight into the feed's block in HBM -- an input hast_gz_open cannot take (plain FASTQ, a
+// pipe) goes through ingest.h into the feed's pinned block and is uploaded -- the feed says who reads (the rule above, from the counts
+// the step before left, tx_feed_plan.h), converts, and deflates and downloads step n while step n + 1 is read and converted.  The steps
+// are the same steps; when an input has ended and left no whole record, or a record is longer than the feed's buffers, the bytes the
+// feed still holds come down and the host loop above ends the run (a .gz still open on the GPU is read through a device buffer).
 // Exit codes: 0 done; 1 usage; 2 an input that cannot be opened, or a .gz that is damaged or fails its CRC; 3 a failing library
 // call or write; 4 --convert device without a usable GPU, or a failing GPU call.
 #include <stdio.h>
@@ -42,7 +48,7 @@ struct Options {
 double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 int usage() {
-    fprintf(stderr, "usage: fake_10x READ1.gz READ2.gz MERGE.txt [--inflate host|zlib] [--block-mb N] [--plain-out] [--stats]\n"
+    fprintf(stderr, "usage: fake_10x READ1.gz READ2.gz MERGE.txt [--inflate host|zlib|device] [--block-mb N] [--plain-out] [--stats]\n"
                     "                [--convert host|device] [--deflate host|device]\n");
     return 1;
 }
@@ -176,6 +182,32 @@ struct Input {
     std::string path;
     hast::BlockSource src;
     bool eof = false;
+    // --inflate device: a .gz that is inflated on the GPU; the host loop reads it through a device buffer of a block and a download
+    hast_gz *gz = nullptr;
+    hast_ctx *ctx = nullptr;
+    uint8_t *d_bounce = nullptr;
+    bool gpu_failed = false;       // the trouble is a failing GPU call, not the input's
+    size_t read(char *dst, size_t cap, std::string &trouble) {
+        if (!gz) return src.read_into(dst, cap, trouble);
+        size_t got = 0;
+        while (got < cap) {        // a short read is followed by another until one returns nothing (include/hast.h)
+            size_t n = 0;
+            const hast_status st = hast_gz_read_device(gz, d_bounce + got, cap - got, &n, nullptr);
+            if (st != HAST_OK) {
+                trouble = hast_last_error();
+                gpu_failed = st != HAST_ERR_IO;
+                return 0;
+            }
+            if (!n) break;
+            got += n;
+        }
+        if (got && (hast_stream_sync(ctx, nullptr) != HAST_OK || hast_memcpy_d2h(ctx, dst, d_bounce, got) != HAST_OK)) {
+            trouble = hast_last_error();
+            gpu_failed = true;
+            return 0;
+        }
+        return got;
+    }
 };
 
 struct Run {
@@ -193,6 +225,11 @@ struct Run {
     uint64_t pairs_device = 0, pairs_host = 0;
     Writer writer[2];
     double write_s = 0;
+    // --inflate device
+    hast_tx_feed *feed = nullptr;  // null: the inputs are inflated on the host
+    int gz_on_device = 0, host_sides = 0;
+    uint64_t steps_on_host = 0;
+    std::string feed_fallback = "none";
 };
 
 void progress(uint64_t before, uint64_t after) {
@@ -214,29 +251,22 @@ bool has_record(const std::vector<uint8_t> &v) {
     return true;
 }
 
-int run(Run &r) {
-    Input in[2];
-    for (int s = 0; s < 2; ++s) {
-        in[s].path = r.o.in[s];
-        if (!in[s].src.open(in[s].path, r.o.block, false)) {
-            fprintf(stderr, "fake_10x: cannot open %s\n", in[s].path.c_str());
-            return 2;
-        }
-    }
-    std::vector<uint8_t> have[2];            // per side: what the step before left + the block just read
+// The program's loop.  have[]: per side, what the step before left + the block just read.  read_done: the reads of the first step have
+// been made (the device feed hands over in the middle of a step: have[] is what that step was given).
+int host_loop(Run &r, Input in[2], std::vector<uint8_t> have[2], bool read_done) {
     std::string trouble;
-    for (int mode = 0; mode != 1;) {
+    for (int mode = 0; mode != 1; read_done = false) {
         // a side that has more than a block waiting, a whole record in it, reads nothing: the other side has to catch up
-        for (int s = 0; s < 2; ++s) {
+        for (int s = 0; s < 2 && !read_done; ++s) {
             if (in[s].eof || (have[s].size() > r.o.block && has_record(have[s]))) continue;
             const size_t at = have[s].size();
             have[s].resize(at + r.o.block);
-            const size_t n = in[s].src.read_into(reinterpret_cast<char *>(have[s].data() + at), r.o.block, trouble);
+            const size_t n = in[s].read(reinterpret_cast<char *>(have[s].data() + at), r.o.block, trouble);
             have[s].resize(at + n);
             r.plain_in += n;
             if (!trouble.empty()) {
                 fprintf(stderr, "fake_10x: %s: %s\n", in[s].path.c_str(), trouble.c_str());
-                return 2;
+                return in[s].gpu_failed ? 4 : 2;
             }
             if (n < r.o.block) in[s].eof = true;
         }
@@ -298,6 +328,149 @@ int run(Run &r) {
     return 0;
 }
 
+int run(Run &r) {
+    Input in[2];
+    for (int s = 0; s < 2; ++s) {
+        in[s].path = r.o.in[s];
+        if (!in[s].src.open(in[s].path, r.o.block, false)) {
+            fprintf(stderr, "fake_10x: cannot open %s\n", in[s].path.c_str());
+            return 2;
+        }
+    }
+    std::vector<uint8_t> have[2];
+    return host_loop(r, in, have, false);
+}
+
+int fail_gpu(const char *what) {
+    fprintf(stderr, "fake_10x: %s: %s\n", what, hast_last_error());
+    return 4;
+}
+
+// --convert device --inflate device: the steps of host_loop with the bytes in HBM (hast_tx_feed_*).  Step n + 1 is read and converted
+// before step n is collected, so the GPU deflates n meanwhile; the collected runs go to the writers in order.
+int feed_loop(Run &r, Input in[2], std::vector<uint8_t> have[2], bool *read_done) {
+    const size_t block = r.o.block;
+    const bool writer_deflates = !r.o.plain_out && r.o.deflate != "device";
+    std::string trouble;
+    auto collect = [&]() -> int {
+        const uint8_t *p[2];
+        uint64_t n_out[2], n_raw[2];
+        if (hast_tx_feed_collect(r.feed, &p[0], &p[1], n_out, n_raw) != HAST_OK) return fail_gpu("the conversion on the device");
+        for (int s = 0; s < 2; ++s) {
+            Writer::Job j;
+            j.p = p[s];
+            j.n = (size_t)n_out[s];
+            j.deflate = writer_deflates;
+            if (!r.writer[s].submit(j)) {
+                fprintf(stderr, "fake_10x: cannot write the outputs\n");
+                return 3;
+            }
+        }
+        return 0;
+    };
+    bool waiting = false;          // a step has been made and not collected
+    int flags = 0;
+    for (;;) {
+        for (int s = 0; s < 2; ++s) {
+            if (!hast_tx_feed_wants(r.feed, s)) continue;
+            size_t got = 0;
+            if (in[s].gz) {
+                uint8_t *d = nullptr;
+                hast_stream fill = nullptr;
+                if (hast_tx_feed_device_block(r.feed, s, &d, &fill) != HAST_OK) return fail_gpu("the feed");
+                while (got < block) {          // a short read is followed by another until one returns nothing (include/hast.h)
+                    size_t n = 0;
+                    const hast_status st = hast_gz_read_device(in[s].gz, d + got, block - got, &n, fill);
+                    if (st == HAST_ERR_IO) {
+                        fprintf(stderr, "fake_10x: %s\n", hast_last_error());
+                        return 2;
+                    }
+                    if (st != HAST_OK) return fail_gpu("the inflate on the device");
+                    if (!n) break;
+                    got += n;
+                }
+            } else {
+                uint8_t *h = nullptr;
+                if (hast_tx_feed_host_block(r.feed, s, &h) != HAST_OK) return fail_gpu("the feed");
+                got = in[s].src.read_into(reinterpret_cast<char *>(h), block, trouble);
+                if (!trouble.empty()) {
+                    fprintf(stderr, "fake_10x: %s: %s\n", in[s].path.c_str(), trouble.c_str());
+                    return 2;
+                }
+            }
+            if (hast_tx_feed_submit(r.feed, s, got) != HAST_OK) return fail_gpu("the feed");
+            r.plain_in += got;
+            if (got < block) in[s].eof = true;
+        }
+        hast_tx_result res;
+        const uint64_t before = r.st.headers;
+        if (hast_tx_feed_step(r.feed, &r.st, &res, &flags) != HAST_OK) return fail_gpu("the conversion on the device");
+        if (flags & (int)HAST_TX_ENDS) break;                    // nothing was converted: this step is the host loop's first
+        progress(before, r.st.headers);
+        ++r.steps;
+        if (flags & (int)HAST_TX_ON_HOST) {
+            ++r.steps_on_host;
+            r.pairs_host += res.pairs;
+        } else {
+            r.pairs_device += res.pairs;
+        }
+        if (waiting)
+            if (const int rc = collect()) return rc;
+        waiting = true;
+        if (flags & (int)HAST_TX_TAIL_TOO_LONG) break;
+    }
+    if (waiting)
+        if (const int rc = collect()) return rc;
+    // the host loop ends the run over what the feed still holds
+    for (int s = 0; s < 2; ++s) {
+        have[s].resize(hast_tx_feed_room(r.feed));
+        size_t n = 0;
+        if (hast_tx_feed_take_tail(r.feed, s, have[s].data(), &n) != HAST_OK) return fail_gpu("the feed");
+        have[s].resize(n);
+        if (in[s].gz && !in[s].eof) {
+            void *d = nullptr;
+            if (hast_dev_alloc(r.ctx, block + 64, &d) != HAST_OK) return fail_gpu("a device buffer of a block");
+            in[s].d_bounce = static_cast<uint8_t *>(d);
+        }
+    }
+    *read_done = (flags & (int)HAST_TX_ENDS) != 0;
+    return 0;
+}
+
+int run_feed(Run &r) {
+    Input in[2];
+    int rc = 0;
+    for (int s = 0; s < 2 && !rc; ++s) {
+        in[s].path = r.o.in[s];
+        in[s].ctx = r.ctx;
+        const hast_status st = hast_gz_open(r.ctx, in[s].path.c_str(), &in[s].gz);
+        if (st == HAST_OK) {
+            ++r.gz_on_device;
+        } else if (st == HAST_ERR_UNSUPPORTED) {                 // plain FASTQ, a pipe, no room: this side comes through the host
+            in[s].gz = nullptr;
+            ++r.host_sides;
+            if (!in[s].src.open(in[s].path, r.o.block, false)) {
+                fprintf(stderr, "fake_10x: cannot open %s\n", in[s].path.c_str());
+                rc = 2;
+            }
+        } else if (st == HAST_ERR_IO) {
+            fprintf(stderr, "fake_10x: cannot open %s: %s\n", in[s].path.c_str(), hast_last_error());
+            rc = 2;
+        } else {
+            rc = fail_gpu("hast_gz_open");
+        }
+    }
+    std::vector<uint8_t> have[2];
+    bool read_done = false;
+    if (!rc) rc = feed_loop(r, in, have, &read_done);
+    if (!rc) rc = host_loop(r, in, have, read_done);
+    for (int s = 0; s < 2; ++s) {
+        if (in[s].gz) hast_gz_close(in[s].gz);
+        if (in[s].d_bounce) hast_dev_free(r.ctx, in[s].d_bounce);
+    }
+    return rc;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -307,7 +480,7 @@ int main(int argc, char **argv) {
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto value = [&]() -> const char * { return i + 1 < argc ? argv[++i] : nullptr; };
-        if (a == "--inflate") { const char *v = value(); if (!v || (strcmp(v, "host") && strcmp(v, "zlib"))) return usage(); r.o.inflate = v; }
+        if (a == "--inflate") { const char *v = value(); if (!v || (strcmp(v, "host") && strcmp(v, "zlib") && strcmp(v, "device"))) return usage(); r.o.inflate = v; }
         else if (a == "--block-mb") { const char *v = value(); if (!v || atoi(v) < 1 || atoi(v) > 1024) return usage(); r.o.block = (size_t)atoi(v) << 20; block_given = true; }
         else if (a == "--convert") { const char *v = value(); if (!v || (strcmp(v, "host") && strcmp(v, "device"))) return usage(); r.o.convert = v; }
         else if (a == "--deflate") { const char *v = value(); if (!v || (strcmp(v, "host") && strcmp(v, "device"))) return usage(); r.o.deflate = v; }
@@ -318,6 +491,7 @@ int main(int argc, char **argv) {
     }
     if (pos.size() != 3) return usage();
     if (r.o.deflate == "device" && r.o.convert != "device") return usage();      // (the encoder takes device memory)
+    if (r.o.inflate == "device" && r.o.convert != "device") return usage();      // (the inflated bytes stay in device memory)
     if (r.o.deflate.empty()) r.o.deflate = r.o.convert;
     r.o.in[0] = pos[0];
     r.o.in[1] = pos[1];
@@ -343,7 +517,19 @@ int main(int argc, char **argv) {
             fprintf(stderr, "fake_10x: --convert device: %s\n", hast_last_error());
             return 4;
         }
+        if (r.o.inflate == "device") {
+            const hast_status st = hast_tx_feed_create(r.tx, r.o.block, !r.o.plain_out && r.o.deflate == "device", &r.feed);
+            if (st == HAST_ERR_UNSUPPORTED) {
+                fprintf(stderr, "WARN: fake_10x: --inflate device cannot take blocks of %zu bytes: inflating on the host\n", r.o.block);
+                r.feed_fallback = "block_too_large";
+            } else if (st != HAST_OK) {
+                fprintf(stderr, "fake_10x: --inflate device: %s\n", hast_last_error());
+                return 4;
+            }
+        }
     }
+    if (r.o.inflate == "device" && !r.tx) r.feed_fallback = r.fallback;
+    if (!r.feed) r.host_sides = 2;
     if (!r.out.open(r.o.plain_out)) {
         fprintf(stderr, "fake_10x: cannot create the outputs in the working directory\n");
         return 3;
@@ -351,7 +537,7 @@ int main(int argc, char **argv) {
     const double t0 = now();
     if (r.tx)
         for (int s = 0; s < 2; ++s) r.writer[s].start(&r.out, s);
-    int rc = run(r);
+    int rc = r.feed ? run_feed(r) : run(r);
     for (int s = 0; s < 2; ++s) {
         if (!r.writer[s].stop() && !rc) {
             fprintf(stderr, "fake_10x: cannot write the outputs\n");
@@ -360,6 +546,9 @@ int main(int argc, char **argv) {
         r.write_s += r.writer[s].busy;
     }
     const bool closed = r.out.close();
+    double collect_wait = 0;
+    if (r.feed) hast_tx_feed_times(r.feed, &r.times, &collect_wait);
+    hast_tx_feed_destroy(r.feed);
     hast_tx_destroy(r.tx);
     if (r.ctx) hast_ctx_destroy(r.ctx);
     hast_tx_map_destroy(r.map);
@@ -375,6 +564,9 @@ int main(int argc, char **argv) {
         fprintf(stderr, "[stats] seconds: upload=%.3f kernels=%.3f deflate=%.3f download=%.3f write=%.3f read_phase=%.3f plain_in_bytes=%llu out_bytes=%llu+%llu\n",
                 r.times.upload_s, r.times.kernel_s, r.times.deflate_s, r.times.download_s, r.write_s, now() - t0, (unsigned long long)r.plain_in,
                 (unsigned long long)r.out.bytes[0], (unsigned long long)r.out.bytes[1]);
+        if (r.o.inflate == "device")
+            fprintf(stderr, "[stats] ingest device: gz_on_device=%d host_sides=%d steps_on_host=%llu collect_wait=%.3f fallback=%s\n", r.gz_on_device, r.host_sides,
+                    (unsigned long long)r.steps_on_host, collect_wait, r.feed_fallback.c_str());
     } else if (r.o.stats) {
         fprintf(stderr, "[stats] transform host: steps=%llu pairs_on_device=0 pairs_on_host=%llu fallback=none\n", (unsigned long long)r.steps,
                 (unsigned long long)r.st.headers);

@@ -36,6 +36,7 @@ struct TxStaging {
 
 struct hast_tx {
     hast_ctx *ctx = nullptr;
+    const hast_tx_map *map = nullptr;        // the caller's (a paired feed converts a step on the host with it)
     TxStaging *io = nullptr;
     int device = 0;
     hipStream_t stream = nullptr;            // the context's, when a call names none
@@ -54,6 +55,12 @@ static void fill_info(const tx::Map &m, hast_tx_map_info *info) {
     info->device_ok = m.device_ok ? 1 : 0;
     snprintf(info->reason, sizeof info->reason, "%s", m.reason.c_str());
 }
+
+namespace hast {
+TxParts tx_parts_of(const hast_tx *t) {
+    return TxParts{t->ctx, t->device, t->max_in, t->map, reinterpret_cast<const TxDevState *>(t->d_scratch + t->plan.state)};
+}
+}  // namespace hast
 
 extern "C" {
 
@@ -137,6 +144,7 @@ hast_status hast_tx_create(hast_ctx *c, const hast_tx_map *m, size_t max_in_byte
     std::vector<tx::TableSlot> table;
     tx::table_build(m->map, table);
     t->ctx = c;
+    t->map = m;
     t->device = hast_ctx_device(c);
     t->stream = ctx_stream_of(c);
     t->max_in = max_in_bytes;

@@ -57,3 +57,19 @@ struct TxStepArgs {
 hipError_t launch_tx_step(const TxStepArgs &a, uint8_t *d_scratch, const TxScratchPlan &plan, hipStream_t s);
 
 }  // namespace hast
+
+// what tx_feed.cpp needs of a hast_tx (tx_api.cpp): whose it is, what it was created for, the map for the steps that go to the host
+// model, and where a step leaves its TxDevState in device memory
+struct hast_tx;
+struct hast_tx_map;
+struct hast_ctx;
+namespace hast {
+struct TxParts {
+    hast_ctx *ctx;
+    int device;
+    size_t max_in;
+    const hast_tx_map *map;
+    const TxDevState *d_state;
+};
+TxParts tx_parts_of(const hast_tx *t);
+}  // namespace hast

@@ -775,6 +775,56 @@ void        hast_tx_destroy(hast_tx *);
 typedef struct { double upload_s, kernel_s, deflate_s, download_s; } hast_tx_times;
 hast_status hast_tx_pair_staged(hast_tx *, const uint8_t *r1, size_t n1, const uint8_t *r2, size_t n2, hast_tx_state *state, int gz,
                                 const uint8_t **out1, const uint8_t **out2, hast_tx_result *res, hast_tx_times *times);
+/* The paired, pipelined device route of one fake_10x run (`fake_10x --convert device --inflate device`; hast_amd/csrc/tx_feed.cpp,
+ * the reading rule: tx_feed_plan.h): both inputs' bytes are WRITTEN IN HBM (hast_gz_read_device) or uploaded from pinned memory, the
+ * whole pairs of every step converted there, both runs deflated as ONE job of the GPU's encoder on a second stream and downloaded
+ * while the next step is read and converted.  side: 0 = read 1, 1 = read 2.  One feed per hast_tx; the map the hast_tx was created from
+ * must outlive the feed (a step whose outputs outgrow their room is converted by hast_tx_pair_host).
+ *   hast_tx_feed_create        ALL device and pinned memory, once: per side two input slots of room bytes (room = 2 * block_bytes + 4096,
+ *                              at least 1 MB; above 128 MB or above what the hast_tx was created for: HAST_ERR_UNSUPPORTED), two output
+ *                              slots for both runs (2 x room + 4 KB a side), with gz_out the encoder's workspace and member buffers, two
+ *                              pinned result slots.  No later call allocates or frees device memory.
+ *   hast_tx_feed_wants         1: this side reads for the next step (up to block_bytes); 0: it has been read to its end (a submit of
+ *                              fewer than block_bytes), has read already, or holds more than a block with a whole record in it -- known
+ *                              from the step before (lines - 4 * pairs >= 4), no byte is looked at on the host
+ *   hast_tx_feed_device_block  where the caller's kernels on *fill_stream (the feed's converting stream) write the side's next up to
+ *                              block_bytes: directly behind the bytes the side carries, so a step sees one contiguous range
+ *   hast_tx_feed_host_block    pinned memory for them instead (plain FASTQ, a pipe); _submit uploads it on a stream of the feed's own
+ *   hast_tx_feed_submit        n_bytes (0 .. block_bytes) of the block just handed out are valid; fewer than block_bytes: the side's end
+ *   hast_tx_feed_step          hast_tx_pair_host(final = 0) over carry + submitted bytes of both sides (a side that did not read: its
+ *                              carry alone): *res (out_bytes = raw_bytes = the runs' sizes) and *state are exactly its.  What is left
+ *                              is copied to the front of the side's other slot, the runs' deflate (gz_out: one job of two runs) is
+ *                              enqueued on a second stream, and the call returns; the download, whose size only the encoder knows,
+ *                              is _collect's, on a stream of its own.  *flags: HAST_TX_ON_HOST the outputs outgrew their room and
+ *                              the step was converted by hast_tx_pair_host (deflated by zlib, level 6, with gz_out), results handed on
+ *                              the same way; HAST_TX_ENDS hast_tx_step_mode over what this step was given is 1 or 2 (an input has ended
+ *                              and left no whole record): nothing was converted, NO collect is due for this step, the caller takes both
+ *                              tails and ends on the host; HAST_TX_TAIL_TOO_LONG the step stands, but a side that has to read next
+ *                              carries more than room - block_bytes (a record longer than the buffers): collect, take the tails, go on
+ *                              on the host.  At most two steps may be waiting for _collect.
+ *   hast_tx_feed_collect       waits for the oldest step not yet collected: *out1 / *out2 (pinned, the feed's) hold out_bytes[] bytes --
+ *                              with gz_out one gzip member per run that had bytes, else the runs as they are -- and stay valid until the
+ *                              next collect BUT ONE returns; raw_bytes[] = the runs' sizes.  A caller that steps n + 1 before it
+ *                              collects n has n's deflate and download run beside n + 1's inflate, upload and conversion.
+ *   hast_tx_feed_take_tail     the bytes a side holds -- what the last step left, and after a step that said HAST_TX_ENDS everything that
+ *                              step was given -- to dst (hast_tx_feed_room bytes of room); the side then holds nothing.
+ *   hast_tx_feed_times         *times is ADDED to as by hast_tx_pair_staged (deflate_s / download_s: what the collects waited for);
+ *                              *collect_wait_s = the seconds spent waiting inside hast_tx_feed_collect */
+typedef struct hast_tx_feed hast_tx_feed;
+#define HAST_TX_ON_HOST 1u
+#define HAST_TX_TAIL_TOO_LONG 4u
+#define HAST_TX_ENDS 8u
+hast_status hast_tx_feed_create(hast_tx *, size_t block_bytes, int gz_out, hast_tx_feed **out);
+int         hast_tx_feed_wants(const hast_tx_feed *, int side);
+size_t      hast_tx_feed_room(const hast_tx_feed *);
+hast_status hast_tx_feed_device_block(hast_tx_feed *, int side, uint8_t **d_buf, hast_stream *fill_stream);
+hast_status hast_tx_feed_host_block(hast_tx_feed *, int side, uint8_t **h_buf);
+hast_status hast_tx_feed_submit(hast_tx_feed *, int side, size_t n_bytes);
+hast_status hast_tx_feed_step(hast_tx_feed *, hast_tx_state *state, hast_tx_result *res, int *flags);
+hast_status hast_tx_feed_collect(hast_tx_feed *, const uint8_t **out1, const uint8_t **out2, uint64_t out_bytes[2], uint64_t raw_bytes[2]);
+hast_status hast_tx_feed_take_tail(hast_tx_feed *, int side, uint8_t *dst, size_t *n_bytes);
+hast_status hast_tx_feed_times(const hast_tx_feed *, hast_tx_times *times, double *collect_wait_s);
+void        hast_tx_feed_destroy(hast_tx_feed *);
 
 #ifdef __cplusplus
 }
