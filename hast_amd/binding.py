@@ -54,6 +54,11 @@ class SqResult(C.Structure):
                 ("flags", C.c_uint32), ("first_bad", C.c_uint32)]
 
 
+class RsBlock(C.Structure):
+    _fields_ = [("consumed", C.c_uint64), ("records", C.c_uint64), ("bases", C.c_uint64), ("name_bytes", C.c_uint64), ("flags", C.c_uint32),
+                ("votes", C.POINTER(C.c_uint32)), ("name_off", C.POINTER(C.c_uint32)), ("names", C.POINTER(C.c_uint8))]
+
+
 class TxMapInfo(C.Structure):
     _fields_ = [("n_keys", C.c_uint64), ("device_ok", C.c_int), ("reason", C.c_char * 60)]
 
@@ -72,6 +77,8 @@ class TxTimes(C.Structure):
 
 
 SQ_NOT_FOUR_LINE, SQ_NO_RECORD = 1, 2
+RS_FASTA, RS_FASTQ = 0, 1
+RS_FORMAT_ERROR, RS_RECORD_TOO_LONG = 1, 4
 KC_HISTO_HIGH = 10000
 
 # every symbol include/hast.h declares: name -> (restype, argtypes)
@@ -222,6 +229,13 @@ ABI_SYMBOLS = {
     "hast_sq_feed_next": (C.c_int, [vp, C.c_int, C.POINTER(SqResult)]),
     "hast_sq_feed_take_tail": (C.c_int, [vp, vp, C.POINTER(C.c_size_t)]),
     "hast_sq_feed_destroy": (None, [vp]),
+    "hast_rs_create": (C.c_int, [vp, C.c_int, C.c_size_t, C.POINTER(vp)]),
+    "hast_rs_host_block": (C.c_int, [vp, C.POINTER(vp)]),
+    "hast_rs_device_block": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp)]),
+    "hast_rs_submit": (C.c_int, [vp, C.c_size_t, C.c_int]),
+    "hast_rs_next": (C.c_int, [vp, C.POINTER(RsBlock)]),
+    "hast_rs_take_tail": (C.c_int, [vp, vp, C.POINTER(C.c_size_t)]),
+    "hast_rs_destroy": (None, [vp]),
     # stage 02: stLFR pairs -> 10x FASTQ (fake_10x.pl)
     "hast_tx_map_load": (C.c_int, [C.c_char_p, C.POINTER(vp), C.POINTER(TxMapInfo)]),
     "hast_tx_map_parse": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(vp), C.POINTER(TxMapInfo)]),
@@ -784,6 +798,61 @@ class SqFramer:
     def close(self):
         if self._h:
             self._lib.hast_sq_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class ReadStream:
+    """The feed of `classify_read --ingest device` (hast_rs_*): raw FASTA / FASTQ bytes in, per-read names and votes out."""
+
+    def __init__(self, ctx: Context, fmt, block_bytes):
+        self._lib = lib()
+        self._ctx = ctx
+        self.block = block_bytes
+        h = C.c_void_p()
+        _ck(self._lib.hast_rs_create(ctx._h, fmt, block_bytes, C.byref(h)))
+        self._h = h
+
+    def submit(self, data: bytes, last=False, device=False):
+        """one block of up to block_bytes; device=True: written into the feed's device block (the stream it names is the context's)"""
+        p, stream = C.c_void_p(), C.c_void_p()
+        if device:
+            _ck(self._lib.hast_rs_device_block(self._h, C.byref(p), C.byref(stream)))
+            assert stream.value == self._ctx.stream
+            if data:
+                _ck(self._lib.hast_memcpy_h2d(self._ctx._h, p, data, len(data)))      # (synchronous: the bytes lie there before the submit)
+        else:
+            _ck(self._lib.hast_rs_host_block(self._h, C.byref(p)))
+            C.memmove(p, data, len(data))
+        _ck(self._lib.hast_rs_submit(self._h, len(data), 1 if last else 0))
+
+    def next(self):
+        """(flags, consumed, bases, names, votes[records, 2]) of the oldest submitted block; copies of the feed's pinned buffers"""
+        b = RsBlock()
+        _ck(self._lib.hast_rs_next(self._h, C.byref(b)))
+        n = b.records
+        if not n:
+            return b.flags, b.consumed, b.bases, [], np.zeros((0, 2), dtype=np.uint32)
+        off = np.ctypeslib.as_array(b.name_off, (n + 1,))
+        raw = C.string_at(b.names, b.name_bytes) if b.name_bytes else b""
+        assert int(off[n]) == b.name_bytes
+        names = [raw[int(off[i]):int(off[i + 1])] for i in range(n)]
+        return b.flags, b.consumed, b.bases, names, np.ctypeslib.as_array(b.votes, (n, 2)).copy()
+
+    def take_tail(self) -> bytes:
+        buf = C.create_string_buffer(self.block)
+        n = C.c_size_t()
+        _ck(self._lib.hast_rs_take_tail(self._h, buf, C.byref(n)))
+        return buf.raw[:n.value]
+
+    def close(self):
+        if self._h:
+            self._lib.hast_rs_destroy(self._h)
             self._h = None
 
     def __enter__(self):

@@ -10,14 +10,24 @@
 // the others over xGMI; every batch of reads is cut into one contiguous share per GPU, balanced by bases, classified at the same
 // time and printed in read order -- per-read rows need no reduction, BASELINE config 5's "barcode-free per-read assignment").
 //
+// --ingest device (opt-in; the default, host, is everything described above): the host moves raw file bytes and formats rows, it never
+// looks at a base.  A .gz input is inflated on the GPU (hast_gz_*) straight into the read-stream feed (hast_rs_*, rules: rs_core.h),
+// anything else is read into the feed's pinned block; the feed frames FASTA / FASTQ on the GPU, classifies the reads where they lie
+// and hands back names and votes.  --block-mb N: the feed's block (default 64; HAST_RS_BLOCK=<bytes> for tests).  What the device
+// route does not take runs through the host route with one WARN line and the same stdout: several --devices (the whole run), an
+// input that is not a regular file, a record that does not fit two blocks (that file, from its start).  --stats: two lines on stderr.
+//
 // Requirement (deviation): k-mer lines must be upper-case A/C/G/T of one length K <= 32 -- what jellyfish/meryl
 // dumps are.  The reference would also store other bytes literally (s03:59-65); we stop with exit 3 instead.
 #include <getopt.h>
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <fcntl.h>
+
 #include <algorithm>
 #include <cerrno>
+#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -29,6 +39,7 @@
 
 #include "../../include/hast.h"
 #include "ingest.h"
+#include "rs_host.h"
 
 namespace {
 
@@ -47,7 +58,10 @@ void print_usage() {   // same flags as the reference (s03:316-324); stderr is f
     fputs("classify_read (MI355X) -- per-read haplotype assignment\n"
           "  classify_read --hap HAP0.mer --hap HAP1.mer --read READS [--read ...] [--format fasta|fastq] [--thread N]\n"
           "  reads may be gzip files when the name ends in .gz; --format defaults to fasta\n"
-          "  --device N / --devices A,B,..   GPU(s); with several, every batch of reads is shared out between them\n",
+          "  --device N / --devices A,B,..   GPU(s); with several, every batch of reads is shared out between them\n"
+          "  --ingest host|device            device: reads are inflated and framed on the GPU (one GPU; default host)\n"
+          "  --block-mb N                    block of the device ingest (default 64)\n"
+          "  --stats                         counts and seconds of the read phase on stderr\n",
           stderr);
 }
 
@@ -69,17 +83,52 @@ bool slurp(const std::string &path, std::vector<char> &out) {
     return ok;
 }
 
+// the rows of n reads: names[name_off[i], name_off[i + 1]) and votes[2 i], votes[2 i + 1] -> "name \t haplotypeN|ambiguous \t density"
+void format_rows(std::string &out, const uint8_t *names, const uint32_t *name_off, const uint32_t *votes, size_t n, const int *total_kmers) {
+    char row[96];
+    for (size_t i = 0; i < n; i++) {
+        const double d0 = (double)votes[2 * i] / total_kmers[0], d1 = (double)votes[2 * i + 1] / total_kmers[1];   // s03:215-216
+        // s03:110-133 for two haplotypes: both zero -> ambiguous 0.0; else the larger density, ties to haplotype0
+        if (!(d0 > 0) && !(d1 > 0)) snprintf(row, sizeof(row), "\tambiguous\t0.0\n");
+        else if (d1 > d0) snprintf(row, sizeof(row), "\thaplotype1\t%0.6f\n", d1);
+        else snprintf(row, sizeof(row), "\thaplotype0\t%0.6f\n", d0);
+        out.append(reinterpret_cast<const char *>(names) + name_off[i], name_off[i + 1] - name_off[i]);
+        out += row;
+    }
+}
+
+// What a FASTQ file's end leaves behind its last complete record (fewer than four newlines) as a batch of one read: the header needs
+// its newline, the bases are the next piece, terminated or not (s03:255-260; hast::rs::fq_tail).  No record: an empty batch.  False:
+// the header starts with '>', the format error.  Both ingest routes end a file through this.
+bool tail_batch(const char *tail, size_t n, std::vector<std::string> &names, std::vector<uint8_t> &bases, std::vector<uint64_t> &offsets) {
+    hast::rs::Tail t;
+    if (!hast::rs::fq_tail(reinterpret_cast<const uint8_t *>(tail), n, &t)) return false;
+    names.clear();
+    if (!t.record) return true;
+    names.push_back(t.name);
+    bases.assign(t.seq.begin(), t.seq.end());
+    bases.resize(bases.size() + 16);
+    offsets.assign({0, (uint64_t)t.seq.size()});
+    return true;
+}
+
+double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
 }  // namespace
 
 int main(int argc, char **argv) {
     static struct option long_options[] = {{"hap", required_argument, NULL, 'p'},    {"read", required_argument, NULL, 'r'},
                                            {"format", required_argument, NULL, 'f'}, {"thread", required_argument, NULL, 't'},
                                            {"help", no_argument, NULL, 'h'},         {"device", required_argument, NULL, 1001},
-                                           {"devices", required_argument, NULL, 1002}, {0, 0, 0, 0}};
+                                           {"devices", required_argument, NULL, 1002}, {"ingest", required_argument, NULL, 1003},
+                                           {"block-mb", required_argument, NULL, 1004}, {"stats", no_argument, NULL, 1005},
+                                           {0, 0, 0, 0}};
     std::vector<std::string> haps, read;
     std::string format = "fasta";
     int t_num = 8, device = 0;
     std::vector<int> devices;
+    bool ingest_device = false, stats = false;
+    long block_mb = 64;
     for (;;) {
         int c = getopt_long(argc, argv, "p:r:t:f:h", long_options, NULL);   // s03:324
         if (c < 0) break;
@@ -98,6 +147,15 @@ int main(int argc, char **argv) {
                 q = *end == ',' ? end + 1 : end;
             }
             break;
+        case 1003:
+            if (strcmp(optarg, "host") != 0 && strcmp(optarg, "device") != 0) { print_usage(); return -1; }
+            ingest_device = strcmp(optarg, "device") == 0;
+            break;
+        case 1004:
+            block_mb = atol(optarg);
+            if (block_mb < 1 || block_mb > 1024) { print_usage(); return -1; }
+            break;
+        case 1005: stats = true; break;
         case 'h':
         default: print_usage(); return -1;
         }
@@ -218,6 +276,10 @@ int main(int argc, char **argv) {
     Batch bt[2];                                            // the batch in flight and the one before it (its buffers are reused)
     int cur = 0;
     std::string bg_error;
+    // what --stats prints; the background thread adds to records / kernels / rows, and is joined before they are read
+    uint64_t st_blocks = 0, st_records = 0, st_gz = 0;
+    double st_read = 0, st_upload = 0, st_kernels = 0, st_rows = 0;
+    std::string st_fallback = "none";
     auto wait_bg = [&]() {
         if (bg.joinable()) bg.join();
         if (!bg_error.empty()) die(4, bg_error);
@@ -225,6 +287,7 @@ int main(int argc, char **argv) {
     auto run_batch = [&](Batch &b) {
         if (b.names.empty()) return;
         const size_t n = b.names.size(), G = ctxs.size();
+        const double t0 = now_s();
         std::vector<uint32_t> v(n * 2, 0);
         if (G == 1) {
             if (hast_classify_perread(ctx, b.bases.data(), b.offsets.data(), n, v.data()) != HAST_OK) {
@@ -257,16 +320,14 @@ int main(int argc, char **argv) {
                     return;
                 }
         }
-        char row[96];
-        for (size_t i = 0; i < b.names.size(); i++) {
-            const double d0 = (double)v[2 * i] / total_kmers[0], d1 = (double)v[2 * i + 1] / total_kmers[1];   // s03:215-216
-            // s03:110-133 for two haplotypes: both zero -> ambiguous 0.0; else the larger density, ties to haplotype0
-            if (!(d0 > 0) && !(d1 > 0)) snprintf(row, sizeof(row), "\tambiguous\t0.0\n");
-            else if (d1 > d0) snprintf(row, sizeof(row), "\thaplotype1\t%0.6f\n", d1);
-            else snprintf(row, sizeof(row), "\thaplotype0\t%0.6f\n", d0);
-            out_rows += b.names[i];
-            out_rows += row;
+        const double t1 = now_s();
+        for (size_t i = 0; i < n; i++) {
+            const uint32_t off[2] = {0, (uint32_t)b.names[i].size()};
+            format_rows(out_rows, reinterpret_cast<const uint8_t *>(b.names[i].data()), off, v.data() + 2 * i, 1, total_kmers);
         }
+        st_records += n;
+        st_kernels += t1 - t0;
+        st_rows += now_s() - t1;
     };
     auto classify_batch = [&]() {
         wait_bg();                                          // one batch in flight; its rows are in out_rows now
@@ -324,8 +385,8 @@ int main(int argc, char **argv) {
     };
     const size_t block_bytes = (size_t)std::max(1L, getenv("HAST_READ_BLOCK_BYTES") ? atol(getenv("HAST_READ_BLOCK_BYTES")) : (256L << 20));
     bool output_failed = false;
-    for (const auto &r : read) {
-        fprintf(stderr, "__process read: %s\n", r.c_str());
+    // the host route for one input: its rows into out_rows; 1: the format error (its message is printed)
+    auto host_file = [&](const std::string &r) -> int {
         hast::BlockSource src;
         if (!src.open(r, block_bytes)) die(2, "cannot open " + r);
         std::vector<char> carry;
@@ -333,7 +394,9 @@ int main(int argc, char **argv) {
         out_rows.clear();
         bool seen_header = false;                       // FASTA: lines before the first '>' belong to no record (s03:286-292)
         for (;;) {
+            const double t_read = now_s();
             std::vector<char> blk = src.next();
+            st_read += now_s() - t_read;
             const bool last = blk.empty();
             if (last && !src.error().empty()) die(2, r + ": " + src.error());
             constexpr size_t kPad = hast::BlockSource::kFrontPad;
@@ -366,22 +429,13 @@ int main(int argc, char **argv) {
                 for (size_t i = 0; i < n_rec; i++) recs.push_back({(uint32_t)(4 * i), (uint32_t)(4 * i + 1), (uint32_t)(4 * i + 2)});
                 consumed = n_rec ? (size_t)allnl[4 * n_rec - 1] + 1 : 0;
                 if (last && n_lines % 4 >= 1) {
-                    // tail: header terminated; bases = next piece, terminated or not (s03:260); make the tail a full record
-                    std::string tail(data + consumed, len - consumed);
-                    size_t he = tail.find('\n');
-                    std::string head = tail.substr(0, he), seq;
-                    size_t s0 = he + 1, se = tail.find('\n', s0);
-                    seq = tail.substr(s0, se == std::string::npos ? std::string::npos : se - s0);
-                    // handled after the block's records, as a one-record batch below
+                    // tail: header terminated; bases = next piece, terminated or not (s03:260); the tail becomes a full record,
+                    // handled after the block's records, as a one-record batch
                     for (const RecSpan &x : recs)
                         if (data[line_start(x.head)] == '>') { fprintf(stderr, "fasta detected . ERROR . please use \"--format fasta\". exit ... \n"); return 1; }
                     build_batch(data);
                     classify_batch();
-                    if (!head.empty() && head[0] == '>') { fprintf(stderr, "fasta detected . ERROR . please use \"--format fasta\". exit ... \n"); return 1; }
-                    names.assign(1, head.empty() ? head : head.substr(1));
-                    bases.assign(seq.begin(), seq.end());
-                    bases.resize(bases.size() + 16);
-                    offsets.assign({0, (uint64_t)seq.size()});
+                    if (!tail_batch(data + consumed, len - consumed, names, bases, offsets)) { fprintf(stderr, "fasta detected . ERROR . please use \"--format fasta\". exit ... \n"); return 1; }
                     classify_batch();
                     break;
                 }
@@ -421,10 +475,158 @@ int main(int argc, char **argv) {
             carry.swap(keep);
             src.recycle(std::move(blk));
         }
+        return 0;
+    };
+    // ---- --ingest device: one feed on the context's GPU (hast_rs_*) ---------------------------------------------------------
+    hast_rs *feed = nullptr;
+    size_t rs_block = (size_t)block_mb << 20;
+    if (getenv("HAST_RS_BLOCK")) rs_block = (size_t)std::max(64L, atol(getenv("HAST_RS_BLOCK")));
+    if (ingest_device && ctxs.size() > 1) {
+        fprintf(stderr, "classify_read: WARN: --ingest device takes one GPU: host ingest for this run (fallback=several_devices)\n");
+        st_fallback = "several_devices";
+        ingest_device = false;
+    }
+    if (ingest_device && hast_rs_create(ctx, fastq ? HAST_RS_FASTQ : HAST_RS_FASTA, rs_block, &feed) != HAST_OK) die(4, "cannot create the device ingest");
+    std::vector<uint8_t> rs_tail;
+    // the device route for one input: its rows into out_rows; 1: the format error (its message is printed), 2: a record too long
+    auto device_file = [&](const std::string &r) -> int {
+        const size_t n = r.size();
+        hast_gz *z = nullptr;
+        if (n > 3 && r.compare(n - 3, 3, ".gz") == 0 && hast_gz_open(ctx, r.c_str(), &z) != HAST_OK) z = nullptr;   // (BGZF, not gzip, unreadable: BlockSource's words)
+        int fd = -1;
+        hast::BlockSource src;
+        const bool plain = !(n > 3 && r.compare(n - 3, 3, ".gz") == 0);
+        if (z) ++st_gz;
+        else if (plain) {
+            if ((fd = open(r.c_str(), O_RDONLY)) < 0) die(2, "cannot open " + r);
+        } else if (!src.open(r, rs_block)) die(2, "cannot open " + r);
+        out_rows.clear();
+        int pending = 0, verdict = 0;
+        uint64_t framed_records = 0;                             // counted once the file is through: a refused file is read again
+        // frame and classify the oldest submitted block, format its rows
+        auto step = [&]() {
+            hast_rs_block b;
+            const double t0 = now_s();
+            if (hast_rs_next(feed, &b) != HAST_OK) die(4, "framing and classifying a block");
+            const double t1 = now_s();
+            --pending;
+            ++st_blocks;
+            st_kernels += t1 - t0;
+            if (b.flags & HAST_RS_FORMAT_ERROR) verdict = 1;
+            else if (b.flags & HAST_RS_RECORD_TOO_LONG) verdict = 2;
+            if (verdict) return;
+            format_rows(out_rows, b.names, b.name_off, b.votes, (size_t)b.records, total_kmers);
+            framed_records += b.records;
+            st_rows += now_s() - t1;
+        };
+        auto submit = [&](size_t n_bytes, bool last) {           // ... and keep one block ahead of the framer
+            const double t0 = now_s();
+            if (hast_rs_submit(feed, n_bytes, last) != HAST_OK) die(4, "submitting a block");
+            st_upload += now_s() - t0;
+            ++pending;
+            if (pending == 2) step();
+        };
+        auto host_block = [&]() {
+            uint8_t *h = nullptr;
+            const double t0 = now_s();
+            if (hast_rs_host_block(feed, &h) != HAST_OK) die(4, "the device ingest's staging block");
+            st_upload += now_s() - t0;
+            return h;
+        };
+        bool ended = false;                                      // the file's last block has been submitted
+        std::vector<char> blk;
+        size_t blk_at = 0;
+        while (!verdict && !ended) {
+            size_t got = 0;
+            const double t0 = now_s();
+            if (z) {
+                uint8_t *d = nullptr;
+                hast_stream fill = nullptr;
+                if (hast_rs_device_block(feed, &d, &fill) != HAST_OK) die(4, "the device ingest's block");
+                if (hast_gz_read_device(z, d, rs_block, &got, fill) != HAST_OK) die(2, r + ": " + hast_last_error());
+            } else if (plain) {
+                uint8_t *h = host_block();
+                while (got < rs_block) {
+                    const ssize_t k = ::read(fd, h + got, rs_block - got);
+                    if (k < 0 && errno == EINTR) continue;
+                    if (k < 0) die(2, r + ": " + strerror(errno));
+                    if (k == 0) break;
+                    got += (size_t)k;
+                }
+            } else {
+                constexpr size_t kPad = hast::BlockSource::kFrontPad;
+                if (blk_at >= blk.size()) {
+                    if (!blk.empty()) src.recycle(std::move(blk));
+                    blk = src.next();
+                    blk_at = kPad;
+                    if (blk.empty() && !src.error().empty()) die(2, r + ": " + src.error());
+                }
+                uint8_t *h = host_block();
+                got = blk.empty() ? 0 : std::min(rs_block, blk.size() - blk_at);
+                if (got) memcpy(h, blk.data() + blk_at, got);
+                blk_at += got;
+            }
+            st_read += now_s() - t0;
+            ended = got == 0;                                    // (only a read that returns nothing ends the stream, include/hast.h)
+            submit(got, ended);
+        }
+        if (!ended) {                                            // given up: the feed wants the file's last block all the same
+            if (!z) (void)host_block();
+            else {
+                uint8_t *d = nullptr;
+                if (hast_rs_device_block(feed, &d, nullptr) != HAST_OK) die(4, "the device ingest's block");
+            }
+            submit(0, true);
+        }
+        while (pending) step();                                  // (before the decoder goes: its kernels wrote the blocks still waiting)
+        if (z) hast_gz_close(z);
+        if (fd >= 0) close(fd);
+        if (!verdict) st_records += framed_records;
+        if (!verdict && fastq) {
+            size_t n_tail = 0;
+            rs_tail.resize(rs_block);
+            if (hast_rs_take_tail(feed, rs_tail.data(), &n_tail) != HAST_OK) die(4, "the end of the input");
+            Batch tb;
+            if (!tail_batch(reinterpret_cast<const char *>(rs_tail.data()), n_tail, tb.names, tb.bases, tb.offsets)) verdict = 1;
+            else {
+                run_batch(tb);
+                if (!bg_error.empty()) die(4, bg_error);
+            }
+        }
+        if (verdict == 1) fprintf(stderr, fastq ? "fasta detected . ERROR . please use \"--format fasta\". exit ... \n" : "fasta detected . ERROR . please use \"--format fastq\". exit ... \n");
+        return verdict;
+    };
+    const double t_phase = now_s();
+    for (const auto &r : read) {
+        fprintf(stderr, "__process read: %s\n", r.c_str());
+        bool on_device = false;
+        if (feed) {
+            struct stat sb;
+            if (stat(r.c_str(), &sb) != 0 || !S_ISREG(sb.st_mode)) {
+                fprintf(stderr, "classify_read: WARN: %s is not a regular file: host ingest for this input (fallback=not_a_regular_file)\n", r.c_str());
+                st_fallback = "not_a_regular_file";
+            } else {
+                const int v = device_file(r);
+                if (v == 1) return 1;
+                on_device = v == 0;
+                if (v == 2) {
+                    fprintf(stderr, "classify_read: WARN: a record of %s does not fit two blocks of %zu bytes: host ingest for this input (fallback=record_too_long)\n",
+                            r.c_str(), rs_block);
+                    st_fallback = "record_too_long";
+                }
+            }
+        }
+        if (!on_device && host_file(r)) return 1;
         wait_bg();
         if (fwrite(out_rows.data(), 1, out_rows.size(), stdout) != out_rows.size()) output_failed = true;
         fprintf(stderr, "__process read done__\n");
     }
+    if (stats) {
+        fprintf(stderr, "[stats] ingest %s: blocks_framed=%llu records=%llu gz_on_device=%llu fallback=%s\n", feed ? "device" : "host", (unsigned long long)st_blocks,
+                (unsigned long long)st_records, (unsigned long long)st_gz, st_fallback.c_str());
+        fprintf(stderr, "[stats] seconds: read=%.3f upload=%.3f kernels=%.3f rows=%.3f read_phase=%.3f\n", st_read, st_upload, st_kernels, st_rows, now_s() - t_phase);
+    }
+    if (feed) hast_rs_destroy(feed);
     // (mkoutput_by_fabulous2.0.sh redirects stdout into a file and goes on: a full disk or a closed pipe must not pass as exit 0)
     if (fflush(stdout) != 0) output_failed = true;
     if (output_failed) {

@@ -1620,6 +1620,16 @@ hast_status commit_framed(hast_ctx *c, const uint32_t *d_votes, const uint32_t *
     HAST_HIP_TRY(launch_commit_votes(d_votes, d_ids, c->d_counts, nullptr, n_reads, hs));
     return HAST_OK;
 }
+// stage 03 (rs_api.cpp): per-window validity, any length, a row of votes per read; the reads lie in the raw view (FASTQ) or in the
+// compacted base buffer (FASTA).  framed_err: what k_build_segments raised for the calls on hs so far (waits for hs).
+hast_status classify_framed_perread(hast_ctx *c, const uint8_t *d_buf, size_t buf_bytes, const uint64_t *d_off, const uint32_t *d_len, uint32_t *d_votes,
+                                    size_t n_reads, hipStream_t hs) {
+    if (hast_status st = need_table(c, 0)) return st;
+    if (n_reads == 0) return HAST_OK;
+    return classify_segmented(c, d_buf, buf_bytes ? buf_bytes : 1, d_off, d_len, 0, n_reads, 1, nullptr, d_votes, hs);
+}
+hast_status framed_err(hast_ctx *c, hipStream_t hs) { return check_classify_err(c, hs); }
+int ctx_device_of(const hast_ctx *c) { return c->device; }
 hipStream_t ctx_stream_of(hast_ctx *c) { return c->stream; }
 size_t ctx_n_barcodes(const hast_ctx *c) { return c->n_barcodes; }
 }  // namespace hast

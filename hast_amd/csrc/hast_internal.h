@@ -19,6 +19,12 @@ hast_status classify_framed(hast_ctx *c, const uint8_t *d_buf, size_t buf_bytes,
                             uint32_t *d_votes, size_t n_reads, hipStream_t hs);
 // ... and the per-barcode bookkeeping once the host has named the barcodes
 hast_status commit_framed(hast_ctx *c, const uint32_t *d_votes, const uint32_t *d_ids, size_t n_reads, hipStream_t hs);
+// ... and stage 03's per-read votes (rs_api.cpp): per-window validity, reads of any length; framed_err waits for hs and reports rows
+// that the segment builder dropped
+hast_status classify_framed_perread(hast_ctx *c, const uint8_t *d_buf, size_t buf_bytes, const uint64_t *d_off, const uint32_t *d_len, uint32_t *d_votes,
+                                    size_t n_reads, hipStream_t hs);
+hast_status framed_err(hast_ctx *c, hipStream_t hs);
+int ctx_device_of(const hast_ctx *c);
 hipStream_t ctx_stream_of(hast_ctx *c);
 size_t ctx_n_barcodes(const hast_ctx *c);
 int kc_device_of(const hast_kc *c);                                                                  // the count table's device (sq_api.cpp)

@@ -1,0 +1,61 @@
+// rs_device.h -- what rs_kernels.hip and rs_api.cpp share: a view of raw FASTA / FASTQ in HBM -> the reads of the per-read classifier
+// (starts + lengths), their names back to back, and what the view consumes.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "nl_index.h"
+#include "rs_core.h"
+
+namespace hast {
+
+struct RsState {               // device memory, copied to the host after the framing
+    uint64_t consumed, records, bases, name_bytes;
+    uint32_t flags;
+    uint32_t n_nl;             // newlines of the view
+    uint32_t n_hdr, seq_total; // FASTA: header lines; sequence bytes of all sequence lines
+};
+
+constexpr uint32_t kRsTile = 256;            // lines / records per tile of the prefix sums
+constexpr uint32_t kRsCopyTile = 4096;       // output bytes a workgroup of k_rs_copy owns at a time: 256 lanes x 16 B
+
+// the scratch a view of up to max_view bytes needs in the worst case: all newlines, or FASTA records of two bytes (">\n")
+struct RsScratchPlan {
+    size_t tile_cnt, nl, line_tile_h, line_tile_s, line_dst, hdr_line, name_pos, name_len, name_tile, name_off, off, len, votes, state, total;
+    size_t max_rec;
+};
+inline RsScratchPlan rs_scratch_plan(int format, size_t max_view) {
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const bool fasta = format == RS_FASTA;
+    const size_t max_lines = max_view + 1, line_tiles = max_lines / kRsTile + 2;
+    const size_t max_rec = (fasta ? max_view / 2 : max_view / 4) + 1, rec_tiles = max_rec / kRsTile + 2;
+    RsScratchPlan p;
+    size_t at = 0;
+    p.tile_cnt = at;    at += up(nl_tiles(max_view) * 4);
+    p.nl = at;          at += up(nl_index_words(max_view) * 4);
+    p.line_tile_h = at; at += fasta ? up(line_tiles * 4) : 0;
+    p.line_tile_s = at; at += fasta ? up(line_tiles * 4) : 0;
+    p.line_dst = at;    at += fasta ? up((max_lines + 1) * 4) : 0;
+    p.hdr_line = at;    at += fasta ? up(max_rec * 4) : 0;
+    p.name_pos = at;    at += up(max_rec * 4);
+    p.name_len = at;    at += up(max_rec * 4);
+    p.name_tile = at;   at += up(rec_tiles * 4);
+    p.name_off = at;    at += up((max_rec + 1) * 4);
+    p.off = at;         at += up(max_rec * 8);
+    p.len = at;         at += up(max_rec * 4);
+    p.votes = at;       at += up(max_rec * 8);
+    p.state = at;       at += up(sizeof(RsState));
+    p.total = at;
+    p.max_rec = max_rec;
+    return p;
+}
+
+// Frames the view d_base[origin, origin + n) (d_base 16-byte aligned, n < 2^32 - 8192).  When the stream has run: the state block
+// holds the result; off[r] / len[r] are the reads -- FASTQ: inside d_base, where they lie; FASTA: inside d_seq (room for n bytes,
+// 16-byte aligned), compacted back to back -- and d_names (room for n bytes) / name_off[records + 1] the names.  Nothing outside the
+// view is read; nothing is written at or behind d_seq + bases or d_names + name_bytes.
+hipError_t launch_rs_frame(int format, const uint8_t *d_base, size_t origin, size_t n, bool last, bool seen_header, uint8_t *d_seq, uint8_t *d_names,
+                           uint8_t *d_scratch, const RsScratchPlan &plan, hipStream_t s);
+
+}  // namespace hast

@@ -1,0 +1,279 @@
+// rs_kernels.hip -- gfx950 device code: a view of raw FASTA or four-line FASTQ in HBM becomes the reads of stage 03's per-read
+// classifier (`classify_read --ingest device`).  The rules are rs_core.h's; the steps, all on one stream:
+//   k_rs_count / k_rs_scan / k_rs_index   the newline index (nl_index.h)
+//   k_rs_lines       FASTA, a lane per line: its class and length; per tile of 256 lines the headers and the sequence bytes
+//   k_rs_scan_lines  FASTA: exclusive scans of the two tile sums
+//   k_rs_line_dst    FASTA, a lane per line: line_dst[j] = sequence bytes in front of line j, hdr_line[r] = the line of header r
+//   k_rs_records     a lane per record: name extent, start and length of the read, the format error; consumed and the counts
+//   k_rs_scan_names  exclusive scan of the name lengths per tile of 256 records
+//   k_rs_names       names gathered back to back: a wave copies its 64 records one after the other, 64 bytes a step
+//   k_rs_copy        FASTA: the sequence lines compacted into one base buffer, the work split by OUTPUT bytes
+// FASTQ reads are classified where they lie in the view; a FASTA read is spread over lines, and a k-mer straddles the line breaks,
+// so its lines are moved together.  Lines range from 60 columns to one line of 10^8 bases: k_rs_copy gives every workgroup a fixed
+// span of the destination and lets it find, by binary search in line_dst, the lines that reach into it.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "nl_index.h"
+#include "rs_device.h"
+
+namespace hast {
+
+__global__ void __launch_bounds__(256) k_rs_count(const uint8_t *base, uint64_t lo, uint64_t hi, uint32_t *tile_cnt) {
+    const uint32_t c = nl_tile_count(base, blockIdx.x, lo, hi);
+    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = c;
+}
+
+__global__ void __launch_bounds__(1024) k_rs_scan(uint32_t *tile_cnt, uint32_t n, RsState *st) {
+    __shared__ uint32_t s_part[1024];
+    const uint32_t n_nl = block_exclusive_scan_1024(tile_cnt, n, s_part);
+    if (threadIdx.x == 0) {
+        st->consumed = st->records = st->bases = st->name_bytes = 0;
+        st->flags = 0;
+        st->n_nl = n_nl;
+        st->n_hdr = st->seq_total = 0;
+    }
+}
+
+// nl[j] = offset of the j-th newline from the view's first byte (base + lo)
+__global__ void __launch_bounds__(256) k_rs_index(const uint8_t *base, uint64_t lo, uint64_t hi, const uint32_t *tile_base, uint32_t *nl) {
+    nl_tile_index(base, blockIdx.x, lo, hi, lo, tile_base, nl);
+}
+
+__global__ void __launch_bounds__(kRsTile) k_rs_lines(const uint8_t *in, RsState *st, const uint32_t *nl, uint32_t *tile_h, uint32_t *tile_s) {
+    __shared__ uint32_t s_h[4], s_s[4];
+    const uint32_t n_lines = st->n_nl, n_tiles = (n_lines + kRsTile - 1) / kRsTile;
+    bool bad = false;
+    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint32_t j = tile * kRsTile + threadIdx.x;
+        uint32_t h = 0, s = 0;
+        if (j < n_lines) {
+            const uint32_t lo = rs::line_lo(nl, j), hi = nl[j], cls = rs::fa_class(in, lo, hi);
+            h = cls == rs::kHeader;
+            s = rs::fa_seq_len(cls, lo, hi);
+            bad |= cls == rs::kBad;
+        }
+        const uint32_t ch = wave_sum(h), cs = wave_sum(s);
+        __syncthreads();                                         // (the sums of the tile before have been read)
+        if ((threadIdx.x & 63) == 0) {
+            s_h[threadIdx.x >> 6] = ch;
+            s_s[threadIdx.x >> 6] = cs;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            tile_h[tile] = s_h[0] + s_h[1] + s_h[2] + s_h[3];
+            tile_s[tile] = s_s[0] + s_s[1] + s_s[2] + s_s[3];
+        }
+    }
+    if (bad) atomicOr(&st->flags, RS_FORMAT_ERROR);
+}
+
+__global__ void __launch_bounds__(1024) k_rs_scan_lines(uint32_t *tile_h, uint32_t *tile_s, RsState *st) {
+    __shared__ uint32_t s_part[1024];
+    const uint32_t n_tiles = (st->n_nl + kRsTile - 1) / kRsTile;
+    const uint32_t m = block_exclusive_scan_1024(tile_h, n_tiles, s_part);
+    __syncthreads();                                             // (s_part is written again)
+    const uint32_t total = block_exclusive_scan_1024(tile_s, n_tiles, s_part);
+    if (threadIdx.x == 0) {
+        st->n_hdr = m;
+        st->seq_total = total;
+    }
+}
+
+__global__ void __launch_bounds__(kRsTile) k_rs_line_dst(const uint8_t *in, const RsState *st, const uint32_t *nl, const uint32_t *tile_h, const uint32_t *tile_s,
+                                                         uint32_t *line_dst, uint32_t *hdr_line) {
+    __shared__ uint32_t s_wh[4], s_ws[4];
+    const uint32_t n_lines = st->n_nl, n_tiles = (n_lines + kRsTile - 1) / kRsTile;
+    if (n_lines == 0 && blockIdx.x == 0 && threadIdx.x == 0) line_dst[0] = 0;
+    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint32_t j = tile * kRsTile + threadIdx.x;
+        uint32_t h = 0, s = 0;
+        if (j < n_lines) {
+            const uint32_t lo = rs::line_lo(nl, j), hi = nl[j], cls = rs::fa_class(in, lo, hi);
+            h = cls == rs::kHeader;
+            s = rs::fa_seq_len(cls, lo, hi);
+        }
+        const uint32_t eh = tile_h[tile] + block_exclusive_sum_256(h, s_wh);
+        const uint32_t es = tile_s[tile] + block_exclusive_sum_256(s, s_ws);
+        if (j < n_lines) {
+            line_dst[j] = es;
+            if (h) hdr_line[eh] = j;
+            if (j == n_lines - 1) line_dst[n_lines] = es + s;
+        }
+        __syncthreads();                                         // (s_wh, s_ws are written again)
+    }
+}
+
+__global__ void __launch_bounds__(kRsTile) k_rs_records(int format, const uint8_t *in, uint64_t n, uint64_t origin, int last, int seen_header, RsState *st,
+                                                        const uint32_t *nl, const uint32_t *line_dst, const uint32_t *hdr_line, uint32_t *name_pos,
+                                                        uint32_t *name_len, uint32_t *name_tile, uint64_t *r_off, uint32_t *r_len) {
+    __shared__ uint32_t s_n[4], s_b[4];
+    const uint32_t n_nl = st->n_nl, m = st->n_hdr, total = st->seq_total;
+    const bool fastq = format == RS_FASTQ;
+    const uint32_t n_rec = fastq ? rs::fq_records(n_nl) : rs::fa_records(m, last != 0);
+    const uint32_t n_tiles = (n_rec + kRsTile - 1) / kRsTile;
+    const uint32_t junk = !fastq && m ? line_dst[hdr_line[0]] : 0;      // sequence bytes in front of the view's first header: no record's
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        st->records = n_rec;
+        st->consumed = fastq ? rs::fq_consumed(nl, n_nl) : rs::fa_consumed(nl, n_nl, n, m, m ? hdr_line[m - 1] : 0, last != 0, seen_header != 0);
+    }
+    unsigned long long bases = 0;                                // lane 0 of the workgroup: over all its tiles
+    bool bad = false;
+    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint32_t r = tile * kRsTile + threadIdx.x;
+        uint32_t nlen = 0, len = 0;
+        if (r < n_rec) {
+            const uint32_t hl = fastq ? 4 * r : hdr_line[r];
+            const uint32_t lo = rs::line_lo(nl, hl), hi = nl[hl];
+            uint32_t npos;
+            rs::name_of(lo, hi, &npos, &nlen);
+            uint64_t off;
+            if (fastq) {
+                bad |= rs::fq_bad_header(in, lo, hi);
+                off = origin + hi + 1;
+                len = nl[hl + 1] - (hi + 1);
+            } else {
+                const uint32_t a = line_dst[hl], b = r + 1 < m ? line_dst[hdr_line[r + 1]] : total;
+                off = a - junk;
+                len = b - a;
+            }
+            name_pos[r] = npos;
+            name_len[r] = nlen;
+            r_off[r] = off;
+            r_len[r] = len;
+        }
+        const uint32_t cn = wave_sum(nlen), cb = wave_sum(len);
+        __syncthreads();                                         // (the sums of the tile before have been read)
+        if ((threadIdx.x & 63) == 0) {
+            s_n[threadIdx.x >> 6] = cn;
+            s_b[threadIdx.x >> 6] = cb;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            name_tile[tile] = s_n[0] + s_n[1] + s_n[2] + s_n[3];
+            bases += (unsigned long long)s_b[0] + s_b[1] + s_b[2] + s_b[3];
+        }
+    }
+    if (threadIdx.x == 0 && bases) atomicAdd(reinterpret_cast<unsigned long long *>(&st->bases), bases);
+    if (bad) atomicOr(&st->flags, RS_FORMAT_ERROR);
+}
+
+__global__ void __launch_bounds__(1024) k_rs_scan_names(uint32_t *name_tile, RsState *st) {
+    __shared__ uint32_t s_part[1024];
+    const uint32_t n_rec = (uint32_t)st->records;
+    const uint32_t total = block_exclusive_scan_1024(name_tile, (n_rec + kRsTile - 1) / kRsTile, s_part);
+    if (threadIdx.x == 0) st->name_bytes = total;
+}
+
+__global__ void __launch_bounds__(kRsTile) k_rs_names(const uint8_t *in, const RsState *st, const uint32_t *name_pos, const uint32_t *name_len,
+                                                      const uint32_t *name_tile, uint32_t *name_off, uint8_t *names) {
+    __shared__ uint32_t s_src[kRsTile], s_dst[kRsTile], s_n[kRsTile];
+    __shared__ uint32_t s_wave[4];
+    const uint32_t n_rec = (uint32_t)st->records, n_tiles = (n_rec + kRsTile - 1) / kRsTile;
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (blockIdx.x == 0 && threadIdx.x == 0) name_off[n_rec] = (uint32_t)st->name_bytes;
+    if (st->flags) return;                                       // the format error: nobody reads the names
+    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint32_t r = tile * kRsTile + threadIdx.x;
+        const uint32_t len = r < n_rec ? name_len[r] : 0;
+        const uint32_t dst = name_tile[tile] + block_exclusive_sum_256(len, s_wave);
+        if (r < n_rec) name_off[r] = dst;
+        s_src[threadIdx.x] = r < n_rec ? name_pos[r] : 0;
+        s_dst[threadIdx.x] = dst;
+        s_n[threadIdx.x] = len;
+        __syncthreads();
+        const uint32_t in_wave = n_rec - tile * kRsTile > wave * 64 ? (n_rec - tile * kRsTile - wave * 64 < 64 ? n_rec - tile * kRsTile - wave * 64 : 64) : 0;
+        for (uint32_t i = 0; i < in_wave; ++i) {
+            const uint32_t j = wave * 64 + i, k = s_n[j];
+            const uint8_t *src = in + s_src[j];
+            uint8_t *d = names + s_dst[j];
+            for (uint32_t b = lane; b < k; b += 64) d[b] = src[b];
+        }
+        __syncthreads();
+    }
+}
+
+// the smallest j in [lo, hi] with line_dst[j + 1] > v; the caller knows that line hi is one
+__device__ __forceinline__ uint32_t rs_first_line_past(const uint32_t *line_dst, uint32_t lo, uint32_t hi, uint32_t v) {
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (line_dst[mid + 1] > v) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
+}
+
+// out[0, bases) = the sequence lines of the complete records, back to back.  Byte p of the output is byte p + junk of the sequence
+// bytes of ALL lines in view order (line_dst counts those): a workgroup takes kRsCopyTile output bytes at a time, finds the first and
+// the last line that reach into them, and every lane moves 16 bytes: it looks its first line up between those two and walks on from
+// there -- 16 bytes at once where they come from one line (out + p is 16-byte aligned, the source is read as it lies), byte by byte
+// across line ends and at the end of the output.
+__global__ void __launch_bounds__(256) k_rs_copy(const uint8_t *in, const RsState *st, const uint32_t *nl, const uint32_t *line_dst, const uint32_t *hdr_line,
+                                                 uint8_t *out) {
+    const uint32_t m = st->n_hdr, bases = (uint32_t)st->bases, n_lines = st->n_nl;
+    if (!m || !bases || st->flags) return;
+    const uint32_t h0 = hdr_line[0], junk = line_dst[h0];
+    const uint32_t n_tiles = (bases + kRsCopyTile - 1) / kRsCopyTile;
+    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint32_t t0 = tile * kRsCopyTile, t1 = bases - t0 < kRsCopyTile ? bases : t0 + kRsCopyTile;
+        uint32_t p = t0 + threadIdx.x * 16;
+        if (p >= t1) continue;
+        const uint32_t e = t1 - p < 16 ? t1 : p + 16;
+        const uint32_t j0 = rs_first_line_past(line_dst, h0, n_lines - 1, t0 + junk);
+        const uint32_t j1 = rs_first_line_past(line_dst, j0, n_lines - 1, t1 - 1 + junk);
+        uint32_t j = rs_first_line_past(line_dst, j0, j1, p + junk);
+        while (p < e) {
+            const uint32_t a = line_dst[j], b = line_dst[j + 1];
+            if (b <= p + junk) {                                 // a header, an empty line: nothing of it is output
+                ++j;
+                continue;
+            }
+            const uint32_t upto = b - junk < e ? b - junk : e, k = upto - p;
+            const uint8_t *src = in + rs::line_lo(nl, j) + (p + junk - a);
+            if (k == 16) {
+                uint4 v;
+                __builtin_memcpy(&v, src, 16);
+                *reinterpret_cast<uint4 *>(out + p) = v;
+            } else {
+                for (uint32_t i = 0; i < k; ++i) out[p + i] = src[i];
+            }
+            p = upto;
+            ++j;
+        }
+    }
+}
+
+hipError_t launch_rs_frame(int format, const uint8_t *d_base, size_t origin, size_t n, bool last, bool seen_header, uint8_t *d_seq, uint8_t *d_names,
+                           uint8_t *d_scratch, const RsScratchPlan &p, hipStream_t s) {
+    const uint64_t lo = origin & 15, hi = lo + n;                // the index's tiles start at the 16-byte boundary in front of the view
+    const uint8_t *in = d_base + origin, *base16 = in - lo;
+    const uint32_t n_tiles = (uint32_t)((hi + kNlTile - 1) / kNlTile), grid = n_tiles ? n_tiles : 1;
+    auto words = [&](size_t at) { return reinterpret_cast<uint32_t *>(d_scratch + at); };
+    uint32_t *tile_cnt = words(p.tile_cnt), *nl = words(p.nl), *tile_h = words(p.line_tile_h), *tile_s = words(p.line_tile_s), *line_dst = words(p.line_dst);
+    uint32_t *hdr_line = words(p.hdr_line), *name_pos = words(p.name_pos), *name_len = words(p.name_len), *name_tile = words(p.name_tile);
+    uint32_t *name_off = words(p.name_off), *r_len = words(p.len);
+    uint64_t *r_off = reinterpret_cast<uint64_t *>(d_scratch + p.off);
+    RsState *st = reinterpret_cast<RsState *>(d_scratch + p.state);
+    auto capped = [](size_t items, uint32_t per) {
+        const size_t t = (items + per - 1) / per;
+        return (uint32_t)(t < 1 ? 1 : t < 2048 ? t : 2048);
+    };
+    const bool fasta = format == RS_FASTA;
+    const uint32_t line_grid = capped(n, kRsTile), rec_grid = capped(fasta ? n / 2 + 1 : n / 4 + 1, kRsTile), copy_grid = capped(n, kRsCopyTile);
+    hipLaunchKernelGGL(k_rs_count, dim3(grid), dim3(256), 0, s, base16, lo, hi, tile_cnt);
+    hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(1024), 0, s, tile_cnt, grid, st);
+    hipLaunchKernelGGL(k_rs_index, dim3(grid), dim3(256), 0, s, base16, lo, hi, tile_cnt, nl);
+    if (fasta) {
+        hipLaunchKernelGGL(k_rs_lines, dim3(line_grid), dim3(kRsTile), 0, s, in, st, nl, tile_h, tile_s);
+        hipLaunchKernelGGL(k_rs_scan_lines, dim3(1), dim3(1024), 0, s, tile_h, tile_s, st);
+        hipLaunchKernelGGL(k_rs_line_dst, dim3(line_grid), dim3(kRsTile), 0, s, in, st, nl, tile_h, tile_s, line_dst, hdr_line);
+    }
+    hipLaunchKernelGGL(k_rs_records, dim3(rec_grid), dim3(kRsTile), 0, s, format, in, (uint64_t)n, (uint64_t)origin, (int)last, (int)seen_header, st, nl, line_dst,
+                       hdr_line, name_pos, name_len, name_tile, r_off, r_len);
+    hipLaunchKernelGGL(k_rs_scan_names, dim3(1), dim3(1024), 0, s, name_tile, st);
+    hipLaunchKernelGGL(k_rs_names, dim3(rec_grid), dim3(kRsTile), 0, s, in, st, name_pos, name_len, name_tile, name_off, d_names);
+    if (fasta) hipLaunchKernelGGL(k_rs_copy, dim3(copy_grid), dim3(256), 0, s, in, st, nl, line_dst, hdr_line, d_seq);
+    return hipGetLastError();
+}
+
+}  // namespace hast

@@ -720,6 +720,53 @@ hast_status hast_sq_feed_next(hast_sq_feed *, int parent, hast_sq_result *res);
 hast_status hast_sq_feed_take_tail(hast_sq_feed *, uint8_t *dst, size_t *n_bytes);
 void        hast_sq_feed_destroy(hast_sq_feed *);
 
+/* ---- stage 03 ingest on the device: raw FASTA / four-line FASTQ in HBM -> per-read votes (`classify_read --ingest device`) ------
+ * The "read stream" feed frames the reads of the per-read classifier on the GPU and classifies them where they lie
+ * (hast_classify_perread's semantics: per-window validity, reads of any length).  The rules are the reference reader's
+ * (03.mkoutput_by_fabulous2.0/src_main/classify.cpp:248-302; hast_amd/csrc/rs_core.h restates them, rs_host.h is the model):
+ *   FASTQ  record i = lines 4i .. 4i+3; name = the header line minus its first byte; sequence = line 4i+1 as it lies; a non-empty
+ *          header that starts with '>' is the format error; what a file's end leaves (fewer than four newlines) is the caller's
+ *          (hast_rs_take_tail).
+ *   FASTA  only newline-terminated lines count; empty lines are skipped; '>' starts a record, a line that starts with '@' or '+' is
+ *          the format error, any other line is appended to the open record (to none before the file's first header); the reads are
+ *          compacted into one base buffer on the device, because a k-mer straddles the line breaks.
+ * One feed per context: two view buffers on the device, two pinned staging blocks, pinned result buffers; the upload of block n+1
+ * (a stream of the feed's own) overlaps the framing and classification of block n (the context's stream).
+ *   hast_rs_create        block_bytes from 64 to 2^30; device scratch for the worst view of 2 x block_bytes (all newlines, FASTA
+ *                         records of two bytes: about 30 bytes per byte of a view), so no input has "too many records".
+ *   hast_rs_host_block    pinned memory for the next up to block_bytes raw bytes (waits until it is free), uploaded by _submit
+ *   hast_rs_device_block  where the caller's kernels write them instead, on the stream *fill (the context's; hast_gz_read_device)
+ *   hast_rs_submit        n_bytes of the block just handed out are valid; last != 0: the file ends with them (n_bytes may then be
+ *                         0).  At most two blocks are submitted and not yet taken by _next.
+ *   hast_rs_next          frames [what the block before left | the oldest submitted block], classifies the complete records and
+ *                         carries [consumed, n) to the front of the next block.  Returns when *out is valid: votes[2 r], votes[2 r + 1]
+ *                         = the hits of read r against haplotype 0 / 1, names[name_off[r] .. name_off[r + 1]) its name; the pointers
+ *                         are the feed's pinned buffers, valid until the next hast_rs_next.  flags != 0: nothing was classified and
+ *                         the file is given up (records = 0) -- HAST_RS_FORMAT_ERROR as above, HAST_RS_RECORD_TOO_LONG when more
+ *                         than block_bytes would have to be carried.  The file's other blocks, up to its `last` one, come back with
+ *                         the same flags, unframed: a caller that stops reading submits an empty `last` block and takes it.
+ *                         After a `last` block the next one starts a new file.
+ *   hast_rs_take_tail     FASTQ, after the `last` block: the bytes behind the last complete record to dst (block_bytes of room). */
+typedef struct hast_rs hast_rs;
+typedef struct {
+    uint64_t consumed, records, bases, name_bytes;
+    uint32_t flags;
+    const uint32_t *votes;     /* [records][2], pinned: hits0, hits1 */
+    const uint32_t *name_off;  /* [records + 1] */
+    const uint8_t *names;
+} hast_rs_block;
+#define HAST_RS_FASTA 0
+#define HAST_RS_FASTQ 1
+#define HAST_RS_FORMAT_ERROR    1u   /* '>' header in fastq / '@','+' line in fasta: nothing classified */
+#define HAST_RS_RECORD_TOO_LONG 4u
+hast_status hast_rs_create(hast_ctx *, int format, size_t block_bytes, hast_rs **out);
+hast_status hast_rs_host_block(hast_rs *, uint8_t **h_buf);
+hast_status hast_rs_device_block(hast_rs *, uint8_t **d_buf, hast_stream *fill);
+hast_status hast_rs_submit(hast_rs *, size_t n_bytes, int last);
+hast_status hast_rs_next(hast_rs *, hast_rs_block *out);
+hast_status hast_rs_take_tail(hast_rs *, uint8_t *dst, size_t *n_bytes);
+void        hast_rs_destroy(hast_rs *);
+
 /* ---- stage 02: stLFR pairs -> 10x FASTQ (02.assemble_by_supernova/fake_10x.pl) ----------------------------------------------
  * The script's conversion, on the host (hast_tx_pair_host: no GPU is touched) and over device memory (hast_tx_pair_device):
  * record i of read 1 goes with record i of read 2; the key in read 1's
