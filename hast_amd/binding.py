@@ -120,6 +120,7 @@ ABI_SYMBOLS = {
     "hast_filter_info": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), u64p]),
     "hast_filter_dense": (C.c_int, [vp, C.POINTER(C.c_int)]),
     "hast_filter_request_ceiling": (C.c_int, [vp, C.POINTER(C.c_double)]),
+    "hast_filter_lookups": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
     "hast_counts_resize": (C.c_int, [vp, C.c_size_t]),
     "hast_counts_bind": (C.c_int, [vp, vp, C.c_size_t]),
     "hast_counts_zero": (C.c_int, [vp, vp]),
@@ -425,6 +426,12 @@ class Context:
         d = C.c_int()
         _ck(self._lib.hast_filter_dense(self._h, C.byref(d)))
         return bool(d.value)
+
+    def filter_lookups(self):
+        """windows k_classify_f has sent to the exact table on this context (HAST_COUNT_LOOKUPS=1 at creation, an error otherwise)"""
+        n = C.c_uint64()
+        _ck(self._lib.hast_filter_lookups(self._h, C.byref(n)))
+        return n.value
 
     def close(self):
         if self._h:

@@ -2019,6 +2019,11 @@ void print_statistics(Run &rs) {
         (void)hast_filter_info(rs.ctx, &f_on, &f_m, &f_t, &f_kp, &f_bytes);
         stat_line("__stats_filter__ mode=%s m=%d t=%d kp=%d bytes=%llu\n", f_on == 2 ? "exact_entries" : f_on == 1 ? "prints" : "off_table_only", f_m, f_t, f_kp,
                   (unsigned long long)f_bytes);
+        uint64_t lk = 0, lk_all = 0;                             // HAST_COUNT_LOOKUPS=1 only: windows the filter sent to the exact table
+        bool counted = false;
+        for (hast_ctx *cx : rs.ctxs)
+            if (hast_filter_lookups(cx, &lk) == HAST_OK) { lk_all += lk; counted = true; }
+        if (counted) stat_line("__stats_lookups__ windows_sent_to_table=%llu\n", (unsigned long long)lk_all);
     }
     if (rs.hbm_thread.joinable()) {
         rs.hbm_stop = true;

@@ -64,7 +64,9 @@ struct hast_ctx {
     bool counts_owned = false;
     // small scratch
     uint32_t *d_err = nullptr;              // [4]
-    unsigned long long *d_cnt = nullptr;    // [8]: [0..1] set sizes, [2] sink of measurement kernels, [3] tile queue of k_classify, [4] segment counter
+    unsigned long long *d_cnt = nullptr;    // [8]: [0..1] set sizes, [2] sink of measurement kernels, [3] tile queue of k_classify, [4] segment counter,
+                                            // [5] windows k_classify_f sent to the exact table (count_lookups)
+    bool count_lookups = false;             // HAST_COUNT_LOOKUPS=1: k_classify_f counts the windows it looks up in the exact table
     void *d_scratch = nullptr;
     size_t scratch_bytes = 0;
     Staging stage[2];
@@ -328,6 +330,7 @@ hast_status hast_ctx_create(int device, int k, hast_ctx **out) {
     if (const char *e = getenv("HAST_PART_SPAN")) c->part_span = (uint32_t)atoi(e);      // (out of commit_plan.h's range: ignored)
     if (const char *e = getenv("HAST_F_GEO")) c->kernel_geo = e[0] != '0';
     if (const char *e = getenv("HAST_F_RL")) c->kernel_rl = e[0] != '0';
+    if (const char *e = getenv("HAST_COUNT_LOOKUPS")) c->count_lookups = atoi(e) != 0;
     if (const char *e = getenv("HAST_TILE_LDS")) {
         const long v = atol(e);
         if (v >= 4096 && v <= 160 * 1024) c->tile_lds = (size_t)v;
@@ -346,6 +349,7 @@ hast_status hast_ctx_create(int device, int k, hast_ctx **out) {
     bail(dev_malloc(&c->d_cnt, 8 * sizeof(unsigned long long)), "dev_malloc(cnt)");
     bail(pinned_malloc(reinterpret_cast<void **>(&c->h_errword), 64, hipHostMallocDefault), "pinned_malloc(err word)");
     if (st == HAST_OK) bail(hipMemsetAsync(c->d_err, 0, 4 * sizeof(uint32_t), c->stream), "hipMemset");
+    if (st == HAST_OK) bail(hipMemsetAsync(c->d_cnt, 0, 8 * sizeof(unsigned long long), c->stream), "hipMemset");
     if (st == HAST_OK) bail(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
     tr("first fill + synchronize");
     for (auto &s : c->stage)
@@ -1252,6 +1256,7 @@ static hast_status classify_rows(hast_ctx *c, const uint8_t *d_bases, size_t bas
     const uint64_t n_tiles = (n_reads + tr - 1) / tr;
     const int grid = (int)std::min<uint64_t>(n_tiles, (uint64_t)c->n_cu * 8);
     a.tile_queue = c->d_cnt + 3;
+    a.lookups = (filt && c->count_lookups) ? c->d_cnt + 5 : nullptr;
     HAST_HIP_TRY(hipMemsetAsync(a.tile_queue, 0, sizeof(unsigned long long), hs));
     hipEvent_t *ev = c->t_slots ? &c->t_ev[3 * (c->t_next % c->t_slots)] : nullptr;
     if (ev) HAST_HIP_TRY(hipEventRecord(ev[0], hs));
@@ -1326,6 +1331,7 @@ hast_status hast_ctx_options(const hast_ctx *c, char *out, size_t cap) {
     if (c->part_span) add("part_span", (long)c->part_span);
     if (!c->kernel_geo) add("kernel_geo", 0);
     if (!c->kernel_rl) add("kernel_rl", 0);
+    if (c->count_lookups) add("count_lookups", 1);
     if (c->tile_lds) add("tile_lds", (long)c->tile_lds);
     if (c->m != default_minimizer_plain(c->k)) add("minimizer", c->m);
     snprintf(out, cap, "%s", s.c_str());
@@ -1354,6 +1360,18 @@ hast_status hast_filter_info(const hast_ctx *c, int *enabled, int *m, int *t, in
 hast_status hast_filter_dense(const hast_ctx *c, int *dense) {
     if (!c || !dense) return set_error(HAST_ERR_INVALID, "null argument");
     *dense = (c->use_filter && c->filter_valid && c->fg.dense) ? 1 : 0;
+    return HAST_OK;
+}
+
+// Measurement (HAST_COUNT_LOOKUPS=1): windows k_classify_f has sent to the exact table on this context since its creation
+hast_status hast_filter_lookups(hast_ctx *c, uint64_t *n) {
+    if (hast_status st = use(c)) return st;
+    if (!n) return set_error(HAST_ERR_INVALID, "null argument");
+    if (!c->count_lookups) return set_error(HAST_ERR_INVALID, "look-ups are not counted (HAST_COUNT_LOOKUPS=1 when the context is created)");
+    unsigned long long v = 0;
+    HAST_HIP_TRY(hipDeviceSynchronize());                          // (launches may be on a caller's stream)
+    HAST_HIP_TRY(hipMemcpy(&v, c->d_cnt + 5, sizeof(v), hipMemcpyDeviceToHost));
+    *n = v;
     return HAST_OK;
 }
 

@@ -288,8 +288,8 @@ constexpr uint32_t kFilterOverflowMark = 0xFFFCu;
 // entries): there is room to file every string under EACH of its W m-mers (W entries with W different pm, i.e. W different
 // codes), and then the probe may pick any position it likes.  It picks the m-mer whose start lies on a fixed grid of the row:
 // the window at position p uses pm = (W - 1 - p) mod W, so the W windows of a grid cell all name the m-mer that starts at the
-// cell's last position -- ceil(windows / W) blocks per read (17 for 150 bp), no t-mer order, no sliding minimum.  Entry format,
-// inversion (block + sub-bucket + entry -> string) and the overflow mark are those of the sampled scheme.  All m-mers of all keys
+// cell's last position -- ceil(windows / W) blocks per read (17 for 150 bp), no t-mer order, no sliding minimum.  The entries
+// are 16 bits as in the sampled scheme but coded by position, and their mark carries a signature (dense entries, below).  All m-mers of all keys
 // are used, so random keys load the sub-buckets as a Poisson variable of mean 2 W N / (8 * 4^m); the rule below keeps that mean
 // at or under kFilterDenseMaxLoad, where P(>= 9 entries) sends under one window per read to the table (0.47 at 2.98, 0.74 at
 // 3.2, 1.3 at 3.5, 2.8 at 4.0 -- past 3.2 the look-ups eat what the blocks save).  W must be a power of two (the mask below).
@@ -297,6 +297,83 @@ constexpr double kFilterDenseMaxLoad = 3.2;
 HAST_HD uint32_t filter_dense_pm(uint32_t p, uint32_t w) { return (w - 1u - p) & (w - 1u); }
 HAST_HD double filter_dense_load(const FilterGeom &g, uint64_t n_keys) {
     return 2.0 * (double)filter_w(g) * (double)n_keys / ((double)kFilterSubs * (double)filter_nblocks(g));
+}
+// ---- dense entries: the sub-bucket is the m-mer's position, the mark says whom it turned away -------------------------------
+// A variant site files its ~2 W strings per block together; hashed into 8 sub-buckets (filter_exact_code) they pile up at random,
+// indexed by pm they land one or two per sub-bucket: 3.68 -> 1.37 windows per read in a marked sub-bucket on clustered keys
+// (profiles/exact_load_sim_pos.txt).  So a DENSE entry is filed without the multiply:
+//     rest       = the K-m flanking bases, rotated as in filter_exact_code (behind the m-mer, then in front of it)
+//     sub-bucket = (pm | rest << log2 W) & 7          (W < 8: the spare sub-bucket bits are the flank's low bits)
+//     14 stored  = rest >> (3 - log2 W)               (all 14 at W = 8)
+// still a bijection (block + sub-bucket + entry give the string back), and filter_dense_code returns it in filter_exact_code's
+// shape (sub-bucket << 14 | stored bits), so filter_exact_sub / filter_exact_entry apply.  The sampled scheme keeps its own code.
+HAST_HD uint32_t filter_dense_code(uint64_t fwd, uint32_t pm, const FilterGeom &g, uint32_t pos_bits) {
+    const int rb = 2 * (g.k - g.m);
+    const uint32_t rot = ((uint32_t)fwd << (2 * pm)) | (uint32_t)(fwd >> (2 * ((uint32_t)g.k - pm)));
+    const uint32_t rest = rot & ((1u << rb) - 1u);
+    return (((pm | (rest << pos_bits)) & 7u) << 14) | (rest >> (3u - pos_bits));
+}
+// (pm, flank bits) of a dense entry: the inverse of the above (stored = entry >> 2)
+HAST_HD uint32_t filter_dense_pm_of(uint32_t sub, uint32_t pos_bits) { return sub & ((1u << pos_bits) - 1u); }
+HAST_HD uint32_t filter_dense_rest_of(uint32_t sub, uint32_t stored, uint32_t pos_bits) { return (stored << (3u - pos_bits)) | (sub >> pos_bits); }
+// The mark of a dense sub-bucket carries a SIGNATURE of the entries it turned away.  Its slot has tag bits 00, so it can never
+// match a window whatever its 14 code bits are: they hold the OR of two bits per turned-away entry (of that entry's 14 stored
+// bits: one multiplicative hash, two different positions out of 14), and only a window whose own two bits are both set can be
+// one of them -- the rest of a marked sub-bucket's windows are proven misses like anywhere else.  kFilterOverflowMark (all 14
+// set) is the mark that turns nobody down.
+HAST_HD uint32_t filter_mark_sig(uint32_t stored14) {
+    const uint32_t h = (stored14 & 0x3FFFu) * 0x9E3779B1u;                        // (a full multiply: the probe gets here rarely)
+    const uint32_t a = ((h >> 24) * 14u) >> 8;                                    // 0 .. 13
+    const uint32_t b = (((h >> 16) & 0xFFu) * 13u) >> 8;                          // 0 .. 12
+    const uint32_t b2 = a + 1u + b;                                               // another position than a, mod 14
+    return (1u << a) | (1u << (b2 >= 14u ? b2 - 14u : b2));
+}
+HAST_HD bool filter_is_mark(uint32_t slot7) { return slot7 != 0 && (slot7 & 3u) == 0; }
+// One filing routine for the build kernel and for a host model of it (tests/native/test_filter_dense_pos.cpp): the same steps, with
+// the words read and written atomically on the device.  `w` = the sub-bucket's 4 words (8 slots that fill in order, 0 = free).
+// INVARIANT, for any order and any interleaving of the calls: every filed entry either sits in a slot of its sub-bucket, or slot 7
+// holds a mark whose signature has both of the entry's bits.  (Slots 0-6 never change once written; slot 7 goes free -> entry ->
+// mark and a mark only gains bits; whoever replaces slot 7's entry by a mark puts that entry's bits in with its own -- in the one
+// compare-and-swap that also proves the slot still held that entry.)  No loop waits for another thread: a failed swap means the
+// word has moved one step along that chain, which is at most 2 + 1 + 14 steps long.
+HAST_HD uint32_t filter_word_load(uint32_t *p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+    return *p;
+#endif
+}
+HAST_HD uint32_t filter_word_cas(uint32_t *p, uint32_t expect, uint32_t v) {      // -> what the word held
+#if defined(__HIP_DEVICE_COMPILE__)
+    return atomicCAS(p, expect, v);
+#else
+    const uint32_t old = *p;
+    if (old == expect) *p = v;
+    return old;
+#endif
+}
+HAST_HD void filter_dense_file(uint32_t *w, uint32_t entry) {
+    for (int i = 0; i < kFilterPrints / 2;) {
+        const uint32_t v = filter_word_load(&w[i]);
+        const uint32_t lo = v & 0xFFFFu, hi = v >> 16;
+        if (lo == entry || hi == entry) return;                      // already there (slot 7: whoever marks it keeps its bits)
+        uint32_t nv;
+        if (lo == 0) nv = v | entry;
+        else if (hi == 0) nv = v | (entry << 16);
+        else { ++i; continue; }
+        if (filter_word_cas(&w[i], v, nv) == v) return;              // else: someone else wrote this word, look again
+    }
+    // full: turned away.  Slot 7 becomes, or stays, a mark with this entry's bits (and those of the entry it held)
+    const uint32_t sig = filter_mark_sig(entry >> 2) << 2;
+    uint32_t v = filter_word_load(&w[kFilterPrints / 2 - 1]);
+    for (;;) {
+        const uint32_t hi = v >> 16;
+        const uint32_t nh = (hi & 3u) ? (sig | (filter_mark_sig(hi >> 2) << 2)) : (hi | sig);
+        if (nh == hi) return;
+        const uint32_t old = filter_word_cas(&w[kFilterPrints / 2 - 1], v, (v & 0xFFFFu) | (nh << 16));
+        if (old == v) return;
+        v = old;
+    }
 }
 // Geometry for K and a key count (m = 15, a 137-GB filter, only where the key count asks for it: above 537M keys).
 // Geometry for K and a key count.  Measured with tools/sim/filter_load_sim.cpp (unscaled: 400M keys, both strands filed):

@@ -25,6 +25,7 @@ struct ClassifyArgs {
     uint16_t *votes16;           // not nullptr: a row's votes go here instead, as vote0 | vote1 << 8 (rows are reads, max_pos <= 255:
                                  // what the partitioned commit keeps of a row anyway)
     unsigned long long *tile_queue; // zeroed before the launch: next tile index (dynamic load balance)
+    unsigned long long *lookups;    // measurement, usually nullptr: k_classify_f adds the windows it sends to the exact table
     const uint64_t *slots;       // table
     uint64_t n_reads;
     const unsigned long long *n_rows_ptr;   // not nullptr: the number of rows is read from here (segment tables built on the device:

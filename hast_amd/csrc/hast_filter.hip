@@ -18,7 +18,9 @@ namespace hast {
 // 16-bit prints that fill in order (0 = free); a print that finds its sub-bucket full is simply not filed: lookups treat a
 // full sub-bucket as "ask the exact table".  An EXACT entry that finds no room instead marks its sub-bucket: slot 7 becomes
 // kFilterOverflowMark (hast_common.h), and only a marked sub-bucket sends a window without a match to the table -- most full
-// sub-buckets hold exactly 8 entries and prove a miss like any other (profiles/tmer_order_sim.txt).
+// sub-buckets hold exactly 8 entries and prove a miss like any other (profiles/tmer_order_sim.txt).  DENSE filters file an entry
+// in the sub-bucket of its m-mer's position and mark with a signature of the entries turned away (filter_dense_file, hast_common.h:
+// the routine the host model of tests/native/test_filter_dense_pos.cpp runs too).
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t sub_load(const uint32_t *w) {                 // prints in a sub-bucket (they fill in order)
     uint32_t n = 0;
@@ -61,11 +63,13 @@ __device__ __forceinline__ void filter_insert(uint32_t *filt, const FilterGeom g
             // exact entry (hast_common.h): the string's code picks the one sub-bucket it can sit in and is stored with the tags.
             // Filed under the sampled m-mer, or -- dense filing -- under every one of the W m-mers (W entries, W different codes)
             const uint32_t pm0 = g.dense ? 0u : filter_sample_pos(s, g), pm1 = g.dense ? filter_w(g) : pm0 + 1u;
+            const uint32_t pb = (uint32_t)filter_pos_bits(g);
             for (uint32_t pm = pm0; pm < pm1; ++pm) {
                 const uint32_t blk = filter_block_of((uint32_t)(s >> (2 * (g.k - g.m - (int)pm))) & (uint32_t)kmer_mask(g.m), g.m);
-                const uint32_t c17 = filter_exact_code(s, pm, g);
+                const uint32_t c17 = g.dense ? filter_dense_code(s, pm, g, pb) : filter_exact_code(s, pm, g);
                 uint32_t *w = filt + (size_t)blk * (kFilterSubs * kFilterPrints / 2) + filter_exact_sub(c17) * (kFilterPrints / 2);
-                if (!sub_insert(w, filter_exact_entry(c17, tags))) sub_mark_overflow(w);     // full: windows that land there ask the table
+                if (g.dense) filter_dense_file(w, filter_exact_entry(c17, tags));            // turned away: the mark says so, with a signature
+                else if (!sub_insert(w, filter_exact_entry(c17, tags))) sub_mark_overflow(w);     // full: windows that land there ask the table
             }
             continue;
         }
@@ -125,6 +129,9 @@ hipError_t launch_filter_build(const uint64_t *slots, TableGeom tg, void *filter
 //               exact entries (EXACT): the window's 17-bit code names ONE sub-bucket and 14 stored bits; one 16-B load;
 //                 compare = 4 xor + 3 v_pk_max_u16; a match carries the tag bits and is added to the read's votes at once,
 //                 only "no match in a sub-bucket that turned a key away" (slot 7 = kFilterOverflowMark) is queued.
+//               DENSE: the sub-bucket is the m-mer's position and the 14 stored bits are the flanks as they stand (no multiply);
+//                 slot 7 with tag bits 00 is a mark whose 14 bits are a signature of the entries turned away, and a window
+//                 without a match is queued only if its own two signature bits are both set there (filter_mark_sig).
 //   V  verify : when a wave's queue holds 64 entries (and at the end of the tile) each lane takes one, canonicalises it
 //               (v_bfrev) and finds it in the exact table (home bucket by the table's own minimizer, then the chain)
 //               and adds its tag bits to the read's votes in LDS.
@@ -222,6 +229,7 @@ __global__ void __launch_bounds__(kThreadsF, DENSE ? HAST_F_MINWAVES_DENSE : HAS
     const uint32_t kshift = 64 - 2 * K, tshift = 64 - 2 * T;
     const uint32_t mmask = (uint32_t)kmer_mask(M);
     const uint32_t nb = a.nbuckets;
+    const uint32_t PB = DENSE ? (uint32_t)filter_pos_bits(fg) : 0u;   // log2 W: the position bits of a dense entry's sub-bucket
     const uint64_t n_rows = a.n_rows_ptr ? min((uint64_t)*a.n_rows_ptr, (uint64_t)a.n_reads) : a.n_reads;   // (never past the table the host sized)
     const uint64_t n_tiles = (n_rows + TR - 1) / TR;
     const uintptr_t base_addr = reinterpret_cast<uintptr_t>(a.bases);
@@ -376,6 +384,9 @@ __global__ void __launch_bounds__(kThreadsF, DENSE ? HAST_F_MINWAVES_DENSE : HAS
             const unsigned long long key = kmer_canon(((unsigned long long)q_hi[e] << 32) | q_lo[e], K);   // queued: the window as read
             const uint32_t rd = q_rd[e];
             qn -= cnt;
+            // HAST_COUNT_LOOKUPS (off by default), exact entries only: with prints every hit comes here, and config 5's kernel,
+            // at its SGPR limit, ran 0.3 % slower for the test alone
+            if (EXACT && a.lookups && lane == 0) atomicAdd(a.lookups, (unsigned long long)cnt);
             for (int pass = 0; pass < (WIDE ? 2 : 1); ++pass) {
                 const u64x2f *tab = tab0 + (WIDE ? (size_t)pass * nb * kPieces : 0);
                 const unsigned long long want = WIDE ? key : (key << 2);
@@ -470,7 +481,7 @@ __global__ void __launch_bounds__(kThreadsF, DENSE ? HAST_F_MINWAVES_DENSE : HAS
             uint32_t fb = ok ? filter_block_of(mm, M) : 0xFFFFFFFFu;  // real blocks are < 4^15
             // of the window as it stands (no canonical form in the probe): a hash for two sub-buckets and a print, or the
             // window's exact code, whose top bits are its one sub-bucket
-            const uint32_t h = EXACT ? filter_exact_code(fwd, pm, fg) : filter_keyhash(fwd);
+            const uint32_t h = DENSE ? filter_dense_code(fwd, pm, fg, PB) : EXACT ? filter_exact_code(fwd, pm, fg) : filter_keyhash(fwd);
             const uint32_t anchor = okm ? (uint32_t)__builtin_amdgcn_readlane((int)fb, (int)__builtin_ctzll(okm)) : last_fb;
             last_fb = anchor;
             fb = ok ? fb : anchor;
@@ -509,7 +520,8 @@ __global__ void __launch_bounds__(kThreadsF, DENSE ? HAST_F_MINWAVES_DENSE : HAS
                 if (hit) atomicAdd(&s_vote[B.meta & 0xFFFFu], (unsigned long long)(m16 & 1u) | ((unsigned long long)((m16 >> 1) & 1u) << 32));
                 // no match in a sub-bucket that turned a key away (slot 7 = the overflow mark): that key may be the window's; a full
                 // sub-bucket without the mark holds every string filed there, and proves a miss
-                pos = valid && !hit && (B.v.w >> 16) == kFilterOverflowMark;
+                // (DENSE: any slot 7 with tag bits 00 is a mark; which windows it sends on is settled below)
+                pos = valid && !hit && (DENSE ? (B.v.w & 0x30000u) == 0 && B.v.w >= 0x10000u : (B.v.w >> 16) == kFilterOverflowMark);
             } else {
             uint32_t acc = pk_min_u16(pk_min_u16(B.v.x ^ B.fpw, B.v.y ^ B.fpw), pk_min_u16(B.v.z ^ B.fpw, B.v.w ^ B.fpw));
             bool full = (B.v.w >> 16) != 0;
@@ -520,7 +532,22 @@ __global__ void __launch_bounds__(kThreadsF, DENSE ? HAST_F_MINWAVES_DENSE : HAS
             const bool match = ((acc - 0x00010001u) & ~acc & 0x80008000u) != 0;      // some halfword of acc is zero
             pos = (int)B.meta < 0 && (match || full);
             }
-            const unsigned long long pmask = ballot64(pos);
+            unsigned long long pmask = ballot64(pos);
+            if (DENSE && pmask) {
+                // some window of the wave sits in a marked sub-bucket (rare): only those whose two signature bits are both in the
+                // mark can be an entry it turned away (fpw holds the complement of the window's 14 stored bits)
+                // Those few windows are taken one by one in SCALAR registers (readlane): the kernel has no vector register to
+                // spare here -- with the signature computed per lane the 150-bp instantiation went from 79 to 81 and lost a wave
+                unsigned long long keep = 0;
+                for (unsigned long long rest = pmask; rest; rest &= rest - 1) {
+                    const int l = (int)__builtin_ctzll(rest);
+                    const uint32_t f = (uint32_t)__builtin_amdgcn_readlane((int)B.fpw, l), s7 = (uint32_t)__builtin_amdgcn_readlane((int)B.v.w, l) >> 16;
+                    const uint32_t sig = filter_mark_sig(~(f >> 2) & 0x3FFFu) << 2;
+                    if ((s7 & sig) == sig) keep |= 1ull << l;
+                }
+                pmask = keep;
+                pos = __builtin_amdgcn_inverse_ballot_w64(keep);
+            }
             if (pmask) {
                 const uint32_t at = qn + lanes_below(pmask);
                 if (pos) {

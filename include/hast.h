@@ -67,7 +67,7 @@ int         hast_ctx_minimizer(const hast_ctx *);
 hast_status hast_ctx_set_minimizer(hast_ctx *, int m);
 int         hast_ctx_device(const hast_ctx *);
 /* Measurement switches.  The environment is read ONCE, when a context is created (HAST_CLASSIFY, HAST_FILTER_*, HAST_COMMIT,
- * HAST_PART_SPAN, HAST_F_GEO, HAST_F_RL, HAST_TILE_LDS, HAST_MINIMIZER); results never depend on them.  hast_ctx_set_option changes one on a live
+ * HAST_PART_SPAN, HAST_F_GEO, HAST_F_RL, HAST_TILE_LDS, HAST_MINIMIZER, HAST_COUNT_LOOKUPS); results never depend on them.  hast_ctx_set_option changes one on a live
  * context: "commit" 0 = by batch size / 1 = one atomic per read / 2 = partitioned; "part_span" 8 .. 13 = barcodes per bin of the
  * partitioned commit as a power of two (0 = by barcode count); "kernel_geo", "kernel_rl" 0 = the generic
  * k_classify_f instantiations instead of the ones with the BASELINE geometry / row length compiled in; "tile_lds" bytes (0 =
@@ -161,7 +161,9 @@ hast_status hast_table_info(const hast_ctx *, uint64_t *n_buckets, uint64_t *byt
  * the key count.  hast_filter_info: *enabled = 0 off, 1 prints, 2 exact entries (known once the filter is built).
  * Exact entries are filed DENSELY -- under every one of a string's W = K-m+1 m-mers instead of under one sampled m-mer -- where W
  * is a power of two <= 8 and the sub-buckets then hold <= 3.2 entries on average (K = 21 up to ~430M keys): the probe takes the
- * m-mer on a fixed grid of the row, ceil(windows / W) blocks per read, no sampling arithmetic.  HAST_FILTER_EXACT=once in the
+ * m-mer on a fixed grid of the row, ceil(windows / W) blocks per read, no sampling arithmetic.  A dense entry sits in the sub-bucket
+ * of its m-mer's position, and a sub-bucket that turned entries away says which (a signature in its mark), so nearly no window
+ * without a match has to ask the table.  HAST_FILTER_EXACT=once in the
  * environment (hast_ctx_set_option "filter_exact_once") keeps exact entries filed once per strand under the sampled m-mer.
  * hast_filter_dense: *dense = 1 when the filter built for the current table is a dense one.  Same results either way. */
 hast_status hast_ctx_set_filter(hast_ctx *, int enable, int m, int t, int kp);
@@ -172,6 +174,11 @@ hast_status hast_filter_dense(const hast_ctx *, int *dense);
  * context's own filter, read in the probe kernel's access shape with no arithmetic -- the request-rate ceiling of this box
  * over this footprint, against which k_classify_f's own request rate is priced in the same run. */
 hast_status hast_filter_request_ceiling(hast_ctx *, double *requests_per_s);
+/* Measurement entry: the windows k_classify_f has sent to the exact table on this context since it was created, for filters
+ * with exact entries (windows without a match in a sub-bucket whose mark says a key like theirs was turned away; filters with
+ * prints send every hit there and are not counted).  Counted only when
+ * HAST_COUNT_LOOKUPS=1 was in the environment at hast_ctx_create (one atomic per 64 look-ups); an error otherwise. */
+hast_status hast_filter_lookups(hast_ctx *, uint64_t *n);
 
 /* ---- per-barcode counters: BarcodeCache (classify.cpp:50-64) -------------------------------
  * Device layout: uint64 counts[n_barcodes][4] = { c0, c1, neg, reserved } (32-byte records: a record is one sector for the commit
