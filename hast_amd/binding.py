@@ -59,6 +59,10 @@ class RsBlock(C.Structure):
                 ("votes", C.POINTER(C.c_uint32)), ("name_off", C.POINTER(C.c_uint32)), ("names", C.POINTER(C.c_uint8))]
 
 
+class RsBinned(C.Structure):
+    _fields_ = [("run", C.POINTER(C.c_uint8) * 3), ("run_bytes", C.c_uint64 * 3), ("raw_bytes", C.c_uint64 * 3), ("count", C.c_uint64 * 3)]
+
+
 class TxMapInfo(C.Structure):
     _fields_ = [("n_keys", C.c_uint64), ("device_ok", C.c_int), ("reason", C.c_char * 60)]
 
@@ -236,6 +240,8 @@ ABI_SYMBOLS = {
     "hast_rs_submit": (C.c_int, [vp, C.c_size_t, C.c_int]),
     "hast_rs_next": (C.c_int, [vp, C.POINTER(RsBlock)]),
     "hast_rs_take_tail": (C.c_int, [vp, vp, C.POINTER(C.c_size_t)]),
+    "hast_rs_set_bins": (C.c_int, [vp, C.c_int, C.c_uint32, C.c_uint32]),
+    "hast_rs_next_binned": (C.c_int, [vp, C.POINTER(RsBlock), C.POINTER(RsBinned)]),
     "hast_rs_destroy": (None, [vp]),
     # stage 02: stLFR pairs -> 10x FASTQ (fake_10x.pl)
     "hast_tx_map_load": (C.c_int, [C.c_char_p, C.POINTER(vp), C.POINTER(TxMapInfo)]),
@@ -838,10 +844,24 @@ class ReadStream:
             C.memmove(p, data, len(data))
         _ck(self._lib.hast_rs_submit(self._h, len(data), 1 if last else 0))
 
-    def next(self):
+    def set_bins(self, mode, total0, total1):
+        """the read bins (hast_rs_set_bins): 0 off, 1 plain, 2 gzip; total0 / total1: the two set sizes"""
+        _ck(self._lib.hast_rs_set_bins(self._h, mode, total0, total1))
+
+    def next_binned(self):
+        """next(), and behind it the bins of the same view: (runs [3 x bytes], raw_bytes [3], count [3]); copies of the pinned buffers"""
+        bins = RsBinned()
+        out = self.next(bins)
+        runs = [C.string_at(bins.run[c], bins.run_bytes[c]) if bins.run_bytes[c] else b"" for c in range(3)]
+        return out + (runs, [int(x) for x in bins.raw_bytes], [int(x) for x in bins.count])
+
+    def next(self, _bins=None):
         """(flags, consumed, bases, names, votes[records, 2]) of the oldest submitted block; copies of the feed's pinned buffers"""
         b = RsBlock()
-        _ck(self._lib.hast_rs_next(self._h, C.byref(b)))
+        if _bins is None:
+            _ck(self._lib.hast_rs_next(self._h, C.byref(b)))
+        else:
+            _ck(self._lib.hast_rs_next_binned(self._h, C.byref(b), C.byref(_bins)))
         n = b.records
         if not n:
             return b.flags, b.consumed, b.bases, [], np.zeros((0, 2), dtype=np.uint32)

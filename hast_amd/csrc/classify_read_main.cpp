@@ -17,6 +17,13 @@
 // route does not take runs through the host route with one WARN line and the same stdout: several --devices (the whole run), an
 // input that is not a regular file, a record that does not fit two blocks (that file, from its start).  --stats: two lines on stderr.
 //
+// --bin-reads (additive, off by default): besides the rows, every read is written, as its bytes lie in the input, to one of
+// DIR/B.haplotype0.E, B.haplotype1.E, B.ambiguous.E (B: the input's basename minus a trailing .gz, E: fasta | fastq by --format, DIR:
+// --bin-dir, default "."; --gz-out: gzip members, ".gz" appended).  The rule is rb_core.h's, the class the row's.  With --ingest device
+// the runs are partitioned (and deflated) on the GPU and come from hast_rs_next_binned; the host route, every fallback and the FASTQ
+// tail write through the model of rb_host.h (zlib members with --gz-out).  A class without reads gets no file; an input that ends in
+// the format error leaves none of its files; a failed write is exit 3.
+//
 // Requirement (deviation): k-mer lines must be upper-case A/C/G/T of one length K <= 32 -- what jellyfish/meryl
 // dumps are.  The reference would also store other bytes literally (s03:59-65); we stop with exit 3 instead.
 #include <getopt.h>
@@ -38,7 +45,10 @@
 #include <vector>
 
 #include "../../include/hast.h"
+#include <zlib.h>
+
 #include "ingest.h"
+#include "rb_host.h"
 #include "rs_host.h"
 
 namespace {
@@ -61,7 +71,10 @@ void print_usage() {   // same flags as the reference (s03:316-324); stderr is f
           "  --device N / --devices A,B,..   GPU(s); with several, every batch of reads is shared out between them\n"
           "  --ingest host|device            device: reads are inflated and framed on the GPU (one GPU; default host)\n"
           "  --block-mb N                    block of the device ingest (default 64)\n"
-          "  --stats                         counts and seconds of the read phase on stderr\n",
+          "  --stats                         counts and seconds of the read phase on stderr\n"
+          "  --bin-reads                     also write every input's reads to B.haplotype0|haplotype1|ambiguous.fasta|fastq\n"
+          "  --gz-out                        (with --bin-reads) gzip those files, names end in .gz\n"
+          "  --bin-dir DIR                   (with --bin-reads) where they go (default: the working directory)\n",
           stderr);
 }
 
@@ -87,10 +100,11 @@ bool slurp(const std::string &path, std::vector<char> &out) {
 void format_rows(std::string &out, const uint8_t *names, const uint32_t *name_off, const uint32_t *votes, size_t n, const int *total_kmers) {
     char row[96];
     for (size_t i = 0; i < n; i++) {
-        const double d0 = (double)votes[2 * i] / total_kmers[0], d1 = (double)votes[2 * i + 1] / total_kmers[1];   // s03:215-216
-        // s03:110-133 for two haplotypes: both zero -> ambiguous 0.0; else the larger density, ties to haplotype0
-        if (!(d0 > 0) && !(d1 > 0)) snprintf(row, sizeof(row), "\tambiguous\t0.0\n");
-        else if (d1 > d0) snprintf(row, sizeof(row), "\thaplotype1\t%0.6f\n", d1);
+        const double d0 = hast::rb::density(votes[2 * i], total_kmers[0]), d1 = hast::rb::density(votes[2 * i + 1], total_kmers[1]);   // s03:215-216
+        // s03:110-133 for two haplotypes: both zero -> ambiguous 0.0; else the larger density, ties to haplotype0 (rb_core.h: the bins' rule)
+        const uint32_t cls = hast::rb::class_of(d0, d1);
+        if (cls == hast::rb::kAmbiguous) snprintf(row, sizeof(row), "\tambiguous\t0.0\n");
+        else if (cls == hast::rb::kHap1) snprintf(row, sizeof(row), "\thaplotype1\t%0.6f\n", d1);
         else snprintf(row, sizeof(row), "\thaplotype0\t%0.6f\n", d0);
         out.append(reinterpret_cast<const char *>(names) + name_off[i], name_off[i + 1] - name_off[i]);
         out += row;
@@ -112,6 +126,72 @@ bool tail_batch(const char *tail, size_t n, std::vector<std::string> &names, std
     return true;
 }
 
+// The three files of one input under --bin-reads.  A file is created at its first byte (a class without reads gets none); start()
+// removes what an earlier input of the same run cannot have written (the names are distinct) but an earlier run may have left.
+struct BinFiles {
+    std::string path[3];
+    FILE *f[3] = {nullptr, nullptr, nullptr};
+    bool gz = false;
+    void start(const std::string &dir, const std::string &base, const char *ext, bool gz_out) {
+        static const char *const cls[3] = {"haplotype0", "haplotype1", "ambiguous"};
+        gz = gz_out;
+        for (int c = 0; c < 3; ++c) {
+            path[c] = dir + "/" + base + "." + cls[c] + "." + ext + (gz ? ".gz" : "");
+            ::remove(path[c].c_str());
+        }
+    }
+    // bytes as they are (the device route's runs: plain, or finished gzip members)
+    bool write(int c, const void *p, size_t n) {
+        if (!n) return true;
+        if (!f[c] && !(f[c] = fopen(path[c].c_str(), "wb"))) return false;
+        return fwrite(p, 1, n, f[c]) == n;
+    }
+    // plain bytes from the host model: with --gz-out one zlib member per call
+    bool write_plain(int c, const std::string &run) {
+        if (run.empty() || !gz) return write(c, run.data(), run.size());
+        z_stream z;
+        memset(&z, 0, sizeof(z));
+        if (deflateInit2(&z, 1, Z_DEFLATED, 15 + 16, 8, Z_DEFAULT_STRATEGY) != Z_OK) return false;
+        std::vector<unsigned char> buf(1u << 20);
+        bool ok = true;
+        size_t at = 0;
+        int rc = Z_OK;
+        while (ok && rc != Z_STREAM_END) {                          // (avail_in is 32 bits wide: a run goes in by pieces)
+            if (z.avail_in == 0 && at < run.size()) {
+                const size_t k = std::min<size_t>(run.size() - at, 1u << 30);
+                z.next_in = reinterpret_cast<Bytef *>(const_cast<char *>(run.data() + at));
+                z.avail_in = (uInt)k;
+                at += k;
+            }
+            z.next_out = buf.data();
+            z.avail_out = (uInt)buf.size();
+            rc = deflate(&z, at == run.size() ? Z_FINISH : Z_NO_FLUSH);
+            if (rc == Z_STREAM_ERROR) ok = false;
+            else ok = write(c, buf.data(), buf.size() - z.avail_out);
+        }
+        deflateEnd(&z);
+        return ok;
+    }
+    bool write_runs(const hast::rb::Runs &r) {
+        for (int c = 0; c < 3; ++c)
+            if (!write_plain(c, r.run[c])) return false;
+        return true;
+    }
+    bool close_all() {
+        bool ok = true;
+        for (int c = 0; c < 3; ++c)
+            if (f[c]) {
+                ok = fclose(f[c]) == 0 && ok;
+                f[c] = nullptr;
+            }
+        return ok;
+    }
+    void discard() {                                                // the input ended in the format error, or is read again from its start
+        (void)close_all();
+        for (int c = 0; c < 3; ++c) ::remove(path[c].c_str());
+    }
+};
+
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 }  // namespace
@@ -122,12 +202,15 @@ int main(int argc, char **argv) {
                                            {"help", no_argument, NULL, 'h'},         {"device", required_argument, NULL, 1001},
                                            {"devices", required_argument, NULL, 1002}, {"ingest", required_argument, NULL, 1003},
                                            {"block-mb", required_argument, NULL, 1004}, {"stats", no_argument, NULL, 1005},
+                                           {"bin-reads", no_argument, NULL, 1006},   {"gz-out", no_argument, NULL, 1007},
+                                           {"bin-dir", required_argument, NULL, 1008},
                                            {0, 0, 0, 0}};
     std::vector<std::string> haps, read;
     std::string format = "fasta";
     int t_num = 8, device = 0;
     std::vector<int> devices;
-    bool ingest_device = false, stats = false;
+    bool ingest_device = false, stats = false, bin_reads = false, gz_out = false;
+    std::string bin_dir = ".";
     long block_mb = 64;
     for (;;) {
         int c = getopt_long(argc, argv, "p:r:t:f:h", long_options, NULL);   // s03:324
@@ -156,6 +239,9 @@ int main(int argc, char **argv) {
             if (block_mb < 1 || block_mb > 1024) { print_usage(); return -1; }
             break;
         case 1005: stats = true; break;
+        case 1006: bin_reads = true; break;
+        case 1007: gz_out = true; break;
+        case 1008: bin_dir = optarg; break;
         case 'h':
         default: print_usage(); return -1;
         }
@@ -164,6 +250,21 @@ int main(int argc, char **argv) {
         print_usage();
         return -1;
     }
+    if (gz_out && !bin_reads) {
+        print_usage();
+        return -1;
+    }
+    std::vector<std::string> bin_base;                                      // per input: its basename minus a trailing .gz
+    if (bin_reads)
+        for (const std::string &r : read) {
+            std::string b = r.substr(r.find_last_of('/') == std::string::npos ? 0 : r.find_last_of('/') + 1);
+            if (b.size() > 3 && b.compare(b.size() - 3, 3, ".gz") == 0) b.resize(b.size() - 3);
+            if (std::find(bin_base.begin(), bin_base.end(), b) != bin_base.end()) {   // two inputs would write the same files
+                print_usage();
+                return -1;
+            }
+            bin_base.push_back(b);
+        }
     if (devices.empty()) devices.push_back(device);
     device = devices[0];
     if (format != "fasta" && format != "fastq") {
@@ -267,6 +368,24 @@ int main(int argc, char **argv) {
         std::vector<uint8_t> bases;
         std::vector<uint64_t> offsets;
         std::vector<std::string> names;
+        std::string raw;                                    // --bin-reads: the view the records lie in, and their extents in it
+        std::vector<hast::rb::Extent> ext;
+    };
+    BinFiles bins;
+    hast::rb::Runs bin_runs;                                // the background thread's while a batch is in flight
+    bool bin_failed = false;
+    uint64_t st_bin[3] = {0, 0, 0}, st_bin_dev = 0, st_bin_host = 0;
+    const uint32_t bin_total[2] = {(uint32_t)total_kmers[0], (uint32_t)total_kmers[1]};
+    std::string raw;                                        // what classify_batch hands on with the batch
+    std::vector<hast::rb::Extent> ext;
+    // the runs of the host model into the input's files
+    auto flush_runs = [&]() {
+        if (!bins.write_runs(bin_runs)) bin_failed = true;
+        for (int c = 0; c < 3; ++c) {
+            st_bin[c] += bin_runs.count[c];
+            st_bin_host += bin_runs.run[c].size();
+        }
+        bin_runs.clear();
     };
     std::thread bg;
     struct Joiner {                                         // every way out of main() waits for the batch in flight
@@ -325,6 +444,10 @@ int main(int argc, char **argv) {
             const uint32_t off[2] = {0, (uint32_t)b.names[i].size()};
             format_rows(out_rows, reinterpret_cast<const uint8_t *>(b.names[i].data()), off, v.data() + 2 * i, 1, total_kmers);
         }
+        if (bin_reads && b.ext.size() == n) {
+            hast::rb::append_runs(reinterpret_cast<const uint8_t *>(b.raw.data()), b.ext.data(), v.data(), n, bin_total[0], bin_total[1], &bin_runs);
+            flush_runs();
+        }
         st_records += n;
         st_kernels += t1 - t0;
         st_rows += now_s() - t1;
@@ -336,12 +459,16 @@ int main(int argc, char **argv) {
         b.bases.swap(bases);
         b.offsets.swap(offsets);
         b.names.swap(names);
+        b.raw.swap(raw);
+        b.ext.swap(ext);
         bg = std::thread([&run_batch, &b] { run_batch(b); });
         cur ^= 1;
         Batch &o = bt[cur];                                 // idle since the wait above: its vectors (and their capacity) are the next work area
         bases.swap(o.bases);
         offsets.swap(o.offsets);
         names.swap(o.names);
+        raw.clear();
+        ext.clear();
     };
     // records = [first, last) pairs of line indices: header line, then sequence lines; fills names/offsets/bases in parallel
     struct RecSpan { uint32_t head, seq_first, seq_end; };             // line indices; sequence lines [seq_first, seq_end)
@@ -382,6 +509,24 @@ int main(int argc, char **argv) {
             }
         });
         offsets[n] = part[T];
+        if (bin_reads) {                                    // the records' extents (rb_core.h) and the bytes they lie in, for the background thread
+            ext.resize(n);
+            uint64_t end = 0;
+            for (size_t i = 0; i < n; i++) {
+                const RecSpan &r = recs[i];
+                ext[i].lo = line_start(r.head);
+                ext[i].hi = fastq ? (uint64_t)allnl[r.head + 3] + 1 : line_start(r.seq_end);
+                end = ext[i].hi;
+            }
+            raw.assign(data, end);
+        }
+    };
+    // the FASTQ tail as a record of the bins: its bytes as they lie, plus a newline if they do not end in one (rb_host.h: append_tail)
+    auto bin_tail = [&](const char *tail, size_t n_tail) {
+        if (!bin_reads || names.empty()) return;
+        raw.assign(tail, n_tail);
+        if (raw.back() != '\n') raw += '\n';
+        ext.assign(1, hast::rb::Extent{0, raw.size()});
     };
     const size_t block_bytes = (size_t)std::max(1L, getenv("HAST_READ_BLOCK_BYTES") ? atol(getenv("HAST_READ_BLOCK_BYTES")) : (256L << 20));
     bool output_failed = false;
@@ -436,6 +581,7 @@ int main(int argc, char **argv) {
                     build_batch(data);
                     classify_batch();
                     if (!tail_batch(data + consumed, len - consumed, names, bases, offsets)) { fprintf(stderr, "fasta detected . ERROR . please use \"--format fasta\". exit ... \n"); return 1; }
+                    bin_tail(data + consumed, len - consumed);
                     classify_batch();
                     break;
                 }
@@ -487,6 +633,7 @@ int main(int argc, char **argv) {
         ingest_device = false;
     }
     if (ingest_device && hast_rs_create(ctx, fastq ? HAST_RS_FASTQ : HAST_RS_FASTA, rs_block, &feed) != HAST_OK) die(4, "cannot create the device ingest");
+    if (feed && bin_reads && hast_rs_set_bins(feed, gz_out ? 2 : 1, bin_total[0], bin_total[1]) != HAST_OK) die(4, "cannot create the device ingest's bins");
     std::vector<uint8_t> rs_tail;
     // the device route for one input: its rows into out_rows; 1: the format error (its message is printed), 2: a record too long
     auto device_file = [&](const std::string &r) -> int {
@@ -506,8 +653,9 @@ int main(int argc, char **argv) {
         // frame and classify the oldest submitted block, format its rows
         auto step = [&]() {
             hast_rs_block b;
+            hast_rs_binned rb;
             const double t0 = now_s();
-            if (hast_rs_next(feed, &b) != HAST_OK) die(4, "framing and classifying a block");
+            if ((bin_reads ? hast_rs_next_binned(feed, &b, &rb) : hast_rs_next(feed, &b)) != HAST_OK) die(4, "framing and classifying a block");
             const double t1 = now_s();
             --pending;
             ++st_blocks;
@@ -517,6 +665,12 @@ int main(int argc, char **argv) {
             if (verdict) return;
             format_rows(out_rows, b.names, b.name_off, b.votes, (size_t)b.records, total_kmers);
             framed_records += b.records;
+            if (bin_reads)
+                for (int c = 0; c < 3; ++c) {
+                    if (!bins.write(c, rb.run[c], (size_t)rb.run_bytes[c])) bin_failed = true;
+                    st_bin[c] += rb.count[c];
+                    st_bin_dev += rb.raw_bytes[c];
+                }
             st_rows += now_s() - t1;
         };
         auto submit = [&](size_t n_bytes, bool last) {           // ... and keep one block ahead of the framer
@@ -589,6 +743,11 @@ int main(int argc, char **argv) {
             Batch tb;
             if (!tail_batch(reinterpret_cast<const char *>(rs_tail.data()), n_tail, tb.names, tb.bases, tb.offsets)) verdict = 1;
             else {
+                if (bin_reads && !tb.names.empty()) {
+                    tb.raw.assign(reinterpret_cast<const char *>(rs_tail.data()), n_tail);
+                    if (tb.raw.back() != '\n') tb.raw += '\n';
+                    tb.ext.assign(1, hast::rb::Extent{0, tb.raw.size()});
+                }
                 run_batch(tb);
                 if (!bg_error.empty()) die(4, bg_error);
             }
@@ -597,8 +756,17 @@ int main(int argc, char **argv) {
         return verdict;
     };
     const double t_phase = now_s();
-    for (const auto &r : read) {
+    // the format error: the input leaves no files, as it leaves no rows
+    auto give_up = [&]() {
+        if (bg.joinable()) bg.join();
+        if (bin_reads) bins.discard();
+        return 1;
+    };
+    for (size_t ri = 0; ri < read.size(); ++ri) {
+        const std::string &r = read[ri];
         fprintf(stderr, "__process read: %s\n", r.c_str());
+        if (bin_reads) bins.start(bin_dir, bin_base[ri], fastq ? "fastq" : "fasta", gz_out);
+        const uint64_t bin_before[5] = {st_bin[0], st_bin[1], st_bin[2], st_bin_dev, st_bin_host};
         bool on_device = false;
         if (feed) {
             struct stat sb;
@@ -607,17 +775,24 @@ int main(int argc, char **argv) {
                 st_fallback = "not_a_regular_file";
             } else {
                 const int v = device_file(r);
-                if (v == 1) return 1;
+                if (v == 1) return give_up();
                 on_device = v == 0;
                 if (v == 2) {
                     fprintf(stderr, "classify_read: WARN: a record of %s does not fit two blocks of %zu bytes: host ingest for this input (fallback=record_too_long)\n",
                             r.c_str(), rs_block);
                     st_fallback = "record_too_long";
+                    if (bin_reads) {                             // the file is read again from its start: so are its bins
+                        bins.discard();
+                        bins.start(bin_dir, bin_base[ri], fastq ? "fastq" : "fasta", gz_out);
+                        st_bin[0] = bin_before[0], st_bin[1] = bin_before[1], st_bin[2] = bin_before[2];
+                        st_bin_dev = bin_before[3], st_bin_host = bin_before[4];
+                    }
                 }
             }
         }
-        if (!on_device && host_file(r)) return 1;
+        if (!on_device && host_file(r)) return give_up();
         wait_bg();
+        if (bin_reads && (!bins.close_all() || bin_failed)) die(3, "writing the reads of " + r + " to " + bin_dir + " failed");
         if (fwrite(out_rows.data(), 1, out_rows.size(), stdout) != out_rows.size()) output_failed = true;
         fprintf(stderr, "__process read done__\n");
     }
@@ -625,6 +800,9 @@ int main(int argc, char **argv) {
         fprintf(stderr, "[stats] ingest %s: blocks_framed=%llu records=%llu gz_on_device=%llu fallback=%s\n", feed ? "device" : "host", (unsigned long long)st_blocks,
                 (unsigned long long)st_records, (unsigned long long)st_gz, st_fallback.c_str());
         fprintf(stderr, "[stats] seconds: read=%.3f upload=%.3f kernels=%.3f rows=%.3f read_phase=%.3f\n", st_read, st_upload, st_kernels, st_rows, now_s() - t_phase);
+        if (bin_reads)
+            fprintf(stderr, "[stats] bins: haplotype0=%llu haplotype1=%llu ambiguous=%llu bytes_on_device=%llu bytes_on_host=%llu gz=%d\n", (unsigned long long)st_bin[0],
+                    (unsigned long long)st_bin[1], (unsigned long long)st_bin[2], (unsigned long long)st_bin_dev, (unsigned long long)st_bin_host, gz_out ? 1 : 0);
     }
     if (feed) hast_rs_destroy(feed);
     // (mkoutput_by_fabulous2.0.sh redirects stdout into a file and goes on: a full disk or a closed pipe must not pass as exit 0)

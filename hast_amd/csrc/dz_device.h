@@ -36,6 +36,8 @@ hipError_t launch_job_one(Job *d_job, uint64_t n_bytes, hipStream_t s);         
 hipError_t launch_job_from_route(Job *d_job, const RouteState *d_rs, hipStream_t s);          // the four runs of a routed block, as they lie in its d_out
 // the two runs of a converted step of stage 02 (tx_feed.cpp): run 0 at offset 0, run 1 at second_off, d_run_bytes[0 .. 1] their sizes in device memory
 hipError_t launch_job_from_tx(Job *d_job, const uint64_t *d_run_bytes, uint64_t second_off, hipStream_t s);
+// the three runs of a binned view of stage 03 (rs_api.cpp): back to back from offset 0, d_run_bytes[0 .. 2] their sizes in device memory
+hipError_t launch_job_from_bins(Job *d_job, const uint64_t *d_run_bytes, hipStream_t s);
 // d_src + job.src_off[r] .. -> members from d_dst[0] on, never at or behind d_dst + cap; d_res says how long they are.
 // literals_only: no match search (Huffman coding alone)
 hipError_t launch_compress(const Job *d_job, const uint8_t *d_src, uint32_t max_pieces, void *d_work, uint8_t *d_dst, uint64_t cap, Result *d_res,

@@ -101,6 +101,21 @@ __global__ void k_dz_job_from_tx(Job *job, const uint64_t *run_bytes, uint64_t s
     job->emit_empty = 0;
 }
 
+// the three runs of a binned view of stage 03's read stream (rs_kernels.hip: k_rb_*): back to back from the buffer's first byte, their
+// sizes where k_rb_scan left them (RbState.raw_bytes); an empty run becomes nothing
+__global__ void k_dz_job_from_bins(Job *job, const uint64_t *run_bytes) {
+    const uint64_t n0 = run_bytes[0], n1 = run_bytes[1], n2 = run_bytes[2];
+    job->src_off[0] = 0;
+    job->n_bytes[0] = n0;
+    job->src_off[1] = n0;
+    job->n_bytes[1] = n1;
+    job->src_off[2] = n0 + n1;
+    job->n_bytes[2] = n2;
+    job->src_off[3] = job->n_bytes[3] = 0;
+    job->n_runs = 3;
+    job->emit_empty = 0;
+}
+
 __global__ void __launch_bounds__(64) k_dz_piece(const Job *d_job, const uint8_t *src, uint32_t max_pieces, void *d_work, int literals_only) {
     __shared__ uint32_t s_in[kPiece / 4 + 2];
     __shared__ uint32_t s_table[kHashSize];               // the match search's table, then the piece's output words
@@ -370,6 +385,10 @@ hipError_t launch_job_from_route(Job *d_job, const RouteState *d_rs, hipStream_t
 }
 hipError_t launch_job_from_tx(Job *d_job, const uint64_t *d_run_bytes, uint64_t second_off, hipStream_t s) {
     hipLaunchKernelGGL(k_dz_job_from_tx, dim3(1), dim3(1), 0, s, d_job, d_run_bytes, second_off);
+    return hipGetLastError();
+}
+hipError_t launch_job_from_bins(Job *d_job, const uint64_t *d_run_bytes, hipStream_t s) {
+    hipLaunchKernelGGL(k_dz_job_from_bins, dim3(1), dim3(1), 0, s, d_job, d_run_bytes);
     return hipGetLastError();
 }
 hipError_t launch_compress(const Job *d_job, const uint8_t *d_src, uint32_t max_pieces, void *d_work, uint8_t *d_dst, uint64_t cap, Result *d_res,

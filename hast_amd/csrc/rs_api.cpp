@@ -4,6 +4,7 @@
 
 #include <new>
 
+#include "dz_device.h"
 #include "hast_internal.h"
 #include "rs_device.h"
 
@@ -35,6 +36,17 @@ struct hast_rs {
     bool seen_header = false;                                // FASTA: a header line has been framed in this file
     bool file_done = false;                                  // FASTQ: the tail is a finished file's (hast_rs_take_tail)
     uint32_t given_up = 0;                                   // the flags that ended this file: its other blocks are not looked at
+    // the read bins (hast_rs_set_bins): nothing of this is allocated before they are first switched on
+    int bin_mode = 0;                                        // 0 off, 1 plain, 2 gzip
+    uint32_t bin_total[2] = {0, 0};
+    RbScratchPlan rb_plan{};
+    uint8_t *d_rb = nullptr, *d_out = nullptr, *h_out = nullptr;       // per-record arrays; the three runs of a view, device and pinned
+    RbState *h_rb = nullptr;                                 // pinned
+    uint8_t *d_gz = nullptr, *h_gz = nullptr, *d_dzwork = nullptr;     // gzip: the members, device and pinned; the encoder's workspace, job and result
+    dz::Job *d_dzjob = nullptr;
+    dz::Result *d_dzres = nullptr, *h_dzres = nullptr;
+    size_t gz_cap = 0, dzwork_bytes = 0;
+    uint32_t dz_pieces = 0;
 };
 
 extern "C" {
@@ -145,7 +157,55 @@ static hast_status rs_grow(hast_rs *f, size_t records, size_t name_bytes) {
     return HAST_OK;
 }
 
-hast_status hast_rs_next(hast_rs *f, hast_rs_block *out) {
+// the buffers of the bins, at the first switch-on of a mode that needs them
+static hast_status rb_alloc(hast_rs *f, int mode) {
+    const size_t view = 2 * f->block;
+    if (!f->d_rb) {
+        f->rb_plan = rb_scratch_plan(f->plan);
+        HAST_HIP_TRY(dev_malloc(&f->d_rb, f->rb_plan.total));
+        HAST_HIP_TRY(dev_malloc(&f->d_out, view + 64));
+        HAST_HIP_TRY(pinned_malloc(&f->h_rb, sizeof(RbState)));
+    }
+    if (mode == 1 && !f->h_out) HAST_HIP_TRY(pinned_malloc(&f->h_out, view));
+    if (mode == 2 && !f->d_gz) {
+        f->dz_pieces = dz::max_pieces(view);
+        f->gz_cap = (size_t)dz::max_out_bytes(view);
+        const size_t work = (dz::workspace_bytes(f->dz_pieces) + 63) & ~(size_t)63;
+        f->dzwork_bytes = work + sizeof(dz::Job) + sizeof(dz::Result);
+        HAST_HIP_TRY(dev_malloc(&f->d_dzwork, f->dzwork_bytes));
+        f->d_dzjob = reinterpret_cast<dz::Job *>(f->d_dzwork + work);
+        f->d_dzres = reinterpret_cast<dz::Result *>(f->d_dzjob + 1);
+        HAST_HIP_TRY(pinned_malloc(&f->h_gz, f->gz_cap));
+        HAST_HIP_TRY(pinned_malloc(&f->h_dzres, sizeof(dz::Result)));
+        HAST_HIP_TRY(dev_malloc(&f->d_gz, f->gz_cap));
+    }
+    return HAST_OK;
+}
+
+hast_status hast_rs_set_bins(hast_rs *f, int mode, uint32_t total0, uint32_t total1) {
+    if (!f) return set_error(HAST_ERR_INVALID, "null feed");
+    if (mode < 0 || mode > 2) return set_error(HAST_ERR_INVALID, "hast_rs_set_bins: mode %d", mode);
+    if (f->n_submitted != f->n_done) return set_error(HAST_ERR_INVALID, "hast_rs_set_bins: a submitted block waits for hast_rs_next");
+    HAST_HIP_TRY(hipSetDevice(f->device));
+    if (mode)
+        if (hast_status st = rb_alloc(f, mode)) return st;
+    f->bin_mode = mode;
+    f->bin_total[0] = total0;
+    f->bin_total[1] = total1;
+    return HAST_OK;
+}
+
+static hast_status rs_next(hast_rs *f, hast_rs_block *out, hast_rs_binned *bins);
+
+hast_status hast_rs_next(hast_rs *f, hast_rs_block *out) { return rs_next(f, out, nullptr); }
+
+hast_status hast_rs_next_binned(hast_rs *f, hast_rs_block *out, hast_rs_binned *bins) {
+    if (!bins) return set_error(HAST_ERR_INVALID, "null argument");
+    *bins = hast_rs_binned{};
+    return rs_next(f, out, bins);
+}
+
+static hast_status rs_next(hast_rs *f, hast_rs_block *out, hast_rs_binned *bins) {
     if (!f || !out) return set_error(HAST_ERR_INVALID, "null argument");
     if (f->n_done == f->n_submitted) return set_error(HAST_ERR_INVALID, "hast_rs_next: no block submitted");
     const int slot = (int)(f->n_done & 1);
@@ -196,7 +256,51 @@ hast_status hast_rs_next(hast_rs *f, hast_rs_block *out) {
     }
     HAST_HIP_TRY(hipMemcpyAsync(f->h_name_off, f->d_scratch + f->plan.name_off, (n_rec + 1) * 4, hipMemcpyDeviceToHost, f->stream));
     if (left) HAST_HIP_TRY(hipMemcpyAsync(f->d_in[slot ^ 1] + f->block - left, f->d_in[slot] + origin + s.consumed, left, hipMemcpyDeviceToDevice, f->stream));
+    const bool binned = bins && f->bin_mode && n_rec;
+    if (binned) {                                    // behind the classification: the votes are read where they lie
+        HAST_HIP_TRY(launch_rb_bin(f->format, f->d_in[slot], origin, n, f->bin_total[0], f->bin_total[1], f->d_scratch, f->plan, f->d_rb, f->rb_plan, f->d_out,
+                                   f->stream));
+        const RbState *d_state = reinterpret_cast<const RbState *>(f->d_rb + f->rb_plan.state);
+        HAST_HIP_TRY(hipMemcpyAsync(f->h_rb, d_state, sizeof(RbState), hipMemcpyDeviceToHost, f->stream));
+        if (f->bin_mode == 2) {
+            HAST_HIP_TRY(dz::launch_job_from_bins(f->d_dzjob, d_state->raw_bytes, f->stream));
+            HAST_HIP_TRY(dz::launch_compress(f->d_dzjob, f->d_out, f->dz_pieces, f->d_dzwork, f->d_gz, f->gz_cap, f->d_dzres, 0, f->stream));
+            HAST_HIP_TRY(hipMemcpyAsync(f->h_dzres, f->d_dzres, sizeof(dz::Result), hipMemcpyDeviceToHost, f->stream));
+        }
+    }
     if (hast_status st = framed_err(f->ctx, f->stream)) return st;           // (waits for the stream)
+    if (binned) {                                    // the sizes are known now: the runs (or their members) come down, and are waited for
+        const RbState b = *f->h_rb;
+        if (b.total > n || b.count[0] + b.count[1] + b.count[2] != n_rec) return set_error(HAST_ERR_INVALID, "hast_rs_next_binned: the runs do not add up");
+        uint64_t at = 0;
+        if (f->bin_mode == 1) {
+            if (b.total) HAST_HIP_TRY(hipMemcpyAsync(f->h_out, f->d_out, (size_t)b.total, hipMemcpyDeviceToHost, f->stream));
+            for (int c = 0; c < 3; ++c) {
+                bins->run[c] = f->h_out + at;
+                bins->run_bytes[c] = b.raw_bytes[c];
+                at += b.raw_bytes[c];
+            }
+        } else {
+            const dz::Result zr = *f->h_dzres;
+            if (zr.flags) return set_error(HAST_ERR_INVALID, "hast_rs_next_binned: the compressed runs do not fit (flags %u)", zr.flags);
+            for (int c = 0; c < 3; ++c) {
+                if (!zr.out_bytes[c]) {
+                    bins->run[c] = f->h_gz + at;
+                    continue;
+                }
+                if (zr.member_off[c] != at || at + zr.out_bytes[c] > f->gz_cap) return set_error(HAST_ERR_INVALID, "the compressed runs are not where they should be");
+                bins->run[c] = f->h_gz + at;
+                bins->run_bytes[c] = zr.out_bytes[c];
+                at += zr.out_bytes[c];
+            }
+            if (at) HAST_HIP_TRY(hipMemcpyAsync(f->h_gz, f->d_gz, (size_t)at, hipMemcpyDeviceToHost, f->stream));
+        }
+        for (int c = 0; c < 3; ++c) {
+            bins->raw_bytes[c] = b.raw_bytes[c];
+            bins->count[c] = b.count[c];
+        }
+        HAST_HIP_TRY(hipStreamSynchronize(f->stream));
+    }
     f->tail = left;
     f->file_done = last && left;                     // FASTQ only: a FASTA file's last view consumes everything
     out->records = n_rec;
@@ -241,6 +345,14 @@ void hast_rs_destroy(hast_rs *f) {
     park_pinned(f->h_votes, f->cap_rec * 8, 3);
     park_pinned(f->h_name_off, f->cap_rec * 4, 3);
     park_pinned(f->h_names, f->cap_names, 3);
+    park_device(f->d_rb, f->rb_plan.total, 3);
+    park_device(f->d_out, 2 * f->block + 64, 3);
+    park_pinned(f->h_out, 2 * f->block, 3);
+    park_pinned(f->h_rb, sizeof(RbState), 3);
+    park_device(f->d_gz, f->gz_cap, 3);
+    park_pinned(f->h_gz, f->gz_cap, 3);
+    park_device(f->d_dzwork, f->dzwork_bytes, 3);
+    park_pinned(f->h_dzres, sizeof(dz::Result), 3);
     if (f->up_stream) (void)hipStreamDestroy(f->up_stream);
     delete f;
 }

@@ -58,4 +58,37 @@ inline RsScratchPlan rs_scratch_plan(int format, size_t max_view) {
 hipError_t launch_rs_frame(int format, const uint8_t *d_base, size_t origin, size_t n, bool last, bool seen_header, uint8_t *d_seq, uint8_t *d_names,
                            uint8_t *d_scratch, const RsScratchPlan &plan, hipStream_t s);
 
+// ---- the read bins (`classify_read --bin-reads`, rules: rb_core.h) --------------------------------------------------------------
+struct RbState {               // device memory, copied to the host behind the partition
+    uint64_t count[3], raw_bytes[3];   // records and bytes per class
+    uint64_t total;                    // raw_bytes[0] + [1] + [2]: the runs lie back to back in the output buffer
+};
+
+constexpr uint32_t kRbCopyTile = kRsCopyTile;       // output bytes a workgroup of k_rb_copy owns at a time: k_rs_copy's figure, untuned there and here
+
+// scratch of its own, allocated when the bins are first switched on: per record its place and its offset in the output
+struct RbScratchPlan {
+    size_t order, dst, tile_cnt, tile_bytes, state, total;
+};
+inline RbScratchPlan rb_scratch_plan(const RsScratchPlan &rs) {
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t rec_tiles = rs.max_rec / kRsTile + 2;
+    RbScratchPlan p;
+    size_t at = 0;
+    p.order = at;      at += up(rs.max_rec * 4);
+    p.dst = at;        at += up((rs.max_rec + 1) * 4);
+    p.tile_cnt = at;   at += up(3 * rec_tiles * 4);
+    p.tile_bytes = at; at += up(3 * rec_tiles * 4);
+    p.state = at;      at += up(sizeof(RbState));
+    p.total = at;
+    return p;
+}
+
+// Behind launch_rs_frame and the classification of the same view, on the same stream: the records of the view d_base[origin, origin + n)
+// are classed by their votes (plan.votes of d_scratch) against the two set sizes and their extents copied to d_out (16-byte aligned,
+// room for n bytes) as three runs back to back, class 0 first.  When the stream has run, the RbState of d_rb says how long they are.
+// Nothing outside the view is read; nothing is written at or behind d_out + total.
+hipError_t launch_rb_bin(int format, const uint8_t *d_base, size_t origin, size_t n, uint32_t total0, uint32_t total1, const uint8_t *d_scratch,
+                         const RsScratchPlan &plan, uint8_t *d_rb, const RbScratchPlan &rb, uint8_t *d_out, hipStream_t s);
+
 }  // namespace hast

@@ -8,6 +8,7 @@
 //   k_rs_scan_names  exclusive scan of the name lengths per tile of 256 records
 //   k_rs_names       names gathered back to back: a wave copies its 64 records one after the other, 64 bytes a step
 //   k_rs_copy        FASTA: the sequence lines compacted into one base buffer, the work split by OUTPUT bytes
+//   k_rb_*           `--bin-reads` (rb_core.h), behind the classification: the records routed to three runs by their votes; see below
 // FASTQ reads are classified where they lie in the view; a FASTA read is spread over lines, and a k-mer straddles the line breaks,
 // so its lines are moved together.  Lines range from 60 columns to one line of 10^8 bases: k_rs_copy gives every workgroup a fixed
 // span of the destination and lets it find, by binary search in line_dst, the lines that reach into it.
@@ -15,6 +16,7 @@
 #include <stdint.h>
 
 #include "nl_index.h"
+#include "rb_core.h"
 #include "rs_device.h"
 
 namespace hast {
@@ -273,6 +275,175 @@ hipError_t launch_rs_frame(int format, const uint8_t *d_base, size_t origin, siz
     hipLaunchKernelGGL(k_rs_scan_names, dim3(1), dim3(1024), 0, s, name_tile, st);
     hipLaunchKernelGGL(k_rs_names, dim3(rec_grid), dim3(kRsTile), 0, s, in, st, name_pos, name_len, name_tile, name_off, d_names);
     if (fasta) hipLaunchKernelGGL(k_rs_copy, dim3(copy_grid), dim3(256), 0, s, in, st, nl, line_dst, hdr_line, d_seq);
+    return hipGetLastError();
+}
+
+// ---- the read bins (rb_core.h): every record, as it lies in the view, to the run of its class ------------------------------------
+//   k_rb_sums    a lane per record: class and extent; per tile of 256 records the records and the bytes of each class
+//   k_rb_scan    exclusive scans of the two tile sums, laid out class by class: a tile's entry is where its class-c records start
+//   k_rb_place   the stable partition: order[j] = the record at place j, dst[j] = its offset in the output (monotone: class 0's
+//                records in input order, then class 1's, then class 2's)
+//   k_rb_copy    k_rs_copy's scheme with records in place of lines and the permutation in front of it: the work is split by OUTPUT
+//                bytes, because a record is anything from ">\n" to one line of 10^8 bases
+struct RbRecord {
+    uint32_t cls, lo, len;
+};
+__device__ __forceinline__ RbRecord rb_record(bool fastq, const uint32_t *nl, uint32_t n_nl, const uint32_t *hdr_line, uint32_t m, const uint32_t *votes,
+                                              uint32_t total0, uint32_t total1, uint32_t r) {
+    uint32_t lo, hi;
+    if (fastq) rb::fq_extent(nl, r, &lo, &hi);
+    else rb::fa_extent(nl, n_nl, hdr_line, m, r, &lo, &hi);
+    RbRecord x;
+    x.cls = rb::read_class(votes[2 * (size_t)r], votes[2 * (size_t)r + 1], total0, total1);
+    x.lo = lo;
+    x.len = hi - lo;
+    return x;
+}
+
+__global__ void __launch_bounds__(kRsTile) k_rb_sums(int format, const RsState *st, const uint32_t *nl, const uint32_t *hdr_line, const uint32_t *votes,
+                                                     uint32_t total0, uint32_t total1, uint32_t *tile_cnt, uint32_t *tile_bytes) {
+    __shared__ uint32_t s_c[3][4], s_b[3][4];
+    const uint32_t n_rec = (uint32_t)st->records, n_tiles = (n_rec + kRsTile - 1) / kRsTile, n_nl = st->n_nl, m = st->n_hdr;
+    const bool fastq = format == RS_FASTQ;
+    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint32_t r = tile * kRsTile + threadIdx.x;
+        uint32_t cls = rb::kClasses, len = 0;
+        if (r < n_rec) {
+            const RbRecord x = rb_record(fastq, nl, n_nl, hdr_line, m, votes, total0, total1, r);
+            cls = x.cls;
+            len = x.len;
+        }
+        const uint32_t c0 = wave_sum(cls == 0), c1 = wave_sum(cls == 1), c2 = wave_sum(cls == 2);
+        const uint32_t b0 = wave_sum(cls == 0 ? len : 0), b1 = wave_sum(cls == 1 ? len : 0), b2 = wave_sum(cls == 2 ? len : 0);
+        __syncthreads();                                         // (the sums of the tile before have been read)
+        if ((threadIdx.x & 63) == 0) {
+            const uint32_t w = threadIdx.x >> 6;
+            s_c[0][w] = c0, s_c[1][w] = c1, s_c[2][w] = c2;
+            s_b[0][w] = b0, s_b[1][w] = b1, s_b[2][w] = b2;
+        }
+        __syncthreads();
+        if (threadIdx.x < 3) {
+            const uint32_t c = threadIdx.x;
+            tile_cnt[c * n_tiles + tile] = s_c[c][0] + s_c[c][1] + s_c[c][2] + s_c[c][3];
+            tile_bytes[c * n_tiles + tile] = s_b[c][0] + s_b[c][1] + s_b[c][2] + s_b[c][3];
+        }
+    }
+}
+
+__global__ void __launch_bounds__(1024) k_rb_scan(const RsState *st, uint32_t *tile_cnt, uint32_t *tile_bytes, RbState *rb) {
+    __shared__ uint32_t s_part[1024];
+    const uint32_t n_rec = (uint32_t)st->records, n_tiles = (n_rec + kRsTile - 1) / kRsTile;
+    const uint32_t records = block_exclusive_scan_1024(tile_cnt, 3 * n_tiles, s_part);
+    __syncthreads();                                             // (s_part is written again)
+    const uint32_t bytes = block_exclusive_scan_1024(tile_bytes, 3 * n_tiles, s_part);
+    __syncthreads();                                             // (the scanned sums of the other threads are read)
+    if (threadIdx.x < 3) {
+        const uint32_t c = threadIdx.x;
+        const uint32_t c_lo = n_tiles ? tile_cnt[c * n_tiles] : 0, c_hi = n_tiles && c < 2 ? tile_cnt[(c + 1) * n_tiles] : records;
+        const uint32_t b_lo = n_tiles ? tile_bytes[c * n_tiles] : 0, b_hi = n_tiles && c < 2 ? tile_bytes[(c + 1) * n_tiles] : bytes;
+        rb->count[c] = c_hi - c_lo;
+        rb->raw_bytes[c] = b_hi - b_lo;
+        if (c == 0) rb->total = bytes;
+    }
+}
+
+__global__ void __launch_bounds__(kRsTile) k_rb_place(int format, const RsState *st, const uint32_t *nl, const uint32_t *hdr_line, const uint32_t *votes,
+                                                      uint32_t total0, uint32_t total1, const uint32_t *tile_cnt, const uint32_t *tile_bytes, const RbState *rb,
+                                                      uint32_t *order, uint32_t *dst) {
+    __shared__ uint32_t s_wc[4], s_wb[4];
+    const uint32_t n_rec = (uint32_t)st->records, n_tiles = (n_rec + kRsTile - 1) / kRsTile, n_nl = st->n_nl, m = st->n_hdr;
+    const bool fastq = format == RS_FASTQ;
+    if (blockIdx.x == 0 && threadIdx.x == 0) dst[n_rec] = (uint32_t)rb->total;
+    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint32_t r = tile * kRsTile + threadIdx.x;
+        RbRecord x;
+        x.cls = rb::kClasses, x.lo = 0, x.len = 0;
+        if (r < n_rec) x = rb_record(fastq, nl, n_nl, hdr_line, m, votes, total0, total1, r);
+        uint32_t place = 0, at = 0;
+        for (uint32_t c = 0; c < rb::kClasses; ++c) {
+            const uint32_t ec = block_exclusive_sum_256(x.cls == c, s_wc), eb = block_exclusive_sum_256(x.cls == c ? x.len : 0, s_wb);
+            if (x.cls == c) {
+                place = tile_cnt[c * n_tiles + tile] + ec;
+                at = tile_bytes[c * n_tiles + tile] + eb;
+            }
+            __syncthreads();                                     // (s_wc, s_wb are written again)
+        }
+        if (r < n_rec) {
+            order[place] = r;
+            dst[place] = at;
+        }
+    }
+}
+
+// the smallest j in [lo, hi] with dst[j + 1] > v; the caller knows that place hi is one
+__device__ __forceinline__ uint32_t rb_first_place_past(const uint32_t *dst, uint32_t lo, uint32_t hi, uint32_t v) {
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (dst[mid + 1] > v) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
+}
+
+// out[0, total) = the three runs.  A workgroup takes kRbCopyTile output bytes at a time, finds the first and the last place that reach
+// into them, and every lane moves 16 bytes: it looks its first place up between those two and walks on from there -- one 16-byte load
+// as the source lies and one aligned 16-byte store where its bytes come from one record (out + p is 16-byte aligned), byte by byte
+// across record ends and at the end of the output.  A load never leaves its record's extent, so nothing outside the view is read.
+__global__ void __launch_bounds__(256) k_rb_copy(int format, const uint8_t *in, const RsState *st, const uint32_t *nl, const uint32_t *hdr_line, const RbState *rb,
+                                                 const uint32_t *order, const uint32_t *dst, uint8_t *out) {
+    const uint32_t n_rec = (uint32_t)st->records, total = (uint32_t)rb->total;
+    if (!n_rec || !total) return;
+    const bool fastq = format == RS_FASTQ;
+    const uint32_t n_tiles = (total + kRbCopyTile - 1) / kRbCopyTile;
+    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint32_t t0 = tile * kRbCopyTile, t1 = total - t0 < kRbCopyTile ? total : t0 + kRbCopyTile;
+        uint32_t p = t0 + threadIdx.x * 16;
+        if (p >= t1) continue;
+        const uint32_t e = t1 - p < 16 ? t1 : p + 16;
+        const uint32_t j0 = rb_first_place_past(dst, 0, n_rec - 1, t0);
+        const uint32_t j1 = rb_first_place_past(dst, j0, n_rec - 1, t1 - 1);
+        uint32_t j = rb_first_place_past(dst, j0, j1, p);
+        while (p < e) {
+            const uint32_t a = dst[j], b = dst[j + 1];
+            if (b <= p) {                                        // (an empty extent: there is none today)
+                ++j;
+                continue;
+            }
+            const uint32_t upto = b < e ? b : e, k = upto - p, r = order[j];
+            const uint8_t *src = in + rs::line_lo(nl, fastq ? 4 * r : hdr_line[r]) + (p - a);
+            if (k == 16) {
+                uint4 v;
+                __builtin_memcpy(&v, src, 16);
+                *reinterpret_cast<uint4 *>(out + p) = v;
+            } else {
+                for (uint32_t i = 0; i < k; ++i) out[p + i] = src[i];
+            }
+            p = upto;
+            ++j;
+        }
+    }
+}
+
+hipError_t launch_rb_bin(int format, const uint8_t *d_base, size_t origin, size_t n, uint32_t total0, uint32_t total1, const uint8_t *d_scratch,
+                         const RsScratchPlan &p, uint8_t *d_rb, const RbScratchPlan &q, uint8_t *d_out, hipStream_t s) {
+    const uint8_t *in = d_base + origin;
+    auto words = [&](size_t at) { return reinterpret_cast<const uint32_t *>(d_scratch + at); };
+    auto own = [&](size_t at) { return reinterpret_cast<uint32_t *>(d_rb + at); };
+    const uint32_t *nl = words(p.nl), *hdr_line = words(p.hdr_line), *votes = words(p.votes);
+    const RsState *st = reinterpret_cast<const RsState *>(d_scratch + p.state);
+    RbState *rb = reinterpret_cast<RbState *>(d_rb + q.state);
+    uint32_t *order = own(q.order), *dst = own(q.dst), *tile_cnt = own(q.tile_cnt), *tile_bytes = own(q.tile_bytes);
+    auto capped = [](size_t items, uint32_t per) {
+        const size_t t = (items + per - 1) / per;
+        return (uint32_t)(t < 1 ? 1 : t < 2048 ? t : 2048);
+    };
+    const uint32_t rec_grid = capped(format == RS_FASTA ? n / 2 + 1 : n / 4 + 1, kRsTile), copy_grid = capped(n, kRbCopyTile);
+    hipLaunchKernelGGL(k_rb_sums, dim3(rec_grid), dim3(kRsTile), 0, s, format, st, nl, hdr_line, votes, total0, total1, tile_cnt, tile_bytes);
+    hipLaunchKernelGGL(k_rb_scan, dim3(1), dim3(1024), 0, s, st, tile_cnt, tile_bytes, rb);
+    hipLaunchKernelGGL(k_rb_place, dim3(rec_grid), dim3(kRsTile), 0, s, format, st, nl, hdr_line, votes, total0, total1, (const uint32_t *)tile_cnt,
+                       (const uint32_t *)tile_bytes, (const RbState *)rb, order, dst);
+    hipLaunchKernelGGL(k_rb_copy, dim3(copy_grid), dim3(256), 0, s, format, in, st, nl, hdr_line, (const RbState *)rb, (const uint32_t *)order,
+                       (const uint32_t *)dst, d_out);
     return hipGetLastError();
 }
 

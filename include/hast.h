@@ -753,7 +753,18 @@ void        hast_sq_feed_destroy(hast_sq_feed *);
  *                         than block_bytes would have to be carried.  The file's other blocks, up to its `last` one, come back with
  *                         the same flags, unframed: a caller that stops reading submits an empty `last` block and takes it.
  *                         After a `last` block the next one starts a new file.
- *   hast_rs_take_tail     FASTQ, after the `last` block: the bytes behind the last complete record to dst (block_bytes of room). */
+ *   hast_rs_take_tail     FASTQ, after the `last` block: the bytes behind the last complete record to dst (block_bytes of room).
+ * The read bins (`classify_read --bin-reads`; rules: hast_amd/csrc/rb_core.h, model: rb_host.h): every record of a view, as its bytes
+ * lie in the input (FASTQ: its four lines; FASTA: from its header line to the next header line, blank lines and '\r' included; the last
+ * record of a file ends behind the last newline), goes to the run of its class -- 0 haplotype0, 1 haplotype1, 2 ambiguous, by the rule
+ * of the rows: d = votes / total, neither above 0: ambiguous, else d1 > d0: haplotype1, else haplotype0.  A run is the records of one
+ * class back to back in input order.  Bytes of no record (junk before a file's first header, an unterminated last FASTA line) go
+ * nowhere; a FASTQ file's tail is the caller's, as before.
+ *   hast_rs_set_bins      mode 0 off, 1 plain, 2 every run deflated on the GPU into one gzip member; total0 / total1: the two set
+ *                         sizes.  Only while no submitted block waits for _next (HAST_ERR_INVALID otherwise).  The buffers of the bins
+ *                         are allocated at the first switch-on and go with hast_rs_destroy: a feed that never asks has none.
+ *   hast_rs_next_binned   hast_rs_next plus the bins of the same view; returns when the runs lie in pinned memory.  With flags != 0,
+ *                         or with the bins switched off, *bins is all zero. */
 typedef struct hast_rs hast_rs;
 typedef struct {
     uint64_t consumed, records, bases, name_bytes;
@@ -771,6 +782,14 @@ hast_status hast_rs_host_block(hast_rs *, uint8_t **h_buf);
 hast_status hast_rs_device_block(hast_rs *, uint8_t **d_buf, hast_stream *fill);
 hast_status hast_rs_submit(hast_rs *, size_t n_bytes, int last);
 hast_status hast_rs_next(hast_rs *, hast_rs_block *out);
+typedef struct {
+    const uint8_t *run[3];      /* pinned, valid until the next hast_rs_next_binned; class 0, 1, 2 */
+    uint64_t run_bytes[3];      /* plain: the run; gzip: ONE complete gzip member, 0 bytes for an empty run */
+    uint64_t raw_bytes[3];      /* the runs' plain sizes either way */
+    uint64_t count[3];          /* records per class */
+} hast_rs_binned;
+hast_status hast_rs_set_bins(hast_rs *, int mode /* 0 off, 1 plain, 2 gzip */, uint32_t total0, uint32_t total1);
+hast_status hast_rs_next_binned(hast_rs *, hast_rs_block *out, hast_rs_binned *bins);
 hast_status hast_rs_take_tail(hast_rs *, uint8_t *dst, size_t *n_bytes);
 void        hast_rs_destroy(hast_rs *);
 
