@@ -80,7 +80,9 @@ class TxTimes(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("upload_s", "kernel_s", "deflate_s", "download_s")]
 
 
-SQ_NOT_FOUR_LINE, SQ_NO_RECORD = 1, 2
+SQ_NOT_FOUR_LINE, SQ_NO_RECORD, SQ_TAIL_TOO_LONG = 1, 2, 4
+SQ_FA_OPEN, SQ_FA_LAST = 1, 2
+SQ_TAKE_FASTQ, SQ_TAKE_FASTA = 1, 2
 RS_FASTA, RS_FASTQ = 0, 1
 RS_FORMAT_ERROR, RS_RECORD_TOO_LONG = 1, 4
 KC_HISTO_HIGH = 10000
@@ -226,6 +228,7 @@ ABI_SYMBOLS = {
     # stage 00 ingest on the device: four-line FASTQ in HBM -> the counter's base stream
     "hast_sq_create": (C.c_int, [vp, C.c_size_t, C.POINTER(vp)]),
     "hast_sq_frame_device": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(SqResult)]),
+    "hast_sq_frame_fasta_device": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_uint, C.POINTER(SqResult)]),
     "hast_sq_destroy": (None, [vp]),
     "hast_sq_feed_create": (C.c_int, [vp, C.c_size_t, C.POINTER(vp)]),
     "hast_sq_feed_host_block": (C.c_int, [vp, C.POINTER(vp)]),
@@ -234,6 +237,9 @@ ABI_SYMBOLS = {
     "hast_sq_feed_next": (C.c_int, [vp, C.c_int, C.POINTER(SqResult)]),
     "hast_sq_feed_take_tail": (C.c_int, [vp, vp, C.POINTER(C.c_size_t)]),
     "hast_sq_feed_destroy": (None, [vp]),
+    "hast_sq_feed_set_formats": (C.c_int, [vp, C.c_uint]),
+    "hast_sq_feed_format": (C.c_int, [vp]),
+    "hast_sq_feed_finish": (C.c_int, [vp, C.c_int, C.POINTER(SqResult)]),
     "hast_rs_create": (C.c_int, [vp, C.c_int, C.c_size_t, C.POINTER(vp)]),
     "hast_rs_host_block": (C.c_int, [vp, C.POINTER(vp)]),
     "hast_rs_device_block": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp)]),
@@ -808,9 +814,70 @@ class SqFramer:
         _ck(self._lib.hast_sq_frame_device(self._h, C.c_void_p(d_in), n_in, C.c_void_p(d_out), cap_out, C.byref(res)))
         return res
 
+    def frame_fasta_device(self, d_in, n_in, d_out, cap_out, in_flags=0) -> SqResult:
+        """a view of raw FASTA (SQ_FA_OPEN: a header came in an earlier view; SQ_FA_LAST: the input ends with it); cap_out >= n_in + 1"""
+        res = SqResult()
+        _ck(self._lib.hast_sq_frame_fasta_device(self._h, C.c_void_p(d_in), n_in, C.c_void_p(d_out), cap_out, in_flags, C.byref(res)))
+        return res
+
     def close(self):
         if self._h:
             self._lib.hast_sq_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class SqFeed:
+    """One input stream of `unshared_kmers --ingest device` (hast_sq_feed_*): raw bytes in, counted in the KmerCounter's table."""
+
+    def __init__(self, kc: KmerCounter, block_bytes, formats=SQ_TAKE_FASTQ):
+        self._lib = lib()
+        self.block = block_bytes
+        h = C.c_void_p()
+        _ck(self._lib.hast_sq_feed_create(kc._h, block_bytes, C.byref(h)))
+        self._h = h
+        if formats != SQ_TAKE_FASTQ:
+            self.set_formats(formats)
+
+    def set_formats(self, mask):
+        _ck(self._lib.hast_sq_feed_set_formats(self._h, mask))
+
+    @property
+    def format(self):
+        return self._lib.hast_sq_feed_format(self._h)
+
+    def submit(self, data: bytes):
+        """up to block_bytes through the pinned staging block"""
+        assert 0 < len(data) <= self.block
+        p = C.c_void_p()
+        _ck(self._lib.hast_sq_feed_host_block(self._h, C.byref(p)))
+        C.memmove(p, data, len(data))
+        _ck(self._lib.hast_sq_feed_submit(self._h, len(data)))
+
+    def next(self, parent) -> SqResult:
+        res = SqResult()
+        _ck(self._lib.hast_sq_feed_next(self._h, parent, C.byref(res)))
+        return res
+
+    def finish(self, parent) -> SqResult:
+        res = SqResult()
+        _ck(self._lib.hast_sq_feed_finish(self._h, parent, C.byref(res)))
+        return res
+
+    def take_tail(self) -> bytes:
+        buf = (C.c_uint8 * self.block)()
+        n = C.c_size_t()
+        _ck(self._lib.hast_sq_feed_take_tail(self._h, buf, C.byref(n)))
+        return bytes(buf[:n.value])
+
+    def close(self):
+        if self._h:
+            self._lib.hast_sq_feed_destroy(self._h)
             self._h = None
 
     def __enter__(self):

@@ -28,6 +28,7 @@ int ctx_device_of(const hast_ctx *c);
 hipStream_t ctx_stream_of(hast_ctx *c);
 size_t ctx_n_barcodes(const hast_ctx *c);
 int kc_device_of(const hast_kc *c);                                                                  // the count table's device (sq_api.cpp)
+int kc_k_of(const hast_kc *c);                                                                       // ... and its K
 // FREES THAT DO NOT STOP THE DEVICE.  hipFree and hipHostFree wait for every stream of the device and hold the runtime's lock while
 // they do: a stream that is closed while another one still decodes (the reader threads of `classify`, the upload thread of a .gz stream
 // that has sent its last byte) made every HIP call of the process wait 20-50 ms, 0.3 s on some boxes of the pool (tools/hipstall,

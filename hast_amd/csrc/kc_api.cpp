@@ -312,6 +312,7 @@ void hast_kc_destroy(hast_kc *c) {
 
 hast_stream hast_kc_stream(hast_kc *c) { return c ? (hast_stream)c->stream : nullptr; }
 int hast::kc_device_of(const hast_kc *c) { return c->device; }
+int hast::kc_k_of(const hast_kc *c) { return c->k; }
 
 hast_status hast_kc_set_slice(hast_kc *c, uint32_t slice, uint32_t n_slices) {
     if (hast_status st = need_table(c)) return st;

@@ -1,6 +1,6 @@
 // sq_core.h -- the rules by which a block of raw four-line FASTQ becomes the k-mer counter's base stream (stage 00 ingest on the
 // device).  Plain integer code: the framing kernels (sq_kernels.hip) and the host model (tests/native/test_sq_core.cpp) step the same
-// functions.
+// functions.  The rules for FASTA (namespace sqfa, `--device-fasta`) are at the end of the file.
 //
 // The stream is what SeqParser (seqstream.h) hands its sink: for every record the bytes of the sequence line, the '\r's in front of
 // the line break stripped, then one '\n'.  The device path takes exactly the inputs on which "a record is four lines" and SeqParser
@@ -54,4 +54,51 @@ SQ_HD bool record_at(const uint8_t *buf, const uint32_t *nl, uint32_t i, uint32_
 }
 
 }  // namespace sq
+
+// ---- FASTA (`unshared_kmers --device-fasta`): the stream SeqParser hands its sink in FASTA mode, view by view ----------------------
+// A view is [bytes carried from the view before | new bytes].  Its lines are the newline-terminated ones and, in a view framed with
+// `last`, the bytes behind the last newline if there are any (SeqParser::finish).  Per line, the '\r's at its end stripped:
+//   length 0        nothing
+//   first byte '>'  a header: one record; one '\n' if a record is open, i.e. a header came earlier in this INPUT -- in an earlier view
+//                   (open_in) or earlier in this one
+//   anything else   the line's bytes as they lie, '@' and '+' lines and non-bases included (the counter breaks at non-bases)
+// With `last` one closing '\n' follows if a record is open at the end of the view.  There is no format error behind an input's first
+// byte.  The kernels (sq_fasta_kernels.hip) and the host model (tests/native/test_sq_fasta.cpp) step these functions.
+#define SQ_FA_OPEN 1u
+#define SQ_FA_LAST 2u
+
+namespace sqfa {
+
+constexpr uint32_t kNothing = 0, kHeader = 1, kSequence = 2;
+
+// lines of a view of n_in bytes with n_nl newlines, nl[j] the offset of the j-th
+SQ_HD uint32_t n_lines(const uint32_t *nl, uint32_t n_nl, uint64_t n_in, bool last) {
+    const uint64_t behind = n_nl ? (uint64_t)nl[n_nl - 1] + 1 : 0;
+    return n_nl + (last && behind < n_in ? 1u : 0u);
+}
+SQ_HD uint32_t line_lo(const uint32_t *nl, uint32_t j) { return j ? nl[j - 1] + 1 : 0; }
+SQ_HD uint32_t line_hi(const uint32_t *nl, uint32_t n_nl, uint64_t n_in, uint32_t j) { return j < n_nl ? nl[j] : (uint32_t)n_in; }
+
+// class of the line [lo, hi); *len: its length without the '\r's at its end
+SQ_HD uint32_t line_class(const uint8_t *buf, uint32_t lo, uint32_t hi, uint32_t *len) {
+    *len = sq::line_len(buf, lo, hi);
+    return *len == 0 ? kNothing : buf[lo] == '>' ? kHeader : kSequence;
+}
+
+// What a line puts into the stream if every header emitted its '\n': the sums of these are what the kernels scan.  Only the view's
+// first header may emit none, so with `raw` the sum over the lines in front of a line and `hdrs` the headers among them:
+SQ_HD uint32_t raw_emit(uint32_t cls, uint32_t len) { return cls == kHeader ? 1u : cls == kSequence ? len : 0u; }
+// ... the line's bytes start at
+SQ_HD uint32_t line_dst(uint32_t raw, uint32_t hdrs, bool open_in) { return raw - (!open_in && hdrs ? 1u : 0u); }
+// ... and it emits
+SQ_HD uint32_t emit(uint32_t cls, uint32_t len, uint32_t hdrs, bool open_in) {
+    return cls == kHeader ? (open_in || hdrs ? 1u : 0u) : cls == kSequence ? len : 0u;
+}
+
+// the results of a view with m headers whose lines' raw_emit sum to raw_total
+SQ_HD uint64_t consumed(const uint32_t *nl, uint32_t n_nl, uint64_t n_in, bool last) { return last ? n_in : n_nl ? (uint64_t)nl[n_nl - 1] + 1 : 0; }
+SQ_HD uint32_t closing(uint32_t m, bool open_in, bool last) { return last && (open_in || m) ? 1u : 0u; }
+SQ_HD uint64_t bases(uint32_t raw_total, uint32_t m) { return raw_total - m; }
+
+}  // namespace sqfa
 }  // namespace hast

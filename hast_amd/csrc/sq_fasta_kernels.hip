@@ -1,0 +1,197 @@
+// sq_fasta_kernels.hip -- gfx950 device code: a view of raw FASTA in HBM becomes the base stream hast_kc_count_device eats (stage 00
+// ingest on the device, `unshared_kmers --device-fasta`).  The rules are sq_core.h's (namespace sqfa); the steps, all on one stream:
+//   k_sqfa_count / k_sqfa_scan / k_sqfa_index   the newline index (nl_index.h)
+//   k_sqfa_lines       a lane per line: stripped length, class, emitted bytes; per tile of 256 lines the headers and the emitted bytes
+//   k_sqfa_scan_lines  one workgroup scans both tile sums; the view's results
+//   k_sqfa_line_dst    a lane per line: line_dst[j] = where in the output line j's bytes start
+//   k_sqfa_copy        the lines compacted into the stream, the work split by OUTPUT bytes
+// A line is anything from a 7-column test file's through an assembler's 60 columns and a 150-base read to a chromosome on one line:
+// a lane or a wave per line would serialise the long ones and starve on the short ones, so k_sqfa_copy gives every workgroup a fixed
+// span of the destination and lets it find, by binary search in line_dst, the lines that reach into it (k_rs_copy's scheme).
+// The view and the output may start at any address: both are tiled at 16-byte boundaries of the ADDRESS, nothing outside
+// [d_in, d_in + n_in) is read and nothing at or behind d_out + out_bytes is written.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "nl_index.h"
+#include "sq_device.h"
+
+namespace hast {
+
+__global__ void __launch_bounds__(256) k_sqfa_count(const uint8_t *base, uint64_t lo, uint64_t hi, uint32_t *tile_cnt) {
+    const uint32_t c = nl_tile_count(base, blockIdx.x, lo, hi);
+    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = c;
+}
+
+__global__ void __launch_bounds__(1024) k_sqfa_scan(uint32_t *tile_cnt, uint32_t n, SqFaState *st) {
+    __shared__ uint32_t s_part[1024];
+    const uint32_t n_nl = block_exclusive_scan_1024(tile_cnt, n, s_part);
+    if (threadIdx.x == 0) {
+        st->consumed = st->out_bytes = st->records = st->bases = 0;
+        st->flags = 0;
+        st->first_bad = sq::kNoBad;
+        st->n_nl = n_nl;
+        st->n_lines = st->lines_bytes = 0;
+    }
+}
+
+// nl[j] = offset of the j-th newline from the view's first byte (base + lo)
+__global__ void __launch_bounds__(256) k_sqfa_index(const uint8_t *base, uint64_t lo, uint64_t hi, const uint32_t *tile_base, uint32_t *nl) {
+    nl_tile_index(base, blockIdx.x, lo, hi, lo, tile_base, nl);
+}
+
+struct SqFaLine {
+    uint32_t h, e;             // a header; sqfa::raw_emit
+};
+__device__ __forceinline__ SqFaLine sqfa_line(const uint8_t *in, const uint32_t *nl, uint32_t n_nl, uint64_t n_in, uint32_t j) {
+    uint32_t len;
+    const uint32_t cls = sqfa::line_class(in, sqfa::line_lo(nl, j), sqfa::line_hi(nl, n_nl, n_in, j), &len);
+    SqFaLine x;
+    x.h = cls == sqfa::kHeader;
+    x.e = sqfa::raw_emit(cls, len);
+    return x;
+}
+
+__global__ void __launch_bounds__(kSqFaTile) k_sqfa_lines(const uint8_t *in, uint64_t n_in, int last, SqFaState *st, const uint32_t *nl, uint32_t *tile_h,
+                                                          uint32_t *tile_e) {
+    __shared__ uint32_t s_h[4], s_e[4];
+    const uint32_t n_nl = st->n_nl, n_lines = sqfa::n_lines(nl, n_nl, n_in, last != 0), n_tiles = (n_lines + kSqFaTile - 1) / kSqFaTile;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        st->n_lines = n_lines;
+        st->consumed = sqfa::consumed(nl, n_nl, n_in, last != 0);
+    }
+    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint32_t j = tile * kSqFaTile + threadIdx.x;
+        SqFaLine x;
+        x.h = x.e = 0;
+        if (j < n_lines) x = sqfa_line(in, nl, n_nl, n_in, j);
+        const uint32_t ch = wave_sum(x.h), ce = wave_sum(x.e);
+        __syncthreads();                                         // (the sums of the tile before have been read)
+        if ((threadIdx.x & 63) == 0) {
+            s_h[threadIdx.x >> 6] = ch;
+            s_e[threadIdx.x >> 6] = ce;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            tile_h[tile] = s_h[0] + s_h[1] + s_h[2] + s_h[3];
+            tile_e[tile] = s_e[0] + s_e[1] + s_e[2] + s_e[3];
+        }
+    }
+}
+
+__global__ void __launch_bounds__(1024) k_sqfa_scan_lines(uint32_t *tile_h, uint32_t *tile_e, SqFaState *st, int open_in, int last) {
+    __shared__ uint32_t s_part[1024];
+    const uint32_t n_tiles = (st->n_lines + kSqFaTile - 1) / kSqFaTile;
+    const uint32_t m = block_exclusive_scan_1024(tile_h, n_tiles, s_part);
+    __syncthreads();                                             // (s_part is written again)
+    const uint32_t raw = block_exclusive_scan_1024(tile_e, n_tiles, s_part);
+    if (threadIdx.x == 0) {
+        const uint32_t lines_bytes = sqfa::line_dst(raw, m, open_in != 0);
+        st->records = m;
+        st->bases = sqfa::bases(raw, m);
+        st->lines_bytes = lines_bytes;
+        st->out_bytes = (uint64_t)lines_bytes + sqfa::closing(m, open_in != 0, last != 0);
+    }
+}
+
+__global__ void __launch_bounds__(kSqFaTile) k_sqfa_line_dst(const uint8_t *in, uint64_t n_in, const SqFaState *st, const uint32_t *nl, const uint32_t *tile_h,
+                                                             const uint32_t *tile_e, int open_in, uint32_t *line_dst) {
+    __shared__ uint32_t s_wh[4], s_we[4];
+    const uint32_t n_nl = st->n_nl, n_lines = st->n_lines, n_tiles = (n_lines + kSqFaTile - 1) / kSqFaTile;
+    if (blockIdx.x == 0 && threadIdx.x == 0) line_dst[n_lines] = st->lines_bytes;
+    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint32_t j = tile * kSqFaTile + threadIdx.x;
+        SqFaLine x;
+        x.h = x.e = 0;
+        if (j < n_lines) x = sqfa_line(in, nl, n_nl, n_in, j);
+        const uint32_t eh = tile_h[tile] + block_exclusive_sum_256(x.h, s_wh);
+        const uint32_t ee = tile_e[tile] + block_exclusive_sum_256(x.e, s_we);
+        if (j < n_lines) line_dst[j] = sqfa::line_dst(ee, eh, open_in != 0);
+        __syncthreads();                                         // (s_wh, s_we are written again)
+    }
+}
+
+// the smallest j in [lo, hi] with line_dst[j + 1] > v; the caller knows that line hi is one
+__device__ __forceinline__ uint32_t sqfa_first_line_past(const uint32_t *line_dst, uint32_t lo, uint32_t hi, uint32_t v) {
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (line_dst[mid + 1] > v) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
+}
+
+// out[0, lines_bytes) = what the lines emit, back to back, and the closing '\n' behind it.  out = out16 + olo with out16 16-byte
+// aligned: a workgroup takes kSqFaCopyTile bytes of out16 at a time, finds the first and the last line that reach into them, and every
+// lane moves the up to 16 bytes of its aligned piece that lie inside the output: it looks its first line up between those two and walks
+// on from there -- one 16-byte load as the source lies and one aligned 16-byte store where the bytes come from one line, byte by byte
+// across line ends and at both ends of the output.  A line that emits and starts with '>' is a header: its one byte is '\n'.  A load
+// never leaves its line, so nothing outside the view is read.
+__global__ void __launch_bounds__(256) k_sqfa_copy(const uint8_t *in, const SqFaState *st, const uint32_t *nl, const uint32_t *line_dst,
+                                                   uint8_t *out16, uint32_t olo) {
+    const uint32_t total = st->lines_bytes, n_lines = st->n_lines;
+    uint8_t *out = out16 + olo;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && st->out_bytes > total) out[total] = '\n';
+    if (!total) return;
+    const uint32_t q_end = olo + total, n_tiles = (q_end + kSqFaCopyTile - 1) / kSqFaCopyTile;
+    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint32_t t0q = tile * kSqFaCopyTile, t1q = q_end - t0q < kSqFaCopyTile ? q_end : t0q + kSqFaCopyTile;
+        const uint32_t q = t0q + threadIdx.x * 16, qs = q < olo ? olo : q, qe = q + 16 < t1q ? q + 16 : t1q;
+        if (q >= t1q || qs >= qe) continue;
+        uint32_t p = qs - olo;
+        const uint32_t e = qe - olo, t0 = (t0q < olo ? olo : t0q) - olo, t1 = t1q - olo;
+        const uint32_t j0 = sqfa_first_line_past(line_dst, 0, n_lines - 1, t0);
+        const uint32_t j1 = sqfa_first_line_past(line_dst, j0, n_lines - 1, t1 - 1);
+        uint32_t j = sqfa_first_line_past(line_dst, j0, j1, p);
+        while (p < e) {
+            const uint32_t a = line_dst[j], b = line_dst[j + 1];
+            if (b <= p) {                                        // an empty line, the header that opens the input: nothing of it is output
+                ++j;
+                continue;
+            }
+            const uint32_t upto = b < e ? b : e, k = upto - p;
+            const uint8_t *line = in + sqfa::line_lo(nl, j);
+            if (line[0] == '>') {
+                out[p] = '\n';
+            } else if (k == 16) {
+                uint4 v;
+                __builtin_memcpy(&v, line + (p - a), 16);
+                *reinterpret_cast<uint4 *>(out + p) = v;
+            } else {
+                const uint8_t *src = line + (p - a);
+                for (uint32_t i = 0; i < k; ++i) out[p + i] = src[i];
+            }
+            p = upto;
+            ++j;
+        }
+    }
+}
+
+hipError_t launch_sq_fasta_frame(const uint8_t *d_in, size_t n_in, uint8_t *d_out, unsigned in_flags, uint8_t *d_scratch, const SqFaScratchPlan &p,
+                                 hipStream_t s) {
+    const uint64_t lo = reinterpret_cast<uintptr_t>(d_in) & 15, hi = lo + n_in;
+    const uint8_t *base = d_in - lo;
+    const uint32_t olo = (uint32_t)(reinterpret_cast<uintptr_t>(d_out) & 15);
+    const int open_in = (in_flags & SQ_FA_OPEN) != 0, last = (in_flags & SQ_FA_LAST) != 0;
+    const uint32_t n_tiles = (uint32_t)((hi + kNlTile - 1) / kNlTile), grid = n_tiles ? n_tiles : 1;
+    auto words = [&](size_t at) { return reinterpret_cast<uint32_t *>(d_scratch + at); };
+    uint32_t *tile_cnt = words(p.tile_cnt), *nl = words(p.nl), *tile_h = words(p.tile_h), *tile_e = words(p.tile_e), *line_dst = words(p.line_dst);
+    SqFaState *st = reinterpret_cast<SqFaState *>(d_scratch + p.state);
+    auto capped = [](size_t items, uint32_t per) {
+        const size_t t = (items + per - 1) / per;
+        return (uint32_t)(t < 1 ? 1 : t < 2048 ? t : 2048);
+    };
+    const uint32_t line_grid = capped(n_in + 1, kSqFaTile), copy_grid = capped(n_in + 16, kSqFaCopyTile);
+    hipLaunchKernelGGL(k_sqfa_count, dim3(grid), dim3(256), 0, s, base, lo, hi, tile_cnt);
+    hipLaunchKernelGGL(k_sqfa_scan, dim3(1), dim3(1024), 0, s, tile_cnt, grid, st);
+    hipLaunchKernelGGL(k_sqfa_index, dim3(grid), dim3(256), 0, s, base, lo, hi, (const uint32_t *)tile_cnt, nl);
+    hipLaunchKernelGGL(k_sqfa_lines, dim3(line_grid), dim3(kSqFaTile), 0, s, d_in, (uint64_t)n_in, last, st, (const uint32_t *)nl, tile_h, tile_e);
+    hipLaunchKernelGGL(k_sqfa_scan_lines, dim3(1), dim3(1024), 0, s, tile_h, tile_e, st, open_in, last);
+    hipLaunchKernelGGL(k_sqfa_line_dst, dim3(line_grid), dim3(kSqFaTile), 0, s, d_in, (uint64_t)n_in, (const SqFaState *)st, (const uint32_t *)nl,
+                       (const uint32_t *)tile_h, (const uint32_t *)tile_e, open_in, line_dst);
+    hipLaunchKernelGGL(k_sqfa_copy, dim3(copy_grid), dim3(256), 0, s, d_in, (const SqFaState *)st, (const uint32_t *)nl, (const uint32_t *)line_dst,
+                       d_out - olo, olo);
+    return hipGetLastError();
+}
+
+}  // namespace hast

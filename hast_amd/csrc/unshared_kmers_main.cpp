@@ -12,7 +12,8 @@
 // Extra options: --device N (repeat it, or --devices a,b,c, to split the key space over several GPUs), --table-gb X (size of the count table per GPU; default: from the input size, at most 85 % of the free HBM), --slices S (process
 // the key space in S passes over the input; doubled automatically when the table overflows), --save-table FILE (the
 // two sets as a binary stage-01 table for `classify --load-table`), --stats, --ingest host|device (HAST_KC_INGEST; device: the files'
-// bytes are inflated and framed on the GPU, see "ingest on the device" below; default host).
+// bytes are inflated and framed on the GPU, see "ingest on the device" below; default host), --device-fasta (HAST_KC_DEVICE_FASTA=1;
+// with --ingest device: FASTA parents are framed on the GPU too instead of going back to the host parser; default off).
 // Exit status: 0 ok / usage; 1 bad arguments, missing or malformed input (the script: exit 1); 4 GPU trouble.
 //
 // Layout: main(), at the end, is the list of the run's phases; each phase is a function above it, in that order.  What the command
@@ -56,7 +57,9 @@ void usage(FILE *f) {
           "    --device N (repeatable) / --devices a,b,c   GPUs; the k-mer space is split between them\n"
           "    --table-gb X  --slices S  --save-table FILE  --stats\n"
           "    --ingest host|device   device: inflate .gz and frame four-line FASTQ on the GPU (one GPU; anything else\n"
-          "                      is read by the host parser after all); default host, or HAST_KC_INGEST\n",
+          "                      is read by the host parser after all); default host, or HAST_KC_INGEST\n"
+          "    --device-fasta    with --ingest device: frame FASTA on the GPU too (records of any length, a line has to fit\n"
+          "                      a block); without it a FASTA parent goes back to the host parser; or HAST_KC_DEVICE_FASTA=1\n",
           f);
 }
 
@@ -73,6 +76,7 @@ struct Options {
     long slices = 1;
     std::string save_table;
     std::string ingest = "host";     // --ingest host|device
+    bool device_fasta = false;       // --device-fasta
 };
 
 // ---- ingest: files -> byte stream of bases -> GPU ---------------------------------------------------------------
@@ -286,6 +290,8 @@ bool gz_files_are_one_stream(const std::vector<Job> &jobs) {
 // The host only moves raw bytes: a .gz file is inflated on the GPU straight into the framer's input (hast_gz_*), anything else is
 // read (or, where hast_gz_open passes, inflated by BlockSource) into pinned memory and uploaded; the framer (hast_sq_*, sq_core.h)
 // turns four-line FASTQ into the base stream and hast_kc_count_device counts it.  One feed per parent's input stream, as a thread.
+// With --device-fasta the feed takes FASTA as well: an input's first byte decides, as it does for SeqParser, and a FASTA input ends in
+// the feed itself (hast_sq_feed_finish) -- there is no tail for the parser, and no record is too long, only a line.
 // The gz files of a parent are read IN ORDER as one stream (`zcat a b`): what file a leaves unframed is carried in front of file
 // b's bytes.  At the end of an input the bytes behind the last complete record go through SeqParser and the ChunkSink, so the
 // unterminated last line and the "ends inside a quality string" error stay the parser's.  Whatever the framer refuses -- a record
@@ -297,6 +303,8 @@ struct DeviceIngest {
     std::mutex mu;
     std::string refused;             // first refusal of the sweep
     uint64_t blocks_framed = 0, gz_on_device = 0;
+    bool fasta = false;              // --device-fasta
+    uint64_t fastq_blocks = 0, fasta_blocks = 0;
     std::string fallback = "none";   // why the host ingest ran after all
     void refuse(const std::string &why) {
         std::lock_guard<std::mutex> g(mu);
@@ -326,7 +334,7 @@ struct DeviceStream {
     ChunkSink sink;
     std::vector<uint8_t> tail;
     int pending = 0;                 // blocks submitted and not framed yet
-    uint64_t blocks = 0, gz_dev = 0;
+    uint64_t blocks = 0, gz_dev = 0, fa_blocks = 0;
     size_t bases = 0;
 
     bool good() { return res.error.empty() && gpu.ok() && !di.is_refused(); }
@@ -351,7 +359,8 @@ struct DeviceStream {
             di.refuse("a full block holds no record");
             return false;
         }
-        if (r.records) ++blocks;
+        if (r.records || r.out_bytes) ++blocks;      // (a FASTA view may hold the middle of a record and no header)
+        if ((r.records || r.out_bytes) && hast_sq_feed_format(feed) == 2) ++fa_blocks;
         res.records += r.records;
         bases += r.bases;
         return true;
@@ -365,6 +374,14 @@ struct DeviceStream {
     bool end_of_input(const std::string &path) {
         while (pending)
             if (!step()) return false;
+        if (hast_sq_feed_format(feed) == 2) {        // FASTA ends in the feed: the unterminated last line and the closing separator
+            hast_sq_result r;
+            std::lock_guard<std::mutex> g(table_mu);
+            if (!ck(hast_sq_feed_finish(feed, job.parent, &r))) return false;
+            res.records += r.records;
+            bases += r.bases;
+            return true;
+        }
         size_t n = 0;
         {
             std::lock_guard<std::mutex> g(table_mu);
@@ -425,7 +442,7 @@ struct DeviceStream {
             if (!h) break;
             const size_t n = fread(h, 1, di.block, fp);
             if (n == 0) break;
-            if (first && h[0] != '@') {
+            if (first && h[0] != '@' && !(di.fasta && h[0] == '>')) {
                 di.refuse(h[0] == '>' ? path + " is FASTA" : path + " does not start with '@'");
                 break;
             }
@@ -452,6 +469,8 @@ struct DeviceStream {
         std::lock_guard<std::mutex> g(di.mu);
         di.blocks_framed += blocks;
         di.gz_on_device += gz_dev;
+        di.fasta_blocks += fa_blocks;
+        di.fastq_blocks += blocks - fa_blocks;
     }
 };
 
@@ -462,6 +481,11 @@ void ingest_device_stream(Gpu &gpu, DeviceIngest &di, int k, Job &job) {
         std::lock_guard<std::mutex> g(*gpu.dev_mu[0]);
         if (hast_sq_feed_create(gpu.kc, di.block, &feed) != HAST_OK) {
             gpu.fail(hast_last_error());
+            return;
+        }
+        if (di.fasta && hast_sq_feed_set_formats(feed, HAST_SQ_TAKE_FASTQ | HAST_SQ_TAKE_FASTA) != HAST_OK) {
+            gpu.fail(hast_last_error());
+            hast_sq_feed_destroy(feed);
             return;
         }
     }
@@ -515,7 +539,7 @@ bool parse_command_line(int argc, char **argv, Options &o, int &status) {
     printf("CMD :");
     for (int i = 0; i < argc; ++i) printf(" %s", argv[i]);
     printf("\n");
-    bool ingest_given = false;
+    bool ingest_given = false, device_fasta_given = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto val = [&]() -> const char * { return i + 1 < argc ? argv[++i] : ""; };
@@ -543,6 +567,7 @@ bool parse_command_line(int argc, char **argv, Options &o, int &status) {
         else if (a == "--save-table") o.save_table = val();
         else if (a == "--stats") o.stats = true;
         else if (a == "--ingest") { o.ingest = val(); ingest_given = true; }
+        else if (a == "--device-fasta") o.device_fasta = device_fasta_given = true;
         else {                                                                  // s00:113-116: message, then a bare `exit`
             printf("unknown option \"%s\"\n", a.c_str());
             return false;
@@ -550,6 +575,8 @@ bool parse_command_line(int argc, char **argv, Options &o, int &status) {
     }
     if (!ingest_given)
         if (const char *e = getenv("HAST_KC_INGEST")) o.ingest = e;
+    if (!device_fasta_given)
+        if (const char *e = getenv("HAST_KC_DEVICE_FASTA")) o.device_fasta = atol(e) != 0;
     if (o.ingest != "host" && o.ingest != "device") {
         printf("ERROR: --ingest %s: host or device\n", o.ingest.c_str());
         status = 1;
@@ -636,6 +663,7 @@ void set_up_device_ingest(Run &r) {
         return;
     }
     r.di.on = true;
+    r.di.fasta = o.device_fasta;
     if (const char *e = getenv("HAST_KC_INGEST_BLOCK"))
         if (atol(e) >= 64) r.di.block = (size_t)atol(e);
     bool any_gz = false;
@@ -705,7 +733,7 @@ Sweep sweep(Run &r, bool take_histo, bool take_sets) {
     const long n_dev = (long)gpu.all.size();
     for (int p = 0; p < 2 && take_histo; ++p) r.histo[p].assign(HAST_KC_HISTO_HIGH + 2, 0);
     for (auto &x : r.stats_sum) x = 0;
-    r.di.blocks_framed = r.di.gz_on_device = 0;
+    r.di.blocks_framed = r.di.gz_on_device = r.di.fastq_blocks = r.di.fasta_blocks = 0;
     if (take_sets)                                                              // a sweep that starts over starts from nothing
         for (hast_kc *k : gpu.all)
             if (hast_kc_selection_clear(k) != HAST_OK) return Sweep::GpuError;
@@ -862,6 +890,9 @@ void print_stats(const Run &r) {
     if (o.ingest == "device")
         fprintf(stderr, "[stats] ingest device: blocks_framed=%llu gz_on_device=%llu fallback=%s\n", (unsigned long long)r.di.blocks_framed,
                 (unsigned long long)r.di.gz_on_device, r.di.fallback.c_str());
+    if (o.ingest == "device" && o.device_fasta)
+        fprintf(stderr, "[stats] ingest device formats: fastq_blocks=%llu fasta_blocks=%llu\n", (unsigned long long)r.di.fastq_blocks,
+                (unsigned long long)r.di.fasta_blocks);
     fprintf(stderr, "[stats] table %.3f s, read+parse+count %.3f s, table passes %.3f s, output %.3f s, total %.3f s\n", r.t_table - r.t_start, r.t_ingest,
             r.t_count - r.t_table - r.t_ingest, r.t_end - r.t_count, r.t_end - r.t_start);
 }

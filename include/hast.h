@@ -704,6 +704,17 @@ typedef struct { uint64_t consumed, out_bytes, records, bases; uint32_t flags, f
 hast_status hast_sq_create(hast_kc *, size_t max_in_bytes, hast_sq **out);
 hast_status hast_sq_frame_device(hast_sq *, const uint8_t *d_in, size_t n_in, uint8_t *d_out, size_t cap_out, hast_sq_result *res);
 void        hast_sq_destroy(hast_sq *);
+/* FASTA, by the same framer: the stream that parser hands the counter in FASTA mode (hast_amd/csrc/sq_core.h, namespace sqfa).  A view
+ * is [bytes carried from the view before | new bytes]; its lines are the newline-terminated ones and, with HAST_SQ_FA_LAST, the bytes
+ * behind the last newline.  An empty line (its trailing '\r's stripped) gives nothing; a '>' line counts one record and gives one '\n'
+ * if a record is open -- a header came earlier in this input: HAST_SQ_FA_OPEN says "in an earlier view"; every other line gives its
+ * bytes as they lie.  With HAST_SQ_FA_LAST one closing '\n' follows if a record is open.  consumed = the byte behind the last newline,
+ * or n_in with HAST_SQ_FA_LAST; bases = the bytes written that are no separators; flags 0, first_bad 0xFFFFFFFF: FASTA has no format
+ * error behind its first byte.  n_in == 0 is valid.  cap_out >= n_in + 1; alignment, reads and writes as hast_sq_frame_device.  The
+ * scratch (~8 bytes per byte of max_in_bytes) is allocated by the first call. */
+#define HAST_SQ_FA_OPEN 1u
+#define HAST_SQ_FA_LAST 2u
+hast_status hast_sq_frame_fasta_device(hast_sq *, const uint8_t *d_in, size_t n_in, uint8_t *d_out, size_t cap_out, unsigned in_flags, hast_sq_result *res);
 
 /* The feed of one input stream of `unshared_kmers --ingest device`: two input and two output buffers on the device and two pinned
  * staging blocks, so that the upload of block n+1 (a stream of the feed's own) overlaps the framing and counting of block n.
@@ -726,6 +737,22 @@ hast_status hast_sq_feed_submit(hast_sq_feed *, size_t n_bytes);
 hast_status hast_sq_feed_next(hast_sq_feed *, int parent, hast_sq_result *res);
 hast_status hast_sq_feed_take_tail(hast_sq_feed *, uint8_t *dst, size_t *n_bytes);
 void        hast_sq_feed_destroy(hast_sq_feed *);
+/* FASTA through the feed:
+ *   hast_sq_feed_set_formats   HAST_SQ_TAKE_FASTQ (the default), or HAST_SQ_TAKE_FASTQ | HAST_SQ_TAKE_FASTA; only while nothing is
+ *                              submitted and nothing is carried.  With FASTA taken, the first byte of an input's first view decides as
+ *                              it does for the host parser: '>' makes the input FASTA until its end, anything else goes the FASTQ way.
+ *   hast_sq_feed_format        of the current input: 0 undecided, 1 FASTQ, 2 FASTA
+ *   hast_sq_feed_next          on a FASTA input: frames the view with the feed's own open state and counts its stream with the last
+ *                              min(K - 1, stream so far) bytes emitted for this input in front, so that the windows across a view
+ *                              boundary are counted exactly once; records of any length pass, only a LINE longer than block_bytes
+ *                              is HAST_SQ_TAIL_TOO_LONG.
+ *   hast_sq_feed_finish        ends a FASTA input: frames what is carried as the last view (possibly no byte), counts it, and starts
+ *                              the next input undecided.  HAST_ERR_INVALID on a FASTQ or undecided input (hast_sq_feed_take_tail). */
+#define HAST_SQ_TAKE_FASTQ 1u
+#define HAST_SQ_TAKE_FASTA 2u
+hast_status hast_sq_feed_set_formats(hast_sq_feed *, unsigned mask);
+int         hast_sq_feed_format(hast_sq_feed *);
+hast_status hast_sq_feed_finish(hast_sq_feed *, int parent, hast_sq_result *res);
 
 /* ---- stage 03 ingest on the device: raw FASTA / four-line FASTQ in HBM -> per-read votes (`classify_read --ingest device`) ------
  * The "read stream" feed frames the reads of the per-read classifier on the GPU and classifies them where they lie
