@@ -553,7 +553,7 @@ std::string finish_segment(hast_gz *g, const Nominal &N, bool &finished) {
             host[i].sym = reinterpret_cast<const uint16_t *>((uintptr_t)(a.tag * 2));
             host[i].out_off = a.out_off;
             host[i].n_out = a.job.n_out;
-            host[i].no_history = a.no_history ? 1u : 0u;
+            host[i].hist_floor = a.hist_floor;
         }
         b->out_lo = b->acc.front().out_off;
         b->out_hi = b->acc.back().out_off + b->acc.back().job.n_out;
@@ -562,14 +562,14 @@ std::string finish_segment(hast_gz *g, const Nominal &N, bool &finished) {
             GZ_HIP(A.acc.ensure(n * sizeof(AccDev)));
             GZ_HIP(A.windows.ensure(n * (size_t)kWindow));
             GZ_HIP(A.need.ensure(windows_scratch_bytes((uint32_t)n)));
-            GZ_HIP(A.crc.ensure(n * sizeof(uint32_t)));
+            GZ_HIP(A.crc.ensure(2 * n * sizeof(uint32_t)));                 // (CRC-32 per chunk, then "a marker below the floor" per chunk)
             GZ_HIP(A.carry.ensure(kWindow));
         }
         if (U.h_crc_cap < n) {
             park_pinned(U.h_crc, 0, 2);
             U.h_crc = nullptr;
             U.h_crc_cap = 0;
-            GZ_HIP(pinned_malloc((void **)&U.h_crc, (n + n / 2 + 64) * sizeof(uint32_t), hipHostMallocDefault));
+            GZ_HIP(pinned_malloc((void **)&U.h_crc, 2 * (n + n / 2 + 64) * sizeof(uint32_t), hipHostMallocDefault));
             U.h_crc_cap = n + n / 2 + 64;
         }
         // (pageable source: the copy is done with `host` when the call returns)
@@ -582,8 +582,8 @@ std::string finish_segment(hast_gz *g, const Nominal &N, bool &finished) {
         // the 32 KB in front of this batch: what the batch before it left (pinned host memory: the batch before may live on another GPU)
         GZ_HIP(hipMemcpyAsync(A.carry.p, g->h_carry, kWindow, hipMemcpyHostToDevice, U.post_stream));
         GZ_HIP(launch_windows((const AccDev *)A.acc.p, (uint32_t)n, (uint8_t *)A.windows.p, (const uint8_t *)A.carry.p, A.need.p, U.post_stream));
-        GZ_HIP(launch_crc((const AccDev *)A.acc.p, (uint32_t)n, (const uint8_t *)A.windows.p, (const uint8_t *)A.carry.p, (uint32_t *)A.crc.p, U.post_stream));
-        GZ_HIP(hipMemcpyAsync(U.h_crc, A.crc.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, U.post_stream));
+        GZ_HIP(launch_crc((const AccDev *)A.acc.p, (uint32_t)n, (const uint8_t *)A.windows.p, (const uint8_t *)A.carry.p, (uint32_t *)A.crc.p, (uint32_t *)A.crc.p + n, U.post_stream));
+        GZ_HIP(hipMemcpyAsync(U.h_crc, A.crc.p, 2 * n * sizeof(uint32_t), hipMemcpyDeviceToHost, U.post_stream));
         GZ_HIP(hipStreamSynchronize(U.post_stream));                        // (h_carry has been read: the copy above is through)
         GZ_HIP(hipMemcpyAsync(g->h_carry, (uint8_t *)A.windows.p + (n - 1) * (size_t)kWindow, kWindow, hipMemcpyDeviceToHost, U.post_stream));
         GZ_HIP(hipStreamSynchronize(U.post_stream));
@@ -591,6 +591,8 @@ std::string finish_segment(hast_gz *g, const Nominal &N, bool &finished) {
         for (size_t i = 0; i < n && bad.empty(); ++i) {
             const Accepted &a = b->acc[i];
             const uint32_t len = a.job.n_out;
+            // a match that reached in front of its member's first byte (k_gz_crc): what it copied is not the member's data, whatever the trailer says
+            if (U.h_crc[n + i]) { bad = "gz: damaged input (distance too far back)"; break; }
             if (len) {
                 g->crc_acc = g->crc_started ? crc_combine_op(g->crc_acc, U.h_crc[i], crc_x2nmodp(len, 3)) : U.h_crc[i];
                 g->crc_started = true;
@@ -889,7 +891,7 @@ hast_status hast_gz_open_multi_ex(hast_ctx *const *ctxs, int n_ctx, const char *
                 step(a.acc.ensure(n_max * sizeof(AccDev)));
                 step(a.windows.ensure(n_max * (size_t)kWindow));
                 step(a.need.ensure(windows_scratch_bytes((uint32_t)n_max)));
-                step(a.crc.ensure(n_max * sizeof(uint32_t)));
+                step(a.crc.ensure(2 * n_max * sizeof(uint32_t)));
                 step(a.carry.ensure(kWindow));
                 a.gap.emplace_back();
                 step(a.gap[0].ensure(8u << 20));                                    // (a round of follow-up jobs' symbols; grows when one needs more)
@@ -897,7 +899,7 @@ hast_status hast_gz_open_multi_ex(hast_ctx *const *ctxs, int n_ctx, const char *
                     park_pinned(U.h_crc, 0, 2);
                     U.h_crc = nullptr;
                     U.h_crc_cap = 0;
-                    step(pinned_malloc((void **)&U.h_crc, (n_max + n_max / 2 + 64) * sizeof(uint32_t), hipHostMallocDefault));
+                    step(pinned_malloc((void **)&U.h_crc, 2 * (n_max + n_max / 2 + 64) * sizeof(uint32_t), hipHostMallocDefault));
                     if (e == hipSuccess) U.h_crc_cap = n_max + n_max / 2 + 64;
                 }
             }

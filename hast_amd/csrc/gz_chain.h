@@ -9,6 +9,7 @@
 // its target, so one round of jobs usually closes all holes -- and checked when their results are back.
 // Pure host code, no HIP: tests/native/test_gz_core.cpp drives it with a CPU stand-in for the kernels.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <functional>
@@ -23,7 +24,14 @@ namespace gz {
 struct Accepted {
     ChunkJob job;                // as decoded (sym_off / n_out say where its symbols are)
     uint64_t out_off = 0;        // offset of its first byte in the inflated stream
-    bool no_history = false;     // a member starts with it: its symbols hold no markers
+    bool no_history = false;     // a member starts with it.  The chain's own bookkeeping (finish_item: a member's first job that got
+                                 // nowhere); readers of the symbols go by hist_floor, of which this is the case kWindow
+    // A match may not reach in front of its member's first byte -- in ANY chunk of the member, and a chunk is decoded before anyone
+    // knows how much of its member lies in front of it.  hist_floor = kWindow - min(kWindow, bytes of the member in front of this
+    // chunk), set when the chunk's offset is final (confirm): a marker kMarker + i with i < hist_floor stands for a byte in front of
+    // the member, and whoever reads the chunk's symbols (k_gz_crc; the test driver's consumer) reports it as "distance too far
+    // back".  no_history is the case hist_floor == kWindow; only chunks in a member's first 32 KB have a floor above 0.
+    uint32_t hist_floor = 0;
     bool member_end = false;     // a member ends behind it: trailer values below
     uint32_t want_crc = 0, want_isize = 0;
     bool is_gap = false;         // decoded by a follow-up job (the owner may have given it a buffer of its own)
@@ -46,6 +54,7 @@ class Chain {
         handed_ = 0;
         confirmed_ = 0;
         out_confirmed_ = 0;
+        member_out_ = 0;
         waiting_gaps_ = false;
         all_in_ = false;
         searched_to_ = 0;
@@ -90,11 +99,12 @@ class Chain {
                 st_.ci++;
             const bool have = st_.ci < cands_.size();
             if (have && cands_[st_.ci].start_bit == st_.end) {
-                // (a member's first chunk decoded with markers allowed holds none if the stream is valid; if it is not, the
-                // member's CRC-32 says so)
+                // (a candidate the search found at a member's first block was decoded with markers allowed.  What refuses a marker in
+                // it is the floor confirm() gives it -- kWindow, no member bytes in front of it; the flag only keeps no_history meaning
+                // "a member starts with it" for such a chunk too)
                 Item it;
                 it.acc.job = cands_[st_.ci];
-                it.acc.no_history = (cands_[st_.ci].flags & kJobNoHistory) != 0;
+                it.acc.no_history = (cands_[st_.ci].flags & kJobNoHistory) != 0 || st_.no_history_next;
                 it.acc.tag = cands_[st_.ci].sym_off;
                 it.before = st_;
                 st_.ci++;
@@ -294,8 +304,11 @@ class Chain {
     // offsets in the inflated stream are known
     void confirm() {
         while (confirmed_ < items_.size() && !items_[confirmed_].pending) {
-            items_[confirmed_].acc.out_off = out_confirmed_;
-            out_confirmed_ += items_[confirmed_].acc.job.n_out;
+            Accepted &a = items_[confirmed_].acc;
+            a.out_off = out_confirmed_;
+            a.hist_floor = kWindow - (uint32_t)std::min<uint64_t>(kWindow, out_confirmed_ - member_out_);
+            out_confirmed_ += a.job.n_out;
+            if (a.member_end) member_out_ = out_confirmed_;
             confirmed_++;
         }
     }
@@ -314,6 +327,7 @@ class Chain {
     std::vector<Item> items_;
     size_t handed_ = 0, confirmed_ = 0;
     uint64_t out_confirmed_ = 0;
+    uint64_t member_out_ = 0;        // offset in the inflated stream of the first byte of the member the next confirmed chunk belongs to
     bool waiting_gaps_ = false;
     State st_;
     std::string err_;

@@ -9,7 +9,8 @@
 //                   symbols are written by all lanes together
 //   k_gz_maps / k_gz_carry / k_gz_window   the 32 KB behind every accepted chunk (each depends on the one in front of it: maps
 //                   composed per group of 64 chunks in LDS, the groups chained by one workgroup, then everything at once)
-//   k_gz_crc        per chunk: CRC-32 of its bytes by 256 slices, combined with GF(2) operators (gz_core.h crc_*)
+//   k_gz_crc        per chunk: CRC-32 of its bytes by 256 slices, combined with GF(2) operators (gz_core.h crc_*); and, since it reads
+//                   every symbol: no marker below the chunk's floor, i.e. no match that reached in front of its member's first byte
 //   k_gz_translate  symbols -> bytes (markers through the window in front of the chunk) straight into the caller's buffer,
 //                   e.g. a block buffer of the FASTQ framer
 // Bound: k_gz_decode by LATENCY per symbol (an LDS table look-up depends on the bits the look-up in front of it consumed), hence by
@@ -542,7 +543,7 @@ __global__ void __launch_bounds__(1024) k_gz_maps(const AccDev *acc, uint32_t n_
         for (uint32_t q = 0; q < kPer; ++q) {
             const uint32_t k = tid + q * 1024;
             uint16_t v;
-            if (k < kWindow - own) v = a.no_history ? (uint16_t)0 : cur[k + own];      // the window in front, shifted (nothing in front of a member)
+            if (k < kWindow - own) v = a.hist_floor == kWindow ? (uint16_t)0 : cur[k + own];      // the window in front, shifted (nothing in front of a member)
             else {
                 v = s[a.n_out - own + (k - (kWindow - own))];
                 if (v >= kMarker) v = cur[v - kMarker];
@@ -595,7 +596,11 @@ __global__ void __launch_bounds__(256) k_gz_window(const uint16_t *maps, uint32_
 
 // ---- CRC-32 of every chunk's bytes: 256 slices of equal length counted from the END (only the first may be short, and a short
 // FIRST operand needs no length), a table-driven CRC per slice, then combined pairwise with x^(8 s 2^k) ---------------------------
-__global__ void __launch_bounds__(256) k_gz_crc(const AccDev *acc, uint32_t n_acc, const uint8_t *windows, const uint8_t *carry, uint32_t *crc_out) {
+// The one kernel that reads every symbol of every accepted chunk, so it also holds the chunk to its floor (AccDev.hist_floor): a
+// marker kMarker + i with i < floor stands for a byte in front of the member's first one -- a match that reached further back than
+// its member began, in a chunk that was decoded before anyone knew where in its member it lies (k_gz_decode refuses such a match only
+// in the chunk that starts a member).  below_out[c] != 0 says so; the host reports "distance too far back".
+__global__ void __launch_bounds__(256) k_gz_crc(const AccDev *acc, uint32_t n_acc, const uint8_t *windows, const uint8_t *carry, uint32_t *crc_out, uint32_t *below_out) {
     __shared__ uint32_t s_tab[256], s_part[256];
     const uint32_t c = blockIdx.x, tid = threadIdx.x;
     if (c >= n_acc) return;
@@ -604,7 +609,10 @@ __global__ void __launch_bounds__(256) k_gz_crc(const AccDev *acc, uint32_t n_ac
     __syncthreads();
     const uint32_t n = a.n_out;
     if (n == 0) {
-        if (tid == 0) crc_out[c] = 0;
+        if (tid == 0) {
+            crc_out[c] = 0;
+            below_out[c] = 0;
+        }
         return;
     }
     const uint8_t *prev = c ? windows + (size_t)(c - 1) * kWindow : carry;
@@ -612,8 +620,11 @@ __global__ void __launch_bounds__(256) k_gz_crc(const AccDev *acc, uint32_t n_ac
     const uint32_t slice = (n + 255) / 256;
     const long long hi = (long long)n - (long long)(255 - tid) * slice, lo = hi - slice;
     uint32_t v = 0xFFFFFFFFu;
+    const uint32_t floor = a.hist_floor;
+    bool below = false;
     auto step = [&](uint32_t x) {
         const uint32_t b = x < kMarker ? x : prev[x - kMarker];
+        below |= x - kMarker < floor;                                        // (a literal wraps to far above any floor)
         v = s_tab[(v ^ b) & 0xFF] ^ (v >> 8);
     };
     // a lane's slice is contiguous: 8 symbols per 16-byte load (the buffer is 16-byte aligned), so that a fetched line is used up
@@ -629,13 +640,16 @@ __global__ void __launch_bounds__(256) k_gz_crc(const AccDev *acc, uint32_t n_ac
     for (; i < hi; ++i) step(s[i]);
     s_part[tid] = hi <= 0 ? 0u : v ^ 0xFFFFFFFFu;
     uint32_t xk = crc_x2nmodp(slice, 3);
-    __syncthreads();
+    const int any_below = __syncthreads_or((int)below);
     for (uint32_t step = 1; step < 256; step <<= 1) {
         if ((tid & (2 * step - 1)) == 0) s_part[tid] = crc_combine_op(s_part[tid], s_part[tid + step], xk);
         xk = crc_multmodp(xk, xk);
         __syncthreads();
     }
-    if (tid == 0) crc_out[c] = s_part[0];
+    if (tid == 0) {
+        crc_out[c] = s_part[0];
+        below_out[c] = any_below ? 1u : 0u;
+    }
 }
 
 // ---- translate: the bytes [o_lo, o_hi) of the inflated stream, taken from the chunks acc[c_first ..], to dst[0 ..) ---------------
@@ -704,9 +718,9 @@ hipError_t launch_windows(const AccDev *d_acc, uint32_t n, uint8_t *d_windows, c
     hipLaunchKernelGGL(k_gz_window, dim3(n), dim3(256), 0, s, maps, n, gwin, d_windows);
     return hipGetLastError();
 }
-hipError_t launch_crc(const AccDev *d_acc, uint32_t n, const uint8_t *d_windows, const uint8_t *d_carry, uint32_t *d_crc, hipStream_t s) {
+hipError_t launch_crc(const AccDev *d_acc, uint32_t n, const uint8_t *d_windows, const uint8_t *d_carry, uint32_t *d_crc, uint32_t *d_below, hipStream_t s) {
     if (!n) return hipSuccess;
-    hipLaunchKernelGGL(k_gz_crc, dim3(n), dim3(256), 0, s, d_acc, n, d_windows, d_carry, d_crc);
+    hipLaunchKernelGGL(k_gz_crc, dim3(n), dim3(256), 0, s, d_acc, n, d_windows, d_carry, d_crc, d_below);
     return hipGetLastError();
 }
 hipError_t launch_translate(const AccDev *d_acc, uint32_t c_first, uint32_t n_chunks, uint32_t max_syms, const uint8_t *d_windows,

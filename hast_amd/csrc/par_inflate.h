@@ -17,7 +17,10 @@
 //   3. in file order (serial, cheap): a chunk is ACCEPTED iff the chunk in front of it, decoded from a boundary already
 //      proven, ended exactly at the bit position the chunk started from -- so by induction from the stream's first block
 //      every accepted chunk starts at a true boundary and a false positive of step 1 can only cost time: the chunk in front
-//      then simply decodes on through it.  The 32-KB window behind each accepted chunk is resolved chunk after chunk;
+//      then simply decodes on through it.  The 32-KB window behind each accepted chunk is resolved chunk after chunk; only
+//      here is it known how many bytes of its member lie in front of a chunk, so here a chunk whose copies read further back
+//      than its member's first byte is refused ("distance too far back", Chunk::min_hist) -- in the chunk a member starts in
+//      the decoder itself refuses them;
 //   4. markers -> bytes through a 64-K look-up table per chunk (all chunks at once, straight into the caller's buffer), and
 //      every member's CRC-32 and ISIZE are checked (per-piece CRCs combined with crc32_combine), so a bug cannot pass as data.
 //
@@ -197,6 +200,10 @@ class ParGzReader {
         size_t n = 0, consumed = 0;
         std::vector<Event> ev;
         size_t hist_lo = 0;                          // lowest index of sym a copy may read (member starts are history barriers)
+        // lowest index of the kWindow symbols of history any copy DID read (kWindow: none).  A searched chunk does not know how much of
+        // its member lies in front of it (hist_lo = 0); once it is accepted that is known, and a copy from further back than the
+        // member's first byte is "distance too far back" there as it is in the chunk that starts the member (make_batch)
+        size_t min_hist = kWindow;
         bool at_member_header = false;               // the chunk ends in front of a gzip header that was not in the buffer yet
         std::vector<uint8_t> lut;                    // marker -> byte (built when the chunk in front has been resolved)
     };
@@ -345,11 +352,12 @@ class ParGzReader {
     }
 
     // ---- step 2: symbols of one Huffman block.  0 = block finished, 1 = more room needed, 2 = input ran out, -1 = error ----
-    static int decode_huffman(Bits &in, const Tables &t, uint16_t *base, size_t &n_out, size_t cap, size_t hist_lo, const char *&err) {
+    static int decode_huffman(Bits &in, const Tables &t, uint16_t *base, size_t &n_out, size_t cap, size_t hist_lo, size_t &min_hist, const char *&err) {
         const uint32_t *const lit = t.lit.data(), *const dst = t.dist.data();
         uint16_t *out = base + n_out;
         uint16_t *const out_stop = base + cap - kOutSlack;
         uint16_t *const lo = base + hist_lo;
+        const uint16_t *lowest = base + min_hist;                      // (only copies out of the history move it: it never rises above base + kWindow)
         constexpr uint32_t LM = (1u << kInflateLitBits) - 1, DM = (1u << kInflateDistBits) - 1;
         constexpr uint32_t kLit = kInflateLit, kEob = kInflateEob, kSub = kInflateSub;
         uint64_t bb = in.bb;
@@ -414,6 +422,7 @@ class ParGzReader {
             bc -= deb;
             if ((size_t)(out - lo) < distance) { err = "deflate: distance too far back"; rc = -1; break; }
             const uint16_t *src = out - distance;
+            if (src < lowest) lowest = src;
             uint16_t *const end = out + len;
             if (distance >= 4) {                                       // 4 symbols at a time; may write up to 3 symbols past `end`
                 do {
@@ -429,6 +438,7 @@ class ParGzReader {
         }
 #undef HAST_PREFILL
         n_out = (size_t)(out - base);
+        min_hist = (size_t)(lowest - base);
         in.bb = bb;
         in.bc = bc;
         in.ip = ip;
@@ -510,6 +520,9 @@ class ParGzReader {
             if (!in_eof_ && (size_t)(rel(c.end_bit) >> 3) + kMinAhead > len) { c.starved = true; return true; }
             in.seek(rel(c.end_bit));
             const size_t n0 = c.n;
+            // (what this block's copies read of the history counts once the block is committed: a block that runs into the zero padding
+            // behind the buffer's last real byte is rolled back, and its last "tokens" were no stream data)
+            size_t block_min_hist = c.min_hist;
             const bool final = in.take(1) != 0;
             const uint32_t type = in.take(2);
             const char *bad = nullptr;
@@ -536,7 +549,7 @@ class ParGzReader {
                 while (!bad && !starved) {
                     ensure(1u << 16);
                     size_t n_abs = kWindow + c.n;
-                    const int rc = decode_huffman(in, t, c.sym.data(), n_abs, c.sym.size(), c.hist_lo, bad);
+                    const int rc = decode_huffman(in, t, c.sym.data(), n_abs, c.sym.size(), c.hist_lo, block_min_hist, bad);
                     c.n = n_abs - kWindow;
                     if (rc == 0) break;
                     if (rc == 2) starved = true;
@@ -570,6 +583,7 @@ class ParGzReader {
                 c.end_bit = (in_base_ + at + 8) * 8;
                 c.at_member_header = true;
             } else c.end_bit = in_base_ * 8 + in.pos();
+            c.min_hist = block_min_hist;                               // the block is committed
         }
     }
     static constexpr size_t kMinAhead = 32;      // a block is only started with this many bytes in the buffer (or at the file's end)
@@ -709,6 +723,7 @@ class ParGzReader {
                     c.err.clear();
                     c.eos = c.at_member_header = false;
                     c.hist_lo = 0;
+                    c.min_hist = kWindow;
                     if (c.sym.size() < kWindow + chunk_bytes_ * 5) c.sym.resize(kWindow + chunk_bytes_ * 5 + kOutSlack);
                     for (size_t k = 0; k < kWindow; ++k) c.sym[k] = (uint16_t)(kMarker + k);
                     const bool ok = decode_blocks(c, c.stop_bit, t);
@@ -758,8 +773,17 @@ class ParGzReader {
         // ---- windows and look-up tables, chunk after chunk (32 KB each) ----------------------------------------------------
         std::vector<uint8_t> window = carry_window_;
         uint64_t member_out = carry_member_out_;
-        for (size_t idx : accepted) {
+        for (size_t ai = 0; ai < accepted.size(); ++ai) {
+            const size_t idx = accepted[ai];
             Chunk &c = *ch[idx];
+            // a match may not reach in front of its member's first byte, in whichever chunk of the member it stands: only now is it
+            // known how many bytes of the member lie in front of this chunk.  What the chunks in front of it hold is delivered
+            if (c.min_hist < kWindow - (size_t)std::min<uint64_t>(member_out, kWindow)) {
+                b.error = "deflate: distance too far back";
+                failed = true;
+                accepted.resize(ai);
+                break;
+            }
             c.lut.resize(65536);
             for (int v = 0; v < 256; ++v) c.lut[(size_t)v] = (uint8_t)v;
             memcpy(c.lut.data() + kMarker, window.data(), kWindow);

@@ -24,6 +24,7 @@ static bool g_wave = false;
 // -S (with -w): what the wave's steps were made of, to stderr at the end -- steps, rounds, rounds with a match, rounds with a copy out of the
 // symbol buffer itself (further back than kRing), tokens, matches, long matches (profiles/round6_gz_decode_latency_ab.txt quotes these)
 static bool g_stats = false;
+static unsigned long long g_accepted = 0;  // -S: chunks the chain accepted (a line of its own on stderr, with and without -w)
 static struct { unsigned long long steps, full, rounds, rounds_match, rounds_far, syms, toks, matches, longs, longs_far; } g_st;      // -w: Huffman blocks decoded the way k_gz_decode does it (64 token parses per step, chain, rounds)
 
 // ---- the symbol loop of k_gz_decode (gz_kernels.hip), lane by lane: every lane parses a token at its own bit offset (parse_token),
@@ -394,6 +395,7 @@ int main(int argc, char **argv) {
     auto consume = [&]() -> bool {
         acc.clear();
         chain.take_confirmed(acc);
+        g_accepted += acc.size();
         for (const Accepted &a : acc) {
             Buf *b = bufs[(size_t)a.tag];
             const uint32_t n = a.job.n_out;
@@ -403,7 +405,8 @@ int main(int argc, char **argv) {
             out.resize(at + n);
             for (uint32_t i = 0; i < n; ++i) {
                 const uint16_t s = b->sym[i];
-                if (s >= kMarker && a.no_history) { fprintf(stderr, "marker in a member's first chunk\n"); return false; }
+                // (what k_gz_crc checks on the device: a marker below the chunk's floor is a byte in front of the member's first one)
+                if (s >= kMarker && (uint32_t)(s - kMarker) < a.hist_floor) { fprintf(stderr, "gz: damaged input (distance too far back)\n"); return false; }
                 out[at + i] = s < kMarker ? (uint8_t)s : window[s - kMarker];
             }
             // the window behind it
@@ -515,6 +518,7 @@ int main(int argc, char **argv) {
         return 3;
     }
     if (!out.empty()) fwrite(out.data(), 1, out.size(), stdout);
+    if (g_stats) fprintf(stderr, "chain accepted %llu chunks\n", g_accepted);
     if (g_stats && g_wave)
         fprintf(stderr, "wave steps %llu (with second-level tables %llu) rounds %llu with_match %llu with_far_copy %llu symbols_in_rounds %llu tokens %llu matches %llu long_matches %llu long_far %llu\n",
                 g_st.steps, g_st.full, g_st.rounds, g_st.rounds_match, g_st.rounds_far, g_st.syms, g_st.toks, g_st.matches, g_st.longs, g_st.longs_far);
