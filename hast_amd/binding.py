@@ -49,6 +49,11 @@ class GzStats(C.Structure):
                [(n, C.c_uint64) for n in ("ring_bytes", "upload_waited_for_ring")] + [("chain_walk_s", C.c_double), ("ring_laps", C.c_uint64)]
 
 
+class GzBlockedStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("members", "batches", "carried")] + \
+               [(n, C.c_double) for n in ("read_s", "upload_s", "kernels_s", "wait_reader_s")] + [("unsupported_offset", C.c_uint64)]
+
+
 class SqResult(C.Structure):
     _fields_ = [("consumed", C.c_uint64), ("out_bytes", C.c_uint64), ("records", C.c_uint64), ("bases", C.c_uint64),
                 ("flags", C.c_uint32), ("first_bad", C.c_uint32)]
@@ -193,6 +198,9 @@ ABI_SYMBOLS = {
     "hast_gz_read_device": (C.c_int, [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), vp]),
     "hast_gz_get_stats": (C.c_int, [vp, C.POINTER(GzStats)]),
     "hast_gz_close": (None, [vp]),
+    "hast_gz_open_blocked": (C.c_int, [vp, C.c_char_p, C.POINTER(vp)]),
+    "hast_gz_open_blocked_ex": (C.c_int, [vp, C.c_char_p, C.c_size_t, C.c_size_t, C.POINTER(vp)]),
+    "hast_gz_get_blocked_stats": (C.c_int, [vp, C.POINTER(GzBlockedStats)]),
     "hast_parse_barcode": (None, [C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "hast_get_hap": (C.c_int, [C.c_char_p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_double, C.c_double]),
     "hast_canon_kmer": (C.c_uint64, [C.c_char_p, C.c_int]),
@@ -673,6 +681,25 @@ class GzReader:
         self._h = h
         self._d = None
         self._cap = 0
+
+    @classmethod
+    def blocked(cls, ctx, path, batch_in=0, batch_out=0):
+        """hast_gz_open_blocked_ex: a blocked-gzip (BGZF) file inflated per member; batch_in / batch_out: bytes a batch, 0 = default"""
+        self = cls.__new__(cls)
+        self._lib = lib()
+        self._ctx = ctx
+        self._d = None
+        self._cap = 0
+        self._h = None
+        h = C.c_void_p()
+        _ck(self._lib.hast_gz_open_blocked_ex(ctx._h, os.fsencode(path), batch_in, batch_out, C.byref(h)))
+        self._h = h
+        return self
+
+    def blocked_stats(self):
+        st = GzBlockedStats()
+        _ck(self._lib.hast_gz_get_blocked_stats(self._h, C.byref(st)))
+        return {n: getattr(st, n) for n, _ in GzBlockedStats._fields_}
 
     def read_device(self, d_dst, cap, stream=None):
         n = C.c_size_t()

@@ -17,6 +17,8 @@
 #include <thread>
 #include <vector>
 
+#include "bz_core.h"
+
 namespace hast {
 
 class BgzfReader {
@@ -127,24 +129,8 @@ class BgzfReader {
         uint32_t crc = 0, isize = 0;
         size_t out_off = 0;
     };
-    // gzip header with the BGZF extra subfield: returns header length and total member length
-    static bool parse_header(const unsigned char *h, size_t n, size_t &hdr, size_t &total) {
-        if (n < 18 || h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || (h[3] & 4) == 0) return false;
-        if (h[3] & ~4u) return false;                              // BGZF writers set FEXTRA only
-        const size_t xlen = h[10] | ((size_t)h[11] << 8);
-        // the BC subfield is the first one in every known writer; look through the part we have
-        size_t p = 12;
-        while (p + 4 <= std::min(n, 12 + xlen)) {
-            const size_t slen = h[p + 2] | ((size_t)h[p + 3] << 8);
-            if (h[p] == 'B' && h[p + 1] == 'C' && slen == 2 && p + 6 <= n) {
-                total = (size_t)(h[p + 4] | ((size_t)h[p + 5] << 8)) + 1;
-                hdr = 12 + xlen;
-                return total >= hdr + 8 + 2;
-            }
-            p += 4 + slen;
-        }
-        return false;
-    }
+    // gzip header with the BGZF extra subfield: returns header length and total member length (the rule: bz_core.h)
+    static bool parse_header(const unsigned char *h, size_t n, size_t &hdr, size_t &total) { return bz::parse_header(h, n, hdr, total); }
     void fill() {                                                  // append only: members gathered for the current call stay where they are
         if (eof_) return;
         const size_t old = in_.size();

@@ -87,6 +87,7 @@ void print_usage() {                              // same flags as the reference
           "                        compressed there and only compressed bytes come back (HAST_PHASE_GZ=1)\n"
           "      --route MODE      device (default): records routed on the GPU; host: parsed again by host threads\n"
           "      --inflate MODE    device (default) | host | zlib: who inflates .gz inputs (HAST_INFLATE)\n"
+          "      --bgzf MODE       host (default) | device: who inflates blocked-gzip (BGZF) inputs (HAST_BGZF)\n"
           "      --gz-ring-bytes N compressed bytes of a .gz input kept on the device at a time (default: whole files up to 2 GB;\n"
           "                        HAST_GZ_RING_BYTES)\n"
           "      --park-gb X       device memory of closed streams kept for reuse instead of freed (default 32; HAST_PARK_GB)\n"
@@ -276,6 +277,7 @@ struct Options {
     // times on the way to BASELINE config 3's 10M barcodes)
     size_t batch_reads = 0, block_mb = 256, initial_barcodes = 1u << 24;
     bool stats = false, host_parse = false, phase_reads = false, gz_out = false;
+    bool bgzf_device = false;                      // --bgzf device: blocked gzip is inflated on the GPU per member (hast_gz_open_blocked)
     double w0 = 1.0, w1 = 1.0;
     // worked out from the above
     size_t block_bytes = 0;                        // --host-parse: bytes per block of a file
@@ -288,7 +290,7 @@ struct Options {
 
 // What a run holds from one phase of main() to the next.
 struct Run {
-    explicit Run(const Options &opt) : o(opt), dev_gz(opt.read.size(), 0) {}
+    explicit Run(const Options &opt) : o(opt), dev_gz(opt.read.size(), 0), dev_bz(opt.read.size(), 0) {}
     const Options &o;
     size_t K = 0;
     hast_ctx *ctx = nullptr;                       // the first GPU's: the table is built there
@@ -296,6 +298,7 @@ struct Run {
     // several GPUs: the blocks of every file go to all of them in turn (a striped stream); HAST_DEAL=files deals whole files
     bool stripe = false;
     std::vector<char> dev_gz;                      // per input: inflated on the GPU
+    std::vector<char> dev_bz;                      // ... as blocked gzip, member by member (--bgzf device; only with dev_gz)
     // the FASTQ streams (and .gz inputs) of the first files, opened by the set-up thread while the table is built
     std::vector<hast_fq *> pre_fq, done_fq;
     std::vector<hast_gz *> pre_gz;
@@ -443,11 +446,12 @@ bool parse_options(int argc, char **argv, Options &o) {
         {"gz-ring-bytes", required_argument, NULL, 1012}, {"stats-json", required_argument, NULL, 1013},
         {"park-gb", required_argument, NULL, 1014},     {"name-cache", required_argument, NULL, 1015},
         {"deal", required_argument, NULL, 1016},        {"route", required_argument, NULL, 1017},
-        {"gz-out", no_argument, NULL, 1018},
+        {"gz-out", no_argument, NULL, 1018},            {"bgzf", required_argument, NULL, 1019},
         {0, 0, 0, 0}};
     static char optstring[] = "p:m:l:r:t:w:u:f:q:h";             // classify.cpp:387
     bool gz_out_flag = false;
     int device = 0;
+    const char *bgzf = getenv("HAST_BGZF");                       // (the alias for runs of the unchanged wrapper; the flag wins)
     {
         const char *pr = getenv("HAST_PHASE_READS");
         o.phase_reads = pr && *pr && strcmp(pr, "0") != 0;
@@ -507,6 +511,7 @@ bool parse_options(int argc, char **argv, Options &o) {
             o.route_mode = optarg;
             break;
         case 1018: o.gz_out = gz_out_flag = true; break;
+        case 1019: bgzf = optarg; break;
         case 1008:
             for (const char *q = optarg; *q;) {
                 char *end;
@@ -533,6 +538,10 @@ bool parse_options(int argc, char **argv, Options &o) {
         return false;
     }
     o.gz_out = o.gz_out && o.phase_reads;
+    if (bgzf && *bgzf) {
+        if (strcmp(bgzf, "host") && strcmp(bgzf, "device")) { print_usage(); return false; }
+        o.bgzf_device = !strcmp(bgzf, "device");
+    }
     if (o.devices.empty()) o.devices.push_back(device);
     // --batch-reads N (tests / small inputs): shrink the blocks so that a batch holds about N records
     o.block_bytes = o.block_mb << 20;
@@ -571,10 +580,14 @@ size_t inputs_open_at_once(const Run &rs, bool same_prefix) {
 
 // .gz inputs are inflated ON THE GPU (hast_gz_*: the compressed bytes cross PCIe, the framer reads the inflated bytes where they
 // lie) when they are ordinary gzip files; blocked gzip (BGZF: thousands of one-block members, which the host inflates side by
-// side), pipes and ".gz" files that are not gzip stay with the host decoders, as does everything under HAST_INFLATE=host|zlib
+// side), pipes and ".gz" files that are not gzip stay with the host decoders, as does everything under HAST_INFLATE=host|zlib.
+// --bgzf device: a blocked-gzip input goes to the GPU too, inflated member by member (hast_gz_open_blocked) -- with one context or
+// whole files dealt to the contexts; a striped run keeps it on the host.
 void find_device_gz_inputs(Run &rs) {
     const char *which = getenv("HAST_INFLATE");
     const bool allow = !rs.o.host_parse && (!which || !strcmp(which, "device"));
+    const char *deal = getenv("HAST_DEAL");
+    const bool blocked_ok = rs.o.bgzf_device && (rs.o.devices.size() <= 1 || (deal && !strcmp(deal, "files")));
     for (size_t i = 0; allow && i < rs.o.read.size(); i++) {
         const std::string &r = rs.o.read[i];
         struct stat sb;
@@ -585,7 +598,9 @@ void find_device_gz_inputs(Run &rs) {
         unsigned char magic[2] = {0, 0};
         const bool gzip_magic = fread(magic, 1, 2, fp) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
         rewind(fp);
-        rs.dev_gz[i] = (gzip_magic || sb.st_size == 0) && !hast::BgzfReader::probe(fp);
+        const bool blocked = hast::BgzfReader::probe(fp);
+        rs.dev_bz[i] = gzip_magic && blocked && blocked_ok;
+        rs.dev_gz[i] = ((gzip_magic || sb.st_size == 0) && !blocked) || rs.dev_bz[i];
         fclose(fp);
     }
 }
@@ -617,6 +632,7 @@ hast_status make_fq(Run &rs, size_t file_index, hast_fq **out) {
 // a .gz input on the device(s): its compressed bytes go there and its first passes are decoded at once
 hast_status open_gz(Run &rs, size_t file_index, hast_gz **out) {
     const char *path = rs.o.read[file_index].c_str();
+    if (rs.dev_bz[file_index]) return hast_gz_open_blocked(rs.ctxs[file_index % rs.ctxs.size()], path, out);
     return rs.stripe ? hast_gz_open_multi(rs.ctxs.data(), (int)rs.ctxs.size(), path, out) : hast_gz_open(rs.ctxs[file_index % rs.ctxs.size()], path, out);
 }
 
@@ -1043,14 +1059,20 @@ void read_phase_host(Run &rs) {
 // Per file a feed (fq_feed.h): a reader thread fills the buffers the library hands out (pread / inflate straight into them), the main
 // thread submits them.  Both passes over the inputs -- this one and the routing pass of --phase-reads -- run their feeds the same way;
 // what they do with a block whose framing has arrived is theirs.
-[[noreturn]] void feed_die(hast::FeedStatus st, const std::string &what) { die(st == hast::FeedStatus::input_failed ? 2 : 4, what.c_str()); }
+// (a blocked-gzip input on the device route -- the feed's handle answers hast_gz_get_blocked_stats: the library's message has the file and
+// the offset; the way round it is named here)
+[[noreturn]] void feed_die(const hast::FqFeed &f, hast::FeedStatus st, const std::string &what) {
+    hast_gz_blocked_stats bs;
+    const bool blocked = f.gz && hast_gz_get_blocked_stats(f.gz, &bs) == HAST_OK;
+    die(st == hast::FeedStatus::input_failed ? 2 : 4, (blocked ? what + " -- classify --bgzf host inflates this input on the host" : what).c_str());
+}
 
 // steps 1 and 2 of a pass's loop: hand empty buffers to the reader, submit what it has filled
 bool pump(hast::FqFeed &f) {
     hast::FeedStatus st = hast::FeedStatus::ok;
     std::string what;
     const bool moved = f.pump(st, what);
-    if (st != hast::FeedStatus::ok) feed_die(st, what);
+    if (st != hast::FeedStatus::ok) feed_die(f, st, what);
     return moved;
 }
 
@@ -1064,7 +1086,7 @@ void open_host_source(const Run &rs, hast::FqFeed &f, size_t cap) {
 void start_feed(const Run &rs, hast::FqFeed &f, hast::FeedWake &wake, size_t cap) {
     std::string what;
     const hast::FeedStatus st = f.start(wake, cap, buffers_per_context(rs), what);
-    if (st != hast::FeedStatus::ok) feed_die(st, what);
+    if (st != hast::FeedStatus::ok) feed_die(f, st, what);
 }
 
 // (a GPU event may be what the loop waits for; a striped stream relays the newline count in front of EVERY block through the loop:
@@ -1104,7 +1126,7 @@ void open_next_classified(Run &rs, ReadPhase &ph) {
             gs = open_gz(rs, fi, &f->gz);
         if (gs == HAST_ERR_UNSUPPORTED) {                  // e.g. no room on the device: the host inflates
             f->gz = nullptr;
-            rs.dev_gz[fi] = 0;
+            rs.dev_gz[fi] = rs.dev_bz[fi] = 0;
             if (set_up_ahead && rs.pre_fq[fi]) {           // (a stream of device-side blocks was set up for it)
                 hast_fq_destroy(rs.pre_fq[fi]);
                 rs.pre_fq[fi] = nullptr;
@@ -1184,7 +1206,12 @@ void retire_classified(Run &rs, hast::FqFeed &f) {
     f.stop_reader();
     if (f.gz) {
         hast_gz_stats gs;
-        if (rs.o.stats && hast_gz_get_stats(f.gz, &gs) == HAST_OK)
+        hast_gz_blocked_stats bs;
+        if (rs.o.stats && rs.dev_bz[f.file_index] && hast_gz_get_blocked_stats(f.gz, &bs) == HAST_OK && hast_gz_get_stats(f.gz, &gs) == HAST_OK)
+            stat_line("__stats_bgzf__ file=%s members=%llu batches=%llu read_s=%.3f upload_s=%.3f kernels_s=%.3f compressed_bytes=%llu inflated_bytes=%llu carried=%llu open_s=%.3f producer_waited_for_reader_s=%.3f\n",
+                      f.name.c_str(), (unsigned long long)bs.members, (unsigned long long)bs.batches, bs.read_s, bs.upload_s, bs.kernels_s, (unsigned long long)gs.compressed_bytes,
+                      (unsigned long long)gs.out_bytes, (unsigned long long)bs.carried, gs.open_s, bs.wait_reader_s);
+        else if (rs.o.stats && hast_gz_get_stats(f.gz, &gs) == HAST_OK)
             stat_line("__stats_gz__ file=%s compressed_bytes=%llu inflated_bytes=%llu chunks=%llu accepted=%llu followup_jobs=%llu followup_rounds=%llu members=%llu "
                             "open_s=%.3f decode_s=%.3f windows_crc_s=%.3f chain_walk_s=%.3f producer_waited_for_upload_s=%.3f producer_waited_for_reader_s=%.3f reader_waited_for_decode_s=%.3f ring_bytes=%llu ring_laps=%llu upload_waited_for_ring=%llu\n",
                     f.name.c_str(), (unsigned long long)gs.compressed_bytes, (unsigned long long)gs.out_bytes, (unsigned long long)gs.chunks,
@@ -1654,7 +1681,7 @@ void open_next_routed(Run &rs, DeviceRouter &dr) {
         const hast_status gs = open_gz(rs, fi, &f->feed.gz);
         if (gs == HAST_ERR_UNSUPPORTED) {
             f->feed.gz = nullptr;
-            rs.dev_gz[fi] = 0;
+            rs.dev_gz[fi] = rs.dev_bz[fi] = 0;
         } else if (gs != HAST_OK) die(2, ("cannot open " + x).c_str());
     }
     const size_t cap = cap_of(rs, fi);
@@ -1925,7 +1952,7 @@ void route_on_host(Run &rs, PhaseReads &pr) {
             DevGzSource src;
             src.ctx = ctx;
             src.cap = 64u << 20;
-            if (hast_gz_open(ctx, x.c_str(), &src.gz) != HAST_OK || hast_dev_alloc(ctx, src.cap, &src.d_buf) != HAST_OK) {
+            if ((rs.dev_bz[fi] ? hast_gz_open_blocked(ctx, x.c_str(), &src.gz) : hast_gz_open(ctx, x.c_str(), &src.gz)) != HAST_OK || hast_dev_alloc(ctx, src.cap, &src.d_buf) != HAST_OK) {
                 src.gz = nullptr;                        // (no room on the device, ...: the host inflates)
                 hast::BlockSource hsrc;
                 if (!hsrc.open(x, 64u << 20)) die(2, ("cannot open " + x).c_str());

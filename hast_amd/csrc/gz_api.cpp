@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../include/hast.h"
+#include "bz_device.h"
 #include "gz_chain.h"
 #include "gz_core.h"
 #include "gz_device.h"
@@ -117,6 +118,7 @@ struct Unit {
 }  // namespace
 
 struct hast_gz {
+    hast::bz::Stream *blocked = nullptr;       // a handle of hast_gz_open_blocked: everything below is unused, the calls dispatch (bz_api.cpp)
     hast_ctx *ctx = nullptr;
     int fd = -1;
     std::string path;
@@ -931,10 +933,15 @@ hast_status hast_gz_open_ex(hast_ctx *ctx, const char *path, size_t chunk_bytes,
     return hast_gz_open_multi_ex(&ctx, 1, path, chunk_bytes, seg_chunks, room, out);
 }
 hast_status hast_gz_open(hast_ctx *ctx, const char *path, hast_gz **out) { return hast_gz_open_multi_ex(&ctx, 1, path, 0, 0, 0, out); }
-int hast_gz_units(const hast_gz *g) { return g ? (int)g->units.size() : 0; }
+int hast_gz_units(const hast_gz *g) { return g ? (g->blocked ? 1 : (int)g->units.size()) : 0; }
 
 void hast_gz_close(hast_gz *g) {
     if (!g) return;
+    if (g->blocked) {
+        hast::bz::stream_close(g->blocked);
+        delete g;
+        return;
+    }
     const bool trace = getenv("HAST_GZ_TRACE") != nullptr;
     auto tr = [&](const char *what) {
         if (trace) fprintf(stderr, "gz close: %s\n", what);
@@ -995,6 +1002,7 @@ void hast_gz_close(hast_gz *g) {
 hast_status hast_gz_read_device(hast_gz *g, uint8_t *d_dst, size_t cap, size_t *n_out, hast_stream s) {
     if (!g || !n_out || (cap && !d_dst)) return set_error(HAST_ERR_INVALID, "null argument");
     *n_out = 0;
+    if (g->blocked) return hast::bz::stream_read(g->blocked, d_dst, cap, n_out, s ? (hipStream_t)s : ctx_stream_of(g->ctx));
     if (!g->err.empty()) return set_error(HAST_ERR_IO, "%s: %s", g->path.c_str(), g->err.c_str());
     // where the caller's buffer lives: the bytes are translated on the unit that decoded them, straight into the buffer when that is
     // the same GPU, through the unit's bounce buffer and a peer copy otherwise
@@ -1116,9 +1124,33 @@ hast_status hast_gz_read_device(hast_gz *g, uint8_t *d_dst, size_t cap, size_t *
 
 hast_status hast_gz_get_stats(hast_gz *g, hast_gz_stats *out) {
     if (!g || !out) return set_error(HAST_ERR_INVALID, "null argument");
+    if (g->blocked) {
+        hast::bz::stream_stats(g->blocked, out, nullptr);
+        return HAST_OK;
+    }
     std::lock_guard<std::mutex> lk(g->mu);
     *out = g->st;
     out->compressed_bytes = g->file_size;
+    return HAST_OK;
+}
+
+// ---- blocked gzip: the handle is a hast_gz, the stream behind it is bz_api.cpp's ----
+hast_status hast_gz_open_blocked_ex(hast_ctx *ctx, const char *path, size_t batch_in_bytes, size_t batch_out_bytes, hast_gz **out) {
+    if (!ctx || !path || !out) return set_error(HAST_ERR_INVALID, "null argument");
+    *out = nullptr;
+    std::unique_ptr<hast_gz> g(new (std::nothrow) hast_gz());
+    if (!g) return set_error(HAST_ERR_OOM, "host allocation failed");
+    if (hast_status st = hast::bz::stream_open(ctx, path, batch_in_bytes, batch_out_bytes, &g->blocked)) return st;
+    g->ctx = ctx;
+    g->path = path;
+    *out = g.release();
+    return HAST_OK;
+}
+hast_status hast_gz_open_blocked(hast_ctx *ctx, const char *path, hast_gz **out) { return hast_gz_open_blocked_ex(ctx, path, 0, 0, out); }
+hast_status hast_gz_get_blocked_stats(hast_gz *g, hast_gz_blocked_stats *out) {
+    if (!g || !out) return set_error(HAST_ERR_INVALID, "null argument");
+    if (!g->blocked) return set_error(HAST_ERR_INVALID, "hast_gz_get_blocked_stats: not a stream of hast_gz_open_blocked");
+    hast::bz::stream_stats(g->blocked, nullptr, out);
     return HAST_OK;
 }
 

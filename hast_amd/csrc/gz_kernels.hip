@@ -19,6 +19,7 @@
 
 #include "gz_core.h"
 #include "gz_device.h"
+#include "gz_wave.h"
 
 namespace hast {
 namespace gz {
@@ -162,48 +163,8 @@ __global__ void __launch_bounds__(64) k_gz_search(ChunkJob *jobs, uint32_t n_job
 // matches longer than 64 symbols, the end-of-block code and invalid codes stop the chain and are dealt with on their own.  On FASTQ
 // a step yields 10 - 30 tokens (bases are 2-bit literals).  tests/native/test_gz_core.cpp -w runs the same steps with plain loops on
 // the CPU against zlib.
-struct WIn {                       // the compressed words around the read position: a ring of 128 words in LDS (s_in[word & 127]),
-    const uint32_t *w;             // always the 128 words from rb on (rb a multiple of 64, the position inside the first 64); the 64
-    uint64_t nwords;               // words behind them wait in a VGPR (nxt), loaded ~20 steps before they are put into the ring
-    uint64_t rb;
-    uint32_t nxt;
-};
-__device__ __forceinline__ uint32_t wload(const WIn &b, uint64_t i) { return i < b.nwords ? b.w[i] : 0u; }
-__device__ __forceinline__ void win_at(WIn &b, uint32_t *s_in, uint64_t pos) {      // (uniform) the ring covers `pos` and the 4 words behind it
-    const uint64_t wi = pos >> 5;
-    const uint32_t lane = threadIdx.x;
-    if (wi < b.rb || wi >= b.rb + 128) {
-        b.rb = wi & ~63ull;
-        __builtin_amdgcn_wave_barrier();
-        s_in[(uint32_t)(b.rb + lane) & 127] = wload(b, b.rb + lane);
-        s_in[(uint32_t)(b.rb + 64 + lane) & 127] = wload(b, b.rb + 64 + lane);
-        b.nxt = wload(b, b.rb + 128 + lane);
-        __builtin_amdgcn_wave_barrier();
-    } else if (wi >= b.rb + 64) {
-        __builtin_amdgcn_wave_barrier();
-        s_in[(uint32_t)(b.rb + lane) & 127] = b.nxt;                          // (the words rb + 128 .. rb + 191 take the place of rb .. rb + 63)
-        b.rb += 64;
-        b.nxt = wload(b, b.rb + 128 + lane);
-        __builtin_amdgcn_wave_barrier();
-    }
-}
-__device__ __forceinline__ uint64_t win_bits(const WIn &b, const uint32_t *s_in, uint64_t pos) {      // the 64 bits at pos + lane
-    const uint32_t rel = (uint32_t)(pos - b.rb * 32) + threadIdx.x, wi = (uint32_t)b.rb + (rel >> 5), sh = rel & 31;
-    const uint32_t w0 = s_in[wi & 127], w1 = s_in[(wi + 1) & 127], w2 = s_in[(wi + 2) & 127];
-    const uint32_t lo = __builtin_amdgcn_alignbit(w1, w0, sh), hi = __builtin_amdgcn_alignbit(w2, w1, sh);
-    return ((uint64_t)hi << 32) | lo;
-}
 __device__ __forceinline__ void sym_store(uint16_t *p, uint16_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
 __device__ __forceinline__ uint16_t sym_load_far(const uint16_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }   // (past the L1)
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x) {              // inclusive prefix sum over the 64 lanes (DPP: rows, then row 15 -> next row, then 31 -> upper half)
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, false);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xF, 0xF, false);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xF, 0xF, false);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xF, 0xF, false);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xA, 0xF, false);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false);
-    return x;
-}
 
 // 5 waves per SIMD (96 VGPRs): a chunk's time is latency, so chunks in flight are throughput; 20 per CU (7.9 KB of LDS each: tables
 // at zlib's own bounds, a ring of 512 symbols).

@@ -564,6 +564,37 @@ int         hast_gz_units(const hast_gz *);
 hast_status hast_gz_read_device(hast_gz *, uint8_t *d_dst, size_t cap, size_t *n_out, hast_stream);
 hast_status hast_gz_get_stats(hast_gz *, hast_gz_stats *out);
 void        hast_gz_close(hast_gz *);
+/* BLOCKED gzip (BGZF: bgzip, htslib, many sequencer pipelines) inflated on the device PER MEMBER.  Every member's header says how
+ * long the member is (the `BC` extra subfield), its trailer what it inflates to, and no match reaches in front of its member: the
+ * members of a piece of the file are found without inflating anything (hast_amd/csrc/bz_core.h), their places in the output are one
+ * prefix sum, and each is decoded by ONE WAVE from a known start straight to bytes (bz_kernels.hip k_bz_inflate) -- none of the
+ * search, chain, marker symbols, windows and translate that hast_gz_open needs for "any gzip".  CRC-32 and ISIZE of every member are
+ * checked on the device (k_bz_crc); the host reads 8 bytes per batch.  Batches of whole members (batch_in_bytes of compressed input,
+ * batch_out_bytes of output; 0 = 32 MB / 192 MB; both at least one member) go through three sets of buffers: one is read and uploaded
+ * while one is decoded and the reader copies out of the third.
+ * The handle is a hast_gz: hast_gz_read_device (same contract: filled to cap except at the end, damage reported by the call BEHIND
+ * the one that delivered the bytes of all members in front of the first bad one), hast_gz_get_stats (compressed_bytes, out_bytes,
+ * members, open_s; the rest 0), hast_gz_units (1) and hast_gz_close work on it.
+ * hast_gz_open_blocked: HAST_ERR_UNSUPPORTED when the path is not a regular file, is empty, does not start with a BGZF member or
+ * the device has no room -- the caller then uses hast_gz_open or the host; HAST_ERR_IO when it cannot be read.  A gzip member that
+ * is not BGZF met in mid-file: the bytes in front of it are delivered, the next call returns HAST_ERR_UNSUPPORTED with the file
+ * offset in hast_last_error() (and in hast_gz_blocked_stats.unsupported_offset).  Bytes that do not start a gzip member end the
+ * stream, as for gzread.
+ * ONE caller stream per handle: every hast_gz_read_device call on a blocked handle must name the same stream (or NULL every time).  A
+ * batch's buffer goes back to the producer behind an event recorded on the stream of the call that finished the batch; copies that
+ * earlier calls put on another stream would not be waited for. */
+typedef struct {
+    uint64_t members, batches;
+    uint64_t carried;              /* members cut by the end of a piece of the file and carried to the front of the next one */
+    double read_s;                 /* pread into pinned memory + the walk over the members (producer thread, wall time) */
+    double upload_s, kernels_s;    /* event pairs on the stream's own HIP stream, over the batches the reader has taken */
+    double wait_reader_s;          /* the producer waited for the reader to be through with a set of buffers */
+    uint64_t unsupported_offset;   /* file offset of a gzip member that is not BGZF, or 0 */
+} hast_gz_blocked_stats;
+hast_status hast_gz_open_blocked(hast_ctx *, const char *path, hast_gz **out);
+hast_status hast_gz_open_blocked_ex(hast_ctx *, const char *path, size_t batch_in_bytes, size_t batch_out_bytes, hast_gz **out);
+/* HAST_ERR_INVALID on a handle of hast_gz_open */
+hast_status hast_gz_get_blocked_stats(hast_gz *, hast_gz_blocked_stats *out);
 
 /* ---- host-side pieces of the path (no device work) ---------------------------------------- */
 /* parseName (classify.cpp:112-119): barcode = head[last '#' + 1 .. last '/'). */
