@@ -22,6 +22,11 @@ constexpr uint32_t kNlTile = 4096;               // bytes per tile = 256 lanes x
 constexpr size_t nl_tiles(size_t n) { return (n + 15) / kNlTile + 2; }
 // words the index of n bytes needs in the worst case, a range that is all newlines
 constexpr size_t nl_index_words(size_t n) { return n + 16; }
+// the grid of a kernel whose workgroups loop over tiles of `per` items: the tiles of the worst case, at least 1, at most 2048
+inline uint32_t capped_grid(size_t items, uint32_t per) {
+    const size_t t = (items + per - 1) / per;
+    return (uint32_t)(t < 1 ? 1 : t < 2048 ? t : 2048);
+}
 
 // bit i set <=> byte i of w (the byte at the lowest address first) is '\n'
 NL_HD uint32_t nl_bits4(uint32_t w) {
@@ -54,10 +59,7 @@ __device__ __forceinline__ uint32_t nl_mask16(const uint8_t *base16, uint64_t at
 // Returns their number.
 __device__ __forceinline__ uint32_t nl_tile_count(const uint8_t *base16, uint64_t tile, uint64_t lo, uint64_t hi) {
     __shared__ uint32_t s_wave[4];
-    const uint32_t c = wave_sum(__popc(nl_mask16(base16, tile * kNlTile + threadIdx.x * 16, lo, hi)));
-    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = c;
-    __syncthreads();
-    return s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    return block_sum_256(__popc(nl_mask16(base16, tile * kNlTile + threadIdx.x * 16, lo, hi)), s_wave);
 }
 
 // The same workgroup once the counts are scanned: nl[tile_base[tile] ...] = position - origin of every newline of the tile, in order.

@@ -18,7 +18,6 @@ struct RsState {               // device memory, copied to the host after the fr
 };
 
 constexpr uint32_t kRsTile = 256;            // lines / records per tile of the prefix sums
-constexpr uint32_t kRsCopyTile = 4096;       // output bytes a workgroup of k_rs_copy owns at a time: 256 lanes x 16 B
 
 // the scratch a view of up to max_view bytes needs in the worst case: all newlines, or FASTA records of two bytes (">\n")
 struct RsScratchPlan {
@@ -63,8 +62,6 @@ struct RbState {               // device memory, copied to the host behind the p
     uint64_t count[3], raw_bytes[3];   // records and bytes per class
     uint64_t total;                    // raw_bytes[0] + [1] + [2]: the runs lie back to back in the output buffer
 };
-
-constexpr uint32_t kRbCopyTile = kRsCopyTile;       // output bytes a workgroup of k_rb_copy owns at a time: k_rs_copy's figure, untuned there and here
 
 // scratch of its own, allocated when the bins are first switched on: per record its place and its offset in the output
 struct RbScratchPlan {

@@ -7,17 +7,17 @@
 //   k_rs_records     a lane per record: name extent, start and length of the read, the format error; consumed and the counts
 //   k_rs_scan_names  exclusive scan of the name lengths per tile of 256 records
 //   k_rs_names       names gathered back to back: a wave copies its 64 records one after the other, 64 bytes a step
-//   k_rs_copy        FASTA: the sequence lines compacted into one base buffer, the work split by OUTPUT bytes
+//   k_rs_copy        FASTA: the sequence lines compacted into one base buffer (span_copy.h)
 //   k_rb_*           `--bin-reads` (rb_core.h), behind the classification: the records routed to three runs by their votes; see below
 // FASTQ reads are classified where they lie in the view; a FASTA read is spread over lines, and a k-mer straddles the line breaks,
-// so its lines are moved together.  Lines range from 60 columns to one line of 10^8 bases: k_rs_copy gives every workgroup a fixed
-// span of the destination and lets it find, by binary search in line_dst, the lines that reach into it.
+// so its lines are moved together.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "nl_index.h"
 #include "rb_core.h"
 #include "rs_device.h"
+#include "span_copy.h"
 
 namespace hast {
 
@@ -55,16 +55,11 @@ __global__ void __launch_bounds__(kRsTile) k_rs_lines(const uint8_t *in, RsState
             s = rs::fa_seq_len(cls, lo, hi);
             bad |= cls == rs::kBad;
         }
-        const uint32_t ch = wave_sum(h), cs = wave_sum(s);
         __syncthreads();                                         // (the sums of the tile before have been read)
-        if ((threadIdx.x & 63) == 0) {
-            s_h[threadIdx.x >> 6] = ch;
-            s_s[threadIdx.x >> 6] = cs;
-        }
-        __syncthreads();
+        const uint32_t sum_h = block_sum_256(h, s_h), sum_s = block_sum_256(s, s_s);
         if (threadIdx.x == 0) {
-            tile_h[tile] = s_h[0] + s_h[1] + s_h[2] + s_h[3];
-            tile_s[tile] = s_s[0] + s_s[1] + s_s[2] + s_s[3];
+            tile_h[tile] = sum_h;
+            tile_s[tile] = sum_s;
         }
     }
     if (bad) atomicOr(&st->flags, RS_FORMAT_ERROR);
@@ -144,16 +139,11 @@ __global__ void __launch_bounds__(kRsTile) k_rs_records(int format, const uint8_
             r_off[r] = off;
             r_len[r] = len;
         }
-        const uint32_t cn = wave_sum(nlen), cb = wave_sum(len);
         __syncthreads();                                         // (the sums of the tile before have been read)
-        if ((threadIdx.x & 63) == 0) {
-            s_n[threadIdx.x >> 6] = cn;
-            s_b[threadIdx.x >> 6] = cb;
-        }
-        __syncthreads();
+        const uint32_t sum_n = block_sum_256(nlen, s_n), sum_b = block_sum_256(len, s_b);
         if (threadIdx.x == 0) {
-            name_tile[tile] = s_n[0] + s_n[1] + s_n[2] + s_n[3];
-            bases += (unsigned long long)s_b[0] + s_b[1] + s_b[2] + s_b[3];
+            name_tile[tile] = sum_n;
+            bases += sum_b;
         }
     }
     if (threadIdx.x == 0 && bases) atomicAdd(reinterpret_cast<unsigned long long *>(&st->bases), bases);
@@ -195,54 +185,21 @@ __global__ void __launch_bounds__(kRsTile) k_rs_names(const uint8_t *in, const R
     }
 }
 
-// the smallest j in [lo, hi] with line_dst[j + 1] > v; the caller knows that line hi is one
-__device__ __forceinline__ uint32_t rs_first_line_past(const uint32_t *line_dst, uint32_t lo, uint32_t hi, uint32_t v) {
-    while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (line_dst[mid + 1] > v) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
-
-// out[0, bases) = the sequence lines of the complete records, back to back.  Byte p of the output is byte p + junk of the sequence
-// bytes of ALL lines in view order (line_dst counts those): a workgroup takes kRsCopyTile output bytes at a time, finds the first and
-// the last line that reach into them, and every lane moves 16 bytes: it looks its first line up between those two and walks on from
-// there -- 16 bytes at once where they come from one line (out + p is 16-byte aligned, the source is read as it lies), byte by byte
-// across line ends and at the end of the output.
+// out[0, bases) = the sequence lines of the complete records, back to back (span_copy.h).  Byte p of the output is byte p + junk of the
+// sequence bytes of ALL lines in view order (line_dst counts those); a header or an empty line emits nothing, and the lines behind the
+// last complete record lie behind the output.
+struct RsLineSrc {
+    static constexpr bool kFills = false;
+    const uint8_t *in;
+    const uint32_t *nl;
+    __device__ __forceinline__ const uint8_t *at(uint32_t j) const { return in + rs::line_lo(nl, j); }
+};
 __global__ void __launch_bounds__(256) k_rs_copy(const uint8_t *in, const RsState *st, const uint32_t *nl, const uint32_t *line_dst, const uint32_t *hdr_line,
                                                  uint8_t *out) {
     const uint32_t m = st->n_hdr, bases = (uint32_t)st->bases, n_lines = st->n_nl;
     if (!m || !bases || st->flags) return;
     const uint32_t h0 = hdr_line[0], junk = line_dst[h0];
-    const uint32_t n_tiles = (bases + kRsCopyTile - 1) / kRsCopyTile;
-    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const uint32_t t0 = tile * kRsCopyTile, t1 = bases - t0 < kRsCopyTile ? bases : t0 + kRsCopyTile;
-        uint32_t p = t0 + threadIdx.x * 16;
-        if (p >= t1) continue;
-        const uint32_t e = t1 - p < 16 ? t1 : p + 16;
-        const uint32_t j0 = rs_first_line_past(line_dst, h0, n_lines - 1, t0 + junk);
-        const uint32_t j1 = rs_first_line_past(line_dst, j0, n_lines - 1, t1 - 1 + junk);
-        uint32_t j = rs_first_line_past(line_dst, j0, j1, p + junk);
-        while (p < e) {
-            const uint32_t a = line_dst[j], b = line_dst[j + 1];
-            if (b <= p + junk) {                                 // a header, an empty line: nothing of it is output
-                ++j;
-                continue;
-            }
-            const uint32_t upto = b - junk < e ? b - junk : e, k = upto - p;
-            const uint8_t *src = in + rs::line_lo(nl, j) + (p + junk - a);
-            if (k == 16) {
-                uint4 v;
-                __builtin_memcpy(&v, src, 16);
-                *reinterpret_cast<uint4 *>(out + p) = v;
-            } else {
-                for (uint32_t i = 0; i < k; ++i) out[p + i] = src[i];
-            }
-            p = upto;
-            ++j;
-        }
-    }
+    span_copy(line_dst, h0, n_lines - 1, junk, bases, out, 0, RsLineSrc{in, nl});
 }
 
 hipError_t launch_rs_frame(int format, const uint8_t *d_base, size_t origin, size_t n, bool last, bool seen_header, uint8_t *d_seq, uint8_t *d_names,
@@ -256,12 +213,8 @@ hipError_t launch_rs_frame(int format, const uint8_t *d_base, size_t origin, siz
     uint32_t *name_off = words(p.name_off), *r_len = words(p.len);
     uint64_t *r_off = reinterpret_cast<uint64_t *>(d_scratch + p.off);
     RsState *st = reinterpret_cast<RsState *>(d_scratch + p.state);
-    auto capped = [](size_t items, uint32_t per) {
-        const size_t t = (items + per - 1) / per;
-        return (uint32_t)(t < 1 ? 1 : t < 2048 ? t : 2048);
-    };
     const bool fasta = format == RS_FASTA;
-    const uint32_t line_grid = capped(n, kRsTile), rec_grid = capped(fasta ? n / 2 + 1 : n / 4 + 1, kRsTile), copy_grid = capped(n, kRsCopyTile);
+    const uint32_t line_grid = capped_grid(n, kRsTile), rec_grid = capped_grid(fasta ? n / 2 + 1 : n / 4 + 1, kRsTile), copy_grid = capped_grid(n, kSpanCopyTile);
     hipLaunchKernelGGL(k_rs_count, dim3(grid), dim3(256), 0, s, base16, lo, hi, tile_cnt);
     hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(1024), 0, s, tile_cnt, grid, st);
     hipLaunchKernelGGL(k_rs_index, dim3(grid), dim3(256), 0, s, base16, lo, hi, tile_cnt, nl);
@@ -283,8 +236,8 @@ hipError_t launch_rs_frame(int format, const uint8_t *d_base, size_t origin, siz
 //   k_rb_scan    exclusive scans of the two tile sums, laid out class by class: a tile's entry is where its class-c records start
 //   k_rb_place   the stable partition: order[j] = the record at place j, dst[j] = its offset in the output (monotone: class 0's
 //                records in input order, then class 1's, then class 2's)
-//   k_rb_copy    k_rs_copy's scheme with records in place of lines and the permutation in front of it: the work is split by OUTPUT
-//                bytes, because a record is anything from ">\n" to one line of 10^8 bases
+//   k_rb_copy    the records compacted into the output in that order (span_copy.h): a record is anything from ">\n" to one line of
+//                10^8 bases
 struct RbRecord {
     uint32_t cls, lo, len;
 };
@@ -302,7 +255,7 @@ __device__ __forceinline__ RbRecord rb_record(bool fastq, const uint32_t *nl, ui
 
 __global__ void __launch_bounds__(kRsTile) k_rb_sums(int format, const RsState *st, const uint32_t *nl, const uint32_t *hdr_line, const uint32_t *votes,
                                                      uint32_t total0, uint32_t total1, uint32_t *tile_cnt, uint32_t *tile_bytes) {
-    __shared__ uint32_t s_c[3][4], s_b[3][4];
+    __shared__ uint32_t s_c[rb::kClasses][4], s_b[rb::kClasses][4];
     const uint32_t n_rec = (uint32_t)st->records, n_tiles = (n_rec + kRsTile - 1) / kRsTile, n_nl = st->n_nl, m = st->n_hdr;
     const bool fastq = format == RS_FASTQ;
     for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
@@ -313,19 +266,13 @@ __global__ void __launch_bounds__(kRsTile) k_rb_sums(int format, const RsState *
             cls = x.cls;
             len = x.len;
         }
-        const uint32_t c0 = wave_sum(cls == 0), c1 = wave_sum(cls == 1), c2 = wave_sum(cls == 2);
-        const uint32_t b0 = wave_sum(cls == 0 ? len : 0), b1 = wave_sum(cls == 1 ? len : 0), b2 = wave_sum(cls == 2 ? len : 0);
         __syncthreads();                                         // (the sums of the tile before have been read)
-        if ((threadIdx.x & 63) == 0) {
-            const uint32_t w = threadIdx.x >> 6;
-            s_c[0][w] = c0, s_c[1][w] = c1, s_c[2][w] = c2;
-            s_b[0][w] = b0, s_b[1][w] = b1, s_b[2][w] = b2;
-        }
-        __syncthreads();
-        if (threadIdx.x < 3) {
-            const uint32_t c = threadIdx.x;
-            tile_cnt[c * n_tiles + tile] = s_c[c][0] + s_c[c][1] + s_c[c][2] + s_c[c][3];
-            tile_bytes[c * n_tiles + tile] = s_b[c][0] + s_b[c][1] + s_b[c][2] + s_b[c][3];
+        for (uint32_t c = 0; c < rb::kClasses; ++c) {
+            const uint32_t sum_c = block_sum_256(cls == c, s_c[c]), sum_b = block_sum_256(cls == c ? len : 0, s_b[c]);
+            if (threadIdx.x == 0) {
+                tile_cnt[c * n_tiles + tile] = sum_c;
+                tile_bytes[c * n_tiles + tile] = sum_b;
+            }
         }
     }
 }
@@ -375,53 +322,22 @@ __global__ void __launch_bounds__(kRsTile) k_rb_place(int format, const RsState 
     }
 }
 
-// the smallest j in [lo, hi] with dst[j + 1] > v; the caller knows that place hi is one
-__device__ __forceinline__ uint32_t rb_first_place_past(const uint32_t *dst, uint32_t lo, uint32_t hi, uint32_t v) {
-    while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (dst[mid + 1] > v) hi = mid;
-        else lo = mid + 1;
+// out[0, total) = the three runs (span_copy.h): item j is the record at place j, and its source lies wherever order[j] says.
+struct RbRecordSrc {
+    static constexpr bool kFills = false;
+    const uint8_t *in;
+    const uint32_t *nl, *hdr_line, *order;
+    bool fastq;
+    __device__ __forceinline__ const uint8_t *at(uint32_t j) const {
+        const uint32_t r = order[j];
+        return in + rs::line_lo(nl, fastq ? 4 * r : hdr_line[r]);
     }
-    return lo;
-}
-
-// out[0, total) = the three runs.  A workgroup takes kRbCopyTile output bytes at a time, finds the first and the last place that reach
-// into them, and every lane moves 16 bytes: it looks its first place up between those two and walks on from there -- one 16-byte load
-// as the source lies and one aligned 16-byte store where its bytes come from one record (out + p is 16-byte aligned), byte by byte
-// across record ends and at the end of the output.  A load never leaves its record's extent, so nothing outside the view is read.
+};
 __global__ void __launch_bounds__(256) k_rb_copy(int format, const uint8_t *in, const RsState *st, const uint32_t *nl, const uint32_t *hdr_line, const RbState *rb,
                                                  const uint32_t *order, const uint32_t *dst, uint8_t *out) {
     const uint32_t n_rec = (uint32_t)st->records, total = (uint32_t)rb->total;
     if (!n_rec || !total) return;
-    const bool fastq = format == RS_FASTQ;
-    const uint32_t n_tiles = (total + kRbCopyTile - 1) / kRbCopyTile;
-    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const uint32_t t0 = tile * kRbCopyTile, t1 = total - t0 < kRbCopyTile ? total : t0 + kRbCopyTile;
-        uint32_t p = t0 + threadIdx.x * 16;
-        if (p >= t1) continue;
-        const uint32_t e = t1 - p < 16 ? t1 : p + 16;
-        const uint32_t j0 = rb_first_place_past(dst, 0, n_rec - 1, t0);
-        const uint32_t j1 = rb_first_place_past(dst, j0, n_rec - 1, t1 - 1);
-        uint32_t j = rb_first_place_past(dst, j0, j1, p);
-        while (p < e) {
-            const uint32_t a = dst[j], b = dst[j + 1];
-            if (b <= p) {                                        // (an empty extent: there is none today)
-                ++j;
-                continue;
-            }
-            const uint32_t upto = b < e ? b : e, k = upto - p, r = order[j];
-            const uint8_t *src = in + rs::line_lo(nl, fastq ? 4 * r : hdr_line[r]) + (p - a);
-            if (k == 16) {
-                uint4 v;
-                __builtin_memcpy(&v, src, 16);
-                *reinterpret_cast<uint4 *>(out + p) = v;
-            } else {
-                for (uint32_t i = 0; i < k; ++i) out[p + i] = src[i];
-            }
-            p = upto;
-            ++j;
-        }
-    }
+    span_copy(dst, 0, n_rec - 1, 0, total, out, 0, RbRecordSrc{in, nl, hdr_line, order, format == RS_FASTQ});
 }
 
 hipError_t launch_rb_bin(int format, const uint8_t *d_base, size_t origin, size_t n, uint32_t total0, uint32_t total1, const uint8_t *d_scratch,
@@ -433,11 +349,7 @@ hipError_t launch_rb_bin(int format, const uint8_t *d_base, size_t origin, size_
     const RsState *st = reinterpret_cast<const RsState *>(d_scratch + p.state);
     RbState *rb = reinterpret_cast<RbState *>(d_rb + q.state);
     uint32_t *order = own(q.order), *dst = own(q.dst), *tile_cnt = own(q.tile_cnt), *tile_bytes = own(q.tile_bytes);
-    auto capped = [](size_t items, uint32_t per) {
-        const size_t t = (items + per - 1) / per;
-        return (uint32_t)(t < 1 ? 1 : t < 2048 ? t : 2048);
-    };
-    const uint32_t rec_grid = capped(format == RS_FASTA ? n / 2 + 1 : n / 4 + 1, kRsTile), copy_grid = capped(n, kRbCopyTile);
+    const uint32_t rec_grid = capped_grid(format == RS_FASTA ? n / 2 + 1 : n / 4 + 1, kRsTile), copy_grid = capped_grid(n, kSpanCopyTile);
     hipLaunchKernelGGL(k_rb_sums, dim3(rec_grid), dim3(kRsTile), 0, s, format, st, nl, hdr_line, votes, total0, total1, tile_cnt, tile_bytes);
     hipLaunchKernelGGL(k_rb_scan, dim3(1), dim3(1024), 0, s, st, tile_cnt, tile_bytes, rb);
     hipLaunchKernelGGL(k_rb_place, dim3(rec_grid), dim3(kRsTile), 0, s, format, st, nl, hdr_line, votes, total0, total1, (const uint32_t *)tile_cnt,

@@ -1,5 +1,5 @@
 // scan_device.h -- the sums and prefix sums over a wave (64 lanes) and over a workgroup that the framing, routing and deflate
-// kernels share (fq_kernels.hip, sq_kernels.hip, dz_kernels.hip, nl_index.h).  Device code only.
+// kernels share (fq_, sq_, sq_fasta_, rs_, tx_ and dz_kernels.hip, nl_index.h).  Device code only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -18,6 +18,15 @@ __device__ __forceinline__ uint32_t wave_inclusive_sum(uint32_t v, uint32_t lane
         if (lane >= (uint32_t)d) v += u;
     }
     return v;
+}
+
+// Workgroup of 256: the sum of v over all its threads, to every thread.  s: 4 words of LDS; one __syncthreads inside, so every thread
+// calls it, and a second call on the same words needs a barrier behind the reads of the first.
+__device__ __forceinline__ uint32_t block_sum_256(uint32_t v, uint32_t *s) {
+    const uint32_t c = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = c;
+    __syncthreads();
+    return s[0] + s[1] + s[2] + s[3];
 }
 
 // Workgroup of 256: the sum of v over the threads in front of this one.  s_wave: 4 words of LDS; one __syncthreads inside, so every

@@ -48,7 +48,6 @@ struct SqFaState {             // device memory; its first 40 bytes are hast_sq_
 };
 
 constexpr uint32_t kSqFaTile = 256;          // lines per tile of the two prefix sums
-constexpr uint32_t kSqFaCopyTile = 4096;     // destination bytes a workgroup of the copy owns at a time (k_rs_copy's figure, untuned)
 
 // the scratch a view of up to max_in bytes needs in the worst case: a newline at every byte (the most lines), ">\n" repeated (the
 // most headers); both stay within one line per byte and one more

@@ -4,10 +4,8 @@
 //   k_sqfa_lines       a lane per line: stripped length, class, emitted bytes; per tile of 256 lines the headers and the emitted bytes
 //   k_sqfa_scan_lines  one workgroup scans both tile sums; the view's results
 //   k_sqfa_line_dst    a lane per line: line_dst[j] = where in the output line j's bytes start
-//   k_sqfa_copy        the lines compacted into the stream, the work split by OUTPUT bytes
-// A line is anything from a 7-column test file's through an assembler's 60 columns and a 150-base read to a chromosome on one line:
-// a lane or a wave per line would serialise the long ones and starve on the short ones, so k_sqfa_copy gives every workgroup a fixed
-// span of the destination and lets it find, by binary search in line_dst, the lines that reach into it (k_rs_copy's scheme).
+//   k_sqfa_copy        the lines compacted into the stream (span_copy.h)
+// A line is anything from a 7-column test file's through an assembler's 60 columns and a 150-base read to a chromosome on one line.
 // The view and the output may start at any address: both are tiled at 16-byte boundaries of the ADDRESS, nothing outside
 // [d_in, d_in + n_in) is read and nothing at or behind d_out + out_bytes is written.
 #include <hip/hip_runtime.h>
@@ -15,6 +13,7 @@
 
 #include "nl_index.h"
 #include "sq_device.h"
+#include "span_copy.h"
 
 namespace hast {
 
@@ -65,16 +64,11 @@ __global__ void __launch_bounds__(kSqFaTile) k_sqfa_lines(const uint8_t *in, uin
         SqFaLine x;
         x.h = x.e = 0;
         if (j < n_lines) x = sqfa_line(in, nl, n_nl, n_in, j);
-        const uint32_t ch = wave_sum(x.h), ce = wave_sum(x.e);
         __syncthreads();                                         // (the sums of the tile before have been read)
-        if ((threadIdx.x & 63) == 0) {
-            s_h[threadIdx.x >> 6] = ch;
-            s_e[threadIdx.x >> 6] = ce;
-        }
-        __syncthreads();
+        const uint32_t sum_h = block_sum_256(x.h, s_h), sum_e = block_sum_256(x.e, s_e);
         if (threadIdx.x == 0) {
-            tile_h[tile] = s_h[0] + s_h[1] + s_h[2] + s_h[3];
-            tile_e[tile] = s_e[0] + s_e[1] + s_e[2] + s_e[3];
+            tile_h[tile] = sum_h;
+            tile_e[tile] = sum_e;
         }
     }
 }
@@ -111,60 +105,22 @@ __global__ void __launch_bounds__(kSqFaTile) k_sqfa_line_dst(const uint8_t *in, 
     }
 }
 
-// the smallest j in [lo, hi] with line_dst[j + 1] > v; the caller knows that line hi is one
-__device__ __forceinline__ uint32_t sqfa_first_line_past(const uint32_t *line_dst, uint32_t lo, uint32_t hi, uint32_t v) {
-    while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (line_dst[mid + 1] > v) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
-
-// out[0, lines_bytes) = what the lines emit, back to back, and the closing '\n' behind it.  out = out16 + olo with out16 16-byte
-// aligned: a workgroup takes kSqFaCopyTile bytes of out16 at a time, finds the first and the last line that reach into them, and every
-// lane moves the up to 16 bytes of its aligned piece that lie inside the output: it looks its first line up between those two and walks
-// on from there -- one 16-byte load as the source lies and one aligned 16-byte store where the bytes come from one line, byte by byte
-// across line ends and at both ends of the output.  A line that emits and starts with '>' is a header: its one byte is '\n'.  A load
-// never leaves its line, so nothing outside the view is read.
+// out[0, lines_bytes) = what the lines emit, back to back (span_copy.h), and the closing '\n' behind it.  out = out16 + olo with out16
+// 16-byte aligned.  A line that emits and starts with '>' is a header: its one byte is '\n'.  An empty line, the header that opens the
+// input: nothing of them is output.
+struct SqFaLineSrc {
+    static constexpr bool kFills = true;
+    const uint8_t *in;
+    const uint32_t *nl;
+    __device__ __forceinline__ const uint8_t *at(uint32_t j) const { return in + sqfa::line_lo(nl, j); }
+    __device__ __forceinline__ bool fill(const uint8_t *line) const { return line[0] == '>'; }
+};
 __global__ void __launch_bounds__(256) k_sqfa_copy(const uint8_t *in, const SqFaState *st, const uint32_t *nl, const uint32_t *line_dst,
                                                    uint8_t *out16, uint32_t olo) {
     const uint32_t total = st->lines_bytes, n_lines = st->n_lines;
-    uint8_t *out = out16 + olo;
-    if (blockIdx.x == 0 && threadIdx.x == 0 && st->out_bytes > total) out[total] = '\n';
+    if (blockIdx.x == 0 && threadIdx.x == 0 && st->out_bytes > total) out16[olo + total] = '\n';
     if (!total) return;
-    const uint32_t q_end = olo + total, n_tiles = (q_end + kSqFaCopyTile - 1) / kSqFaCopyTile;
-    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const uint32_t t0q = tile * kSqFaCopyTile, t1q = q_end - t0q < kSqFaCopyTile ? q_end : t0q + kSqFaCopyTile;
-        const uint32_t q = t0q + threadIdx.x * 16, qs = q < olo ? olo : q, qe = q + 16 < t1q ? q + 16 : t1q;
-        if (q >= t1q || qs >= qe) continue;
-        uint32_t p = qs - olo;
-        const uint32_t e = qe - olo, t0 = (t0q < olo ? olo : t0q) - olo, t1 = t1q - olo;
-        const uint32_t j0 = sqfa_first_line_past(line_dst, 0, n_lines - 1, t0);
-        const uint32_t j1 = sqfa_first_line_past(line_dst, j0, n_lines - 1, t1 - 1);
-        uint32_t j = sqfa_first_line_past(line_dst, j0, j1, p);
-        while (p < e) {
-            const uint32_t a = line_dst[j], b = line_dst[j + 1];
-            if (b <= p) {                                        // an empty line, the header that opens the input: nothing of it is output
-                ++j;
-                continue;
-            }
-            const uint32_t upto = b < e ? b : e, k = upto - p;
-            const uint8_t *line = in + sqfa::line_lo(nl, j);
-            if (line[0] == '>') {
-                out[p] = '\n';
-            } else if (k == 16) {
-                uint4 v;
-                __builtin_memcpy(&v, line + (p - a), 16);
-                *reinterpret_cast<uint4 *>(out + p) = v;
-            } else {
-                const uint8_t *src = line + (p - a);
-                for (uint32_t i = 0; i < k; ++i) out[p + i] = src[i];
-            }
-            p = upto;
-            ++j;
-        }
-    }
+    span_copy(line_dst, 0, n_lines - 1, 0, total, out16, olo, SqFaLineSrc{in, nl});
 }
 
 hipError_t launch_sq_fasta_frame(const uint8_t *d_in, size_t n_in, uint8_t *d_out, unsigned in_flags, uint8_t *d_scratch, const SqFaScratchPlan &p,
@@ -177,11 +133,7 @@ hipError_t launch_sq_fasta_frame(const uint8_t *d_in, size_t n_in, uint8_t *d_ou
     auto words = [&](size_t at) { return reinterpret_cast<uint32_t *>(d_scratch + at); };
     uint32_t *tile_cnt = words(p.tile_cnt), *nl = words(p.nl), *tile_h = words(p.tile_h), *tile_e = words(p.tile_e), *line_dst = words(p.line_dst);
     SqFaState *st = reinterpret_cast<SqFaState *>(d_scratch + p.state);
-    auto capped = [](size_t items, uint32_t per) {
-        const size_t t = (items + per - 1) / per;
-        return (uint32_t)(t < 1 ? 1 : t < 2048 ? t : 2048);
-    };
-    const uint32_t line_grid = capped(n_in + 1, kSqFaTile), copy_grid = capped(n_in + 16, kSqFaCopyTile);
+    const uint32_t line_grid = capped_grid(n_in + 1, kSqFaTile), copy_grid = capped_grid(n_in + 16, kSpanCopyTile);
     hipLaunchKernelGGL(k_sqfa_count, dim3(grid), dim3(256), 0, s, base, lo, hi, tile_cnt);
     hipLaunchKernelGGL(k_sqfa_scan, dim3(1), dim3(1024), 0, s, tile_cnt, grid, st);
     hipLaunchKernelGGL(k_sqfa_index, dim3(grid), dim3(256), 0, s, base, lo, hi, (const uint32_t *)tile_cnt, nl);

@@ -55,12 +55,10 @@ __global__ void __launch_bounds__(kSqRecTile) k_sq_records(const uint8_t *in, Sq
             r_len[i] = len = ls + 1;
             if (i == n_rec - 1) st->consumed = (uint64_t)nl[4 * (uint64_t)i + 3] + 1;
         }
-        const uint32_t c = wave_sum(len);
         __syncthreads();                                         // (s of the tile before has been read)
-        if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = c;
-        __syncthreads();
+        const uint32_t sum = block_sum_256(len, s);
         if (threadIdx.x == 0) {
-            const uint32_t sum = s[0] + s[1] + s[2] + s[3], in_tile = n_rec - tile * kSqRecTile < kSqRecTile ? n_rec - tile * kSqRecTile : kSqRecTile;
+            const uint32_t in_tile = n_rec - tile * kSqRecTile < kSqRecTile ? n_rec - tile * kSqRecTile : kSqRecTile;
             tile_sum[tile] = sum;
             bases += sum - in_tile;
         }
@@ -118,7 +116,7 @@ hipError_t launch_sq_frame(const uint8_t *d_in, size_t n_in, uint8_t *d_out, uin
     uint32_t *r_src = reinterpret_cast<uint32_t *>(d_scratch + p.r_src), *r_len = reinterpret_cast<uint32_t *>(d_scratch + p.r_len);
     uint32_t *r_tile = reinterpret_cast<uint32_t *>(d_scratch + p.r_tile);
     SqState *st = reinterpret_cast<SqState *>(d_scratch + p.state);
-    const uint32_t max_rec_tiles = (uint32_t)((n_in / 4 + kSqRecTile - 1) / kSqRecTile), rec_grid = max_rec_tiles < 1 ? 1 : max_rec_tiles < 2048 ? max_rec_tiles : 2048;
+    const uint32_t rec_grid = capped_grid(n_in / 4, kSqRecTile);
     hipLaunchKernelGGL(k_sq_count, dim3(grid), dim3(256), 0, s, base, lo, hi, tile_cnt);
     hipLaunchKernelGGL(k_sq_scan, dim3(1), dim3(1024), 0, s, tile_cnt, grid, st);
     hipLaunchKernelGGL(k_sq_index, dim3(grid), dim3(256), 0, s, base, lo, hi, tile_cnt, nl);

@@ -51,14 +51,6 @@ __global__ void __launch_bounds__(256) k_tx_index(TxSides in, const uint32_t *ti
     nl_tile_index(in.base[s], blockIdx.x, in.lo[s], in.hi[s], in.lo[s], s ? tile_base1 : tile_base0, s ? nl1 : nl0);
 }
 
-// the sum of v over a workgroup of 256, to thread 0 only; s: 4 words of LDS, a barrier between two calls on the same words
-__device__ __forceinline__ uint32_t block_sum_256_to_0(uint32_t v, uint32_t *s) {
-    const uint32_t c = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = c;
-    __syncthreads();
-    return s[0] + s[1] + s[2] + s[3];
-}
-
 __global__ void __launch_bounds__(kTxTile) k_tx_keys(const uint8_t *r1, TxDevState *st, const uint32_t *nl1, const uint32_t *nl2, const tx::TableSlot *table,
                                                      uint32_t n_slots, uint32_t *slot, uint32_t *tile_kept) {
     __shared__ uint32_t s[4];
@@ -78,7 +70,7 @@ __global__ void __launch_bounds__(kTxTile) k_tx_keys(const uint8_t *r1, TxDevSta
             }
         }
         __syncthreads();                                         // (s of the tile before has been read)
-        const uint32_t kept = block_sum_256_to_0(found != tx::kNoSlot ? 1u : 0u, s);
+        const uint32_t kept = block_sum_256(found != tx::kNoSlot ? 1u : 0u, s);
         if (threadIdx.x == 0) tile_kept[tile] = kept;
     }
 }
@@ -119,7 +111,7 @@ __global__ void __launch_bounds__(kTxTile) k_tx_sizes(const TxDevState *st, cons
     for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         __syncthreads();                                         // (the LDS words of the tile before have been read)
         const TxPair p = tx_pair_of(tile, m, nl1, nl2, slot, tile_rank, table, used, s_rank);
-        const uint32_t sum0 = block_sum_256_to_0(p.plan.rec1_len, s0), sum1 = block_sum_256_to_0(p.plan.rec2_len, s1);
+        const uint32_t sum0 = block_sum_256(p.plan.rec1_len, s0), sum1 = block_sum_256(p.plan.rec2_len, s1);
         if (threadIdx.x == 0) {
             tile_out0[tile] = sum0;
             tile_out1[tile] = sum1;
@@ -188,7 +180,7 @@ hipError_t launch_tx_step(const TxStepArgs &a, uint8_t *d_scratch, const TxScrat
     uint32_t *slot = words(p.slot), *tile_kept = words(p.tile_kept), *out0 = words(p.tile_out[0]), *out1 = words(p.tile_out[1]);
     TxDevState *st = reinterpret_cast<TxDevState *>(d_scratch + p.state);
     const size_t least = a.n_in[0] < a.n_in[1] ? a.n_in[0] : a.n_in[1];
-    const uint32_t max_tiles = (uint32_t)((least / 4 + kTxTile - 1) / kTxTile), grid = max_tiles < 1 ? 1 : max_tiles < 2048 ? max_tiles : 2048;
+    const uint32_t grid = capped_grid(least / 4, kTxTile);
     hipLaunchKernelGGL(k_tx_count, dim3(n_tiles, 2), dim3(256), 0, s, in, cnt0, cnt1);
     hipLaunchKernelGGL(k_tx_scan, dim3(1), dim3(1024), 0, s, cnt0, cnt1, n_tiles, st);
     hipLaunchKernelGGL(k_tx_index, dim3(n_tiles, 2), dim3(256), 0, s, in, cnt0, cnt1, nl0, nl1);
