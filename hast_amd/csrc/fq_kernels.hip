@@ -14,16 +14,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <algorithm>
-
 #include "bf_core.h"
 #include "fq_device.h"
 #include "nl_index.h"
+#include "record_gather.h"
 
 namespace hast {
 
 // tiles are 4-KB aligned pieces of the buffer (a device allocation: 16-byte aligned); parse_lo / parse_hi bound the bytes that belong
-// to this parse.  The index itself is nl_index.h's, shared with stage 00's framer (sq_kernels.hip).
+// to this parse, read from FqState on the device: k_fq_begin decides them there (why these are not nl_kernels.hip's k_nl_count / _index).
 __global__ void __launch_bounds__(256) k_fq_count(const uint8_t *buf, const FqState *st, uint32_t *tile_cnt) {
     const uint64_t lo = st->parse_lo, hi = st->parse_hi;
     const uint64_t tile = blockIdx.x;                                                      // tiles cover the buffer from byte 0
@@ -348,54 +347,34 @@ __global__ void __launch_bounds__(kRouteTile) k_route_class(const uint8_t *buf, 
             r_cls[c] = cls;
         }
         __syncthreads();
-        if (threadIdx.x < 8) tile_sum[(size_t)tile * 8 + threadIdx.x] = s_sum[threadIdx.x];
+        if (threadIdx.x < 8) tile_sum[(size_t)threadIdx.x * n_tiles + tile] = s_sum[threadIdx.x];    // as k_rb_sums
         __syncthreads();
     }
 }
 
-// exclusive scan of the tiles' byte sums per class, in place; totals and class counts -> rs.  One workgroup.
+// exclusive scans of the tiles' byte sums and record counts, in place, class by class: a tile's entry in row c < 4 is where its
+// class-c records start.  Totals and class counts -> rs, as differences.  One workgroup.
 __global__ void __launch_bounds__(1024) k_route_scan(uint32_t *tile_sum, RouteState *rs) {
-    __shared__ uint32_t s_part[4][1024];
-    __shared__ uint32_t s_cnt[4];
+    __shared__ uint32_t s_part[1024];
     const uint32_t n = (rs->n_cand + kRouteTile - 1) / kRouteTile;
-    const uint32_t per = (n + 1023) / 1024, lo = threadIdx.x * per, hi = lo + per < n ? lo + per : n;
-    if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0;
-    uint32_t sum[4] = {0, 0, 0, 0}, cnt[4] = {0, 0, 0, 0};
-    for (uint32_t i = lo; i < hi; ++i)
-        for (int c = 0; c < 4; ++c) { sum[c] += tile_sum[(size_t)i * 8 + c]; cnt[c] += tile_sum[(size_t)i * 8 + 4 + c]; }
-    for (int c = 0; c < 4; ++c) s_part[c][threadIdx.x] = sum[c];
-    __syncthreads();
-    for (int c = 0; c < 4; ++c) if (cnt[c]) atomicAdd(&s_cnt[c], cnt[c]);
-    for (uint32_t d = 1; d < 1024; d <<= 1) {
-        uint32_t v[4];
-        for (int c = 0; c < 4; ++c) v[c] = threadIdx.x >= d ? s_part[c][threadIdx.x - d] : 0;
-        __syncthreads();
-        for (int c = 0; c < 4; ++c) s_part[c][threadIdx.x] += v[c];
-        __syncthreads();
-    }
-    // class c's run starts behind the runs of the classes in front of it
-    uint32_t base[4];
-    base[0] = 0;
-    for (int c = 1; c < 4; ++c) base[c] = base[c - 1] + s_part[c - 1][1023];
-    uint32_t run[4];
-    for (int c = 0; c < 4; ++c) run[c] = base[c] + (threadIdx.x ? s_part[c][threadIdx.x - 1] : 0);
-    for (uint32_t i = lo; i < hi; ++i)
-        for (int c = 0; c < 4; ++c) {
-            const uint32_t v = tile_sum[(size_t)i * 8 + c];
-            tile_sum[(size_t)i * 8 + c] = run[c];
-            run[c] += v;
-        }
+    uint32_t *tile_cnt = tile_sum + 4 * (size_t)n;
+    const uint32_t bytes = block_exclusive_scan_1024(tile_sum, 4 * n, s_part);
+    __syncthreads();                                             // (s_part is written again)
+    const uint32_t records = block_exclusive_scan_1024(tile_cnt, 4 * n, s_part);
+    __syncthreads();                                             // (the scanned sums of the other threads are read)
     if (threadIdx.x < 4) {
-        rs->bytes[threadIdx.x] = s_part[threadIdx.x][1023];
-        rs->count[threadIdx.x] = s_cnt[threadIdx.x];
+        const uint32_t c = threadIdx.x;
+        const uint32_t b_lo = n ? tile_sum[c * n] : 0, b_hi = n && c < 3 ? tile_sum[(c + 1) * n] : bytes;
+        const uint32_t c_lo = n ? tile_cnt[c * n] : 0, c_hi = n && c < 3 ? tile_cnt[(c + 1) * n] : records;
+        rs->bytes[c] = b_hi - b_lo;
+        rs->count[c] = c_hi - c_lo;
     }
 }
 
 // the records of a tile to their places: a lane per record finds its offset (prefix sum over the records of its class in front of
-// it in the tile), then every wave copies its 64 records one after the other, 64 bytes per step
+// it in the tile), then the tile is gathered (record_gather.h: a wave per record)
 __global__ void __launch_bounds__(kRouteTile) k_route_copy(const uint8_t *buf, const uint32_t *r_start, const uint32_t *r_len, const uint8_t *r_cls,
                                                            const uint32_t *tile_base, const RouteState *rs, uint8_t *out) {
-    __shared__ uint32_t s_src[kRouteTile], s_dst[kRouteTile], s_n[kRouteTile];
     __shared__ uint32_t s_wave[4][4];
     const uint32_t n_cand = rs->n_cand, n_tiles = (n_cand + kRouteTile - 1) / kRouteTile;
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -411,21 +390,10 @@ __global__ void __launch_bounds__(kRouteTile) k_route_copy(const uint8_t *buf, c
         __syncthreads();
         uint32_t dst = 0;
         if (cls < 4) {
-            dst = tile_base[(size_t)tile * 8 + cls] + incl[cls] - len;
+            dst = tile_base[(size_t)cls * n_tiles + tile] + incl[cls] - len;
             for (uint32_t w = 0; w < wave; ++w) dst += s_wave[w][cls];
         }
-        s_src[threadIdx.x] = c < n_cand ? r_start[c] : 0;
-        s_dst[threadIdx.x] = dst;
-        s_n[threadIdx.x] = len;
-        __syncthreads();
-        for (uint32_t r = 0; r < 64; ++r) {
-            const uint32_t i = wave * 64 + r;
-            const uint32_t n = s_n[i];
-            const uint8_t *src = buf + s_src[i];
-            uint8_t *d = out + s_dst[i];
-            for (uint32_t b = lane; b < n; b += 64) d[b] = src[b];
-        }
-        __syncthreads();
+        record_gather_256<GatherBytes>(buf, out, c < n_cand ? r_start[c] : 0, dst, len, n_cand - tile * kRouteTile);
     }
 }
 
@@ -509,7 +477,7 @@ __global__ void __launch_bounds__(256) k_fq_name_claim(const uint32_t *text, uin
 hipError_t launch_fq_name_claim(const uint32_t *d_text, uint32_t n, NameEntry *tab, uint32_t mask, uint32_t *d_n_ids, uint32_t limit, void *d_text_of_id,
                                 uint32_t *h_ids, uint32_t *h_unknown, uint32_t *d_ids, hipStream_t s) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_fq_name_claim, dim3((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024), dim3(256), 0, s, d_text, n, (const FqState *)nullptr, tab, mask, d_n_ids,
+    hipLaunchKernelGGL(k_fq_name_claim, dim3(capped_grid(n, 256, 1024)), dim3(256), 0, s, d_text, n, (const FqState *)nullptr, tab, mask, d_n_ids,
                        limit, reinterpret_cast<uint4 *>(d_text_of_id), h_ids, h_unknown, d_ids);
     return hipGetLastError();
 }
@@ -517,18 +485,18 @@ hipError_t launch_fq_name_claim(const uint32_t *d_text, uint32_t n, NameEntry *t
 hipError_t launch_fq_name_claim_framed(const uint32_t *d_text, const FqState *d_st, uint32_t cap, NameEntry *tab, uint32_t mask, uint32_t *d_n_ids, uint32_t limit,
                                        void *d_text_of_id, uint32_t *h_ids, uint32_t *h_unknown, uint32_t *d_ids, hipStream_t s) {
     if (cap == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_fq_name_claim, dim3((cap + 255) / 256 < 1024 ? (cap + 255) / 256 : 1024), dim3(256), 0, s, d_text, cap, d_st, tab, mask, d_n_ids, limit,
+    hipLaunchKernelGGL(k_fq_name_claim, dim3(capped_grid(cap, 256, 1024)), dim3(256), 0, s, d_text, cap, d_st, tab, mask, d_n_ids, limit,
                        reinterpret_cast<uint4 *>(d_text_of_id), h_ids, h_unknown, d_ids);
     return hipGetLastError();
 }
 hipError_t launch_fq_name(const uint32_t *d_text, uint32_t n, const NameEntry *tab, uint32_t mask, uint32_t *h_ids, uint32_t *h_unknown, hipStream_t s) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_fq_name, dim3((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024), dim3(256), 0, s, d_text, n, tab, mask, h_ids, h_unknown);
+    hipLaunchKernelGGL(k_fq_name, dim3(capped_grid(n, 256, 1024)), dim3(256), 0, s, d_text, n, tab, mask, h_ids, h_unknown);
     return hipGetLastError();
 }
 hipError_t launch_names_insert(const NamePub *pubs, uint32_t n, NameEntry *tab, uint32_t mask, hipStream_t s) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_names_insert, dim3((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024), dim3(256), 0, s, pubs, n, tab, mask);
+    hipLaunchKernelGGL(k_names_insert, dim3(capped_grid(n, 256, 1024)), dim3(256), 0, s, pubs, n, tab, mask);
     return hipGetLastError();
 }
 
@@ -616,15 +584,15 @@ hipError_t launch_fq_field2(const uint8_t *d_buf, const FqState *d_st, const uin
     if (e != hipSuccess) return e;
     // (the candidates are counted on the device; a record holds four newlines, so a view of view_bytes has at most view_bytes / 4 + 2:
     // a small block gets a small grid, the kernel strides over whatever there is)
-    const uint64_t most = std::min<uint64_t>(view_bytes / 4 + 2, max_rec);
-    const dim3 grid((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(1024, (most + 255) / 256)));
+    const uint64_t most = view_bytes / 4 + 2 < max_rec ? view_bytes / 4 + 2 : max_rec;
+    const dim3 grid(capped_grid(most, 256, 1024));
     if (striped) hipLaunchKernelGGL(k_fq_field2<true>, grid, dim3(256), 0, s, d_buf, d_st, d_nl, last, d_text, d_fpos, d_flen, h_f, h_cap, max_rec, d_ts);
     else hipLaunchKernelGGL(k_fq_field2<false>, grid, dim3(256), 0, s, d_buf, d_st, d_nl, last, d_text, d_fpos, d_flen, h_f, h_cap, max_rec, d_ts);
     return hipGetLastError();
 }
 hipError_t launch_tally_add(const uint32_t *d_ids, uint32_t n, unsigned long long *d_counts, uint32_t limit, TallyState *d_ts, hipStream_t s) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_tally_add, dim3((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024), dim3(256), 0, s, d_ids, n, d_counts, limit, d_ts);
+    hipLaunchKernelGGL(k_tally_add, dim3(capped_grid(n, 256, 1024)), dim3(256), 0, s, d_ids, n, d_counts, limit, d_ts);
     return hipGetLastError();
 }
 

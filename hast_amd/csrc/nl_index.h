@@ -1,8 +1,11 @@
-// nl_index.h -- the newline index of a byte range in HBM: where every '\n' of [lo, hi) lies, in order.  One implementation for the
-// framers of `classify` (fq_kernels.hip) and of stage 00's device ingest (sq_kernels.hip): a count per 4-KB tile, an exclusive scan of
-// the counts (scan_device.h), then every tile writes its positions at its scanned base.
+// nl_index.h -- the newline index of a byte range in HBM: where every '\n' of [lo, hi) lies, in order.  One implementation for every
+// framer: a count per 4-KB tile, an exclusive scan of the counts (scan_device.h), then every tile writes its positions at its scanned
+// base.
 // The range may start and end at any address.  Tiles are cut at 16-byte boundaries of the ADDRESS; a 16-byte piece that straddles an
 // edge of the range is read byte by byte, so nothing outside [lo, hi) is touched.
+// A range the HOST knows (rs_, sq_, sq_fasta_, tx_kernels.hip) goes through k_nl_count / k_nl_index (nl_kernels.hip); the scan between
+// them is each family's own: it also initialises its state.  k_fq_count / k_fq_index stay apart: their range is decided on the device
+// (k_fq_begin, FqState) and they zero the tiles outside it.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -22,11 +25,27 @@ constexpr uint32_t kNlTile = 4096;               // bytes per tile = 256 lanes x
 constexpr size_t nl_tiles(size_t n) { return (n + 15) / kNlTile + 2; }
 // words the index of n bytes needs in the worst case, a range that is all newlines
 constexpr size_t nl_index_words(size_t n) { return n + 16; }
-// the grid of a kernel whose workgroups loop over tiles of `per` items: the tiles of the worst case, at least 1, at most 2048
-inline uint32_t capped_grid(size_t items, uint32_t per) {
+// the grid of a kernel whose workgroups loop over tiles of `per` items: the tiles of the worst case, at least 1, at most `cap`
+inline uint32_t capped_grid(size_t items, uint32_t per, uint32_t cap = 2048) {
     const size_t t = (items + per - 1) / per;
-    return (uint32_t)(t < 1 ? 1 : t < 2048 ? t : 2048);
+    return (uint32_t)(t < 1 ? 1 : t < cap ? t : cap);
 }
+
+// a range as the index wants it: the 16-byte boundary in front of it and the bytes [lo, hi) behind that, lo in 0..15
+struct NlRange {
+    const uint8_t *base16;
+    uint64_t lo, hi;
+    uint32_t tiles() const { return (uint32_t)((hi + kNlTile - 1) / kNlTile); }
+    uint32_t grid() const { return tiles() ? tiles() : 1; }
+};
+inline NlRange nl_range(const uint8_t *p, size_t n) {
+    const uint64_t lo = reinterpret_cast<uintptr_t>(p) & 15;
+    return NlRange{p - lo, lo, lo + n};
+}
+struct NlSides {               // one or two ranges a launch, and where each side's tile counts and offsets go
+    NlRange r[2];
+    uint32_t *tile_cnt[2], *nl[2];
+};
 
 // bit i set <=> byte i of w (the byte at the lowest address first) is '\n'
 NL_HD uint32_t nl_bits4(uint32_t w) {
@@ -75,6 +94,10 @@ __device__ __forceinline__ void nl_tile_index(const uint8_t *base16, uint64_t ti
         m &= m - 1;
     }
 }
+
+// (nl_kernels.hip) 1 or 2 ranges in one launch of `grid` tiles each
+void launch_nl_count(const NlSides &in, uint32_t sides, uint32_t grid, hipStream_t s);
+void launch_nl_index(const NlSides &in, uint32_t sides, uint32_t grid, hipStream_t s);
 
 }  // namespace hast
 #endif

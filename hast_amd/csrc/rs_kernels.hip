@@ -1,12 +1,12 @@
 // rs_kernels.hip -- gfx950 device code: a view of raw FASTA or four-line FASTQ in HBM becomes the reads of stage 03's per-read
 // classifier (`classify_read --ingest device`).  The rules are rs_core.h's; the steps, all on one stream:
-//   k_rs_count / k_rs_scan / k_rs_index   the newline index (nl_index.h)
+//   k_nl_count / k_rs_scan / k_nl_index   the newline index (nl_kernels.hip)
 //   k_rs_lines       FASTA, a lane per line: its class and length; per tile of 256 lines the headers and the sequence bytes
 //   k_rs_scan_lines  FASTA: exclusive scans of the two tile sums
 //   k_rs_line_dst    FASTA, a lane per line: line_dst[j] = sequence bytes in front of line j, hdr_line[r] = the line of header r
 //   k_rs_records     a lane per record: name extent, start and length of the read, the format error; consumed and the counts
 //   k_rs_scan_names  exclusive scan of the name lengths per tile of 256 records
-//   k_rs_names       names gathered back to back: a wave copies its 64 records one after the other, 64 bytes a step
+//   k_rs_names       names gathered back to back (record_gather.h)
 //   k_rs_copy        FASTA: the sequence lines compacted into one base buffer (span_copy.h)
 //   k_rb_*           `--bin-reads` (rb_core.h), behind the classification: the records routed to three runs by their votes; see below
 // FASTQ reads are classified where they lie in the view; a FASTA read is spread over lines, and a k-mer straddles the line breaks,
@@ -16,15 +16,11 @@
 
 #include "nl_index.h"
 #include "rb_core.h"
+#include "record_gather.h"
 #include "rs_device.h"
 #include "span_copy.h"
 
 namespace hast {
-
-__global__ void __launch_bounds__(256) k_rs_count(const uint8_t *base, uint64_t lo, uint64_t hi, uint32_t *tile_cnt) {
-    const uint32_t c = nl_tile_count(base, blockIdx.x, lo, hi);
-    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = c;
-}
 
 __global__ void __launch_bounds__(1024) k_rs_scan(uint32_t *tile_cnt, uint32_t n, RsState *st) {
     __shared__ uint32_t s_part[1024];
@@ -35,11 +31,6 @@ __global__ void __launch_bounds__(1024) k_rs_scan(uint32_t *tile_cnt, uint32_t n
         st->n_nl = n_nl;
         st->n_hdr = st->seq_total = 0;
     }
-}
-
-// nl[j] = offset of the j-th newline from the view's first byte (base + lo)
-__global__ void __launch_bounds__(256) k_rs_index(const uint8_t *base, uint64_t lo, uint64_t hi, const uint32_t *tile_base, uint32_t *nl) {
-    nl_tile_index(base, blockIdx.x, lo, hi, lo, tile_base, nl);
 }
 
 __global__ void __launch_bounds__(kRsTile) k_rs_lines(const uint8_t *in, RsState *st, const uint32_t *nl, uint32_t *tile_h, uint32_t *tile_s) {
@@ -159,10 +150,8 @@ __global__ void __launch_bounds__(1024) k_rs_scan_names(uint32_t *name_tile, RsS
 
 __global__ void __launch_bounds__(kRsTile) k_rs_names(const uint8_t *in, const RsState *st, const uint32_t *name_pos, const uint32_t *name_len,
                                                       const uint32_t *name_tile, uint32_t *name_off, uint8_t *names) {
-    __shared__ uint32_t s_src[kRsTile], s_dst[kRsTile], s_n[kRsTile];
     __shared__ uint32_t s_wave[4];
     const uint32_t n_rec = (uint32_t)st->records, n_tiles = (n_rec + kRsTile - 1) / kRsTile;
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (blockIdx.x == 0 && threadIdx.x == 0) name_off[n_rec] = (uint32_t)st->name_bytes;
     if (st->flags) return;                                       // the format error: nobody reads the names
     for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
@@ -170,18 +159,7 @@ __global__ void __launch_bounds__(kRsTile) k_rs_names(const uint8_t *in, const R
         const uint32_t len = r < n_rec ? name_len[r] : 0;
         const uint32_t dst = name_tile[tile] + block_exclusive_sum_256(len, s_wave);
         if (r < n_rec) name_off[r] = dst;
-        s_src[threadIdx.x] = r < n_rec ? name_pos[r] : 0;
-        s_dst[threadIdx.x] = dst;
-        s_n[threadIdx.x] = len;
-        __syncthreads();
-        const uint32_t in_wave = n_rec - tile * kRsTile > wave * 64 ? (n_rec - tile * kRsTile - wave * 64 < 64 ? n_rec - tile * kRsTile - wave * 64 : 64) : 0;
-        for (uint32_t i = 0; i < in_wave; ++i) {
-            const uint32_t j = wave * 64 + i, k = s_n[j];
-            const uint8_t *src = in + s_src[j];
-            uint8_t *d = names + s_dst[j];
-            for (uint32_t b = lane; b < k; b += 64) d[b] = src[b];
-        }
-        __syncthreads();
+        record_gather_256<GatherBytes>(in, names, r < n_rec ? name_pos[r] : 0, dst, len, n_rec - tile * kRsTile);
     }
 }
 
@@ -204,9 +182,7 @@ __global__ void __launch_bounds__(256) k_rs_copy(const uint8_t *in, const RsStat
 
 hipError_t launch_rs_frame(int format, const uint8_t *d_base, size_t origin, size_t n, bool last, bool seen_header, uint8_t *d_seq, uint8_t *d_names,
                            uint8_t *d_scratch, const RsScratchPlan &p, hipStream_t s) {
-    const uint64_t lo = origin & 15, hi = lo + n;                // the index's tiles start at the 16-byte boundary in front of the view
-    const uint8_t *in = d_base + origin, *base16 = in - lo;
-    const uint32_t n_tiles = (uint32_t)((hi + kNlTile - 1) / kNlTile), grid = n_tiles ? n_tiles : 1;
+    const uint8_t *in = d_base + origin;
     auto words = [&](size_t at) { return reinterpret_cast<uint32_t *>(d_scratch + at); };
     uint32_t *tile_cnt = words(p.tile_cnt), *nl = words(p.nl), *tile_h = words(p.line_tile_h), *tile_s = words(p.line_tile_s), *line_dst = words(p.line_dst);
     uint32_t *hdr_line = words(p.hdr_line), *name_pos = words(p.name_pos), *name_len = words(p.name_len), *name_tile = words(p.name_tile);
@@ -215,9 +191,11 @@ hipError_t launch_rs_frame(int format, const uint8_t *d_base, size_t origin, siz
     RsState *st = reinterpret_cast<RsState *>(d_scratch + p.state);
     const bool fasta = format == RS_FASTA;
     const uint32_t line_grid = capped_grid(n, kRsTile), rec_grid = capped_grid(fasta ? n / 2 + 1 : n / 4 + 1, kRsTile), copy_grid = capped_grid(n, kSpanCopyTile);
-    hipLaunchKernelGGL(k_rs_count, dim3(grid), dim3(256), 0, s, base16, lo, hi, tile_cnt);
+    const NlSides view{{nl_range(in, n)}, {tile_cnt}, {nl}};
+    const uint32_t grid = view.r[0].grid();
+    launch_nl_count(view, 1, grid, s);
     hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(1024), 0, s, tile_cnt, grid, st);
-    hipLaunchKernelGGL(k_rs_index, dim3(grid), dim3(256), 0, s, base16, lo, hi, tile_cnt, nl);
+    launch_nl_index(view, 1, grid, s);
     if (fasta) {
         hipLaunchKernelGGL(k_rs_lines, dim3(line_grid), dim3(kRsTile), 0, s, in, st, nl, tile_h, tile_s);
         hipLaunchKernelGGL(k_rs_scan_lines, dim3(1), dim3(1024), 0, s, tile_h, tile_s, st);

@@ -1,13 +1,13 @@
 // sq_fasta_kernels.hip -- gfx950 device code: a view of raw FASTA in HBM becomes the base stream hast_kc_count_device eats (stage 00
 // ingest on the device, `unshared_kmers --device-fasta`).  The rules are sq_core.h's (namespace sqfa); the steps, all on one stream:
-//   k_sqfa_count / k_sqfa_scan / k_sqfa_index   the newline index (nl_index.h)
+//   k_nl_count / k_sqfa_scan / k_nl_index   the newline index (nl_kernels.hip)
 //   k_sqfa_lines       a lane per line: stripped length, class, emitted bytes; per tile of 256 lines the headers and the emitted bytes
 //   k_sqfa_scan_lines  one workgroup scans both tile sums; the view's results
 //   k_sqfa_line_dst    a lane per line: line_dst[j] = where in the output line j's bytes start
 //   k_sqfa_copy        the lines compacted into the stream (span_copy.h)
 // A line is anything from a 7-column test file's through an assembler's 60 columns and a 150-base read to a chromosome on one line.
-// The view and the output may start at any address: both are tiled at 16-byte boundaries of the ADDRESS, nothing outside
-// [d_in, d_in + n_in) is read and nothing at or behind d_out + out_bytes is written.
+// The view and the output may start at any address (nl_index.h, span_copy.h): nothing outside [d_in, d_in + n_in) is read and
+// nothing at or behind d_out + out_bytes is written.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -16,11 +16,6 @@
 #include "span_copy.h"
 
 namespace hast {
-
-__global__ void __launch_bounds__(256) k_sqfa_count(const uint8_t *base, uint64_t lo, uint64_t hi, uint32_t *tile_cnt) {
-    const uint32_t c = nl_tile_count(base, blockIdx.x, lo, hi);
-    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = c;
-}
 
 __global__ void __launch_bounds__(1024) k_sqfa_scan(uint32_t *tile_cnt, uint32_t n, SqFaState *st) {
     __shared__ uint32_t s_part[1024];
@@ -32,11 +27,6 @@ __global__ void __launch_bounds__(1024) k_sqfa_scan(uint32_t *tile_cnt, uint32_t
         st->n_nl = n_nl;
         st->n_lines = st->lines_bytes = 0;
     }
-}
-
-// nl[j] = offset of the j-th newline from the view's first byte (base + lo)
-__global__ void __launch_bounds__(256) k_sqfa_index(const uint8_t *base, uint64_t lo, uint64_t hi, const uint32_t *tile_base, uint32_t *nl) {
-    nl_tile_index(base, blockIdx.x, lo, hi, lo, tile_base, nl);
 }
 
 struct SqFaLine {
@@ -125,18 +115,17 @@ __global__ void __launch_bounds__(256) k_sqfa_copy(const uint8_t *in, const SqFa
 
 hipError_t launch_sq_fasta_frame(const uint8_t *d_in, size_t n_in, uint8_t *d_out, unsigned in_flags, uint8_t *d_scratch, const SqFaScratchPlan &p,
                                  hipStream_t s) {
-    const uint64_t lo = reinterpret_cast<uintptr_t>(d_in) & 15, hi = lo + n_in;
-    const uint8_t *base = d_in - lo;
     const uint32_t olo = (uint32_t)(reinterpret_cast<uintptr_t>(d_out) & 15);
     const int open_in = (in_flags & SQ_FA_OPEN) != 0, last = (in_flags & SQ_FA_LAST) != 0;
-    const uint32_t n_tiles = (uint32_t)((hi + kNlTile - 1) / kNlTile), grid = n_tiles ? n_tiles : 1;
     auto words = [&](size_t at) { return reinterpret_cast<uint32_t *>(d_scratch + at); };
     uint32_t *tile_cnt = words(p.tile_cnt), *nl = words(p.nl), *tile_h = words(p.tile_h), *tile_e = words(p.tile_e), *line_dst = words(p.line_dst);
     SqFaState *st = reinterpret_cast<SqFaState *>(d_scratch + p.state);
     const uint32_t line_grid = capped_grid(n_in + 1, kSqFaTile), copy_grid = capped_grid(n_in + 16, kSpanCopyTile);
-    hipLaunchKernelGGL(k_sqfa_count, dim3(grid), dim3(256), 0, s, base, lo, hi, tile_cnt);
+    const NlSides view{{nl_range(d_in, n_in)}, {tile_cnt}, {nl}};
+    const uint32_t grid = view.r[0].grid();
+    launch_nl_count(view, 1, grid, s);
     hipLaunchKernelGGL(k_sqfa_scan, dim3(1), dim3(1024), 0, s, tile_cnt, grid, st);
-    hipLaunchKernelGGL(k_sqfa_index, dim3(grid), dim3(256), 0, s, base, lo, hi, (const uint32_t *)tile_cnt, nl);
+    launch_nl_index(view, 1, grid, s);
     hipLaunchKernelGGL(k_sqfa_lines, dim3(line_grid), dim3(kSqFaTile), 0, s, d_in, (uint64_t)n_in, last, st, (const uint32_t *)nl, tile_h, tile_e);
     hipLaunchKernelGGL(k_sqfa_scan_lines, dim3(1), dim3(1024), 0, s, tile_h, tile_e, st, open_in, last);
     hipLaunchKernelGGL(k_sqfa_line_dst, dim3(line_grid), dim3(kSqFaTile), 0, s, d_in, (uint64_t)n_in, (const SqFaState *)st, (const uint32_t *)nl,

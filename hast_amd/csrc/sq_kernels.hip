@@ -1,28 +1,21 @@
 // sq_kernels.hip -- gfx950 device code: a block of raw four-line FASTQ in HBM becomes the base stream hast_kc_count_device eats
 // (stage 00 ingest on the device).  The rules are sq_core.h's; the steps, all on one stream:
-//   k_sq_count      newlines per 4-KB tile of the block (16 bytes per lane)
+//   k_nl_count      newlines per 4-KB tile of the block (nl_kernels.hip)
 //   k_sq_scan       exclusive scan of the tile counts; the block's newline and record counts
-//   k_sq_index      offsets of all newlines, in order
+//   k_nl_index      offsets of all newlines, in order (nl_kernels.hip)
 //   k_sq_records    a lane per record: the four extents, the rules, the record's output length and where its sequence lies
 //   k_sq_scan_out   exclusive scan of the output lengths per tile of 256 records; the block's verdict
-//   k_sq_copy       every wave copies its 64 records one after the other, 64 bytes a step, and ends each with '\n'
+//   k_sq_copy       the sequences gathered back to back, each ended with '\n' (record_gather.h)
 // A block that breaks a rule is not copied at all: k_sq_copy reads the verdict on the device.
-// The block may start at any address: the tiles are cut at 16-byte boundaries of the ADDRESS, and the 16-byte pieces that reach
-// outside the block are read byte by byte, so nothing outside [d_in, d_in + n_in) is touched.
+// The block may start at any address (nl_index.h): nothing outside [d_in, d_in + n_in) is touched.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "nl_index.h"
+#include "record_gather.h"
 #include "sq_device.h"
 
 namespace hast {
-
-// The newline index is nl_index.h's, shared with the framer of `classify` (fq_kernels.hip); here its offsets count from the block's
-// first byte, base + lo.
-__global__ void __launch_bounds__(256) k_sq_count(const uint8_t *base, uint64_t lo, uint64_t hi, uint32_t *tile_cnt) {
-    const uint32_t c = nl_tile_count(base, blockIdx.x, lo, hi);
-    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = c;
-}
 
 __global__ void __launch_bounds__(1024) k_sq_scan(uint32_t *tile_cnt, uint32_t n, SqState *st) {
     __shared__ uint32_t s_part[1024];
@@ -34,11 +27,6 @@ __global__ void __launch_bounds__(1024) k_sq_scan(uint32_t *tile_cnt, uint32_t n
         st->flags = n_nl < 4 ? SQ_NO_RECORD : 0u;
         st->first_bad = sq::kNoBad;
     }
-}
-
-// nl[j] = offset of the j-th newline from the block's first byte (base + lo)
-__global__ void __launch_bounds__(256) k_sq_index(const uint8_t *base, uint64_t lo, uint64_t hi, const uint32_t *tile_base, uint32_t *nl) {
-    nl_tile_index(base, blockIdx.x, lo, hi, lo, tile_base, nl);
 }
 
 __global__ void __launch_bounds__(kSqRecTile) k_sq_records(const uint8_t *in, SqState *st, const uint32_t *nl, uint32_t *r_src, uint32_t *r_len, uint32_t *tile_sum) {
@@ -83,43 +71,28 @@ __global__ void __launch_bounds__(1024) k_sq_scan_out(uint32_t *tile_sum, SqStat
 
 __global__ void __launch_bounds__(kSqRecTile) k_sq_copy(const uint8_t *in, const SqState *st, const uint32_t *r_src, const uint32_t *r_len, const uint32_t *tile_base,
                                                         uint8_t *out) {
-    __shared__ uint32_t s_src[kSqRecTile], s_dst[kSqRecTile], s_n[kSqRecTile];
     __shared__ uint32_t s_wave[4];
     if (st->flags) return;
     const uint32_t n_rec = st->n_rec, n_tiles = (n_rec + kSqRecTile - 1) / kSqRecTile;
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const uint32_t i = tile * kSqRecTile + threadIdx.x;
-        const uint32_t len = i < n_rec ? r_len[i] : 0;
-        s_src[threadIdx.x] = i < n_rec ? r_src[i] : 0;
-        s_dst[threadIdx.x] = tile_base[tile] + block_exclusive_sum_256(len, s_wave);
-        s_n[threadIdx.x] = len;
-        __syncthreads();
-        for (uint32_t r = 0; r < 64; ++r) {
-            const uint32_t j = wave * 64 + r;
-            const uint32_t n = s_n[j];                           // sequence + '\n'; 0 behind the last record
-            if (n == 0) break;
-            const uint8_t *src = in + s_src[j];
-            uint8_t *d = out + s_dst[j];
-            for (uint32_t b = lane; b + 1 < n; b += 64) d[b] = src[b];
-            if (lane == ((n - 1) & 63)) d[n - 1] = '\n';
-        }
-        __syncthreads();
+        const uint32_t len = i < n_rec ? r_len[i] : 0;           // sequence + '\n'
+        const uint32_t dst = tile_base[tile] + block_exclusive_sum_256(len, s_wave);
+        record_gather_256<GatherLines>(in, out, i < n_rec ? r_src[i] : 0, dst, len, n_rec - tile * kSqRecTile);
     }
 }
 
 hipError_t launch_sq_frame(const uint8_t *d_in, size_t n_in, uint8_t *d_out, uint8_t *d_scratch, const SqScratchPlan &p, hipStream_t s) {
-    const uint64_t lo = reinterpret_cast<uintptr_t>(d_in) & 15, hi = lo + n_in;
-    const uint8_t *base = d_in - lo;
-    const uint32_t n_tiles = (uint32_t)((hi + kNlTile - 1) / kNlTile), grid = n_tiles ? n_tiles : 1;
     uint32_t *tile_cnt = reinterpret_cast<uint32_t *>(d_scratch + p.tile_cnt), *nl = reinterpret_cast<uint32_t *>(d_scratch + p.nl);
     uint32_t *r_src = reinterpret_cast<uint32_t *>(d_scratch + p.r_src), *r_len = reinterpret_cast<uint32_t *>(d_scratch + p.r_len);
     uint32_t *r_tile = reinterpret_cast<uint32_t *>(d_scratch + p.r_tile);
     SqState *st = reinterpret_cast<SqState *>(d_scratch + p.state);
     const uint32_t rec_grid = capped_grid(n_in / 4, kSqRecTile);
-    hipLaunchKernelGGL(k_sq_count, dim3(grid), dim3(256), 0, s, base, lo, hi, tile_cnt);
+    const NlSides block{{nl_range(d_in, n_in)}, {tile_cnt}, {nl}};
+    const uint32_t grid = block.r[0].grid();
+    launch_nl_count(block, 1, grid, s);
     hipLaunchKernelGGL(k_sq_scan, dim3(1), dim3(1024), 0, s, tile_cnt, grid, st);
-    hipLaunchKernelGGL(k_sq_index, dim3(grid), dim3(256), 0, s, base, lo, hi, tile_cnt, nl);
+    launch_nl_index(block, 1, grid, s);
     hipLaunchKernelGGL(k_sq_records, dim3(rec_grid), dim3(kSqRecTile), 0, s, d_in, st, nl, r_src, r_len, r_tile);
     hipLaunchKernelGGL(k_sq_scan_out, dim3(1), dim3(1024), 0, s, r_tile, st);
     hipLaunchKernelGGL(k_sq_copy, dim3(rec_grid), dim3(kSqRecTile), 0, s, d_in, st, r_src, r_len, r_tile, d_out);

@@ -1,9 +1,9 @@
 // tx_kernels.hip -- gfx950 device code: two buffers of raw four-line FASTQ in HBM (stLFR read 1 and read 2) become two runs of 10x
 // records (stage 02's fake_10x.pl; hast_tx_pair_device).  The rules are tx_core.h's, what is decided per record tx_plan.h's; the
 // steps, all on one stream, shaped as sq_kernels.hip's:
-//   k_tx_count      newlines per 4-KB tile of both inputs (blockIdx.y = the side)
+//   k_nl_count      newlines per 4-KB tile of both inputs (nl_kernels.hip)
 //   k_tx_scan       exclusive scan of both sides' tile counts; lines[], the pairs m of the step
-//   k_tx_index      offsets of all newlines of both sides, in order
+//   k_nl_index      offsets of all newlines of both sides, in order (nl_kernels.hip)
 //   k_tx_keys       a lane per pair: the key of the read-1 header, its slot in the map's table (kNoSlot: dropped); kept pairs per tile
 //   k_tx_scan_kept  exclusive scan of the kept pairs per tile; used
 //   k_tx_sizes      a lane per pair: its rank among the kept, N, the plan; both records' lengths summed per tile
@@ -20,17 +20,6 @@
 
 namespace hast {
 
-struct TxSides {               // both inputs as nl_index.h wants them: a 16-byte aligned base and the range inside it
-    const uint8_t *base[2];
-    uint64_t lo[2], hi[2];
-};
-
-__global__ void __launch_bounds__(256) k_tx_count(TxSides in, uint32_t *tile_cnt0, uint32_t *tile_cnt1) {
-    const uint32_t s = blockIdx.y;
-    const uint32_t c = nl_tile_count(in.base[s], blockIdx.x, in.lo[s], in.hi[s]);
-    if (threadIdx.x == 0) (s ? tile_cnt1 : tile_cnt0)[blockIdx.x] = c;
-}
-
 __global__ void __launch_bounds__(1024) k_tx_scan(uint32_t *tile_cnt0, uint32_t *tile_cnt1, uint32_t n, TxDevState *st) {
     __shared__ uint32_t s_part[1024];
     const uint32_t n_nl0 = block_exclusive_scan_1024(tile_cnt0, n, s_part);
@@ -43,12 +32,6 @@ __global__ void __launch_bounds__(1024) k_tx_scan(uint32_t *tile_cnt0, uint32_t 
         st->lines[1] = n_nl1;
         st->refused = st->pad = 0;
     }
-}
-
-// nl[j] = offset of the j-th newline from the side's first byte
-__global__ void __launch_bounds__(256) k_tx_index(TxSides in, const uint32_t *tile_base0, const uint32_t *tile_base1, uint32_t *nl0, uint32_t *nl1) {
-    const uint32_t s = blockIdx.y;
-    nl_tile_index(in.base[s], blockIdx.x, in.lo[s], in.hi[s], in.lo[s], s ? tile_base1 : tile_base0, s ? nl1 : nl0);
 }
 
 __global__ void __launch_bounds__(kTxTile) k_tx_keys(const uint8_t *r1, TxDevState *st, const uint32_t *nl1, const uint32_t *nl2, const tx::TableSlot *table,
@@ -166,24 +149,17 @@ __global__ void __launch_bounds__(kTxTile) k_tx_copy(const uint8_t *r1, const ui
 }
 
 hipError_t launch_tx_step(const TxStepArgs &a, uint8_t *d_scratch, const TxScratchPlan &p, hipStream_t s) {
-    TxSides in;
-    uint32_t n_tiles = 1;
-    for (int side = 0; side < 2; ++side) {
-        in.lo[side] = reinterpret_cast<uintptr_t>(a.d_in[side]) & 15;
-        in.hi[side] = in.lo[side] + a.n_in[side];
-        in.base[side] = a.d_in[side] - in.lo[side];
-        const uint32_t t = (uint32_t)((in.hi[side] + kNlTile - 1) / kNlTile);
-        if (t > n_tiles) n_tiles = t;
-    }
     auto words = [&](size_t at) { return reinterpret_cast<uint32_t *>(d_scratch + at); };
     uint32_t *cnt0 = words(p.tile_cnt[0]), *cnt1 = words(p.tile_cnt[1]), *nl0 = words(p.nl[0]), *nl1 = words(p.nl[1]);
     uint32_t *slot = words(p.slot), *tile_kept = words(p.tile_kept), *out0 = words(p.tile_out[0]), *out1 = words(p.tile_out[1]);
     TxDevState *st = reinterpret_cast<TxDevState *>(d_scratch + p.state);
+    const NlSides in{{nl_range(a.d_in[0], a.n_in[0]), nl_range(a.d_in[1], a.n_in[1])}, {cnt0, cnt1}, {nl0, nl1}};
+    const uint32_t n_tiles = in.r[0].grid() > in.r[1].grid() ? in.r[0].grid() : in.r[1].grid();
     const size_t least = a.n_in[0] < a.n_in[1] ? a.n_in[0] : a.n_in[1];
     const uint32_t grid = capped_grid(least / 4, kTxTile);
-    hipLaunchKernelGGL(k_tx_count, dim3(n_tiles, 2), dim3(256), 0, s, in, cnt0, cnt1);
+    launch_nl_count(in, 2, n_tiles, s);
     hipLaunchKernelGGL(k_tx_scan, dim3(1), dim3(1024), 0, s, cnt0, cnt1, n_tiles, st);
-    hipLaunchKernelGGL(k_tx_index, dim3(n_tiles, 2), dim3(256), 0, s, in, cnt0, cnt1, nl0, nl1);
+    launch_nl_index(in, 2, n_tiles, s);
     hipLaunchKernelGGL(k_tx_keys, dim3(grid), dim3(kTxTile), 0, s, a.d_in[0], st, nl0, nl1, a.d_table, a.n_slots, slot, tile_kept);
     hipLaunchKernelGGL(k_tx_scan_kept, dim3(1), dim3(1024), 0, s, tile_kept, st);
     hipLaunchKernelGGL(k_tx_sizes, dim3(grid), dim3(kTxTile), 0, s, st, nl0, nl1, slot, tile_kept, a.d_table, a.used, out0, out1);

@@ -42,7 +42,7 @@ struct StepResult {            // hast_tx_result, and whether the step was refus
 static StepResult device_model(const std::vector<tx::TableSlot> &table, const std::vector<uint8_t> in[2], uint64_t used, uint64_t cap0, uint64_t cap1,
                                std::string out[2]) {
     StepResult r;
-    // k_tx_count / k_tx_scan / k_tx_index: the newline index of both sides
+    // k_nl_count / k_tx_scan / k_nl_index: the newline index of both sides
     std::vector<uint32_t> nl[2];
     for (int s = 0; s < 2; ++s) {
         for (size_t i = 0; i < in[s].size(); ++i)

@@ -25,13 +25,16 @@ def constant(text, name):
 
 
 def test_capped_grid_caps_at_2048():
-    body = re.search(r"inline uint32_t capped_grid\(size_t items, uint32_t per\) \{(.*?)\n\}", src("nl_index.h"), re.S)
+    body = re.search(r"inline uint32_t capped_grid\(size_t items, uint32_t per, uint32_t cap = (\d+)\) \{(.*?)\n\}", src("nl_index.h"), re.S)
     assert body, "capped_grid is no longer where it was" + MOVE
-    caps = {int(x) for x in re.findall(r"\b(\d{3,})\b", body.group(1))}
-    assert caps == {pg.GRID_CAP}, "capped_grid caps at %s, the tests assume %d" % (sorted(caps), pg.GRID_CAP) + MOVE
+    assert int(body.group(1)) == pg.GRID_CAP, "capped_grid caps at %s by default, the tests assume %d" % (body.group(1), pg.GRID_CAP) + MOVE
+    # the cap is the parameter and nothing else: no other number in the body, and the tiles are held against `cap`
+    assert not re.findall(r"\b(\d{3,})\b", body.group(2)) and re.search(r"t < cap \? t : cap", body.group(2)), "capped_grid's body" + MOVE
     # every loop the big views are meant for takes its grid from it
     for name, n in (("rs_kernels.hip", 2), ("sq_kernels.hip", 1), ("sq_fasta_kernels.hip", 1), ("tx_kernels.hip", 1)):
-        assert len(re.findall(r"capped_grid\(", src(name))) >= n, name + MOVE
+        calls = re.findall(r"capped_grid\(([^;]*?)\)[,;]", src(name))
+        assert len(calls) >= n, name + MOVE
+        assert all(re.fullmatch(r"[^,]+, k\w+Tile", c) for c in calls), "%s passes a cap of its own: %s" % (name, calls) + MOVE
 
 
 def test_tile_constants():
@@ -54,11 +57,14 @@ def test_fixed_grids_of_the_fq_kernels():
 def test_name_insert_and_tally_launches_cap_at_1024():
     text = src("fq_kernels.hip")
     for kernel, launches in (("k_fq_name_claim", 2), ("k_fq_name", 1), ("k_names_insert", 1), ("k_tally_add", 1)):
-        grids = re.findall(r"hipLaunchKernelGGL\(%s,\s*dim3\(\((\w+) \+ 255\) / 256 < (\d+) \? \(\1 \+ 255\) / 256 : (\d+)\), dim3\(256\)" % kernel, text)
+        grids = re.findall(r"hipLaunchKernelGGL\(%s,\s*dim3\(capped_grid\(\w+, (\d+), (\d+)\)\), dim3\((\d+)\)" % kernel, text)
         assert len(grids) == launches, (kernel, grids, MOVE)
-        assert all(int(a) == int(b) == pg.NAME_GRID_CAP for _, a, b in grids), "%s: %s, the tests assume a cap of %d" % (kernel, grids, pg.NAME_GRID_CAP) + MOVE
-    m = re.search(r"const dim3 grid\(\(unsigned\)std::max<uint64_t>\(1, std::min<uint64_t>\((\d+), \(most \+ 255\) / 256\)\)\);", text)
-    assert m and int(m.group(1)) == pg.NAME_GRID_CAP, "k_fq_field2's grid" + MOVE
+        assert all(int(per) == int(block) == pg.TILE and int(cap) == pg.NAME_GRID_CAP for per, cap, block in grids), \
+            "%s: %s, the tests assume a cap of %d" % (kernel, grids, pg.NAME_GRID_CAP) + MOVE
+    m = re.search(r"const dim3 grid\(capped_grid\(most, (\d+), (\d+)\)\);", text)
+    assert m and int(m.group(1)) == pg.TILE and int(m.group(2)) == pg.NAME_GRID_CAP, "k_fq_field2's grid" + MOVE
+    for kernel in ("k_fq_field2<true>", "k_fq_field2<false>"):
+        assert re.search(r"hipLaunchKernelGGL\(%s, grid, dim3\(256\)" % re.escape(kernel), text), kernel + MOVE
 
 
 def test_the_block_scan_takes_ceil_n_over_1024_a_thread():
@@ -78,17 +84,14 @@ def test_sizes_follow_from_the_caps():
 
 
 def test_scan_runs_cover_every_tile_once():
-    """the index arithmetic of block_exclusive_scan_1024 (and of k_route_scan, whose lo is not clamped: hi < lo ends its loops), restated
-    in past_grid_corpus.scan_runs: at n = 2050 every thread up to 682 takes three tiles, thread 683 one, the rest none"""
+    """the index arithmetic of block_exclusive_scan_1024, restated in past_grid_corpus.scan_runs: at n = 2050 every thread up to 682 takes
+    three tiles, thread 683 one, the rest none"""
     for n in (0, 1, 1023, 1024, 1025, 2047, 2048, 2049, 2050, 3 * 2050, 4097, 65536 + 5):
         runs = pg.scan_runs(n)
         covered = [i for lo, hi in runs for i in range(lo, hi)]
         assert covered == list(range(n)), n
         per = -(-n // pg.SCAN_THREADS)
         assert all(hi - lo <= per for lo, hi in runs)
-        # the unclamped variant: lo = t * per, hi = min(lo + per, n); a thread past the end has hi < lo and loops over nothing
-        loose = [i for t in range(pg.SCAN_THREADS) for i in range(t * per, min(t * per + per, n))]
-        assert loose == covered, n
     runs = pg.scan_runs(-(-pg.N2 // pg.TILE))
     assert runs[682] == (2046, 2049) and runs[683] == (2049, 2050) and all(lo == hi == 2050 for lo, hi in runs[684:])
     # a thread that summed its run but rewrote one value too few, or started one late, would show: the exclusive scan by runs

@@ -343,7 +343,7 @@ def test_sq_fasta_view_past_one_grid(sq_model, sqfa_model):
 
 # ---- stage 01: routing, names, tallies (fq_kernels.hip) ----------------------------------------------------------------------
 def test_fq_routing_past_one_grid():
-    """k_route_class (1024 workgroups: three walks), k_route_scan (its own scan, three tiles a thread), k_route_copy and k_fq_records
+    """k_route_class (1024 workgroups: three walks), k_route_scan (four class rows a scan: nine entries a thread), k_route_copy and k_fq_records
     (2048 workgroups: two walks) on one block"""
     data, cls_of = pg.route_fastq(N2)
     want, want_dropped = fq_gpu._awk_route(data, cls_of)
