@@ -864,6 +864,7 @@ class SqFeed:
 
     def __init__(self, kc: KmerCounter, block_bytes, formats=SQ_TAKE_FASTQ):
         self._lib = lib()
+        self._kc = kc
         self.block = block_bytes
         h = C.c_void_p()
         _ck(self._lib.hast_sq_feed_create(kc._h, block_bytes, C.byref(h)))
@@ -878,12 +879,18 @@ class SqFeed:
     def format(self):
         return self._lib.hast_sq_feed_format(self._h)
 
-    def submit(self, data: bytes):
-        """up to block_bytes through the pinned staging block"""
+    def submit(self, data: bytes, device=None):
+        """up to block_bytes through the pinned staging block; device=<a Context on the table's device>: written into the feed's
+        device block instead, once the table's stream has run dry (nothing reads the view any more), with a synchronous copy"""
         assert 0 < len(data) <= self.block
         p = C.c_void_p()
-        _ck(self._lib.hast_sq_feed_host_block(self._h, C.byref(p)))
-        C.memmove(p, data, len(data))
+        if device is not None:
+            _ck(self._lib.hast_sq_feed_device_block(self._h, C.byref(p)))
+            self._kc.sync()
+            _ck(self._lib.hast_memcpy_h2d(device._h, p, data, len(data)))
+        else:
+            _ck(self._lib.hast_sq_feed_host_block(self._h, C.byref(p)))
+            C.memmove(p, data, len(data))
         _ck(self._lib.hast_sq_feed_submit(self._h, len(data)))
 
     def next(self, parent) -> SqResult:

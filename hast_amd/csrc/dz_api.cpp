@@ -8,14 +8,32 @@
 
 using namespace hast;
 
-#define DZ_HIP(expr)                                                                          \
-    do {                                                                                      \
-        const hipError_t e_ = (expr);                                                         \
-        if (e_ != hipSuccess) {                                                               \
-            st = set_error(e_ == hipErrorOutOfMemory ? HAST_ERR_OOM : HAST_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-            goto out;                                                                         \
-        }                                                                                     \
-    } while (0)
+namespace hast {
+namespace dz {
+
+size_t slot_bytes(uint32_t max_pieces, uint32_t n_jobs) { return ((workspace_bytes(max_pieces) + 63) & ~(size_t)63) + n_jobs * (sizeof(Job) + sizeof(Result)); }
+hipError_t slot_alloc(EncoderSlot *s, uint32_t max_pieces, uint32_t n_jobs) {
+    *s = EncoderSlot{nullptr, slot_bytes(max_pieces, n_jobs), max_pieces, n_jobs};
+    return dev_malloc(&s->d_work, s->bytes);
+}
+void slot_release(EncoderSlot *s, bool park) {
+    park ? park_device(s->d_work, s->bytes, 3) : (void)hipFree(s->d_work);
+    *s = EncoderSlot{};
+}
+
+static hast_status compress_one(const EncoderSlot &z, const uint8_t *d_src, size_t n_bytes, uint8_t *d_dst, size_t cap, size_t *n_out, int literals_only, hipStream_t hs) {
+    Result res;
+    HAST_HIP_TRY(launch_job_one(z.job(), n_bytes, hs));
+    HAST_HIP_TRY(launch_compress(z.job(), d_src, z.max_pieces, z.d_work, d_dst, cap, z.res(), literals_only, hs));
+    HAST_HIP_TRY(hipMemcpyAsync(&res, z.res(), sizeof res, hipMemcpyDeviceToHost, hs));
+    HAST_HIP_TRY(hipStreamSynchronize(hs));
+    if (res.flags) return set_error(HAST_ERR_INVALID, "hast_dz_compress_device: the member did not fit its bound (flags %u)", res.flags);
+    *n_out = (size_t)res.out_bytes[0];
+    return HAST_OK;
+}
+
+}  // namespace dz
+}  // namespace hast
 
 extern "C" {
 
@@ -28,30 +46,14 @@ hast_status hast_dz_compress_device_ex(hast_ctx *c, const uint8_t *d_src, size_t
     if (cap < dz::bound(n_bytes))
         return set_error(HAST_ERR_INVALID, "hast_dz_compress_device: %zu bytes of room, %zu bytes of input can take %zu", cap, n_bytes, (size_t)dz::bound(n_bytes));
     if (n_bytes / dz::kPiece >= (1ull << 31)) return set_error(HAST_ERR_INVALID, "hast_dz_compress_device: input too large for one member");
-    hast_status st = HAST_OK;
     hipStream_t hs = stream ? static_cast<hipStream_t>(stream) : ctx_stream_of(c);
-    const uint32_t max_pieces = (uint32_t)dz::n_pieces(n_bytes);
-    const size_t work_bytes = (dz::workspace_bytes(max_pieces) + 63) & ~(size_t)63;
-    void *d_work = nullptr;
-    dz::Job *d_job = nullptr;
-    dz::Result *d_res = nullptr;
-    dz::Result res;
+    dz::EncoderSlot z;
     *n_out = 0;
-    DZ_HIP(hipSetDevice(hast_ctx_device(c)));
-    DZ_HIP(dev_malloc(&d_work, work_bytes + sizeof(dz::Job) + sizeof(dz::Result)));
-    d_job = reinterpret_cast<dz::Job *>(static_cast<uint8_t *>(d_work) + work_bytes);
-    d_res = reinterpret_cast<dz::Result *>(d_job + 1);
-    DZ_HIP(dz::launch_job_one(d_job, n_bytes, hs));
-    DZ_HIP(dz::launch_compress(d_job, d_src, max_pieces, d_work, d_dst, cap, d_res, (flags & HAST_DZ_LITERALS_ONLY) ? 1 : 0, hs));
-    DZ_HIP(hipMemcpyAsync(&res, d_res, sizeof res, hipMemcpyDeviceToHost, hs));
-    DZ_HIP(hipStreamSynchronize(hs));
-    if (res.flags) st = set_error(HAST_ERR_INVALID, "hast_dz_compress_device: the member did not fit its bound (flags %u)", res.flags);
-    else *n_out = (size_t)res.out_bytes[0];
-out:
-    if (d_work) {
-        (void)hipStreamSynchronize(hs);                     // (nothing of this call may still read the workspace)
-        (void)hipFree(d_work);
-    }
+    HAST_HIP_TRY(hipSetDevice(hast_ctx_device(c)));
+    HAST_HIP_TRY(dz::slot_alloc(&z, (uint32_t)dz::n_pieces(n_bytes)));
+    const hast_status st = dz::compress_one(z, d_src, n_bytes, d_dst, cap, n_out, (flags & HAST_DZ_LITERALS_ONLY) ? 1 : 0, hs);
+    (void)hipStreamSynchronize(hs);                         // (nothing of this call may still read the workspace)
+    dz::slot_release(&z, false);
     return st;
 }
 

@@ -52,6 +52,39 @@ constexpr uint32_t kMemberHead = 10, kMemberTail = 2 + 8;
 GZ_HD uint64_t n_pieces(uint64_t n) { return (n + kPiece - 1) / kPiece; }
 GZ_HD uint64_t bound(uint64_t n) { return kMemberHead + n + 5 * n_pieces(n) + kMemberTail; }
 
+// ---- a compression call as it lies in device memory (the launchers: dz_device.h) ----
+constexpr int kMaxRuns = 4;
+// What to compress: up to four runs of bytes inside one device buffer, a gzip member each.  The sizes may be known on the device only
+// (the routed runs of a FASTQ block: launch_job_from_route), so the kernels read them here and the grids are sized by an upper bound.
+struct Job {
+    uint64_t src_off[kMaxRuns], n_bytes[kMaxRuns];
+    uint32_t n_runs;
+    uint32_t emit_empty;        // 1: a run of 0 bytes becomes an empty member (20 bytes); 0: it becomes nothing
+};
+struct Result {
+    uint64_t out_bytes[kMaxRuns];       // bytes of every member; the members lie back to back from d_dst[0] on
+    uint64_t member_off[kMaxRuns];
+    uint32_t flags;                     // 1: the members do not fit cap, 2: more pieces than the workspace holds (nothing is written then)
+    uint32_t reserved;
+};
+constexpr uint32_t kResOverflow = 1, kResPieces = 2;
+
+// the host's check of a Result before it copies members: those of the first n_runs runs lie back to back from 0 on and end inside
+// cap.  off[c]: where run c's member lies (an empty run's: where it would), *total: the bytes of all of them
+enum Layout { kLayoutOk = 0, kLayoutGap = 1, kLayoutPastCap = 2 };  // (a gap or an overlap)
+inline Layout member_layout(const Result &r, int n_runs, uint64_t cap, uint64_t off[kMaxRuns], uint64_t *total) {
+    uint64_t at = 0;
+    for (int c = 0; c < n_runs; ++c) {
+        off[c] = at;
+        if (!r.out_bytes[c]) continue;
+        if (r.member_off[c] != at) return kLayoutGap;
+        if (r.out_bytes[c] > cap || at > cap - r.out_bytes[c]) return kLayoutPastCap;
+        at += r.out_bytes[c];
+    }
+    *total = at;
+    return kLayoutOk;
+}
+
 // ---- match search ------------------------------------------------------------------------------------------------------------
 GZ_HD uint32_t load4(const uint8_t *in, uint32_t p) {
     return (uint32_t)in[p] | ((uint32_t)in[p + 1] << 8) | ((uint32_t)in[p + 2] << 16) | ((uint32_t)in[p + 3] << 24);

@@ -10,27 +10,24 @@
 namespace hast {
 namespace dz {
 
-constexpr int kMaxRuns = 4;
-// What to compress: up to four runs of bytes inside one device buffer, a gzip member each.  The sizes may be known on the device only
-// (the routed runs of a FASTQ block: launch_job_from_route), so the kernels read them here and the grids are sized by an upper bound.
-struct Job {
-    uint64_t src_off[kMaxRuns], n_bytes[kMaxRuns];
-    uint32_t n_runs;
-    uint32_t emit_empty;        // 1: a run of 0 bytes becomes an empty member (20 bytes); 0: it becomes nothing
-};
-struct Result {
-    uint64_t out_bytes[kMaxRuns];       // bytes of every member; the members lie back to back from d_dst[0] on
-    uint64_t member_off[kMaxRuns];
-    uint32_t flags;                     // 1: the members do not fit cap, 2: more pieces than the workspace holds (nothing is written then)
-    uint32_t reserved;
-};
-constexpr uint32_t kResOverflow = 1, kResPieces = 2;
-
+// (Job and Result: dz_core.h)
 // pieces a job of n_bytes in all can have at most, whatever its runs are
 inline uint32_t max_pieces(uint64_t n_bytes) { return (uint32_t)(n_bytes / kPiece) + kMaxRuns; }
 // most bytes the members of such a job take
 inline uint64_t max_out_bytes(uint64_t n_bytes) { return n_bytes + 5ull * max_pieces(n_bytes) + (uint64_t)kMaxRuns * (kMemberHead + kMemberTail); }
 size_t workspace_bytes(uint32_t max_pieces);
+
+// the encoder's device memory, one allocation: the workspace, behind it the Job and Result of n_jobs calls that take turns in it
+struct EncoderSlot {
+    uint8_t *d_work = nullptr;
+    size_t bytes = 0;
+    uint32_t max_pieces = 0, n_jobs = 0;
+    Job *job(uint32_t i = 0) const { return reinterpret_cast<Job *>(d_work + bytes - n_jobs * (sizeof(Job) + sizeof(Result))) + i; }
+    Result *res(uint32_t i = 0) const { return reinterpret_cast<Result *>(job(n_jobs)) + i; }
+};
+size_t slot_bytes(uint32_t max_pieces, uint32_t n_jobs);
+hipError_t slot_alloc(EncoderSlot *s, uint32_t max_pieces, uint32_t n_jobs = 1);
+void slot_release(EncoderSlot *s, bool park);  // parked at site 3 (hast_internal.h), or freed
 
 hipError_t launch_job_one(Job *d_job, uint64_t n_bytes, hipStream_t s);                       // one run from offset 0, empty member for 0 bytes
 hipError_t launch_job_from_route(Job *d_job, const RouteState *d_rs, hipStream_t s);          // the four runs of a routed block, as they lie in its d_out

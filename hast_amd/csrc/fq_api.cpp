@@ -61,14 +61,12 @@ struct Slot {
     uint8_t *d_rcls = nullptr, *d_out = nullptr, *h_out = nullptr;
     RouteState *d_rs = nullptr, *h_rs = nullptr;       // h_rs pinned
     size_t route_rec = 0;                              // record slots the routing arrays hold
-    // ... as gzip members (hast_fq_set_route_gz): the members back to back and their pinned copy, the encoder's workspace, the call's
-    // description and result (dz_device.h) behind it, the result's pinned copy
+    // ... as gzip members (hast_fq_set_route_gz): the members back to back and their pinned copy, the encoder's memory (dz_device.h),
+    // the result's pinned copy
     uint8_t *d_gz = nullptr, *h_gz = nullptr;
-    void *d_dzwork = nullptr;
-    dz::Job *d_dzjob = nullptr;
-    dz::Result *d_dzres = nullptr, *h_dzres = nullptr;
-    size_t gz_cap = 0, dzwork_bytes = 0;
-    uint32_t dz_pieces = 0;
+    dz::EncoderSlot enc;
+    dz::Result *h_dzres = nullptr;
+    size_t gz_cap = 0;
     bool gz = false;                                   // this block's runs were compressed
     std::vector<uint32_t> v_rstart, v_rlen;            // host copies for a block the caller routes itself (rare)
     std::vector<uint8_t> v_rcls, v_tail;
@@ -158,6 +156,18 @@ static hast_status grow_records(Slot &s, size_t cap) {
     return HAST_OK;
 }
 
+// the members' buffers and the encoder's memory go back (parked, as a closed stream's)
+static void release_gz(Slot &s) {
+    park_device(s.d_gz, s.gz_cap, 3);
+    park_pinned(s.h_gz, s.gz_cap, 3);
+    park_pinned(s.h_dzres, sizeof(dz::Result), 3);
+    dz::slot_release(&s.enc, true);
+    s.d_gz = s.h_gz = nullptr;
+    s.h_dzres = nullptr;
+    s.gz_cap = 0;
+    s.gz = false;
+}
+
 static void free_slot(Slot &s) {
     park_pinned(s.h_cnt, 64, 3);
     park_pinned(s.h_last, 64, 3);
@@ -181,10 +191,7 @@ static void free_slot(Slot &s) {
     park_pinned(s.h_rs, 64, 3);
     park_device(s.d_ts, 0, 3);
     park_pinned(s.h_ts, 64, 3);
-    park_device(s.d_gz, s.gz_cap, 3);
-    park_device(s.d_dzwork, s.dzwork_bytes, 3);
-    park_pinned(s.h_gz, s.gz_cap, 3);
-    park_pinned(s.h_dzres, 64, 3);
+    release_gz(s);
     if (s.copied) (void)hipEventDestroy(s.copied);
     if (s.parsed) (void)hipEventDestroy(s.parsed);
     if (s.done) (void)hipEventDestroy(s.done);
@@ -223,9 +230,9 @@ static hast_status enqueue_route(hast_fq *f, Slot &s, hast_names *tab, bool stri
     if (s.gz) {
         // the runs stay in HBM and are compressed there, a gzip member each (dz_kernels.hip); their sizes come back with the block's
         // state, the members themselves once hast_fq_next_routed knows how long they are
-        HAST_HIP_TRY(dz::launch_job_from_route(s.d_dzjob, s.d_rs, hs));
-        HAST_HIP_TRY(dz::launch_compress(s.d_dzjob, s.d_out, s.dz_pieces, s.d_dzwork, s.d_gz, s.gz_cap, s.d_dzres, 0, hs));
-        HAST_HIP_TRY(hipMemcpyAsync(s.h_dzres, s.d_dzres, sizeof(dz::Result), hipMemcpyDeviceToHost, hs));
+        HAST_HIP_TRY(dz::launch_job_from_route(s.enc.job(), s.d_rs, hs));
+        HAST_HIP_TRY(dz::launch_compress(s.enc.job(), s.d_out, s.enc.max_pieces, s.enc.d_work, s.d_gz, s.gz_cap, s.enc.res(), 0, hs));
+        HAST_HIP_TRY(hipMemcpyAsync(s.h_dzres, s.enc.res(), sizeof(dz::Result), hipMemcpyDeviceToHost, hs));
         return HAST_OK;
     }
     if (view_bytes) HAST_HIP_TRY(hipMemcpyAsync(s.h_out, s.d_out, std::min(view_bytes, s.h_buf_bytes), hipMemcpyDeviceToHost, hs));
@@ -950,31 +957,14 @@ hast_status hast_fq_set_route_gz(hast_fq *f, int on) {
         for (Slot &s : f->slots) {
             if (s.d_gz) continue;
             HAST_HIP_TRY(hipSetDevice(dev_of(f, s)));
-            s.dz_pieces = dz::max_pieces(s.h_buf_bytes);
             s.gz_cap = (size_t)dz::max_out_bytes(s.h_buf_bytes);
-            const size_t work = (dz::workspace_bytes(s.dz_pieces) + 63) & ~(size_t)63;
-            s.dzwork_bytes = work + sizeof(dz::Job) + sizeof(dz::Result);
             HAST_HIP_TRY(dev_malloc(&s.d_gz, s.gz_cap));
-            HAST_HIP_TRY(dev_malloc(&s.d_dzwork, s.dzwork_bytes));
-            s.d_dzjob = reinterpret_cast<dz::Job *>(static_cast<uint8_t *>(s.d_dzwork) + work);
-            s.d_dzres = reinterpret_cast<dz::Result *>(s.d_dzjob + 1);
+            HAST_HIP_TRY(dz::slot_alloc(&s.enc, dz::max_pieces(s.h_buf_bytes)));
             HAST_HIP_TRY(pinned_malloc(&s.h_gz, s.gz_cap));
             HAST_HIP_TRY(pinned_malloc(&s.h_dzres, sizeof(dz::Result)));
         }
     else
-        for (Slot &s : f->slots) {                          // switched off: the members' buffers and the workspace go back (parked, as a closed stream's)
-            if (!s.d_gz) continue;
-            park_device(s.d_gz, s.gz_cap, 3);
-            park_device(s.d_dzwork, s.dzwork_bytes, 3);
-            park_pinned(s.h_gz, s.gz_cap, 3);
-            park_pinned(s.h_dzres, 64, 3);
-            s.d_gz = s.h_gz = nullptr;
-            s.d_dzwork = nullptr;
-            s.d_dzjob = nullptr;
-            s.d_dzres = s.h_dzres = nullptr;
-            s.gz_cap = s.dzwork_bytes = 0;
-            s.gz = false;
-        }
+        for (Slot &s : f->slots) release_gz(s);
     f->route_gz = on != 0;
     return HAST_OK;
 }
@@ -1019,19 +1009,18 @@ hast_status hast_fq_next_routed(hast_fq *f, hast_fq_routed *out) {
     if (s.gz) {
         // gzip members instead of plain runs (a block the caller routes itself has none: its records go by `bytes`)
         const dz::Result zr = *s.h_dzres;
-        uint64_t total = 0;
+        uint64_t total = 0, off[dz::kMaxRuns];
         for (int c = 0; c < 4; ++c) {
             out->run[c] = nullptr;
             out->run_bytes[c] = 0;
         }
         if (!(rs.flags & 1)) {
             if (zr.flags) return set_error(HAST_ERR_INVALID, "the compressed runs overflow their buffer (flags %u)", zr.flags);
+            if (dz::member_layout(zr, 4, s.gz_cap, off, &total)) return set_error(HAST_ERR_INVALID, "the compressed runs are not where they should be");
             for (int c = 0; c < 4; ++c) {
-                if (!zr.out_bytes[c]) continue;
-                if (zr.member_off[c] != total || total + zr.out_bytes[c] > s.gz_cap) return set_error(HAST_ERR_INVALID, "the compressed runs are not where they should be");
-                out->run[c] = s.h_gz + total;
+                if (!zr.out_bytes[c]) continue;              // (an empty run's pointer stays null)
+                out->run[c] = s.h_gz + off[c];
                 out->run_bytes[c] = zr.out_bytes[c];
-                total += zr.out_bytes[c];
             }
             if (total) {
                 HAST_HIP_TRY(hipMemcpyAsync(s.h_gz, s.d_gz, total, hipMemcpyDeviceToHost, hs));

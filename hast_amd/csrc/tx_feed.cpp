@@ -90,11 +90,9 @@ struct hast_tx_feed {
     txfeed::Side side[2];
     // outputs
     size_t cap_out = 0, off1 = 0, cap_gz = 0, cap_host = 0;
-    uint32_t max_pieces = 0;
     uint8_t *d_out[2] = {nullptr, nullptr}, *d_gz[2] = {nullptr, nullptr}, *h_out[2] = {nullptr, nullptr};
-    void *d_work = nullptr;
-    dz::Job *d_job[2] = {nullptr, nullptr};
-    dz::Result *d_res[2] = {nullptr, nullptr}, *h_res = nullptr;         // h_res: pinned, two of them
+    dz::EncoderSlot enc;                                                 // one workspace, a job and a result per output slot
+    dz::Result *h_res = nullptr;                                         // pinned, two of them
     hipEvent_t conv_ev[2] = {nullptr, nullptr}, done_ev[2] = {nullptr, nullptr};
     uint64_t n_steps = 0, n_collected = 0;
     Waiting waiting[2];
@@ -148,23 +146,10 @@ hast_status hast_tx_feed_create(hast_tx *t, size_t block_bytes, int gz_out, hast
         if (e == hipSuccess && !(f->h_fall[s] = static_cast<uint8_t *>(malloc(f->room)))) e = hipErrorOutOfMemory;
     }
     if (e == hipSuccess && f->gz) {
-        f->max_pieces = dz::max_pieces(2 * (uint64_t)f->cap_out);
         f->cap_gz = (size_t)dz::max_out_bytes(2 * (uint64_t)f->cap_out);
         if (f->cap_gz > f->cap_host) f->cap_host = f->cap_gz;
-        const size_t work = (dz::workspace_bytes(f->max_pieces) + 63) & ~(size_t)63;
-        e = dev_malloc(&f->d_work, work + 2 * (sizeof(dz::Job) + sizeof(dz::Result)));
-        if (e == hipSuccess) {
-            uint8_t *at = static_cast<uint8_t *>(f->d_work) + work;
-            for (int slot = 0; slot < 2; ++slot) {
-                f->d_job[slot] = reinterpret_cast<dz::Job *>(at);
-                at += sizeof(dz::Job);
-            }
-            for (int slot = 0; slot < 2; ++slot) {
-                f->d_res[slot] = reinterpret_cast<dz::Result *>(at);
-                at += sizeof(dz::Result);
-            }
-            e = pinned_malloc(&f->h_res, 2 * sizeof(dz::Result));
-        }
+        e = dz::slot_alloc(&f->enc, dz::max_pieces(2 * (uint64_t)f->cap_out), 2);
+        if (e == hipSuccess) e = pinned_malloc(&f->h_res, 2 * sizeof(dz::Result));
         for (int slot = 0; slot < 2 && e == hipSuccess; ++slot) e = dev_malloc(&f->d_gz[slot], f->cap_gz + 64);
     }
     for (int slot = 0; slot < 2 && e == hipSuccess; ++slot) e = pinned_malloc(&f->h_out[slot], f->cap_host);
@@ -279,12 +264,12 @@ hast_status hast_tx_feed_step(hast_tx_feed *f, hast_tx_state *state, hast_tx_res
         if (!ok) return set_error(HAST_ERR_OOM, "hast_tx_feed_step: zlib could not deflate a run");
         *flags |= (int)HAST_TX_ON_HOST;
     } else {
-        if (f->gz) HAST_HIP_TRY(dz::launch_job_from_tx(f->d_job[slot], f->parts.d_state->out_bytes, f->off1, f->cs));
+        if (f->gz) HAST_HIP_TRY(dz::launch_job_from_tx(f->enc.job(slot), f->parts.d_state->out_bytes, f->off1, f->cs));
         HAST_HIP_TRY(hipEventRecord(f->conv_ev[slot], f->cs));
         HAST_HIP_TRY(hipStreamWaitEvent(f->zs, f->conv_ev[slot], 0));
         if (f->gz) {
-            HAST_HIP_TRY(dz::launch_compress(f->d_job[slot], f->d_out[slot], f->max_pieces, f->d_work, f->d_gz[slot], f->cap_gz, f->d_res[slot], 0, f->zs));
-            HAST_HIP_TRY(hipMemcpyAsync(f->h_res + slot, f->d_res[slot], sizeof(dz::Result), hipMemcpyDeviceToHost, f->zs));
+            HAST_HIP_TRY(dz::launch_compress(f->enc.job(slot), f->d_out[slot], f->enc.max_pieces, f->enc.d_work, f->d_gz[slot], f->cap_gz, f->enc.res(slot), 0, f->zs));
+            HAST_HIP_TRY(hipMemcpyAsync(f->h_res + slot, f->enc.res(slot), sizeof(dz::Result), hipMemcpyDeviceToHost, f->zs));
         }
         HAST_HIP_TRY(hipEventRecord(f->done_ev[slot], f->zs));
     }
@@ -398,7 +383,7 @@ void hast_tx_feed_destroy(hast_tx_feed *f) {
             if (ev) (void)hipEventDestroy(ev);
         free(f->h_fall[s]);
     }
-    if (f->d_work) (void)hipFree(f->d_work);
+    dz::slot_release(&f->enc, false);
     if (f->h_res) (void)hipHostFree(f->h_res);
     for (hipStream_t s : {f->cs, f->us, f->zs, f->ds})
         if (s) (void)hipStreamDestroy(s);

@@ -316,3 +316,14 @@ def test_no_larger_than_zlib_level_1_on_the_same_pieces(fast_driver, tmp_path, n
     assert gzip.decompress(blob) == data
     print("%s: %d -> %d bytes, zlib level 1 in pieces %d" % (name, len(data), len(blob), zlib_level_1_in_pieces(data)))
     assert len(blob) <= zlib_level_1_in_pieces(data)
+
+
+def test_member_layout(tmp_path):
+    """dz::member_layout, the host's check of an encoder result before it copies members (tests/native/test_dz_members.cpp): back to
+    back with 1 to 4 runs, empty runs in every position, a gap, an overlap, the last member ending at cap and one byte past it"""
+    exe = str(tmp_path / "test_dz_members")
+    subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-o", exe,
+                    os.path.join(ROOT, "tests", "native", "test_dz_members.cpp")], check=True)
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    assert r.returncode == 0, r.stderr[-2000:].decode(errors="replace")
+    assert r.stdout.startswith(b"ok cases=") and int(r.stdout.split(b"=")[1]) > 100, r.stdout

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import hast_amd
-from hast_amd import KmerCounter, SqFramer, SqResult
+from hast_amd import KmerCounter, SqFeed, SqFramer, SqResult
 from tests import sq_corpus as sc
 from tests.conftest import GOLDEN
 
@@ -240,3 +240,73 @@ def test_framed_stream_counts_to_the_parsers_table(rig, tmp_path):
                 rig.ctx.free(d_in)
                 rig.ctx.free(d_out)
     assert np.array_equal(tables[0][0], tables[1][0]) and tables[0][1:] == tables[1][1:]
+
+
+# ---- hast_sq_feed with host and device blocks in turn ----------------------------------------------------------------------------
+def feed_files():
+    """three small inputs: reads long enough for windows of 11 in records that fit a block of 64, '\\r\\n' without the last line
+    break, and records of up to 340 bytes, which blocks of 64 and 100 cannot hold (HAST_SQ_TAIL_TOO_LONG)"""
+    corpus = {name: data for name, data, _ in sc.valid_corpus()}
+    return {"reads24": sc.fastq(31, 260, (24, 0, 13, 23, 1), b"\n"), "crlf20_nonl": sc.fastq(32, 200, (20, 11, 12), b"\r\n", False),
+            "n65_b2_nonl": corpus["n65_b2_nonl"]}
+
+
+def table_of(kc):
+    kc.sync()
+    histo, stats = kc.histo(0), kc.stats()
+    n = kc.select(0, 1, 1000)
+    kc.release_table()
+    assert n == 0 or kc.selection_sort(0) == n
+    return histo.tolist(), stats["distinct"], stats["total"], kc.selection_text(0, 0, n) if n else b""
+
+
+def feed_model(model, data, block):
+    """the feed restated on the host over the framer's model: (base stream, tail, None), or (base stream so far, None, i) where view i
+    leaves more than a block"""
+    carried, stream = b"", []
+    for i, at in enumerate(range(0, len(data), block)):
+        view = carried + data[at:at + block]
+        res, out = model(as_array(view))
+        assert not res["flags"] & hast_amd.SQ_NOT_FOUR_LINE
+        if len(view) - res["consumed"] > block:
+            return b"".join(stream), None, i
+        stream.append(out.tobytes())
+        carried = view[res["consumed"]:]
+    return b"".join(stream), carried, None
+
+
+def run_feed(ctx, data, block, mixed):
+    """(table, tail, None) or (table so far, None, the view that left too much); mixed: every block with i % 3 == 1 is written into
+    the feed's device block; the feed is always one block ahead of the framer"""
+    blocks = [data[at:at + block] for at in range(0, len(data), block)]
+    with KmerCounter(11, table_bytes=64 << 20) as kc:
+        with SqFeed(kc, block) as feed:
+            def submit(i):
+                feed.submit(blocks[i], device=ctx if mixed and i % 3 == 1 else None)
+            submit(0)
+            for i in range(len(blocks)):
+                if i + 1 < len(blocks):
+                    submit(i + 1)
+                res = feed.next(0)
+                if res.flags & hast_amd.SQ_TAIL_TOO_LONG:
+                    return table_of(kc), None, i
+                assert res.flags & ~hast_amd.SQ_NO_RECORD == 0, (i, res.flags)
+            return table_of(kc), feed.take_tail(), None
+
+
+@pytest.mark.parametrize("block", (64, 100, 4096))
+@pytest.mark.parametrize("name", sorted(feed_files()))
+def test_feed_with_device_blocks_equals_host_blocks_and_the_model(rig, model, name, block):
+    data = feed_files()[name]
+    assert 1000 < len(data) < 20000
+    stream, want_tail, want_stop = feed_model(model, data, block)
+    assert (want_stop is not None) == (name == "n65_b2_nonl" and block < 4096)
+    with KmerCounter(11, table_bytes=64 << 20) as kc:
+        if stream:
+            kc.count(0, as_array(stream))
+        want = table_of(kc)
+    assert want_stop is not None or (want[2][0] > 0 and len(data) > 2 * block)
+    for mixed in (True, False):
+        got, tail, stop = run_feed(rig.ctx, data, block, mixed)
+        assert (tail, stop) == (want_tail, want_stop), (name, block, mixed)
+        assert got == want, (name, block, mixed)
