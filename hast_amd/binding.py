@@ -190,6 +190,8 @@ ABI_SYMBOLS = {
     "hast_dz_bound": (C.c_size_t, [C.c_size_t]),
     "hast_dz_compress_device": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), vp]),
     "hast_dz_compress_device_ex": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_uint, vp]),
+    "hast_dz_bound_blocked": (C.c_size_t, [C.c_size_t]),
+    "hast_dz_compress_blocked_device": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), vp]),
     "hast_gz_open": (C.c_int, [vp, C.c_char_p, C.POINTER(vp)]),
     "hast_gz_open_ex": (C.c_int, [vp, C.c_char_p, C.c_size_t, C.c_size_t, C.c_double, C.POINTER(vp)]),
     "hast_gz_open_multi": (C.c_int, [C.POINTER(vp), C.c_int, C.c_char_p, C.POINTER(vp)]),
@@ -632,6 +634,13 @@ class Context:
         _ck(self._lib.hast_dz_compress_device_ex(self._h, C.c_void_p(d_src), n_bytes, C.c_void_p(d_dst), cap, C.byref(n), 1 if literals_only else 0, stream))
         return n.value
 
+    def dz_compress_blocked_device(self, d_src, n_bytes, d_dst, cap, stream=None) -> int:
+        """the n_bytes at d_src as blocked gzip (BGZF members of at most 49 152 bytes of input; 0 bytes: the end-of-file block),
+        written to d_dst (room: cap >= dz_bound_blocked(n_bytes)); returns the size"""
+        n = C.c_size_t()
+        _ck(self._lib.hast_dz_compress_blocked_device(self._h, C.c_void_p(d_src), n_bytes, C.c_void_p(d_dst), cap, C.byref(n), stream))
+        return n.value
+
     def synth_keys_device(self, p, hap, first, n, d_out, stream=None):
         _ck(self._lib.hast_synth_keys_device(self._h, C.byref(p), hap, first, n, C.c_void_p(d_out), stream))
 
@@ -647,6 +656,11 @@ class Context:
 def dz_bound(n_bytes: int) -> int:
     """the most bytes Context.dz_compress_device can write for n_bytes of input"""
     return lib().hast_dz_bound(n_bytes)
+
+
+def dz_bound_blocked(n_bytes: int) -> int:
+    """the most bytes Context.dz_compress_blocked_device can write for n_bytes of input"""
+    return lib().hast_dz_bound_blocked(n_bytes)
 
 
 def kc_find_bounds(histo: np.ndarray):

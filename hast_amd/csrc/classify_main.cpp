@@ -85,6 +85,9 @@ void print_usage() {                              // same flags as the reference
           "                        input to <name>.{paternal,maternal,homozygous,nobarcode}.fastq (HAST_PHASE_READS=1)\n"
           "      --gz-out          with --phase-reads: the four files are gzip, <name>.<class>.fastq.gz; records routed on the GPU are\n"
           "                        compressed there and only compressed bytes come back (HAST_PHASE_GZ=1)\n"
+          "      --gz-format FMT   with --gz-out: gzip (default) | bgzf: every member written, on the GPU or by the host, is blocked gzip\n"
+          "                        (BGZF, at most 48 KB of records a member) and every file ends with BGZF's end-of-file block: gzip -dc\n"
+          "                        reads the files as before, bgzip / htslib readers and --bgzf device can split them (HAST_PHASE_GZ_FORMAT)\n"
           "      --route MODE      device (default): records routed on the GPU; host: parsed again by host threads\n"
           "      --inflate MODE    device (default) | host | zlib: who inflates .gz inputs (HAST_INFLATE)\n"
           "      --bgzf MODE       host (default) | device: who inflates blocked-gzip (BGZF) inputs (HAST_BGZF)\n"
@@ -277,6 +280,10 @@ struct Options {
     // times on the way to BASELINE config 3's 10M barcodes)
     size_t batch_reads = 0, block_mb = 256, initial_barcodes = 1u << 24;
     bool stats = false, host_parse = false, phase_reads = false, gz_out = false;
+    bool gz_bgzf = false;                          // --gz-format bgzf: what --gz-out writes is blocked gzip (BGZF) with an end-of-file block per file
+    hast::quartering::GzFormat gz_format() const {
+        return !gz_out ? hast::quartering::GzFormat::kNone : gz_bgzf ? hast::quartering::GzFormat::kBgzf : hast::quartering::GzFormat::kGzip;
+    }
     bool bgzf_device = false;                      // --bgzf device: blocked gzip is inflated on the GPU per member (hast_gz_open_blocked)
     double w0 = 1.0, w1 = 1.0;
     // worked out from the above
@@ -447,11 +454,14 @@ bool parse_options(int argc, char **argv, Options &o) {
         {"park-gb", required_argument, NULL, 1014},     {"name-cache", required_argument, NULL, 1015},
         {"deal", required_argument, NULL, 1016},        {"route", required_argument, NULL, 1017},
         {"gz-out", no_argument, NULL, 1018},            {"bgzf", required_argument, NULL, 1019},
+        {"gz-format", required_argument, NULL, 1020},
         {0, 0, 0, 0}};
     static char optstring[] = "p:m:l:r:t:w:u:f:q:h";             // classify.cpp:387
     bool gz_out_flag = false;
     int device = 0;
     const char *bgzf = getenv("HAST_BGZF");                       // (the alias for runs of the unchanged wrapper; the flag wins)
+    const char *gz_format = getenv("HAST_PHASE_GZ_FORMAT");       // (the same; ignored where nothing is written as gzip)
+    bool gz_format_flag = false;
     {
         const char *pr = getenv("HAST_PHASE_READS");
         o.phase_reads = pr && *pr && strcmp(pr, "0") != 0;
@@ -512,6 +522,7 @@ bool parse_options(int argc, char **argv, Options &o) {
             break;
         case 1018: o.gz_out = gz_out_flag = true; break;
         case 1019: bgzf = optarg; break;
+        case 1020: gz_format = optarg; gz_format_flag = true; break;
         case 1008:
             for (const char *q = optarg; *q;) {
                 char *end;
@@ -538,6 +549,16 @@ bool parse_options(int argc, char **argv, Options &o) {
         return false;
     }
     o.gz_out = o.gz_out && o.phase_reads;
+    // --gz-format says how --gz-out writes: without it there is nothing to say (the variable alone is ignored then, as HAST_PHASE_GZ is)
+    if (gz_format_flag && !o.gz_out) {
+        fputs("classify: --gz-format needs --gz-out\n", stderr);
+        print_usage();
+        return false;
+    }
+    if (o.gz_out && gz_format && *gz_format) {
+        if (strcmp(gz_format, "gzip") && strcmp(gz_format, "bgzf")) { print_usage(); return false; }
+        o.gz_bgzf = !strcmp(gz_format, "bgzf");
+    }
     if (bgzf && *bgzf) {
         if (strcmp(bgzf, "host") && strcmp(bgzf, "device")) { print_usage(); return false; }
         o.bgzf_device = !strcmp(bgzf, "device");
@@ -1691,7 +1712,7 @@ void open_next_routed(Run &rs, DeviceRouter &dr) {
     if (rs.stripe) lane_tabs = dr.tabs;
     else lane_tabs.push_back(dr.tabs[fi % rs.ctxs.size()]);
     CK(hast_fq_set_route(f->feed.fq, lane_tabs.data(), (int)lane_tabs.size()), "switching the FASTQ stream to routing");
-    CK(hast_fq_set_route_gz(f->feed.fq, rs.o.gz_out ? 1 : 0), "switching the routed runs to gzip members");
+    CK(hast_fq_set_route_gz(f->feed.fq, rs.o.gz_out ? (rs.o.gz_bgzf ? 2 : 1) : 0), "switching the routed runs to gzip members");
     start_feed(rs, f->feed, dr.wake, cap);
     RoutedFeed *fp = f.get();
     for (int c = 0; c < 4; c++) f->wth[c] = std::thread(write_runs, fp, c, dr.suffix[c], std::ref(dr.wake));
@@ -1715,7 +1736,7 @@ void runs_from_device(Run &rs, PhaseReads &pr, RoutedFeed &f, const hast_fq_rout
             pr.bytes_routed += raw[c];                   // (the records' bytes, as without the flag; the members' sizes: __stats_route_gz__)
             dev.bytes_in += raw[c];
             dev.bytes_out += b.run_bytes[c];
-            dev.members += b.run_bytes[c] != 0;
+            dev.members += rs.o.gz_bgzf ? hq::bgzf_member_count(raw[c]) : b.run_bytes[c] != 0;
         }
     }
     f.counts[4] += (long long)b.n_records;
@@ -1725,6 +1746,15 @@ void runs_from_device(Run &rs, PhaseReads &pr, RoutedFeed &f, const hast_fq_rout
 
 void point_at_own(WriteJob &j) {
     for (int c = 0; c < 4; c++) { j.p[c] = reinterpret_cast<const uint8_t *>((*j.own)[(size_t)c].data()); j.n[c] = (*j.own)[(size_t)c].size(); }
+}
+
+// n bytes of records as the host compresses them, appended to out: one gzip member, or the BGZF members of their slices
+void host_members(Run &rs, const char *p, size_t n, std::string &out, hq::GzOutStats &host, const char *what) {
+    const size_t before = out.size();
+    if (!(rs.o.gz_bgzf ? hq::bgzf_members(p, n, out) : hq::gz_member(p, n, out))) die(2, what);
+    host.bytes_in += n;
+    host.bytes_out += out.size() - before;
+    host.members += rs.o.gz_bgzf ? hq::bgzf_member_count(n) : 1;
 }
 
 // a block the device handed over: every record by the host's rules, in input order
@@ -1748,10 +1778,7 @@ void runs_from_host(Run &rs, PhaseReads &pr, RoutedFeed &f, const hast_fq_routed
         for (int c = 0; c < 4; c++) {
             std::string &plain = (*j.own)[(size_t)c], z;
             if (plain.empty()) continue;
-            if (!hq::gz_member(plain.data(), plain.size(), z)) die(2, "cannot compress a block of routed records");
-            host.bytes_in += plain.size();
-            host.bytes_out += z.size();
-            host.members++;
+            host_members(rs, plain.data(), plain.size(), z, host, "cannot compress a block of routed records");
             plain.swap(z);
         }
     point_at_own(j);
@@ -1773,13 +1800,8 @@ void append_tail(Run &rs, PhaseReads &pr, RoutedFeed &f, const hast_fq_routed &b
     if (c >= 0) {
         std::string rec(rest);
         if (rec.back() != '\n') rec.push_back('\n');
-        if (rs.o.gz_out) {                                  // a member of its own behind the block's
-            const size_t before = (*j.own)[(size_t)c].size();
-            if (!hq::gz_member(rec.data(), rec.size(), (*j.own)[(size_t)c])) die(2, "cannot compress the last record");
-            host.bytes_in += rec.size();
-            host.bytes_out += (*j.own)[(size_t)c].size() - before;
-            host.members++;
-        } else (*j.own)[(size_t)c].append(rec);
+        if (rs.o.gz_out) host_members(rs, rec.data(), rec.size(), (*j.own)[(size_t)c], host, "cannot compress the last record");      // a member of its own behind the block's
+        else (*j.own)[(size_t)c].append(rec);
         f.counts[c]++;
     }
     point_at_own(j);
@@ -1821,7 +1843,7 @@ bool commit_when_written(RoutedFeed &f) {
     return true;
 }
 
-void retire_routed(Run &rs, RoutedFeed &f) {
+void retire_routed(Run &rs, PhaseReads &pr, RoutedFeed &f) {
     f.feed.stop_reader();
     {
         std::lock_guard<std::mutex> g(f.wmu);
@@ -1829,8 +1851,16 @@ void retire_routed(Run &rs, RoutedFeed &f) {
     }
     f.wcv.notify_all();
     for (std::thread &w : f.wth) w.join();
-    for (FILE *&o : f.out)
-        if (o && fclose(o) != 0) die_routed_write(f);
+    for (FILE *&o : f.out) {
+        if (!o) continue;
+        if (rs.o.gz_bgzf) {                                 // every BGZF file that exists ends with one end-of-file block
+            if (fwrite(hq::kBgzfEof, 1, sizeof hq::kBgzfEof, o) != sizeof hq::kBgzfEof) die_routed_write(f);
+            hq::GzOutStats &host = pr.gz_in[f.feed.file_index].host;
+            host.bytes_out += sizeof hq::kBgzfEof;
+            host.members++;
+        }
+        if (fclose(o) != 0) die_routed_write(f);
+    }
     if (f.feed.gz) {
         hast_gz *z = f.feed.gz;
         rs.gz_closers.emplace_back([z] { hast_gz_close(z); });
@@ -1889,7 +1919,7 @@ void route_on_device(Run &rs, PhaseReads &pr) {
                 progress = true;
             }
             if (f.feed.drained() && !f.block_open) {
-                retire_routed(rs, f);
+                retire_routed(rs, pr, f);
                 const size_t idx = f.feed.file_index;
                 dr.finished[idx] = std::move(dr.active[fi]);
                 dr.active.erase(dr.active.begin() + (long)fi);
@@ -1956,12 +1986,12 @@ void route_on_host(Run &rs, PhaseReads &pr) {
                 src.gz = nullptr;                        // (no room on the device, ...: the host inflates)
                 hast::BlockSource hsrc;
                 if (!hsrc.open(x, 64u << 20)) die(2, ("cannot open " + x).c_str());
-                rc = hq::route(name, cls_of, hsrc, "-", o.t_num, "classify", o.gz_out, &pr.gz_in[fi].host);
-            } else rc = hq::route(name, cls_of, src, "-", o.t_num, "classify", o.gz_out, &pr.gz_in[fi].host);
+                rc = hq::route(name, cls_of, hsrc, "-", o.t_num, "classify", o.gz_format(), &pr.gz_in[fi].host);
+            } else rc = hq::route(name, cls_of, src, "-", o.t_num, "classify", o.gz_format(), &pr.gz_in[fi].host);
         } else {
             hast::BlockSource hsrc;
             if (!hsrc.open(x, 64u << 20)) die(2, ("cannot open " + x).c_str());
-            rc = hq::route(name, cls_of, hsrc, gz_name ? "-" : x, o.t_num, "classify", o.gz_out, &pr.gz_in[fi].host);       // (awk's FILENAME behind `gzip -dc` is "-")
+            rc = hq::route(name, cls_of, hsrc, gz_name ? "-" : x, o.t_num, "classify", o.gz_format(), &pr.gz_in[fi].host);       // (awk's FILENAME behind `gzip -dc` is "-")
         }
         if (rc) {
             fprintf(stderr, "classify: ERROR: routing the reads of %s failed\n", x.c_str());
@@ -1996,8 +2026,9 @@ void phase_reads(Run &rs) {
     if (o.stats && o.gz_out)                                // one line per input, in the order of the inputs
         for (size_t i = 0; i < o.read.size(); i++) {
             const PhaseReads::GzIn &g = pr.gz_in[i];
-            stat_line("__stats_route_gz__ file=%s device_bytes_in=%llu device_bytes_out=%llu device_members=%llu host_bytes_in=%llu host_bytes_out=%llu host_members=%llu\n",
-                      o.read[i].c_str(), g.dev.bytes_in, g.dev.bytes_out, g.dev.members, g.host.bytes_in, g.host.bytes_out, g.host.members);
+            // (format=bgzf is said, gzip is not: the line of a run without --gz-format stays what it was, and what sums its fields still can)
+            stat_line("__stats_route_gz__ file=%s%s device_bytes_in=%llu device_bytes_out=%llu device_members=%llu host_bytes_in=%llu host_bytes_out=%llu host_members=%llu\n",
+                      o.read[i].c_str(), o.gz_bgzf ? " format=bgzf" : "", g.dev.bytes_in, g.dev.bytes_out, g.dev.members, g.host.bytes_in, g.host.bytes_out, g.host.members);
         }
 }
 

@@ -23,6 +23,7 @@
 #pragma once
 #include <stdint.h>
 
+#include "bz_core.h"
 #include "gz_core.h"
 
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -52,6 +53,39 @@ constexpr uint32_t kMemberHead = 10, kMemberTail = 2 + 8;
 GZ_HD uint64_t n_pieces(uint64_t n) { return (n + kPiece - 1) / kPiece; }
 GZ_HD uint64_t bound(uint64_t n) { return kMemberHead + n + 5 * n_pieces(n) + kMemberTail; }
 
+// ---- BLOCKED gzip (BGZF, bz_core.h) out of the same pieces ------------------------------------------------------------------------
+// A run's pieces, unchanged, framed as members of at most kBlockedPieces pieces: 18 bytes of header with the BC subfield (BSIZE =
+// the member's bytes - 1), the pieces, the empty final block, CRC-32 and ISIZE of THAT member's input.  A run of n > 0 bytes is
+// n_members(n) such members back to back; an empty run with emit_empty is one empty member, which is BGZF's end-of-file block.
+// Four pieces do not always fit a member (18 + 4 * (16384 + 5) + 10 = 65 584 bytes when every piece is stored), three do.
+constexpr uint32_t kBlockedPieces = 3, kBlockedInput = kBlockedPieces * kPiece;
+constexpr uint32_t kBlockedHead = 18, kBlockedFrame = kBlockedHead + kMemberTail;
+static_assert(kBlockedHead == bz::kMinHeader, "the header is the BC subfield alone");
+static_assert(kBlockedFrame + kBlockedPieces * (kPiece + 5) <= bz::kMaxMember, "a member of stored pieces fits BSIZE");
+static_assert(kBlockedFrame + (kBlockedPieces + 1) * (kPiece + 5) > bz::kMaxMember, "... and one piece more would not");
+static_assert(kBlockedInput <= bz::kMaxIsize, "a member inflates to no more than a BGZF block may");
+GZ_HD uint64_t n_members(uint64_t n) { return (n + kBlockedInput - 1) / kBlockedInput; }
+GZ_HD uint64_t bound_blocked(uint64_t n) { return n + 5 * n_pieces(n) + kBlockedFrame * (n_members(n) ? n_members(n) : 1); }
+// input bytes of a run of n that lie in front of the end of the member piece idx belongs to (where its CRC term is advanced to)
+GZ_HD uint64_t blocked_member_end(uint64_t n, uint64_t idx) {
+    const uint64_t e = (idx / kBlockedPieces + 1) * kBlockedInput;
+    return e < n ? e : n;
+}
+// header and trailer of a member of `total` bytes in all (byte stores: a member starts at any address)
+GZ_HD void put_blocked_frame(uint8_t *m, uint32_t total, uint32_t crc, uint32_t isize) {
+    const uint32_t bsize = total - 1;
+    m[0] = 0x1f; m[1] = 0x8b; m[2] = 8; m[3] = 4;           // FEXTRA
+    m[4] = m[5] = m[6] = m[7] = 0;                          // MTIME
+    m[8] = 0; m[9] = 0xff;                                  // XFL, OS: unknown
+    m[10] = 6; m[11] = 0;                                   // XLEN
+    m[12] = 'B'; m[13] = 'C'; m[14] = 2; m[15] = 0;
+    m[16] = (uint8_t)bsize; m[17] = (uint8_t)(bsize >> 8);
+    uint8_t *t = m + total - kMemberTail;
+    t[0] = 3; t[1] = 0;                                     // the empty final block (fixed code: BFINAL = 1, BTYPE = 01b, end of block)
+    for (uint32_t k = 0; k < 4; ++k) t[2 + k] = (uint8_t)(crc >> (8 * k)), t[6 + k] = (uint8_t)(isize >> (8 * k));
+}
+// (the host's statement of a blocked run: blocked_run, at the end of this file)
+
 // ---- a compression call as it lies in device memory (the launchers: dz_device.h) ----
 constexpr int kMaxRuns = 4;
 // What to compress: up to four runs of bytes inside one device buffer, a gzip member each.  The sizes may be known on the device only
@@ -59,15 +93,18 @@ constexpr int kMaxRuns = 4;
 struct Job {
     uint64_t src_off[kMaxRuns], n_bytes[kMaxRuns];
     uint32_t n_runs;
-    uint32_t emit_empty;        // 1: a run of 0 bytes becomes an empty member (20 bytes); 0: it becomes nothing
+    uint32_t emit_empty;        // 1: a run of 0 bytes becomes an empty member (20 bytes; blocked: 28); 0: it becomes nothing
 };
 struct Result {
-    uint64_t out_bytes[kMaxRuns];       // bytes of every member; the members lie back to back from d_dst[0] on
+    uint64_t out_bytes[kMaxRuns];       // bytes of every run's member (blocked: members); they lie back to back from d_dst[0] on
     uint64_t member_off[kMaxRuns];
     uint32_t flags;                     // 1: the members do not fit cap, 2: more pieces than the workspace holds (nothing is written then)
     uint32_t reserved;
 };
 constexpr uint32_t kResOverflow = 1, kResPieces = 2;
+// how launch_compress is to work (its flags word)
+constexpr uint32_t kLiteralsOnly = 1;   // no match search (Huffman coding alone)
+constexpr uint32_t kBlocked = 2;        // the runs leave as blocked gzip
 
 // the host's check of a Result before it copies members: those of the first n_runs runs lie back to back from 0 on and end inside
 // cap.  off[c]: where run c's member lies (an empty run's: where it would), *total: the bytes of all of them
@@ -405,6 +442,33 @@ GZ_HD uint32_t crc_bytes(const uint32_t *table, const uint8_t *p, uint32_t n) { 
 // what a slice's CRC adds to the CRC of the whole it lies in: bytes_behind = bytes of the whole behind the slice.  The whole's CRC
 // is the XOR of its slices' terms (crc_combine_op is linear in crc_a).
 GZ_HD uint32_t crc_term(uint32_t crc, uint64_t bytes_behind) { return crc ? gz::crc_multmodp(gz::crc_x2nmodp(bytes_behind, 3), crc) : 0u; }
+
+// ---- a blocked run on the host -------------------------------------------------------------------------------------------------
+// The host's statement of a blocked run (what k_dz_scan<true> and k_dz_gather do between them): pieces = the n_pieces(n) pieces'
+// bytes back to back as a member holds them (a stored one with its 5 bytes), sizes = their lengths, crcs = the CRC-32 of every
+// piece's own input.  out has bound_blocked(n) bytes; returns the bytes written.
+inline uint64_t blocked_run(const uint8_t *pieces, const uint32_t *sizes, const uint32_t *crcs, uint64_t n, bool emit_empty, uint8_t *out) {
+    const uint64_t np = n_pieces(n);
+    if (!np) {
+        if (emit_empty) put_blocked_frame(out, kBlockedFrame, 0, 0);
+        return emit_empty ? kBlockedFrame : 0;
+    }
+    uint64_t at = 0;
+    for (uint64_t i = 0; i < np; i += kBlockedPieces) {
+        const uint64_t end = blocked_member_end(n, i);
+        uint32_t body = 0, crc = 0;
+        for (uint64_t k = i; k < i + kBlockedPieces && k < np; ++k) {
+            const uint64_t piece_end = (k + 1) * kPiece < n ? (k + 1) * kPiece : n;
+            for (uint32_t b = 0; b < sizes[k]; ++b) out[at + kBlockedHead + body + b] = pieces[b];
+            pieces += sizes[k];
+            body += sizes[k];
+            crc ^= crc_term(crcs[k], end - piece_end);
+        }
+        put_blocked_frame(out + at, kBlockedFrame + body, crc, (uint32_t)(end - i * kPiece));
+        at += kBlockedFrame + body;
+    }
+    return at;
+}
 
 }  // namespace dz
 }  // namespace hast

@@ -15,6 +15,10 @@ namespace dz {
 inline uint32_t max_pieces(uint64_t n_bytes) { return (uint32_t)(n_bytes / kPiece) + kMaxRuns; }
 // most bytes the members of such a job take
 inline uint64_t max_out_bytes(uint64_t n_bytes) { return n_bytes + 5ull * max_pieces(n_bytes) + (uint64_t)kMaxRuns * (kMemberHead + kMemberTail); }
+// ... as blocked gzip: a frame per member, and a run's last member may be short
+inline uint64_t max_out_bytes_blocked(uint64_t n_bytes) {
+    return n_bytes + 5ull * max_pieces(n_bytes) + (uint64_t)kBlockedFrame * (n_bytes / kBlockedInput + kMaxRuns);
+}
 size_t workspace_bytes(uint32_t max_pieces);
 
 // the encoder's device memory, one allocation: the workspace, behind it the Job and Result of n_jobs calls that take turns in it
@@ -36,9 +40,9 @@ hipError_t launch_job_from_tx(Job *d_job, const uint64_t *d_run_bytes, uint64_t 
 // the three runs of a binned view of stage 03 (rs_api.cpp): back to back from offset 0, d_run_bytes[0 .. 2] their sizes in device memory
 hipError_t launch_job_from_bins(Job *d_job, const uint64_t *d_run_bytes, hipStream_t s);
 // d_src + job.src_off[r] .. -> members from d_dst[0] on, never at or behind d_dst + cap; d_res says how long they are.
-// literals_only: no match search (Huffman coding alone)
+// flags: 0, or kLiteralsOnly | kBlocked (dz_core.h); blocked: every run becomes members of at most kBlockedPieces pieces
 hipError_t launch_compress(const Job *d_job, const uint8_t *d_src, uint32_t max_pieces, void *d_work, uint8_t *d_dst, uint64_t cap, Result *d_res,
-                           int literals_only, hipStream_t s);
+                           uint32_t flags, hipStream_t s);
 
 }  // namespace dz
 }  // namespace hast

@@ -4,7 +4,8 @@
 //                 wave, tree and header by lane 0), bits placed by a prefix sum and OR-ed into LDS, whole words to the piece's slot of
 //                 the workspace; CRC-32 of the piece by 64 slices.  61 KB of LDS: two pieces a CU.
 //   k_dz_scan     one workgroup: where every piece lands in its member (prefix sum of the sizes), the members' CRC-32 (XOR of the
-//                 pieces' terms), sizes, headers and trailers
+//                 pieces' terms), sizes, headers and trailers; k_dz_scan<true>: the same for blocked gzip (BGZF), members of three
+//                 pieces with a frame each, written by a lane per member
 //   k_dz_gather   a workgroup per piece: its bytes to their place (stored pieces straight from the input), whole words where the
 //                 destination allows
 // All global stores are plain vector stores.  The output is a function of the input bytes alone (dz_core.h says why).
@@ -22,7 +23,7 @@ namespace {
 struct Workspace {              // views into d_work
     uint8_t *slots;             // max_pieces x kSlotBytes
     uint32_t *sizes, *crcs;     // per piece: bytes in its slot (kStoredFlag | input bytes: stored), its term of the member's CRC-32
-    uint64_t *offs;             // per piece: where it starts in its member
+    uint64_t *offs;             // per piece: where it starts in its member (blocked: behind the start of its run's first member)
 };
 __host__ __device__ inline Workspace workspace_at(void *d_work, uint32_t max_pieces) {
     Workspace w;
@@ -116,7 +117,7 @@ __global__ void k_dz_job_from_bins(Job *job, const uint64_t *run_bytes) {
     job->emit_empty = 0;
 }
 
-__global__ void __launch_bounds__(64) k_dz_piece(const Job *d_job, const uint8_t *src, uint32_t max_pieces, void *d_work, int literals_only) {
+__global__ void __launch_bounds__(64) k_dz_piece(const Job *d_job, const uint8_t *src, uint32_t max_pieces, void *d_work, uint32_t flags) {
     __shared__ uint32_t s_in[kPiece / 4 + 2];
     __shared__ uint32_t s_table[kHashSize];               // the match search's table, then the piece's output words
     __shared__ uint64_t s_startm[kPiece / 64], s_matchm[kPiece / 64];
@@ -157,7 +158,7 @@ __global__ void __launch_bounds__(64) k_dz_piece(const Job *d_job, const uint8_t
     for (uint32_t base = 0; base < n; base += 64) {
         const uint32_t at = base + lane;
         uint32_t len = 0, dist = 0;
-        if (at < n && !literals_only) probe(in, n, s_table, at, len, dist);
+        if (at < n && !(flags & kLiteralsOnly)) probe(in, n, s_table, at, len, dist);
         __syncthreads();                                    // every lane has read the table ...
         if (at < n) enter(in, n, s_table, at);              // ... before this step's positions go in (atomic max: order does not matter)
         const uint32_t end = base + 64 < n ? base + 64 : n;
@@ -215,8 +216,9 @@ __global__ void __launch_bounds__(64) k_dz_piece(const Job *d_job, const uint8_t
         const uint32_t slice = (n + 63) / 64;
         const uint32_t lo = lane * slice < n ? lane * slice : n, hi = lo + slice < n ? lo + slice : n;
         const uint32_t c = wave_xor(crc_term(crc_bytes(s_crc, in + lo, hi - lo), n - hi));
-        // ... and what it adds to the member's CRC: the piece knows how many bytes of its run lie behind it, so k_dz_scan only XORs
-        if (lane == 0) ws.crcs[p] = crc_term(c, run_bytes - piece_off - n);
+        // ... and what it adds to the member's CRC: the piece knows how many bytes of its member lie behind it (the run's, or in
+        // blocked mode those of its group of kBlockedPieces pieces), so k_dz_scan only XORs
+        if (lane == 0) ws.crcs[p] = crc_term(c, ((flags & kBlocked) ? blocked_member_end(run_bytes, idx) : run_bytes) - piece_off - n);
     }
     if (cb >= n) {                                          // not smaller than its bytes: a stored block, copied from the input by k_dz_gather
         if (lane == 0) ws.sizes[p] = n | kStoredFlag;
@@ -260,6 +262,11 @@ __global__ void __launch_bounds__(64) k_dz_piece(const Job *d_job, const uint8_t
 }
 
 // One workgroup.  Per run: the pieces' places in the member, the member's CRC-32, size, header and trailer.
+// kBlockedRun: the run leaves as blocked gzip (dz_core.h).  A piece's place is then the prefix sum of the sizes plus a frame for every
+// member in front of its own plus that member's header, and header and trailer of a member are written by the lane that holds the
+// member's first piece: it reads the sizes and CRC terms of the (at most two) pieces behind it where k_dz_piece left them, not from
+// its neighbours in the lap, so a member whose pieces lie in two laps (member 85: pieces 255, 256, 257) is no special case.
+template <bool kBlockedRun>
 __global__ void __launch_bounds__(256) k_dz_scan(const Job *d_job, uint32_t max_pieces, void *d_work, uint8_t *dst, uint64_t cap, Result *res) {
     __shared__ uint64_t s_scan[256];
     __shared__ uint32_t s_x[256];
@@ -284,7 +291,18 @@ __global__ void __launch_bounds__(256) k_dz_scan(const Job *d_job, uint32_t max_
             if (tid == 0) res->out_bytes[r] = 0, res->member_off[r] = ~0ull;
             continue;
         }
-        uint64_t at = kMemberHead;                          // uniform: where the next piece starts in the member
+        if (kBlockedRun && np == 0) {                       // (emit_empty) the end-of-file block
+            const bool fits = member_off + kBlockedFrame <= cap;
+            if (tid == 0) {
+                res->out_bytes[r] = fits ? kBlockedFrame : 0;
+                res->member_off[r] = fits ? member_off : ~0ull;
+                if (fits) put_blocked_frame(dst + member_off, kBlockedFrame, 0, 0);
+            }
+            if (!fits) flags |= kResOverflow;
+            else member_off += kBlockedFrame;
+            continue;
+        }
+        uint64_t at = kBlockedRun ? 0 : kMemberHead;        // uniform: where the next piece starts in the member (blocked: the sizes in front of it)
         uint32_t x = 0;
         for (uint64_t c = 0; c < np; c += 256) {
             const uint64_t i = c + tid;
@@ -302,22 +320,41 @@ __global__ void __launch_bounds__(256) k_dz_scan(const Job *d_job, uint32_t max_
                 s_scan[tid] += u;
                 __syncthreads();
             }
-            if (i < np) ws.offs[first + i] = at + s_scan[tid] - sz;
+            if (i < np) {
+                const uint64_t in_front = at + s_scan[tid] - sz;
+                if (!kBlockedRun) ws.offs[first + i] = in_front;
+                else {
+                    ws.offs[first + i] = in_front + (i / kBlockedPieces) * kBlockedFrame + kBlockedHead;
+                    if (i % kBlockedPieces == 0) {          // the member's first piece: its frame
+                        uint32_t total = kBlockedFrame + (uint32_t)sz, crc = ws.crcs[first + i];
+                        for (uint64_t k = i + 1; k < i + kBlockedPieces && k < np; ++k) {
+                            const uint32_t w = ws.sizes[first + k];
+                            total += (w & kStoredFlag) ? (w & ~kStoredFlag) + 5 : w;
+                            crc ^= ws.crcs[first + k];
+                        }
+                        const uint64_t start = member_off + in_front + (i / kBlockedPieces) * kBlockedFrame;
+                        // (a run that does not fit cap is reported below; what is written of it lies in front of cap)
+                        if (start + total <= cap) put_blocked_frame(dst + start, total, crc, (uint32_t)(blocked_member_end(nb, i) - i * kPiece));
+                    }
+                }
+            }
             at += s_scan[255];
             __syncthreads();
         }
-        s_x[tid] = x;
-        __syncthreads();
-        for (uint32_t d = 128; d; d >>= 1) {
-            if (tid < d) s_x[tid] ^= s_x[tid + d];
+        if (!kBlockedRun) {
+            s_x[tid] = x;
             __syncthreads();
+            for (uint32_t d = 128; d; d >>= 1) {
+                if (tid < d) s_x[tid] ^= s_x[tid + d];
+                __syncthreads();
+            }
         }
-        const uint64_t total = at + kMemberTail;
+        const uint64_t total = kBlockedRun ? at + n_members(nb) * kBlockedFrame : at + kMemberTail;
         const bool fits = member_off + total <= cap;
         if (tid == 0) {
             res->out_bytes[r] = fits ? total : 0;
             res->member_off[r] = fits ? member_off : ~0ull;
-            if (fits) {
+            if (fits && !kBlockedRun) {
                 uint8_t *m = dst + member_off;
                 const uint8_t head[kMemberHead] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 3};
                 for (uint32_t k = 0; k < kMemberHead; ++k) m[k] = head[k];
@@ -392,9 +429,10 @@ hipError_t launch_job_from_bins(Job *d_job, const uint64_t *d_run_bytes, hipStre
     return hipGetLastError();
 }
 hipError_t launch_compress(const Job *d_job, const uint8_t *d_src, uint32_t max_pieces, void *d_work, uint8_t *d_dst, uint64_t cap, Result *d_res,
-                           int literals_only, hipStream_t s) {
-    if (max_pieces) hipLaunchKernelGGL(k_dz_piece, dim3(max_pieces), dim3(64), 0, s, d_job, d_src, max_pieces, d_work, literals_only);
-    hipLaunchKernelGGL(k_dz_scan, dim3(1), dim3(256), 0, s, d_job, max_pieces, d_work, d_dst, cap, d_res);
+                           uint32_t flags, hipStream_t s) {
+    if (max_pieces) hipLaunchKernelGGL(k_dz_piece, dim3(max_pieces), dim3(64), 0, s, d_job, d_src, max_pieces, d_work, flags);
+    if (flags & kBlocked) hipLaunchKernelGGL(k_dz_scan<true>, dim3(1), dim3(256), 0, s, d_job, max_pieces, d_work, d_dst, cap, d_res);
+    else hipLaunchKernelGGL(k_dz_scan<false>, dim3(1), dim3(256), 0, s, d_job, max_pieces, d_work, d_dst, cap, d_res);
     if (max_pieces) hipLaunchKernelGGL(k_dz_gather, dim3(max_pieces), dim3(256), 0, s, d_job, d_src, max_pieces, (const void *)d_work, d_dst, (const Result *)d_res);
     return hipGetLastError();
 }

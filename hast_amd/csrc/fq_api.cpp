@@ -128,7 +128,7 @@ struct hast_fq {
     // routing (hast_fq_set_route): the blocks are not classified; their records leave the GPU as four runs by barcode class
     bool route = false;
     std::vector<hast_names *> route_tab;                       // per lane (one for a plain stream): barcode text -> class on that GPU
-    bool route_gz = false;                                     // ... and the runs leave the GPU as gzip members (hast_fq_set_route_gz)
+    int route_gz = 0;                                          // ... and the runs leave the GPU as gzip members (hast_fq_set_route_gz; 2: blocked gzip)
     // tallies (hast_fq_set_tally): the blocks are not classified; field 2 of their header lines is counted per key
     bool tally = false;
     std::vector<hast_tally *> tallies;                         // per lane (one for a plain stream)
@@ -231,7 +231,7 @@ static hast_status enqueue_route(hast_fq *f, Slot &s, hast_names *tab, bool stri
         // the runs stay in HBM and are compressed there, a gzip member each (dz_kernels.hip); their sizes come back with the block's
         // state, the members themselves once hast_fq_next_routed knows how long they are
         HAST_HIP_TRY(dz::launch_job_from_route(s.enc.job(), s.d_rs, hs));
-        HAST_HIP_TRY(dz::launch_compress(s.enc.job(), s.d_out, s.enc.max_pieces, s.enc.d_work, s.d_gz, s.gz_cap, s.enc.res(), 0, hs));
+        HAST_HIP_TRY(dz::launch_compress(s.enc.job(), s.d_out, s.enc.max_pieces, s.enc.d_work, s.d_gz, s.gz_cap, s.enc.res(), f->route_gz == 2 ? dz::kBlocked : 0, hs));
         HAST_HIP_TRY(hipMemcpyAsync(s.h_dzres, s.enc.res(), sizeof(dz::Result), hipMemcpyDeviceToHost, hs));
         return HAST_OK;
     }
@@ -913,7 +913,7 @@ hast_status hast_fq_set_route(hast_fq *f, hast_names *const *tables, int n_table
     if (f->tally && tables) return set_error(HAST_ERR_INVALID, "hast_fq_set_route: the stream tallies (hast_fq_set_tally with NULL first)");
     if (!tables) {
         f->route = false;
-        f->route_gz = false;
+        f->route_gz = 0;
         f->route_tab.clear();
         return HAST_OK;
     }
@@ -953,11 +953,15 @@ hast_status hast_fq_set_route_gz(hast_fq *f, int on) {
     if (!f->route) return set_error(HAST_ERR_INVALID, "hast_fq_set_route_gz: the stream does not route (hast_fq_set_route)");
     for (const Slot &s : f->slots)
         if (s.state != Slot::FREE) return set_error(HAST_ERR_INVALID, "hast_fq_set_route_gz: a block is in hand (commit it first)");
+    if (on != 0 && on != 1 && on != 2) return set_error(HAST_ERR_INVALID, "hast_fq_set_route_gz: on is 0, 1 or 2, got %d", on);
     if (on)
         for (Slot &s : f->slots) {
-            if (s.d_gz) continue;
+            // (blocked members need more room for the same runs: a frame per 49 152 bytes)
+            const size_t cap = (size_t)(on == 2 ? dz::max_out_bytes_blocked(s.h_buf_bytes) : dz::max_out_bytes(s.h_buf_bytes));
+            if (s.d_gz && s.gz_cap >= cap) continue;
+            if (s.d_gz) release_gz(s);
             HAST_HIP_TRY(hipSetDevice(dev_of(f, s)));
-            s.gz_cap = (size_t)dz::max_out_bytes(s.h_buf_bytes);
+            s.gz_cap = cap;
             HAST_HIP_TRY(dev_malloc(&s.d_gz, s.gz_cap));
             HAST_HIP_TRY(dz::slot_alloc(&s.enc, dz::max_pieces(s.h_buf_bytes)));
             HAST_HIP_TRY(pinned_malloc(&s.h_gz, s.gz_cap));
@@ -965,7 +969,7 @@ hast_status hast_fq_set_route_gz(hast_fq *f, int on) {
         }
     else
         for (Slot &s : f->slots) release_gz(s);
-    f->route_gz = on != 0;
+    f->route_gz = on;
     return HAST_OK;
 }
 

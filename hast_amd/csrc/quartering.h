@@ -57,7 +57,47 @@ inline bool gz_member(const char *p, size_t n, std::string &out) {
     out.resize(at + written);
     return rc == Z_STREAM_END;
 }
-struct GzOutStats {             // --stats: what went into and came out of the encoder, members written
+// --gz-format bgzf: the same bytes as BLOCKED gzip (BGZF: bgzip, htslib, hast_gz_open_blocked), the host twin of the device encoder's
+// blocked mode (dz_core.h): raw deflate (level 1) over slices of at most kBgzfSlice bytes -- what a member of the device's holds --
+// each wrapped as a member of its own: 18 bytes of header with the BC subfield (BSIZE = the member's bytes - 1), CRC-32 and ISIZE of
+// the slice.  n bytes -> ceil(n / kBgzfSlice) members appended to out (n = 0: nothing); host-made members need not equal the
+// device's byte for byte.  False: zlib failed.
+enum class GzFormat { kNone, kGzip, kBgzf };    // how the four files are written: plain, gzip members, BGZF members
+constexpr size_t kBgzfSlice = 3 * 16384;
+constexpr size_t kBgzfFrame = 18 + 2 + 8;       // header + the empty final block the device writes + trailer: a member's bytes beside its pieces
+// the end-of-file block every BGZF file ends with: an empty member
+constexpr unsigned char kBgzfEof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+inline size_t bgzf_member_count(size_t n) { return (n + kBgzfSlice - 1) / kBgzfSlice; }
+inline bool bgzf_members(const char *p, size_t n, std::string &out) {
+    for (size_t done = 0; done < n;) {
+        const size_t take = std::min(n - done, kBgzfSlice);
+        z_stream z;
+        memset(&z, 0, sizeof z);
+        if (deflateInit2(&z, 1, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) return false;
+        const size_t at = out.size(), room = deflateBound(&z, (uLong)take);
+        out.resize(at + 18 + room + 8);
+        z.next_in = reinterpret_cast<Bytef *>(const_cast<char *>(p + done));
+        z.avail_in = (uInt)take;
+        z.next_out = reinterpret_cast<Bytef *>(&out[at + 18]);
+        z.avail_out = (uInt)room;
+        const int rc = deflate(&z, Z_FINISH);
+        const size_t total = 18 + (room - z.avail_out) + 8;
+        deflateEnd(&z);
+        if (rc != Z_STREAM_END || total > (1u << 16)) return false;     // (deflateBound of 48 KB is 48 KB + 22 bytes: it fits)
+        memcpy(&out[at], kBgzfEof, 16);
+        out[at + 16] = (char)((total - 1) & 0xFF);
+        out[at + 17] = (char)((total - 1) >> 8);
+        const uint32_t crc = (uint32_t)crc32(0, reinterpret_cast<const Bytef *>(p + done), (uInt)take), isize = (uint32_t)take;
+        for (int k = 0; k < 4; k++) {
+            out[at + total - 8 + k] = (char)(crc >> (8 * k));
+            out[at + total - 4 + k] = (char)(isize >> (8 * k));
+        }
+        out.resize(at + total);
+        done += take;
+    }
+    return true;
+}
+struct GzOutStats {             // --stats: what went into and came out of the encoder, members written (an end-of-file block is one)
     unsigned long long bytes_in = 0, bytes_out = 0, members = 0;
 };
 
@@ -96,10 +136,12 @@ inline bool load_list(const std::string &path, uint8_t cls, ClassMap &map) {
 // Routes the records of one input.  src: next() -> a block with kFrontPad bytes of room in front of its data (empty = end of input),
 // recycle(), error().  log_name: what awk's FILENAME would be (the path as given, "-" behind `gzip -dc`).  who: the program's name in
 // messages.  Returns 0, or the exit code of a failure (2: I/O, 3: a record larger than 4 GB).
-// gz_out: the four files are <prefix>.<class>.fastq.gz, every worker's share of a block one gzip member (gz_stats: totals, may be null)
+// format other than kNone: the four files are <prefix>.<class>.fastq.gz, every worker's share of a block one gzip member, or (kBgzf)
+// BGZF members of at most kBgzfSlice bytes and an end-of-file block where a file ends (gz_stats: totals, may be null)
 template <class Source>
-int route(const std::string &prefix, const ClassMap &cls_of, Source &src, const std::string &log_name, int t_num, const char *who, bool gz_out = false,
-          GzOutStats *gz_stats = nullptr) {
+int route(const std::string &prefix, const ClassMap &cls_of, Source &src, const std::string &log_name, int t_num, const char *who,
+          GzFormat format = GzFormat::kNone, GzOutStats *gz_stats = nullptr) {
+    const bool gz_out = format != GzFormat::kNone, bgzf = format == GzFormat::kBgzf;
     hast::WorkerPool pool(t_num);
     const int T = pool.size();
     const char *suffix_plain[4] = {".nobarcode.fastq", ".paternal.fastq", ".maternal.fastq", ".homozygous.fastq"};
@@ -116,15 +158,15 @@ int route(const std::string &prefix, const ClassMap &cls_of, Source &src, const 
         bool z_failed = false;
         GzOutStats z;
     };
-    // a worker's four buffers, each replaced by one gzip member of its bytes
+    // a worker's four buffers, each replaced by one gzip member of its bytes (BGZF: by the members of its slices)
     auto compress_local = [&](Local &L) {
         for (int c = 0; c < 4; c++) {
             if (L.buf[c].empty()) continue;
             L.zbuf.clear();
-            if (!gz_member(L.buf[c].data(), L.buf[c].size(), L.zbuf)) L.z_failed = true;
+            if (!(bgzf ? bgzf_members(L.buf[c].data(), L.buf[c].size(), L.zbuf) : gz_member(L.buf[c].data(), L.buf[c].size(), L.zbuf))) L.z_failed = true;
             L.z.bytes_in += L.buf[c].size();
             L.z.bytes_out += L.zbuf.size();
-            L.z.members++;
+            L.z.members += bgzf ? bgzf_member_count(L.buf[c].size()) : 1;
             L.buf[c].swap(L.zbuf);
         }
     };
@@ -238,8 +280,14 @@ int route(const std::string &prefix, const ClassMap &cls_of, Source &src, const 
         carry.swap(keep);
         src.recycle(std::move(blk));
     }
-    for (FILE *f : out)
-        if (f && fclose(f) != 0) write_failed = true;
+    for (FILE *f : out) {
+        if (!f) continue;
+        if (bgzf && !write_failed) {                                // every BGZF file that exists ends with one end-of-file block
+            if (fwrite(kBgzfEof, 1, sizeof kBgzfEof, f) != sizeof kBgzfEof) write_failed = true;
+            if (gz_stats) gz_stats->bytes_out += sizeof kBgzfEof, gz_stats->members++;
+        }
+        if (fclose(f) != 0) write_failed = true;
+    }
     if (write_failed) return 2;
     FILE *lg = fopen("filter_reads.log", "ab");
     if (lg) {

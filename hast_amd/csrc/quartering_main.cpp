@@ -5,10 +5,13 @@
 //   awk -v prefix=NAME -F '#|/' -f quartering_fastq.awk paternal.unique.barcodes maternal.unique.barcodes
 //       homozygous.unique.barcodes READS   (READS may be "-" behind `gzip -dc`)).
 //
-//   quartering_fastq [-t N] [--gz-out] --prefix NAME paternal.barcodes maternal.barcodes homozygous.barcodes READS|-|READS.gz
+//   quartering_fastq [-t N] [--gz-out [--gz-format gzip|bgzf]] --prefix NAME paternal.barcodes maternal.barcodes homozygous.barcodes READS|-|READS.gz
 //
 // --gz-out: the four files are written as <prefix>.<class>.fastq.gz (gzip members made by zlib, quartering.h), which is what stage 02
 // compresses them into anyway; `gzip -dc` of each is the plain file byte for byte.
+// --gz-format bgzf (only with --gz-out; the default is gzip): the members are blocked gzip (BGZF), at most 48 KB of records each, and
+// every file ends with BGZF's end-of-file block: `gzip -dc` reads them as before, bgzip / htslib readers and `classify --bgzf device`
+// can split them.  Another value, or the flag without --gz-out: the usage text and exit code 255.
 //
 // (the routing itself: quartering.h, shared with `classify`)
 // Same outputs byte for byte: the four FASTQ files (created only when something is routed to them), the
@@ -24,7 +27,10 @@
 
 int main(int argc, char **argv) {
     static struct option lo[] = {{"prefix", required_argument, NULL, 'p'}, {"thread", required_argument, NULL, 't'},
-                                 {"block-mb", required_argument, NULL, 'b'}, {"gz-out", no_argument, NULL, 'z'}, {0, 0, 0, 0}};
+                                 {"block-mb", required_argument, NULL, 'b'}, {"gz-out", no_argument, NULL, 'z'}, {"gz-format", required_argument, NULL, 'F'},
+                                 {0, 0, 0, 0}};
+    const char *usage = "usage: quartering_fastq [-t N] [--gz-out [--gz-format gzip|bgzf]] --prefix NAME paternal.barcodes maternal.barcodes homozygous.barcodes READS|-\n";
+    const char *gz_format = nullptr;
     std::string prefix;
     int t_num = 8;
     size_t block_mb = 64;
@@ -36,11 +42,21 @@ int main(int argc, char **argv) {
         else if (c == 't') t_num = atoi(optarg);
         else if (c == 'b') block_mb = (size_t)std::max(1L, atol(optarg));
         else if (c == 'z') gz_out = true;
+        else if (c == 'F') gz_format = optarg;
         else return 2;
     }
     if (argc - optind != 4 || t_num < 1) {
-        fprintf(stderr, "usage: quartering_fastq [-t N] [--gz-out] --prefix NAME paternal.barcodes maternal.barcodes homozygous.barcodes READS|-\n");
+        fputs(usage, stderr);
         return 2;
+    }
+    using hast::quartering::GzFormat;
+    GzFormat format = gz_out ? GzFormat::kGzip : GzFormat::kNone;
+    if (gz_format) {
+        if (!gz_out || (strcmp(gz_format, "gzip") && strcmp(gz_format, "bgzf"))) {
+            fputs(usage, stderr);
+            return 255;
+        }
+        if (!strcmp(gz_format, "bgzf")) format = GzFormat::kBgzf;
     }
     hast::quartering::ClassMap cls_of;
     for (int i = 0; i < 3; i++)
@@ -54,5 +70,5 @@ int main(int argc, char **argv) {
         fprintf(stderr, "quartering_fastq: cannot open %s\n", reads.c_str());
         return 2;
     }
-    return hast::quartering::route(prefix, cls_of, src, reads, t_num, "quartering_fastq", gz_out);
+    return hast::quartering::route(prefix, cls_of, src, reads, t_num, "quartering_fastq", format);
 }

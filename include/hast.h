@@ -443,6 +443,8 @@ hast_status hast_fq_next_routed(hast_fq *, hast_fq_routed *out);
  * Memory while the switch is on, per buffer slot of the stream: about two blocks of device memory (the members' buffer and the
  * encoder's workspace) and one block of pinned host memory; on = 0 gives them back.  Only between files, like
  * hast_fq_set_route, and only on a stream that routes.
+ * on = 2: the same with BLOCKED gzip (BGZF, hast_dz_compress_blocked_device below): run[c] holds a whole number of BGZF members
+ * back to back, one per 49 152 bytes of the run, and no end-of-file block (the caller writes one where its file ends).
  * hast_fq_routed_raw_bytes: the uncompressed bytes of the open block's four runs (what run_bytes[] would have been). */
 hast_status hast_fq_set_route_gz(hast_fq *, int on);
 hast_status hast_fq_routed_raw_bytes(hast_fq *, uint64_t out[4]);
@@ -497,12 +499,19 @@ hast_status hast_fq_next_tallied(hast_fq *, hast_fq_tallied *out);
  * hast_dz_compress_device_ex / HAST_DZ_LITERALS_ONLY are a TEST HOOK, not part of the interface a caller should build on and not
  * promised to stay: flags = HAST_DZ_LITERALS_ONLY switches the match search off (Huffman coding of the bytes alone), which is how
  * tests/test_dz_gpu.py gets a block whose symbol histogram is the input's byte histogram (code lengths that have to be limited to
- * 15 bits); no program of this tree passes it. */
+ * 15 bits); no program of this tree passes it.
+ * BLOCKED gzip (BGZF: what bgzip / htslib write and seek in, what hast_gz_open_blocked inflates a wave per member):
+ * hast_dz_compress_blocked_device writes the same pieces, three to a member: 18 bytes of header with the BC subfield, at most
+ * 49 152 bytes of input, CRC-32 and ISIZE of that member alone; ceil(n_bytes / 49 152) members back to back, each at most 64 KB.
+ * n_bytes == 0 writes the 28 bytes of BGZF's end-of-file block.  hast_dz_bound_blocked(n) is its bound; cap below it is
+ * HAST_ERR_INVALID.  gzip -dc and zlib read the result as they read any series of members. */
 #define HAST_DZ_LITERALS_ONLY 1u
 size_t      hast_dz_bound(size_t n_bytes);
 hast_status hast_dz_compress_device(hast_ctx *, const uint8_t *d_src, size_t n_bytes, uint8_t *d_dst, size_t cap, size_t *n_out, hast_stream);
 hast_status hast_dz_compress_device_ex(hast_ctx *, const uint8_t *d_src, size_t n_bytes, uint8_t *d_dst, size_t cap, size_t *n_out, unsigned flags,
                                        hast_stream);
+size_t      hast_dz_bound_blocked(size_t n_bytes);
+hast_status hast_dz_compress_blocked_device(hast_ctx *, const uint8_t *d_src, size_t n_bytes, uint8_t *d_dst, size_t cap, size_t *n_out, hast_stream);
 
 /* ---- gzip input decoded on the device (gzstream.h:47, classify.cpp:245-254: one zlib stream per .gz file) -----------------
  * HAST's real inputs are ordinary .fq.gz files: ONE deflate stream per file, which the reference inflates on the thread that
