@@ -20,12 +20,12 @@
 #include <sys/stat.h>
 
 #include <algorithm>
-#include <chrono>
 #include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/hast.h"
+#include "cli_common.h"
 #include "bf_host.h"
 #include "fq_feed.h"
 #include "ingest.h"
@@ -47,7 +47,7 @@ struct Stats {
     double setup_s = 0, read_s = 0, merge_s = 0, gpu_wait_s = 0;
 };
 
-double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+using hast::now_s;
 
 int usage() {
     fprintf(stderr, "usage: barcode_freq [--count device|host] [--device N | --devices a,b,...] [--inflate device|host|zlib] [--block-mb N]\n"
@@ -55,26 +55,8 @@ int usage() {
     return 255;
 }
 
-// a count with an optional K / M / G (as classify's options take them)
-bool parse_count(const char *text, uint64_t *out) {
-    if (!text || *text < '0' || *text > '9') return false;
-    errno = 0;
-    char *end = nullptr;
-    const unsigned long long v = strtoull(text, &end, 10);
-    if (errno || end == text) return false;
-    int shift = 0;
-    switch (*end) {
-    case 'K': case 'k': shift = 10; end++; break;
-    case 'M': case 'm': shift = 20; end++; break;
-    case 'G': case 'g': shift = 30; end++; break;
-    default: break;
-    }
-    if (*end || (shift && v > (~0ull >> shift))) return false;
-    *out = v << shift;
-    return true;
-}
-
-bool ends_gz(const std::string &p) { return p.size() > 3 && p.compare(p.size() - 3, 3, ".gz") == 0; }
+using hast::ends_gz;
+using hast::parse_count;
 
 // ---- the host route (and "-" on either route): an input block by block through the model
 int count_on_host(const Options &o, const std::string &path, hast::bf::Model &m, Stats &st) {
@@ -176,9 +158,9 @@ int open_next(Device &d) {
 // the oldest submitted block of a feed: what the device counted is in its tally; what it left goes into the map
 int tally_block(Device &d, hast::FqFeed &f) {
     hast_fq_tallied b;
-    const double t0 = now();
+    const double t0 = now_s();
     if (hast_fq_next_tallied(f.fq, &b) != HAST_OK) return fail_gpu("tallying a block");
-    d.st.gpu_wait_s += now() - t0;
+    d.st.gpu_wait_s += now_s() - t0;
     f.opened++;
     d.st.blocks++;
     d.st.header_lines += b.n_records;
@@ -306,20 +288,20 @@ int main(int argc, char **argv) {
         if (!o.block_given && atol(e) >= 1) { o.block = (size_t)atol(e); o.block_given = true; }
     if (o.inflate == "zlib") setenv("HAST_INFLATE", "zlib", 1);
 
-    const double t_start = now();
+    const double t_start = now_s();
     Stats st;
     hast::bf::Model model;
     hast::bf::Rows rows;
     int rc = 0;
     if (o.count == "host") {
-        const double t0 = now();
+        const double t0 = now_s();
         for (size_t i = 0; i < o.in.size() && !rc; ++i) rc = count_on_host(o, o.in[i], model, st);
-        st.read_s = now() - t0;
+        st.read_s = now_s() - t0;
     } else {
         Device d(o, st, model);
         for (const std::string &p : o.in)
             if (p != "-") d.files.push_back(p);
-        const double t0 = now();
+        const double t0 = now_s();
         if (!d.files.empty()) {
             for (size_t i = 0; i < o.devices.size() && !rc; ++i) {
                 hast_ctx *c = nullptr;
@@ -330,20 +312,20 @@ int main(int argc, char **argv) {
                 d.tallies.push_back(t);
             }
         }
-        st.setup_s = now() - t0;
-        const double t1 = now();
+        st.setup_s = now_s() - t0;
+        const double t1 = now_s();
         if (!rc && !d.files.empty()) rc = run_device(d);
         for (size_t i = 0; i < o.in.size() && !rc; ++i)
             if (o.in[i] == "-") rc = count_on_host(o, o.in[i], model, st);
-        st.read_s = now() - t1;
-        const double t2 = now();
+        st.read_s = now_s() - t1;
+        const double t2 = now_s();
         if (!rc) rc = read_tallies(d, rows);
-        st.merge_s = now() - t2;
+        st.merge_s = now_s() - t2;
         for (hast_tally *t : d.tallies) hast_tally_destroy(t);
         for (hast_ctx *c : d.ctxs) hast_ctx_destroy(c);
     }
     if (rc) return rc;
-    const double t2 = now();
+    const double t2 = now_s();
     for (auto &kv : model.counts) rows.emplace_back(kv.first, kv.second);
     hast::bf::merge_rows(rows);
     st.header_lines += model.header_lines;
@@ -359,7 +341,7 @@ int main(int argc, char **argv) {
     }
     std::string out;
     hast::bf::print_rows(rows, out);
-    st.merge_s += now() - t2;
+    st.merge_s += now_s() - t2;
     if ((out.size() && fwrite(out.data(), 1, out.size(), stdout) != out.size()) || fflush(stdout) != 0) {
         fprintf(stderr, "barcode_freq: cannot write the rows\n");
         return 3;
@@ -369,7 +351,7 @@ int main(int argc, char **argv) {
                 (unsigned long long)st.header_lines, (unsigned long long)st.on_device, (unsigned long long)st.on_host, (unsigned long long)st.no_field,
                 (unsigned long long)st.distinct, st.dictionary_full);
         fprintf(stderr, "[stats] seconds: setup=%.3f read_phase=%.3f gpu_wait=%.3f merge=%.3f total=%.3f blocks=%llu plain_in_bytes=%llu\n", st.setup_s, st.read_s, st.gpu_wait_s,
-                st.merge_s, now() - t_start, (unsigned long long)st.blocks, (unsigned long long)st.plain_in);
+                st.merge_s, now_s() - t_start, (unsigned long long)st.blocks, (unsigned long long)st.plain_in);
     }
     return 0;
 }

@@ -49,15 +49,15 @@
 #include <vector>
 
 #include "../../include/hast.h"
+#include "cli_common.h"
 #include "fq_feed.h"
 #include "ingest.h"
 #include "quartering.h"
 
 namespace {
 
-double now_s() {
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
+using hast::now_s;
+using hast::parse_count;
 
 void logtime() {                                  // classify.cpp:17-21
     time_t now = time(0);
@@ -205,24 +205,6 @@ bool write_stats_json(const std::string &path) {
     if (path == "-") return fputs(js.c_str(), stderr) >= 0;
     FILE *f = fopen(path.c_str(), "wb");
     return f && fwrite(js.data(), 1, js.size(), f) == js.size() && fclose(f) == 0;
-}
-
-// the whole input, front to back (also from a pipe, which has no size to ask for)
-bool slurp(const std::string &path, std::vector<char> &out) {
-    FILE *f = fopen(path.c_str(), "rb");
-    if (!f) return false;
-    out.clear();
-    size_t have = 0;
-    for (;;) {
-        if (out.size() - have < (1u << 20)) out.resize(std::max<size_t>(out.size() * 2, 4u << 20));
-        const size_t n = fread(out.data() + have, 1, out.size() - have, f);
-        have += n;
-        if (n == 0) break;
-    }
-    const bool ok = !ferror(f);
-    fclose(f);
-    out.resize(have);
-    return ok;
 }
 
 // the reference's startup self-test (TestAll, classify.cpp:341-367) on our host primitives
@@ -405,25 +387,6 @@ void flush_counts(Run &rs, size_t new_cap) {
     acc.device_cap = new_cap;
 }
 
-// a count or a size on the command line: decimal digits and at most one of K, M, G behind them (powers of 1024, either case); anything
-// else -- no digits, a sign, a fraction, another suffix, trailing bytes, more than 64 bits hold -- is not a number
-bool parse_count(const char *text, uint64_t *out) {
-    if (!text || *text < '0' || *text > '9') return false;
-    errno = 0;
-    char *end = nullptr;
-    const unsigned long long v = strtoull(text, &end, 10);
-    if (errno || end == text) return false;
-    int shift = 0;
-    switch (*end) {
-    case 'K': case 'k': shift = 10; end++; break;
-    case 'M': case 'm': shift = 20; end++; break;
-    case 'G': case 'g': shift = 30; end++; break;
-    default: break;
-    }
-    if (*end || (shift && v > (~0ull >> shift))) return false;
-    *out = (uint64_t)v << shift;
-    return true;
-}
 // a plain non-negative decimal number, fractions allowed ("1.5"), nothing behind it
 bool parse_amount(const char *text, double *out) {
     if (!text || !((*text >= '0' && *text <= '9') || *text == '.')) return false;
@@ -524,14 +487,7 @@ bool parse_options(int argc, char **argv, Options &o) {
         case 1019: bgzf = optarg; break;
         case 1020: gz_format = optarg; gz_format_flag = true; break;
         case 1008:
-            for (const char *q = optarg; *q;) {
-                char *end;
-                const long v = strtol(q, &end, 10);
-                if (end == q || v < 0) { print_usage(); return false; }
-                o.devices.push_back((int)v);
-                q = *end == ',' ? end + 1 : end;
-                if (*end && *end != ',') { print_usage(); return false; }
-            }
+            if (!hast::parse_device_list(optarg, o.devices)) { print_usage(); return false; }
             break;
         case 'h':
         default: print_usage(); return false;
@@ -582,7 +538,7 @@ struct InputName {
 InputName input_name(const std::string &path) {
     InputName n;
     n.base = path.substr(path.find_last_of('/') == std::string::npos ? 0 : path.find_last_of('/') + 1);
-    n.gz = n.base.size() >= 3 && n.base.compare(n.base.size() - 3, 3, ".gz") == 0;
+    n.gz = hast::ends_gz(n.base, 0);
     if (n.gz) n.base.resize(n.base.size() - 3);
     return n;
 }
@@ -772,56 +728,24 @@ void load_saved_table(Run &rs) {
 // returns 0, or the exit status of a K the reference does not have either
 int build_table(Run &rs) {
     const Options &o = rs.o;
-    // K = length of the first line of hap0 (classify.cpp:35-36); the files themselves are streamed into the table by the
-    // library (hast_table_insert_text_file), a pipe or the like is read into memory first
-    // (a pipe can be read only once: it is read whole now and its first bytes serve as the head)
-    const std::string *hap_path[2] = {&o.hap0, &o.hap1};
-    std::vector<char> txt[2], head;
-    bool streamed[2] = {false, false};
-    size_t text_bytes[2] = {0, 0};
-    for (int h = 0; h < 2; h++) {
-        struct stat sb;
-        if (stat(hap_path[h]->c_str(), &sb) == 0 && S_ISREG(sb.st_mode)) {
-            streamed[h] = true;
-            text_bytes[h] = (size_t)sb.st_size;
-        } else {
-            if (!slurp(*hap_path[h], txt[h])) die(2, ("cannot read " + *hap_path[h]).c_str());
-            text_bytes[h] = txt[h].size();
-        }
-    }
-    if (streamed[0]) {
-        FILE *f = fopen(o.hap0.c_str(), "rb");
-        if (!f) die(2, ("cannot read " + o.hap0).c_str());
-        head.resize(4096);
-        head.resize(fread(head.data(), 1, head.size(), f));
-        fclose(f);
-    } else head.assign(txt[0].begin(), txt[0].begin() + (long)std::min<size_t>(txt[0].size(), 4096));
-    const void *nl0 = memchr(head.data(), '\n', head.size());
-    rs.K = nl0 ? (size_t)((const char *)nl0 - head.data()) : head.size();   // :35-36
+    // K = length of the first line of hap0 (classify.cpp:35-36); hast::KmerFiles has the rest
+    hast::KmerFiles kf;
+    std::string msg;
+    if (int code = kf.open(o.hap0, o.hap1, &msg)) die(code, msg.c_str());
+    rs.K = kf.K;
     if (rs.K < 1 || rs.K > 32) {
-        fprintf(stderr, "classify: ERROR: K=%zu%s (length of the first line of %s) is outside [1,32]\n", rs.K, (!nl0 && head.size() == 4096) ? " or more" : "", o.hap0.c_str());
+        fprintf(stderr, "classify: ERROR: K=%zu%s (length of the first line of %s) is outside [1,32]\n", rs.K, (!kf.head_has_newline && kf.head.size() == 4096) ? " or more" : "", o.hap0.c_str());
         return 3;
     }
     if (hast_ctx_create(o.devices[0], (int)rs.K, &rs.ctx) != HAST_OK) die(4, "cannot create GPU context");
     rs.t_ctx = now_s();
     contexts_ready(rs);
-    CK(hast_table_reserve(rs.ctx, text_bytes[0] / (rs.K + 1) + text_bytes[1] / (rs.K + 1) + 2, 0.0), "allocating the k-mer table");
+    CK(hast_table_reserve(rs.ctx, kf.capacity(), 0.0), "allocating the k-mer table");
     for (int h = 0; h < 2; h++) {
         fprintf(stderr, "__load hap%d kmers__\n", h);
         uint64_t lines = 0;
-        hast_status st = streamed[h] ? hast_table_insert_text_file(rs.ctx, h, hap_path[h]->c_str(), &lines)
-                                     : hast_table_insert_text(rs.ctx, h, txt[h].data(), txt[h].size(), &lines);
-        if (st == HAST_ERR_FORMAT) die(3, "k-mer file is not one K-mer per line");
-        if (st == HAST_ERR_IO) die(2, ("cannot read " + *hap_path[h]).c_str());
-        if (st != HAST_OK) die(4, "building the k-mer table");
-        if (h == 0 && !nl0 && text_bytes[0] == rs.K) {
-            // a single unterminated line: the reference still inserts the FIRST line of hap0 (:35-39)
-            uint64_t key = hast_canon_kmer(head.data(), (int)rs.K);
-            CK(hast_table_insert_keys(rs.ctx, 0, &key, 1), "building the k-mer table");
-            lines = 1;
-        }
+        if (int code = kf.insert(rs.ctx, h, false, false, &lines, &msg)) die(code, msg.empty() ? "k-mer file is not one K-mer per line" : msg.c_str());
         fprintf(stderr, "Recorded %llu haplotype %d specific %zu-mers\n", (unsigned long long)lines, h, rs.K);   // :45
-        std::vector<char>().swap(txt[h]);
     }
     rs.t_loaded = now_s();
     return 0;
@@ -900,22 +824,20 @@ void wait_for_stream_setup(Run &rs) {
 struct FileState {
     std::string name;
     std::unique_ptr<hast::BlockSource> src;
-    std::vector<char> carry;                       // bytes of an incomplete record at the end of a block
+    hast::BlockWork work;                          // (carries the bytes of an incomplete record at the end of a block)
 };
 
 struct HostParser {
-    explicit HostParser(Run &run) : rs(run), T(run.pool->size()), nl((size_t)T), part_bytes((size_t)T + 1), part_max((size_t)T), part_err((size_t)T) {}
+    explicit HostParser(Run &run) : rs(run), T(run.pool->size()), part_bytes((size_t)T + 1), part_max((size_t)T), part_err((size_t)T) {}
     Run &rs;
     const int T;
-    std::vector<std::vector<uint32_t>> nl;         // per-worker newline positions of the current block
-    std::vector<uint32_t> allnl;
     std::vector<uint64_t> part_bytes;
     std::vector<uint32_t> part_max, part_err;
     const std::string *cur_name = nullptr;
     size_t next_ctx = 0;
 
     // parse `n_rec` complete records whose newline positions are in allnl (4 per record) from `data`
-    void parse_records(const char *data, size_t n_rec) {
+    void parse_records(const char *data, const std::vector<uint32_t> &allnl, size_t n_rec) {
         if (n_rec == 0) return;
         uint8_t *hb;
         uint64_t *ho;
@@ -977,48 +899,19 @@ struct HostParser {
     bool process_block(FileState &fs) {
         cur_name = &fs.name;
         hast::BlockSource &src = *fs.src;
-        std::vector<char> &carry = fs.carry;
-        std::vector<char> blk = src.next();
-        const bool last = blk.empty();
-        if (last && !src.error().empty()) die(2, (fs.name + ": " + src.error()).c_str());
-        constexpr size_t kPad = hast::BlockSource::kFrontPad;
+        hast::BlockWork &w = fs.work;
         // work area = carry (incomplete record of the previous block) + this block's data
-        const char *data;
-        size_t len;
-        if (last) {
-            data = carry.data();
-            len = carry.size();
-        } else if (carry.size() <= kPad) {
-            if (!carry.empty()) memcpy(blk.data() + kPad - carry.size(), carry.data(), carry.size());   // in front, no block copy
-            data = blk.data() + kPad - carry.size();
-            len = blk.size() - kPad + carry.size();
-        } else {                                                                     // giant record: slow path
-            carry.insert(carry.end(), blk.begin() + kPad, blk.end());
-            data = carry.data();
-            len = carry.size();
-        }
+        if (!w.next(src)) die(2, (fs.name + ": " + src.error()).c_str());
+        const char *data = w.data;
+        const size_t len = w.len;
         if (len == 0) return false;
         if (len >= (1ull << 32)) die(3, "a single FASTQ record spans more than 4 GB");
-        // newline index, in parallel
-        rs.pool->run([&](int t) {
-            auto &v = nl[t];
-            v.clear();
-            const size_t lo = len * (size_t)t / T, hi_ = len * (size_t)(t + 1) / T;
-            const char *p = data + lo, *e = data + hi_;
-            while (p < e && (p = (const char *)memchr(p, '\n', (size_t)(e - p)))) {
-                v.push_back((uint32_t)(p - data));
-                ++p;
-            }
-        });
-        std::vector<size_t> cum(T + 1, 0);
-        for (int t = 0; t < T; t++) cum[t + 1] = cum[t] + nl[t].size();
-        const size_t total_nl = cum[T];
-        allnl.resize(total_nl);
-        rs.pool->run([&](int t) { if (!nl[t].empty()) memcpy(allnl.data() + cum[t], nl[t].data(), nl[t].size() * 4); });
-        const size_t n_rec = total_nl / 4;
-        parse_records(data, n_rec);
+        w.index(*rs.pool);
+        std::vector<uint32_t> &allnl = w.nl;
+        const size_t n_rec = allnl.size() / 4;
+        parse_records(data, allnl, n_rec);
         const size_t consumed = n_rec ? (size_t)allnl[4 * n_rec - 1] + 1 : 0;
-        if (last) {
+        if (w.last) {
             // end of input: what is left holds < 4 newlines.  Reference framing (classify.cpp:257-268): the
             // header must be newline-terminated; bases are whatever follows up to the next newline or EOF.
             const char *p = data + consumed, *e = data + len;
@@ -1034,14 +927,11 @@ struct HostParser {
                 allnl.clear();
                 for (size_t i = 0; i < tail.size(); i++)
                     if (tail[i] == '\n') allnl.push_back((uint32_t)i);
-                parse_records(tail.data(), 1);
+                parse_records(tail.data(), allnl, 1);
             }
             return false;
         }
-        // keep the incomplete record for the next block
-        std::vector<char> rest(data + consumed, data + len);
-        carry.swap(rest);
-        src.recycle(std::move(blk));
+        w.keep(src, consumed);                                                       // the incomplete record, for the next block
         return true;
     }
 };

@@ -30,28 +30,28 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
-#include <fcntl.h>
-
 #include <algorithm>
 #include <cerrno>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <string>
 #include <thread>
-#include <string_view>
 #include <vector>
 
 #include "../../include/hast.h"
 #include <zlib.h>
 
+#include "cli_common.h"
 #include "ingest.h"
+#include "raw_blocks.h"
 #include "rb_host.h"
 #include "rs_host.h"
 
 namespace {
+
+using hast::now_s;
 
 [[noreturn]] void die(int code, const std::string &what) {
     fprintf(stderr, "classify_read: ERROR: %s", what.c_str());
@@ -76,24 +76,6 @@ void print_usage() {   // same flags as the reference (s03:316-324); stderr is f
           "  --gz-out                        (with --bin-reads) gzip those files, names end in .gz\n"
           "  --bin-dir DIR                   (with --bin-reads) where they go (default: the working directory)\n",
           stderr);
-}
-
-// the whole input, front to back (also from a pipe, which has no size to ask for)
-bool slurp(const std::string &path, std::vector<char> &out) {
-    FILE *f = fopen(path.c_str(), "rb");
-    if (!f) return false;
-    out.clear();
-    size_t have = 0;
-    for (;;) {
-        if (out.size() - have < (1u << 20)) out.resize(std::max<size_t>(out.size() * 2, 4u << 20));
-        const size_t n = fread(out.data() + have, 1, out.size() - have, f);
-        have += n;
-        if (n == 0) break;
-    }
-    const bool ok = !ferror(f);
-    fclose(f);
-    out.resize(have);
-    return ok;
 }
 
 // the rows of n reads: names[name_off[i], name_off[i + 1]) and votes[2 i], votes[2 i + 1] -> "name \t haplotypeN|ambiguous \t density"
@@ -192,11 +174,71 @@ struct BinFiles {
     }
 };
 
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+// the format error in the reference's words (s03:262,288); false, for the caller to hand on
+bool wrong_format(bool fastq) {
+    fprintf(stderr, fastq ? "fasta detected . ERROR . please use \"--format fasta\". exit ... \n" : "fasta detected . ERROR . please use \"--format fastq\". exit ... \n");
+    return false;
+}
 
-}  // namespace
+struct Options {
+    std::vector<std::string> haps, read, bin_base;          // bin_base: with --bin-reads, per input its basename minus a trailing .gz
+    std::string format = "fasta", bin_dir = ".";
+    std::vector<int> devices;
+    bool fastq = false, ingest_device = false, stats = false, bin_reads = false, gz_out = false;
+    long t_num = 8, block_mb = 64;
+};
 
-int main(int argc, char **argv) {
+// a parsed batch of reads on its way to the GPU
+struct Batch {
+    std::vector<uint8_t> bases;
+    std::vector<uint64_t> offsets;
+    std::vector<std::string> names;
+    std::string raw;                                        // --bin-reads: the view the records lie in, and their extents in it
+    std::vector<hast::rb::Extent> ext;
+};
+
+// What the ONE background thread works on: the host route hands it a batch (HostRoute::classify_batch) so that the upload, the kernel
+// and the formatting of block i run while block i + 1 is indexed and copied; one thread, so rows stay in order.  From that hand-over to
+// wait() everything here is the thread's alone; the main thread touches it, run_batch and DeviceRoute::step included, only after wait().
+struct Shared {
+    Batch bt[2];                                            // the batch in flight and the one before it (its buffers are reused)
+    int cur = 0;
+    std::string out_rows;                                   // the rows of the input at hand
+    BinFiles bins;
+    hast::rb::Runs bin_runs;
+    bool bin_failed = false;
+    std::string error;                                      // the thread's failure, said by wait()
+    uint64_t st_records = 0;                                // what --stats prints of them
+    struct BinStats { uint64_t cls[3] = {0, 0, 0}, dev = 0, host = 0; } st_bin;
+    double st_kernels = 0, st_rows = 0;
+    std::thread thread;
+    ~Shared() { join(); }                                   // every way out of main() waits for the batch in flight
+    void join() { if (thread.joinable()) thread.join(); }
+    void wait() {
+        join();
+        if (!error.empty()) die(4, error);
+    }
+};
+
+// what one phase of main() leaves to the next
+struct Run {
+    explicit Run(const Options &opt) : o(opt), pool(opt.t_num) {}
+    const Options o;
+    size_t K = 0, rs_block = 0;                             // rs_block: the device ingest's block
+    hast_ctx *ctx = nullptr;                                // ctxs[0]: the table is built there
+    std::vector<hast_ctx *> ctxs;
+    int total_kmers[2] = {0, 0};                            // s03:50,68 (an `int` in the reference)
+    hast::WorkerPool pool;
+    hast_rs *feed = nullptr;                                // --ingest device
+    uint64_t st_blocks = 0, st_gz = 0;                      // the main thread's part of --stats
+    double st_read = 0, st_upload = 0, t_phase = 0;
+    std::string st_fallback = "none";
+    bool output_failed = false;
+    Shared sh;                                              // (last: its thread is joined before anything above goes)
+};
+
+// false: the usage text or the reference's word on --format has been printed, the exit status is -1
+bool parse_options(int argc, char **argv, Options &o) {
     static struct option long_options[] = {{"hap", required_argument, NULL, 'p'},    {"read", required_argument, NULL, 'r'},
                                            {"format", required_argument, NULL, 'f'}, {"thread", required_argument, NULL, 't'},
                                            {"help", no_argument, NULL, 'h'},         {"device", required_argument, NULL, 1001},
@@ -205,613 +247,481 @@ int main(int argc, char **argv) {
                                            {"bin-reads", no_argument, NULL, 1006},   {"gz-out", no_argument, NULL, 1007},
                                            {"bin-dir", required_argument, NULL, 1008},
                                            {0, 0, 0, 0}};
-    std::vector<std::string> haps, read;
-    std::string format = "fasta";
-    int t_num = 8, device = 0;
-    std::vector<int> devices;
-    bool ingest_device = false, stats = false, bin_reads = false, gz_out = false;
-    std::string bin_dir = ".";
-    long block_mb = 64;
-    for (;;) {
+    int device = 0;
+    bool ok = true;
+    while (ok) {
         int c = getopt_long(argc, argv, "p:r:t:f:h", long_options, NULL);   // s03:324
         if (c < 0) break;
         switch (c) {
-        case 'p': haps.push_back(optarg); break;
-        case 'r': read.push_back(optarg); break;
-        case 'f': format = optarg; break;
-        case 't': t_num = atoi(optarg); break;
+        case 'p': o.haps.push_back(optarg); break;
+        case 'r': o.read.push_back(optarg); break;
+        case 'f': o.format = optarg; break;
+        case 't': o.t_num = atoi(optarg); break;
         case 1001: device = atoi(optarg); break;
-        case 1002:
-            for (const char *q = optarg; *q;) {
-                char *end;
-                const long v = strtol(q, &end, 10);
-                if (end == q || v < 0 || (*end && *end != ',')) { print_usage(); return -1; }
-                devices.push_back((int)v);
-                q = *end == ',' ? end + 1 : end;
-            }
-            break;
-        case 1003:
-            if (strcmp(optarg, "host") != 0 && strcmp(optarg, "device") != 0) { print_usage(); return -1; }
-            ingest_device = strcmp(optarg, "device") == 0;
-            break;
-        case 1004:
-            block_mb = atol(optarg);
-            if (block_mb < 1 || block_mb > 1024) { print_usage(); return -1; }
-            break;
-        case 1005: stats = true; break;
-        case 1006: bin_reads = true; break;
-        case 1007: gz_out = true; break;
-        case 1008: bin_dir = optarg; break;
+        case 1002: ok = hast::parse_device_list(optarg, o.devices); break;
+        case 1003: o.ingest_device = strcmp(optarg, "device") == 0; ok = o.ingest_device || strcmp(optarg, "host") == 0; break;
+        case 1004: o.block_mb = atol(optarg); ok = o.block_mb >= 1 && o.block_mb <= 1024; break;
+        case 1005: o.stats = true; break;
+        case 1006: o.bin_reads = true; break;
+        case 1007: o.gz_out = true; break;
+        case 1008: o.bin_dir = optarg; break;
         case 'h':
-        default: print_usage(); return -1;
+        default: ok = false;
         }
     }
-    if (haps.size() != 2 || read.empty() || t_num < 1) {                     // s03:351-354
+    ok = ok && o.haps.size() == 2 && !o.read.empty() && o.t_num >= 1;        // s03:351-354
+    ok = ok && !(o.gz_out && !o.bin_reads);
+    for (size_t i = 0; ok && o.bin_reads && i < o.read.size(); ++i) {
+        const std::string &r = o.read[i];
+        std::string b = r.substr(r.find_last_of('/') == std::string::npos ? 0 : r.find_last_of('/') + 1);
+        if (hast::ends_gz(b)) b.resize(b.size() - 3);
+        ok = std::find(o.bin_base.begin(), o.bin_base.end(), b) == o.bin_base.end();   // two inputs would write the same files
+        o.bin_base.push_back(b);
+    }
+    if (!ok) {
         print_usage();
-        return -1;
+        return false;
     }
-    if (gz_out && !bin_reads) {
-        print_usage();
-        return -1;
+    if (o.devices.empty()) o.devices.push_back(device);
+    o.fastq = o.format == "fastq";
+    if (o.format != "fasta" && !o.fastq) {
+        fprintf(stderr, " ERROR : invalid format : [%s] . exit ...\n", o.format.c_str());
+        return false;
     }
-    std::vector<std::string> bin_base;                                      // per input: its basename minus a trailing .gz
-    if (bin_reads)
-        for (const std::string &r : read) {
-            std::string b = r.substr(r.find_last_of('/') == std::string::npos ? 0 : r.find_last_of('/') + 1);
-            if (b.size() > 3 && b.compare(b.size() - 3, 3, ".gz") == 0) b.resize(b.size() - 3);
-            if (std::find(bin_base.begin(), bin_base.end(), b) != bin_base.end()) {   // two inputs would write the same files
-                print_usage();
-                return -1;
-            }
-            bin_base.push_back(b);
-        }
-    if (devices.empty()) devices.push_back(device);
-    device = devices[0];
-    if (format != "fasta" && format != "fastq") {
-        fprintf(stderr, " ERROR : invalid format : [%s] . exit ...\n", format.c_str());
-        return -1;
-    }
-    fprintf(stderr, "__START__\n");
-    // ---- load_kmers (s03:51-70) --------------------------------------------------------------------
-    // K = length of the first line of the first file (s03:57-58); regular files are streamed into the table by the library,
-    // which also checks on the device that every line is K upper-case A/C/G/T bytes; anything else is read into memory first
-    // (a pipe can be read only once: it is read whole now and its first bytes serve as the head)
-    std::vector<char> txt[2], head;
-    bool streamed[2] = {false, false};
-    size_t text_bytes[2] = {0, 0};
-    for (int h = 0; h < 2; h++) {
-        struct stat sb;
-        if (stat(haps[h].c_str(), &sb) == 0 && S_ISREG(sb.st_mode)) {
-            streamed[h] = true;
-            text_bytes[h] = (size_t)sb.st_size;
-        } else {
-            if (!slurp(haps[h], txt[h])) die(2, "cannot read " + haps[h]);
-            text_bytes[h] = txt[h].size();
-        }
-    }
-    if (streamed[0]) {
-        FILE *f = fopen(haps[0].c_str(), "rb");
-        if (!f) die(2, "cannot read " + haps[0]);
-        head.resize(4096);
-        head.resize(fread(head.data(), 1, head.size(), f));
-        fclose(f);
-    } else head.assign(txt[0].begin(), txt[0].begin() + (long)std::min<size_t>(txt[0].size(), 4096));
-    const void *nl0 = memchr(head.data(), '\n', head.size());
-    const size_t K = nl0 ? (size_t)((const char *)nl0 - head.data()) : head.size();   // s03:57-58
-    if (K < 1 || K > 32) die(3, "K (length of the first k-mer line) must be in [1,32]");
-    hast_ctx *ctx = nullptr;
-    if (hast_ctx_create(device, (int)K, &ctx) != HAST_OK) die(4, "cannot create GPU context");
-    if (hast_ctx_set_text_check(ctx, 1) != HAST_OK) die(4, "cannot create GPU context");
-    if (hast_table_reserve(ctx, text_bytes[0] / (K + 1) + text_bytes[1] / (K + 1) + 2, 0.0) != HAST_OK) die(4, "allocating the k-mer table");
-    int total_kmers[2] = {0, 0};                                             // s03:50,68 (an `int` in the reference)
+    return true;
+}
+
+// ---- load_kmers (s03:51-70): hast::KmerFiles reads; ours are the library's check, on the device, that every line is K upper-case
+// A/C/G/T bytes, the complete lines only of a file read into memory (s03:63), and the words of what goes wrong
+void load_kmers(Run &rs) {
+    hast::KmerFiles kf;
+    std::string msg;
+    if (int code = kf.open(rs.o.haps[0], rs.o.haps[1], &msg)) die(code, msg);
+    rs.K = kf.K;                                                                // s03:57-58
+    if (rs.K < 1 || rs.K > 32) die(3, "K (length of the first k-mer line) must be in [1,32]");
+    if (hast_ctx_create(rs.o.devices[0], (int)rs.K, &rs.ctx) != HAST_OK) die(4, "cannot create GPU context");
+    if (hast_ctx_set_text_check(rs.ctx, 1) != HAST_OK) die(4, "cannot create GPU context");
+    if (hast_table_reserve(rs.ctx, kf.capacity(), 0.0) != HAST_OK) die(4, "allocating the k-mer table");
     for (int h = 0; h < 2; h++) {
         fprintf(stderr, "__load hap%d kmers__\n", h);
         uint64_t lines = 0;
-        hast_status st;
-        if (streamed[h]) st = hast_table_insert_text_file(ctx, h, haps[h].c_str(), &lines);
-        else {
-            // complete lines only: a trailing piece without '\n' is dropped (s03:63) -- except a lone first line
-            size_t usable = txt[h].size();
-            while (usable && txt[h][usable - 1] != '\n') usable--;
-            st = hast_table_insert_text(ctx, h, txt[h].data(), usable, &lines);
-        }
-        if (st == HAST_ERR_FORMAT) die(3, std::string(hast_last_error()) + " (k-mer files must hold one K-mer of upper-case A/C/G/T per line)");
-        if (st == HAST_ERR_IO) die(2, "cannot read " + haps[h]);
-        if (st != HAST_OK) die(4, "building the k-mer table");
-        if (h == 0 && !nl0 && text_bytes[0] == K) {
-            for (size_t i = 0; i < K; i++)
-                if (!strchr("ACGT", head[i])) die(3, "k-mer files must hold upper-case A/C/G/T lines only");
-            uint64_t key = hast_canon_kmer(head.data(), (int)K);
-            if (hast_table_insert_keys(ctx, 0, &key, 1) != HAST_OK) die(4, "building the k-mer table");
-            lines = 1;
-        }
-        total_kmers[h] = (int)lines;
-        fprintf(stderr, "Recorded %d haplotype %d specific %zu-mers\n", total_kmers[h], h, K);
-        std::vector<char>().swap(txt[h]);
+        if (int code = kf.insert(rs.ctx, h, true, true, &lines, &msg))
+            die(code, msg.empty() ? std::string(hast_last_error()) + " (k-mer files must hold one K-mer of upper-case A/C/G/T per line)" : msg);
+        rs.total_kmers[h] = (int)lines;
+        fprintf(stderr, "Recorded %d haplotype %d specific %zu-mers\n", rs.total_kmers[h], h, rs.K);
     }
-    // the other GPUs get a copy of the finished table, peer to peer
-    std::vector<hast_ctx *> ctxs{ctx};
-    for (size_t i = 1; i < devices.size(); i++) {
+}
+
+// the other GPUs get a copy of the finished table, peer to peer
+void clone_to_other_gpus(Run &rs) {
+    rs.ctxs.assign(1, rs.ctx);
+    for (size_t i = 1; i < rs.o.devices.size(); i++) {
         hast_ctx *c2 = nullptr;
-        if (hast_ctx_create(devices[i], (int)K, &c2) != HAST_OK) die(4, "cannot create GPU context");
-        ctxs.push_back(c2);
+        if (hast_ctx_create(rs.o.devices[i], (int)rs.K, &c2) != HAST_OK) die(4, "cannot create GPU context");
+        rs.ctxs.push_back(c2);
     }
-    if (ctxs.size() > 1) {
-        // (all at once: every GPU pulls its copy over its own xGMI link; the source's filter is built first, the clones only read the source)
-        if (hast_filter_build(ctx) != HAST_OK) die(4, "building the k-mer filter");
-        std::vector<std::thread> cloners;
-        std::vector<int> failed(ctxs.size(), 0);
-        for (size_t i = 1; i < ctxs.size(); i++)
-            cloners.emplace_back([&, i] { failed[i] = hast_table_clone(ctxs[i], ctx) != HAST_OK; });
-        for (std::thread &t : cloners) t.join();
-        for (int f : failed)
-            if (f) die(4, "copying the k-mer table to another GPU");
+    if (rs.ctxs.size() == 1) return;
+    // (all at once: every GPU pulls its copy over its own xGMI link; the source's filter is built first, the clones only read the source)
+    if (hast_filter_build(rs.ctx) != HAST_OK) die(4, "building the k-mer filter");
+    std::vector<std::thread> cloners;
+    std::vector<int> failed(rs.ctxs.size(), 0);
+    for (size_t i = 1; i < rs.ctxs.size(); i++)
+        cloners.emplace_back([&rs, &failed, i] { failed[i] = hast_table_clone(rs.ctxs[i], rs.ctx) != HAST_OK; });
+    for (std::thread &t : cloners) t.join();
+    for (int f : failed)
+        if (f) die(4, "copying the k-mer table to another GPU");
+}
+
+// --ingest device: one feed on the context's GPU (hast_rs_*), unless the run has several
+void create_device_feed(Run &rs) {
+    const Options &o = rs.o;
+    rs.rs_block = (size_t)o.block_mb << 20;
+    if (getenv("HAST_RS_BLOCK")) rs.rs_block = (size_t)std::max(64L, atol(getenv("HAST_RS_BLOCK")));
+    if (!o.ingest_device) return;
+    if (rs.ctxs.size() > 1) {
+        fprintf(stderr, "classify_read: WARN: --ingest device takes one GPU: host ingest for this run (fallback=several_devices)\n");
+        rs.st_fallback = "several_devices";
+        return;
     }
-    // ---- reads: block ingest with t_num parser threads (ingest.h), one GPU batch per block ------------------------
-    // Framing as in the reference: FASTQ = 4 getlines per record, the header must be newline-terminated (s03:255-263);
-    // FASTA = '>' lines start a record, other non-empty lines are appended, a last line without '\n' is dropped
-    // (s03:279-296).  Rows of a file are printed when the file is done, like PrintOutput after the loop (s03:269,301).
-    hast::WorkerPool pool(t_num);
-    const int T = pool.size();
-    std::vector<std::vector<uint32_t>> nl(T);
-    std::vector<uint32_t> allnl;
-    std::vector<uint8_t> bases;
-    std::vector<uint64_t> offsets;
-    std::vector<std::string> names;
-    std::vector<uint64_t> part(T + 1);
-    std::vector<int> bad(T);
-    std::string out_rows;
-    const bool fastq = format == "fastq";
-    // Classify the parsed batch (names/offsets/bases) and append its rows.  The batch is handed to ONE background thread (rows
-    // stay in order) so that the upload, the kernel and the formatting of block i run while block i+1 is indexed and copied.
-    struct Batch {
-        std::vector<uint8_t> bases;
-        std::vector<uint64_t> offsets;
-        std::vector<std::string> names;
-        std::string raw;                                    // --bin-reads: the view the records lie in, and their extents in it
-        std::vector<hast::rb::Extent> ext;
-    };
-    BinFiles bins;
-    hast::rb::Runs bin_runs;                                // the background thread's while a batch is in flight
-    bool bin_failed = false;
-    uint64_t st_bin[3] = {0, 0, 0}, st_bin_dev = 0, st_bin_host = 0;
-    const uint32_t bin_total[2] = {(uint32_t)total_kmers[0], (uint32_t)total_kmers[1]};
-    std::string raw;                                        // what classify_batch hands on with the batch
-    std::vector<hast::rb::Extent> ext;
-    // the runs of the host model into the input's files
-    auto flush_runs = [&]() {
-        if (!bins.write_runs(bin_runs)) bin_failed = true;
+    if (hast_rs_create(rs.ctx, o.fastq ? HAST_RS_FASTQ : HAST_RS_FASTA, rs.rs_block, &rs.feed) != HAST_OK) die(4, "cannot create the device ingest");
+    if (o.bin_reads && hast_rs_set_bins(rs.feed, o.gz_out ? 2 : 1, (uint32_t)rs.total_kmers[0], (uint32_t)rs.total_kmers[1]) != HAST_OK) die(4, "cannot create the device ingest's bins");
+}
+
+// the votes of b's reads, one contiguous share of the reads per GPU; what went wrong, or nothing
+std::string classify_shares(Run &rs, const Batch &b, std::vector<uint32_t> &v) {
+    const size_t n = b.names.size(), G = rs.ctxs.size();
+    if (G == 1) return hast_classify_perread(rs.ctx, b.bases.data(), b.offsets.data(), n, v.data()) == HAST_OK ? "" : hast_last_error();
+    // cut where the bases divide evenly (reads differ in length by orders of magnitude); the shares run at the same time, every one
+    // on a thread of its own (a context is driven by one thread)
+    std::vector<size_t> cut(G + 1, n);
+    cut[0] = 0;
+    const uint64_t total = b.offsets[n] - b.offsets[0];
+    for (size_t g = 1; g < G; g++) {
+        const uint64_t want = b.offsets[0] + total * g / G;
+        cut[g] = (size_t)(std::lower_bound(b.offsets.begin(), b.offsets.begin() + (long)n, want) - b.offsets.begin());
+        if (cut[g] < cut[g - 1]) cut[g] = cut[g - 1];
+    }
+    std::vector<std::string> errs(G);
+    std::vector<std::thread> th;
+    for (size_t g = 0; g < G; g++)
+        th.emplace_back([&rs, &b, &v, &cut, &errs, g] {
+            const size_t lo = cut[g], hi = cut[g + 1];
+            if (hi > lo && hast_classify_perread(rs.ctxs[g], b.bases.data(), b.offsets.data() + lo, hi - lo, v.data() + 2 * lo) != HAST_OK)
+                errs[g] = hast_last_error();
+        });
+    for (std::thread &t : th) t.join();
+    for (const std::string &e : errs)
+        if (!e.empty()) return e;
+    return "";
+}
+
+// Classify the parsed batch and append its rows (and, with --bin-reads, its reads through the host model into the input's files).
+// The background thread's work; the device route's FASTQ tail runs it on the main thread.
+void run_batch(Run &rs, Batch &b) {
+    Shared &sh = rs.sh;
+    if (b.names.empty()) return;
+    const size_t n = b.names.size();
+    const double t0 = now_s();
+    std::vector<uint32_t> v(n * 2, 0);
+    const std::string trouble = classify_shares(rs, b, v);
+    if (!trouble.empty()) return (void)(sh.error = "classifying a batch (" + trouble + ")");
+    const double t1 = now_s();
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t off[2] = {0, (uint32_t)b.names[i].size()};
+        format_rows(sh.out_rows, reinterpret_cast<const uint8_t *>(b.names[i].data()), off, v.data() + 2 * i, 1, rs.total_kmers);
+    }
+    if (rs.o.bin_reads && b.ext.size() == n) {
+        hast::rb::append_runs(reinterpret_cast<const uint8_t *>(b.raw.data()), b.ext.data(), v.data(), n, (uint32_t)rs.total_kmers[0], (uint32_t)rs.total_kmers[1], &sh.bin_runs);
+        if (!sh.bins.write_runs(sh.bin_runs)) sh.bin_failed = true;
         for (int c = 0; c < 3; ++c) {
-            st_bin[c] += bin_runs.count[c];
-            st_bin_host += bin_runs.run[c].size();
+            sh.st_bin.cls[c] += sh.bin_runs.count[c];
+            sh.st_bin.host += sh.bin_runs.run[c].size();
         }
-        bin_runs.clear();
-    };
-    std::thread bg;
-    struct Joiner {                                         // every way out of main() waits for the batch in flight
-        std::thread &t;
-        ~Joiner() { if (t.joinable()) t.join(); }
-    } joiner{bg};
-    Batch bt[2];                                            // the batch in flight and the one before it (its buffers are reused)
-    int cur = 0;
-    std::string bg_error;
-    // what --stats prints; the background thread adds to records / kernels / rows, and is joined before they are read
-    uint64_t st_blocks = 0, st_records = 0, st_gz = 0;
-    double st_read = 0, st_upload = 0, st_kernels = 0, st_rows = 0;
-    std::string st_fallback = "none";
-    auto wait_bg = [&]() {
-        if (bg.joinable()) bg.join();
-        if (!bg_error.empty()) die(4, bg_error);
-    };
-    auto run_batch = [&](Batch &b) {
-        if (b.names.empty()) return;
-        const size_t n = b.names.size(), G = ctxs.size();
-        const double t0 = now_s();
-        std::vector<uint32_t> v(n * 2, 0);
-        if (G == 1) {
-            if (hast_classify_perread(ctx, b.bases.data(), b.offsets.data(), n, v.data()) != HAST_OK) {
-                bg_error = std::string("classifying a batch (") + hast_last_error() + ")";
-                return;
-            }
-        } else {
-            // one contiguous share of the reads per GPU, cut where the bases divide evenly (reads differ in length by orders of
-            // magnitude); the shares run at the same time, every one on a thread of its own (a context is driven by one thread)
-            std::vector<size_t> cut(G + 1, n);
-            cut[0] = 0;
-            const uint64_t total = b.offsets[n] - b.offsets[0];
-            for (size_t g = 1; g < G; g++) {
-                const uint64_t want = b.offsets[0] + total * g / G;
-                cut[g] = (size_t)(std::lower_bound(b.offsets.begin(), b.offsets.begin() + (long)n, want) - b.offsets.begin());
-                if (cut[g] < cut[g - 1]) cut[g] = cut[g - 1];
-            }
-            std::vector<std::string> errs(G);
-            std::vector<std::thread> th;
-            for (size_t g = 0; g < G; g++)
-                th.emplace_back([&, g] {
-                    const size_t lo = cut[g], hi = cut[g + 1];
-                    if (hi > lo && hast_classify_perread(ctxs[g], b.bases.data(), b.offsets.data() + lo, hi - lo, v.data() + 2 * lo) != HAST_OK)
-                        errs[g] = hast_last_error();
-                });
-            for (std::thread &t : th) t.join();
-            for (const std::string &e : errs)
-                if (!e.empty()) {
-                    bg_error = "classifying a batch (" + e + ")";
-                    return;
-                }
-        }
-        const double t1 = now_s();
-        for (size_t i = 0; i < n; i++) {
-            const uint32_t off[2] = {0, (uint32_t)b.names[i].size()};
-            format_rows(out_rows, reinterpret_cast<const uint8_t *>(b.names[i].data()), off, v.data() + 2 * i, 1, total_kmers);
-        }
-        if (bin_reads && b.ext.size() == n) {
-            hast::rb::append_runs(reinterpret_cast<const uint8_t *>(b.raw.data()), b.ext.data(), v.data(), n, bin_total[0], bin_total[1], &bin_runs);
-            flush_runs();
-        }
-        st_records += n;
-        st_kernels += t1 - t0;
-        st_rows += now_s() - t1;
-    };
-    auto classify_batch = [&]() {
-        wait_bg();                                          // one batch in flight; its rows are in out_rows now
-        if (names.empty()) return;
-        Batch &b = bt[cur];
-        b.bases.swap(bases);
-        b.offsets.swap(offsets);
-        b.names.swap(names);
-        b.raw.swap(raw);
-        b.ext.swap(ext);
-        bg = std::thread([&run_batch, &b] { run_batch(b); });
-        cur ^= 1;
-        Batch &o = bt[cur];                                 // idle since the wait above: its vectors (and their capacity) are the next work area
-        bases.swap(o.bases);
-        offsets.swap(o.offsets);
-        names.swap(o.names);
-        raw.clear();
-        ext.clear();
-    };
-    // records = [first, last) pairs of line indices: header line, then sequence lines; fills names/offsets/bases in parallel
-    struct RecSpan { uint32_t head, seq_first, seq_end; };             // line indices; sequence lines [seq_first, seq_end)
+        sh.bin_runs.clear();
+    }
+    sh.st_records += n;
+    sh.st_kernels += t1 - t0;
+    sh.st_rows += now_s() - t1;
+}
+
+// the FASTQ tail as a record of the bins: its bytes as they lie, plus a newline if they do not end in one (rb_host.h: append_tail)
+void bin_tail(Batch &b, const char *tail, size_t n_tail) {
+    b.raw.assign(tail, n_tail);
+    if (b.raw.back() != '\n') b.raw += '\n';
+    b.ext.assign(1, hast::rb::Extent{0, b.raw.size()});
+}
+
+// ---- the host route: block ingest with t_num parser threads (ingest.h), one GPU batch per block ------------------------
+// Framing as in the reference: FASTQ = 4 getlines per record, the header must be newline-terminated (s03:255-263);
+// FASTA = '>' lines start a record, other non-empty lines are appended, a last line without '\n' is dropped
+// (s03:279-296).  Rows of a file are printed when the file is done, like PrintOutput after the loop (s03:269,301).
+struct HostRoute {
+    explicit HostRoute(Run &run) : rs(run), T(run.pool.size()), part((size_t)T + 1), bad((size_t)T), hl((size_t)T) {}
+    Run &rs;
+    const int T;
+    const size_t block_bytes = (size_t)std::max(1L, getenv("HAST_READ_BLOCK_BYTES") ? atol(getenv("HAST_READ_BLOCK_BYTES")) : (256L << 20));
+    Batch w;                                                // the batch being parsed: classify_batch hands it to the background thread
+    struct RecSpan { uint32_t head, seq_first, seq_end; };  // line indices; sequence lines [seq_first, seq_end)
     std::vector<RecSpan> recs;
-    auto line_start = [&](size_t i) -> size_t { return i ? (size_t)allnl[i - 1] + 1 : 0; };
-    auto build_batch = [&](const char *data) {
+    std::vector<uint64_t> part;
+    std::vector<int> bad;
+    std::vector<std::vector<uint32_t>> hl;
+    bool seen_header = false;                               // FASTA: lines before the first '>' belong to no record (s03:286-292)
+
+    static size_t line_start(const hast::BlockWork &a, size_t i) { return i ? (size_t)a.nl[i - 1] + 1 : 0; }
+    // recs (over the area's lines) -> names/offsets/bases of w, in parallel
+    void build_batch(const hast::BlockWork &a) {
         const size_t n = recs.size();
-        names.assign(n, std::string());
-        offsets.assign(n + 1, 0);
-        if (n == 0) { bases.clear(); return; }
-        std::vector<uint64_t> len(n);
-        pool.run([&](int t) {
+        const char *data = a.data;
+        w.names.assign(n, std::string());
+        w.offsets.assign(n + 1, 0);
+        if (n == 0) return w.bases.clear();
+        rs.pool.run([&](int t) {
             uint64_t sum = 0;
             for (size_t i = n * (size_t)t / T; i < n * (size_t)(t + 1) / T; i++) {
                 const RecSpan &r = recs[i];
-                uint64_t l = 0;
-                if (r.seq_end > r.seq_first) l = ((uint64_t)allnl[r.seq_end - 1] - line_start(r.seq_first)) - (r.seq_end - r.seq_first - 1);
-                len[i] = l;
-                sum += l;
+                if (r.seq_end > r.seq_first) sum += ((uint64_t)a.nl[r.seq_end - 1] - line_start(a, r.seq_first)) - (r.seq_end - r.seq_first - 1);
             }
             part[t + 1] = sum;
         });
         part[0] = 0;
         for (int t = 0; t < T; t++) part[t + 1] += part[t];
-        bases.resize(part[T] + 16);
-        pool.run([&](int t) {
+        w.bases.resize(part[T] + 16);
+        rs.pool.run([&](int t) {
             uint64_t off = part[t];
             for (size_t i = n * (size_t)t / T; i < n * (size_t)(t + 1) / T; i++) {
                 const RecSpan &r = recs[i];
-                const size_t hs = line_start(r.head), he = allnl[r.head];
-                names[i].assign(data + hs + (he > hs ? 1 : 0), data + he);               // head.substr(1), s03:207
-                offsets[i] = off;
+                const size_t hs = line_start(a, r.head), he = a.nl[r.head];
+                w.names[i].assign(data + hs + (he > hs ? 1 : 0), data + he);             // head.substr(1), s03:207
+                w.offsets[i] = off;
                 for (uint32_t li = r.seq_first; li < r.seq_end; li++) {
-                    const size_t ls = line_start(li), le = allnl[li];
-                    memcpy(bases.data() + off, data + ls, le - ls);
+                    const size_t ls = line_start(a, li), le = a.nl[li];
+                    memcpy(w.bases.data() + off, data + ls, le - ls);
                     off += le - ls;
                 }
             }
         });
-        offsets[n] = part[T];
-        if (bin_reads) {                                    // the records' extents (rb_core.h) and the bytes they lie in, for the background thread
-            ext.resize(n);
-            uint64_t end = 0;
-            for (size_t i = 0; i < n; i++) {
-                const RecSpan &r = recs[i];
-                ext[i].lo = line_start(r.head);
-                ext[i].hi = fastq ? (uint64_t)allnl[r.head + 3] + 1 : line_start(r.seq_end);
-                end = ext[i].hi;
-            }
-            raw.assign(data, end);
+        w.offsets[n] = part[T];
+        if (!rs.o.bin_reads) return;
+        w.ext.resize(n);                                    // the records' extents (rb_core.h) and the bytes they lie in, for the background thread
+        uint64_t end = 0;
+        for (size_t i = 0; i < n; i++) {
+            const RecSpan &r = recs[i];
+            w.ext[i].lo = line_start(a, r.head);
+            w.ext[i].hi = rs.o.fastq ? (uint64_t)a.nl[r.head + 3] + 1 : line_start(a, r.seq_end);
+            end = w.ext[i].hi;
         }
-    };
-    // the FASTQ tail as a record of the bins: its bytes as they lie, plus a newline if they do not end in one (rb_host.h: append_tail)
-    auto bin_tail = [&](const char *tail, size_t n_tail) {
-        if (!bin_reads || names.empty()) return;
-        raw.assign(tail, n_tail);
-        if (raw.back() != '\n') raw += '\n';
-        ext.assign(1, hast::rb::Extent{0, raw.size()});
-    };
-    const size_t block_bytes = (size_t)std::max(1L, getenv("HAST_READ_BLOCK_BYTES") ? atol(getenv("HAST_READ_BLOCK_BYTES")) : (256L << 20));
-    bool output_failed = false;
-    // the host route for one input: its rows into out_rows; 1: the format error (its message is printed)
-    auto host_file = [&](const std::string &r) -> int {
+        w.raw.assign(data, end);
+    }
+    // w to the background thread; the batch before the one in flight becomes the next work area
+    void classify_batch() {
+        Shared &sh = rs.sh;
+        sh.wait();                                          // one batch in flight; its rows are in out_rows now
+        if (w.names.empty()) return;
+        Batch &b = sh.bt[sh.cur];
+        std::swap(b, w);
+        sh.thread = std::thread(run_batch, std::ref(rs), std::ref(b));
+        sh.cur ^= 1;
+        Batch &o = sh.bt[sh.cur];                           // idle since the wait above: its vectors (and their capacity) are the next work area
+        w.bases.swap(o.bases);
+        w.offsets.swap(o.offsets);
+        w.names.swap(o.names);
+        w.raw.clear();
+        w.ext.clear();
+    }
+    // One area of a FASTQ file: its complete records as a batch; at the end of the file what is left behind them (header terminated;
+    // bases = next piece, terminated or not, s03:260) as a batch of one.  false: the format error
+    bool fastq_area(const hast::BlockWork &a, size_t *consumed) {
+        const size_t n_lines = a.nl.size(), n_rec = n_lines / 4;
+        for (size_t i = 0; i < n_rec; i++) recs.push_back({(uint32_t)(4 * i), (uint32_t)(4 * i + 1), (uint32_t)(4 * i + 2)});
+        *consumed = n_rec ? (size_t)a.nl[4 * n_rec - 1] + 1 : 0;
+        for (const RecSpan &x : recs)
+            if (a.len && a.data[line_start(a, x.head)] == '>') return wrong_format(true);
+        build_batch(a);
+        classify_batch();
+        if (!a.last || n_lines % 4 == 0) return true;
+        if (!tail_batch(a.data + *consumed, a.len - *consumed, w.names, w.bases, w.offsets)) return wrong_format(true);
+        if (rs.o.bin_reads && !w.names.empty()) bin_tail(w, a.data + *consumed, a.len - *consumed);
+        classify_batch();
+        return true;
+    }
+    // One area of a FASTA file: header lines have '>' as their first byte; '@' / '+' at the start of a non-empty line is the
+    // reference's format error (false)
+    bool fasta_area(const hast::BlockWork &a, size_t *consumed) {
+        const size_t n_lines = a.nl.size();                 // complete ('\n'-terminated) lines in the work area
+        rs.pool.run([&](int t) {
+            bad[t] = 0;
+            hl[t].clear();
+            for (size_t i = n_lines * (size_t)t / T; i < n_lines * (size_t)(t + 1) / T; i++) {
+                const size_t ls = line_start(a, i);
+                if (a.nl[i] == ls) continue;                                            // empty line: skipped (s03:280)
+                const char c = a.data[ls];
+                if (c == '>') hl[t].push_back((uint32_t)i);
+                else if (c == '@' || c == '+') bad[t] = 1;
+            }
+        });
+        std::vector<uint32_t> heads;
+        for (int t = 0; t < T; t++) {
+            if (bad[t]) return wrong_format(false);
+            heads.insert(heads.end(), hl[t].begin(), hl[t].end());
+        }
+        // complete records: header j .. header j+1; at EOF the last header's record ends at the last complete line
+        for (size_t j = 0; j + 1 < heads.size(); j++) recs.push_back({heads[j], heads[j] + 1, heads[j + 1]});
+        if (a.last && !heads.empty()) recs.push_back({heads.back(), heads.back() + 1, (uint32_t)n_lines});
+        if (!heads.empty()) seen_header = true;
+        if (a.last) *consumed = a.len;
+        else if (!heads.empty()) *consumed = line_start(a, heads.back());     // carry the (possibly incomplete) last record
+        else *consumed = seen_header ? 0 : (n_lines ? (size_t)a.nl[n_lines - 1] + 1 : 0);   // no header yet: drop complete lines
+        build_batch(a);
+        classify_batch();
+        return true;
+    }
+    // one input: its rows into out_rows; 1: the format error (its message is printed)
+    int file(const std::string &r) {
         hast::BlockSource src;
         if (!src.open(r, block_bytes)) die(2, "cannot open " + r);
-        std::vector<char> carry;
-        wait_bg();
-        out_rows.clear();
-        bool seen_header = false;                       // FASTA: lines before the first '>' belong to no record (s03:286-292)
+        hast::BlockWork a;
+        rs.sh.wait();
+        rs.sh.out_rows.clear();
+        seen_header = false;
         for (;;) {
             const double t_read = now_s();
-            std::vector<char> blk = src.next();
-            st_read += now_s() - t_read;
-            const bool last = blk.empty();
-            if (last && !src.error().empty()) die(2, r + ": " + src.error());
-            constexpr size_t kPad = hast::BlockSource::kFrontPad;
-            const char *data;
-            size_t len;
-            if (last) { data = carry.data(); len = carry.size(); }
-            else if (carry.size() <= kPad) {
-                if (!carry.empty()) memcpy(blk.data() + kPad - carry.size(), carry.data(), carry.size());
-                data = blk.data() + kPad - carry.size();
-                len = blk.size() - kPad + carry.size();
-            } else {
-                carry.insert(carry.end(), blk.begin() + kPad, blk.end());
-                data = carry.data();
-                len = carry.size();
-            }
-            if (len >= (1ull << 32)) die(3, "a single record spans more than 4 GB");
-            pool.run([&](int t) {
-                auto &v = nl[t];
-                v.clear();
-                const char *p = data + len * (size_t)t / T, *e = data + len * (size_t)(t + 1) / T;
-                while (p < e && (p = (const char *)memchr(p, '\n', (size_t)(e - p)))) { v.push_back((uint32_t)(p - data)); ++p; }
-            });
-            allnl.clear();
-            for (int t = 0; t < T; t++) allnl.insert(allnl.end(), nl[t].begin(), nl[t].end());
-            const size_t n_lines = allnl.size();                 // complete ('\n'-terminated) lines in the work area
+            if (!a.next(src)) die(2, r + ": " + src.error());
+            rs.st_read += now_s() - t_read;
+            if (a.len >= (1ull << 32)) die(3, "a single record spans more than 4 GB");
+            a.index(rs.pool);
             recs.clear();
             size_t consumed = 0;
-            if (fastq) {
-                const size_t n_rec = n_lines / 4;
-                for (size_t i = 0; i < n_rec; i++) recs.push_back({(uint32_t)(4 * i), (uint32_t)(4 * i + 1), (uint32_t)(4 * i + 2)});
-                consumed = n_rec ? (size_t)allnl[4 * n_rec - 1] + 1 : 0;
-                if (last && n_lines % 4 >= 1) {
-                    // tail: header terminated; bases = next piece, terminated or not (s03:260); the tail becomes a full record,
-                    // handled after the block's records, as a one-record batch
-                    for (const RecSpan &x : recs)
-                        if (data[line_start(x.head)] == '>') { fprintf(stderr, "fasta detected . ERROR . please use \"--format fasta\". exit ... \n"); return 1; }
-                    build_batch(data);
-                    classify_batch();
-                    if (!tail_batch(data + consumed, len - consumed, names, bases, offsets)) { fprintf(stderr, "fasta detected . ERROR . please use \"--format fasta\". exit ... \n"); return 1; }
-                    bin_tail(data + consumed, len - consumed);
-                    classify_batch();
-                    break;
-                }
-                for (const RecSpan &x : recs)
-                    if (len && data[line_start(x.head)] == '>') { fprintf(stderr, "fasta detected . ERROR . please use \"--format fasta\". exit ... \n"); return 1; }
-            } else {
-                // header lines (first byte '>'); '@'/'+' at the start of a non-empty line is the reference's format error
-                std::vector<std::vector<uint32_t>> hl(T);
-                pool.run([&](int t) {
-                    bad[t] = 0;
-                    hl[t].clear();
-                    for (size_t i = n_lines * (size_t)t / T; i < n_lines * (size_t)(t + 1) / T; i++) {
-                        const size_t ls = line_start(i);
-                        if (allnl[i] == ls) continue;                                       // empty line: skipped (s03:280)
-                        const char c = data[ls];
-                        if (c == '>') hl[t].push_back((uint32_t)i);
-                        else if (c == '@' || c == '+') bad[t] = 1;
-                    }
-                });
-                std::vector<uint32_t> heads;
-                for (int t = 0; t < T; t++) {
-                    if (bad[t]) { fprintf(stderr, "fasta detected . ERROR . please use \"--format fastq\". exit ... \n"); return 1; }
-                    heads.insert(heads.end(), hl[t].begin(), hl[t].end());
-                }
-                // complete records: header j .. header j+1; at EOF the last header's record ends at the last complete line
-                for (size_t j = 0; j + 1 < heads.size(); j++) recs.push_back({heads[j], heads[j] + 1, heads[j + 1]});
-                if (last && !heads.empty()) recs.push_back({heads.back(), heads.back() + 1, (uint32_t)n_lines});
-                if (!heads.empty()) seen_header = true;
-                if (last) consumed = len;
-                else if (!heads.empty()) consumed = line_start(heads.back());      // carry the (possibly incomplete) last record
-                else consumed = seen_header ? 0 : (n_lines ? (size_t)allnl[n_lines - 1] + 1 : 0);   // no header yet: drop complete lines
-            }
-            build_batch(data);
-            classify_batch();
-            if (last) break;
-            std::vector<char> keep(data + consumed, data + len);
-            carry.swap(keep);
-            src.recycle(std::move(blk));
+            if (!(rs.o.fastq ? fastq_area(a, &consumed) : fasta_area(a, &consumed))) return 1;
+            if (a.last) return 0;
+            a.keep(src, consumed);
         }
-        return 0;
-    };
-    // ---- --ingest device: one feed on the context's GPU (hast_rs_*) ---------------------------------------------------------
-    hast_rs *feed = nullptr;
-    size_t rs_block = (size_t)block_mb << 20;
-    if (getenv("HAST_RS_BLOCK")) rs_block = (size_t)std::max(64L, atol(getenv("HAST_RS_BLOCK")));
-    if (ingest_device && ctxs.size() > 1) {
-        fprintf(stderr, "classify_read: WARN: --ingest device takes one GPU: host ingest for this run (fallback=several_devices)\n");
-        st_fallback = "several_devices";
-        ingest_device = false;
     }
-    if (ingest_device && hast_rs_create(ctx, fastq ? HAST_RS_FASTQ : HAST_RS_FASTA, rs_block, &feed) != HAST_OK) die(4, "cannot create the device ingest");
-    if (feed && bin_reads && hast_rs_set_bins(feed, gz_out ? 2 : 1, bin_total[0], bin_total[1]) != HAST_OK) die(4, "cannot create the device ingest's bins");
-    std::vector<uint8_t> rs_tail;
-    // the device route for one input: its rows into out_rows; 1: the format error (its message is printed), 2: a record too long
-    auto device_file = [&](const std::string &r) -> int {
-        const size_t n = r.size();
-        hast_gz *z = nullptr;
-        if (n > 3 && r.compare(n - 3, 3, ".gz") == 0 && hast_gz_open(ctx, r.c_str(), &z) != HAST_OK) z = nullptr;   // (BGZF, not gzip, unreadable: BlockSource's words)
-        int fd = -1;
-        hast::BlockSource src;
-        const bool plain = !(n > 3 && r.compare(n - 3, 3, ".gz") == 0);
-        if (z) ++st_gz;
-        else if (plain) {
-            if ((fd = open(r.c_str(), O_RDONLY)) < 0) die(2, "cannot open " + r);
-        } else if (!src.open(r, rs_block)) die(2, "cannot open " + r);
-        out_rows.clear();
-        int pending = 0, verdict = 0;
-        uint64_t framed_records = 0;                             // counted once the file is through: a refused file is read again
-        // frame and classify the oldest submitted block, format its rows
-        auto step = [&]() {
-            hast_rs_block b;
-            hast_rs_binned rb;
-            const double t0 = now_s();
-            if ((bin_reads ? hast_rs_next_binned(feed, &b, &rb) : hast_rs_next(feed, &b)) != HAST_OK) die(4, "framing and classifying a block");
-            const double t1 = now_s();
-            --pending;
-            ++st_blocks;
-            st_kernels += t1 - t0;
-            if (b.flags & HAST_RS_FORMAT_ERROR) verdict = 1;
-            else if (b.flags & HAST_RS_RECORD_TOO_LONG) verdict = 2;
-            if (verdict) return;
-            format_rows(out_rows, b.names, b.name_off, b.votes, (size_t)b.records, total_kmers);
-            framed_records += b.records;
-            if (bin_reads)
-                for (int c = 0; c < 3; ++c) {
-                    if (!bins.write(c, rb.run[c], (size_t)rb.run_bytes[c])) bin_failed = true;
-                    st_bin[c] += rb.count[c];
-                    st_bin_dev += rb.raw_bytes[c];
-                }
-            st_rows += now_s() - t1;
-        };
-        auto submit = [&](size_t n_bytes, bool last) {           // ... and keep one block ahead of the framer
-            const double t0 = now_s();
-            if (hast_rs_submit(feed, n_bytes, last) != HAST_OK) die(4, "submitting a block");
-            st_upload += now_s() - t0;
-            ++pending;
-            if (pending == 2) step();
-        };
-        auto host_block = [&]() {
-            uint8_t *h = nullptr;
-            const double t0 = now_s();
-            if (hast_rs_host_block(feed, &h) != HAST_OK) die(4, "the device ingest's staging block");
-            st_upload += now_s() - t0;
-            return h;
-        };
-        bool ended = false;                                      // the file's last block has been submitted
-        std::vector<char> blk;
-        size_t blk_at = 0;
-        while (!verdict && !ended) {
-            size_t got = 0;
-            const double t0 = now_s();
-            if (z) {
-                uint8_t *d = nullptr;
-                hast_stream fill = nullptr;
-                if (hast_rs_device_block(feed, &d, &fill) != HAST_OK) die(4, "the device ingest's block");
-                if (hast_gz_read_device(z, d, rs_block, &got, fill) != HAST_OK) die(2, r + ": " + hast_last_error());
-            } else if (plain) {
-                uint8_t *h = host_block();
-                while (got < rs_block) {
-                    const ssize_t k = ::read(fd, h + got, rs_block - got);
-                    if (k < 0 && errno == EINTR) continue;
-                    if (k < 0) die(2, r + ": " + strerror(errno));
-                    if (k == 0) break;
-                    got += (size_t)k;
-                }
-            } else {
-                constexpr size_t kPad = hast::BlockSource::kFrontPad;
-                if (blk_at >= blk.size()) {
-                    if (!blk.empty()) src.recycle(std::move(blk));
-                    blk = src.next();
-                    blk_at = kPad;
-                    if (blk.empty() && !src.error().empty()) die(2, r + ": " + src.error());
-                }
-                uint8_t *h = host_block();
-                got = blk.empty() ? 0 : std::min(rs_block, blk.size() - blk_at);
-                if (got) memcpy(h, blk.data() + blk_at, got);
-                blk_at += got;
+};
+
+// ---- the device route: an input's raw bytes (raw_blocks.h) through the run's feed, one block ahead of the framer ----
+struct DeviceRoute {
+    explicit DeviceRoute(Run &run) : rs(run), sh(run.sh), feed(run.feed) {}
+    Run &rs;
+    Shared &sh;                                             // (no batch is in flight while an input is on this route)
+    hast_rs *feed;
+    int pending = 0;                                        // blocks submitted and not framed yet
+    int verdict = 0;                                        // of the input at hand; 1: the format error, 2: a record too long
+    uint64_t framed_records = 0;                            // counted once the file is through: a refused file is read again
+    std::vector<uint8_t> tail;
+
+    void step() {                                           // frame and classify the oldest submitted block, format its rows
+        hast_rs_block b;
+        hast_rs_binned rb;
+        const double t0 = now_s();
+        if ((rs.o.bin_reads ? hast_rs_next_binned(feed, &b, &rb) : hast_rs_next(feed, &b)) != HAST_OK) die(4, "framing and classifying a block");
+        const double t1 = now_s();
+        --pending;
+        ++rs.st_blocks;
+        sh.st_kernels += t1 - t0;
+        if (b.flags & HAST_RS_FORMAT_ERROR) verdict = 1;
+        else if (b.flags & HAST_RS_RECORD_TOO_LONG) verdict = 2;
+        if (verdict) return;
+        format_rows(sh.out_rows, b.names, b.name_off, b.votes, (size_t)b.records, rs.total_kmers);
+        framed_records += b.records;
+        if (rs.o.bin_reads)
+            for (int c = 0; c < 3; ++c) {
+                if (!sh.bins.write(c, rb.run[c], (size_t)rb.run_bytes[c])) sh.bin_failed = true;
+                sh.st_bin.cls[c] += rb.count[c];
+                sh.st_bin.dev += rb.raw_bytes[c];
             }
-            st_read += now_s() - t0;
-            ended = got == 0;                                    // (only a read that returns nothing ends the stream, include/hast.h)
-            submit(got, ended);
+        sh.st_rows += now_s() - t1;
+    }
+    void submit(size_t n) {                                 // (empty: the input's last) ... and keep one block ahead of the framer
+        const double t0 = now_s();
+        if (hast_rs_submit(feed, n, n == 0) != HAST_OK) die(4, "submitting a block");
+        rs.st_upload += now_s() - t0;
+        if (++pending == 2) step();
+    }
+    uint8_t *block(bool on_device, hast_stream *fill) {     // the block the next bytes go to: the decoder's, or the pinned one
+        uint8_t *b = nullptr;
+        const double t0 = now_s();
+        if (on_device && hast_rs_device_block(feed, &b, fill) != HAST_OK) die(4, "the device ingest's block");
+        if (!on_device && hast_rs_host_block(feed, &b) != HAST_OK) die(4, "the device ingest's staging block");
+        if (!on_device) rs.st_upload += now_s() - t0;
+        return b;
+    }
+    // what a FASTQ file leaves behind its last complete record, classified here and now
+    void fastq_tail() {
+        size_t n_tail = 0;
+        tail.resize(rs.rs_block);
+        if (hast_rs_take_tail(feed, tail.data(), &n_tail) != HAST_OK) die(4, "the end of the input");
+        Batch tb;
+        const char *t = reinterpret_cast<const char *>(tail.data());
+        if (!tail_batch(t, n_tail, tb.names, tb.bases, tb.offsets)) return (void)(verdict = 1);
+        if (rs.o.bin_reads && !tb.names.empty()) bin_tail(tb, t, n_tail);
+        run_batch(rs, tb);
+        if (!sh.error.empty()) die(4, sh.error);
+    }
+    // one input: its rows into out_rows; 1: the format error (its message is printed), 2: a record too long
+    int file(const std::string &r) {
+        hast::RawBlocks raw;
+        std::string err;
+        if (!raw.open(r, hast::ends_gz(r), rs.ctx, rs.rs_block, &err)) die(2, err);
+        const bool on_device = raw.kind() == hast::RawBlocks::gz_on_device;
+        if (on_device) ++rs.st_gz;
+        sh.out_rows.clear();
+        verdict = 0;
+        framed_records = 0;
+        size_t got = 1;
+        while (!verdict && got) {                           // (only a read that returns nothing ends the stream, include/hast.h)
+            const double t0 = now_s();
+            hast_stream fill = nullptr;
+            uint8_t *b = block(on_device, &fill);
+            if (!(on_device ? raw.read_device(b, fill, &got) : raw.read_host(b, &got, &err))) die(2, r + ": " + (on_device ? hast_last_error() : err));
+            rs.st_read += now_s() - t0;
+            submit(got);
         }
-        if (!ended) {                                            // given up: the feed wants the file's last block all the same
-            if (!z) (void)host_block();
-            else {
-                uint8_t *d = nullptr;
-                if (hast_rs_device_block(feed, &d, nullptr) != HAST_OK) die(4, "the device ingest's block");
-            }
-            submit(0, true);
+        if (got) {                                          // given up: the feed wants the file's last block all the same
+            block(on_device, nullptr);
+            submit(0);
         }
-        while (pending) step();                                  // (before the decoder goes: its kernels wrote the blocks still waiting)
-        if (z) hast_gz_close(z);
-        if (fd >= 0) close(fd);
-        if (!verdict) st_records += framed_records;
-        if (!verdict && fastq) {
-            size_t n_tail = 0;
-            rs_tail.resize(rs_block);
-            if (hast_rs_take_tail(feed, rs_tail.data(), &n_tail) != HAST_OK) die(4, "the end of the input");
-            Batch tb;
-            if (!tail_batch(reinterpret_cast<const char *>(rs_tail.data()), n_tail, tb.names, tb.bases, tb.offsets)) verdict = 1;
-            else {
-                if (bin_reads && !tb.names.empty()) {
-                    tb.raw.assign(reinterpret_cast<const char *>(rs_tail.data()), n_tail);
-                    if (tb.raw.back() != '\n') tb.raw += '\n';
-                    tb.ext.assign(1, hast::rb::Extent{0, tb.raw.size()});
-                }
-                run_batch(tb);
-                if (!bg_error.empty()) die(4, bg_error);
-            }
-        }
-        if (verdict == 1) fprintf(stderr, fastq ? "fasta detected . ERROR . please use \"--format fasta\". exit ... \n" : "fasta detected . ERROR . please use \"--format fastq\". exit ... \n");
+        while (pending) step();                             // (before the decoder goes: its kernels wrote the blocks still waiting)
+        raw.close();
+        if (!verdict) sh.st_records += framed_records;
+        if (!verdict && rs.o.fastq) fastq_tail();
+        if (verdict == 1) wrong_format(rs.o.fastq);
         return verdict;
-    };
-    const double t_phase = now_s();
-    // the format error: the input leaves no files, as it leaves no rows
-    auto give_up = [&]() {
-        if (bg.joinable()) bg.join();
-        if (bin_reads) bins.discard();
-        return 1;
-    };
-    for (size_t ri = 0; ri < read.size(); ++ri) {
-        const std::string &r = read[ri];
-        fprintf(stderr, "__process read: %s\n", r.c_str());
-        if (bin_reads) bins.start(bin_dir, bin_base[ri], fastq ? "fastq" : "fasta", gz_out);
-        const uint64_t bin_before[5] = {st_bin[0], st_bin[1], st_bin[2], st_bin_dev, st_bin_host};
-        bool on_device = false;
-        if (feed) {
-            struct stat sb;
-            if (stat(r.c_str(), &sb) != 0 || !S_ISREG(sb.st_mode)) {
-                fprintf(stderr, "classify_read: WARN: %s is not a regular file: host ingest for this input (fallback=not_a_regular_file)\n", r.c_str());
-                st_fallback = "not_a_regular_file";
-            } else {
-                const int v = device_file(r);
-                if (v == 1) return give_up();
-                on_device = v == 0;
-                if (v == 2) {
-                    fprintf(stderr, "classify_read: WARN: a record of %s does not fit two blocks of %zu bytes: host ingest for this input (fallback=record_too_long)\n",
-                            r.c_str(), rs_block);
-                    st_fallback = "record_too_long";
-                    if (bin_reads) {                             // the file is read again from its start: so are its bins
-                        bins.discard();
-                        bins.start(bin_dir, bin_base[ri], fastq ? "fastq" : "fasta", gz_out);
-                        st_bin[0] = bin_before[0], st_bin[1] = bin_before[1], st_bin[2] = bin_before[2];
-                        st_bin_dev = bin_before[3], st_bin_host = bin_before[4];
-                    }
-                }
-            }
+    }
+};
+
+// One input down the ladder: the device route if there is one and it takes the input, else (with one WARN line) the host route; then its
+// bins closed and its rows written.  1: the format error -- the input leaves no files, as it leaves no rows, and the run ends.
+int process_input(Run &rs, HostRoute &host, DeviceRoute *dev, size_t ri) {
+    const Options &o = rs.o;
+    Shared &sh = rs.sh;
+    const std::string &r = o.read[ri];
+    fprintf(stderr, "__process read: %s\n", r.c_str());
+    if (o.bin_reads) sh.bins.start(o.bin_dir, o.bin_base[ri], o.fastq ? "fastq" : "fasta", o.gz_out);
+    const Shared::BinStats bin_before = sh.st_bin;
+    int v = -1;                                             // the device route's word on the input; -1: not asked
+    struct stat sb;
+    if (dev && (stat(r.c_str(), &sb) != 0 || !S_ISREG(sb.st_mode))) {
+        fprintf(stderr, "classify_read: WARN: %s is not a regular file: host ingest for this input (fallback=not_a_regular_file)\n", r.c_str());
+        rs.st_fallback = "not_a_regular_file";
+    } else if (dev) v = dev->file(r);
+    if (v == 2) {
+        fprintf(stderr, "classify_read: WARN: a record of %s does not fit two blocks of %zu bytes: host ingest for this input (fallback=record_too_long)\n",
+                r.c_str(), rs.rs_block);
+        rs.st_fallback = "record_too_long";
+        if (o.bin_reads) {                                  // the file is read again from its start: so are its bins
+            sh.bins.discard();
+            sh.bins.start(o.bin_dir, o.bin_base[ri], o.fastq ? "fastq" : "fasta", o.gz_out);
+            sh.st_bin = bin_before;
         }
-        if (!on_device && host_file(r)) return give_up();
-        wait_bg();
-        if (bin_reads && (!bins.close_all() || bin_failed)) die(3, "writing the reads of " + r + " to " + bin_dir + " failed");
-        if (fwrite(out_rows.data(), 1, out_rows.size(), stdout) != out_rows.size()) output_failed = true;
-        fprintf(stderr, "__process read done__\n");
     }
-    if (stats) {
-        fprintf(stderr, "[stats] ingest %s: blocks_framed=%llu records=%llu gz_on_device=%llu fallback=%s\n", feed ? "device" : "host", (unsigned long long)st_blocks,
-                (unsigned long long)st_records, (unsigned long long)st_gz, st_fallback.c_str());
-        fprintf(stderr, "[stats] seconds: read=%.3f upload=%.3f kernels=%.3f rows=%.3f read_phase=%.3f\n", st_read, st_upload, st_kernels, st_rows, now_s() - t_phase);
-        if (bin_reads)
-            fprintf(stderr, "[stats] bins: haplotype0=%llu haplotype1=%llu ambiguous=%llu bytes_on_device=%llu bytes_on_host=%llu gz=%d\n", (unsigned long long)st_bin[0],
-                    (unsigned long long)st_bin[1], (unsigned long long)st_bin[2], (unsigned long long)st_bin_dev, (unsigned long long)st_bin_host, gz_out ? 1 : 0);
+    if (v == 1 || (v != 0 && host.file(r))) {               // (give up: the feed and the contexts stay as they are)
+        sh.join();
+        if (o.bin_reads) sh.bins.discard();
+        return 1;
     }
-    if (feed) hast_rs_destroy(feed);
+    sh.wait();
+    if (o.bin_reads && (!sh.bins.close_all() || sh.bin_failed)) die(3, "writing the reads of " + r + " to " + o.bin_dir + " failed");
+    if (fwrite(sh.out_rows.data(), 1, sh.out_rows.size(), stdout) != sh.out_rows.size()) rs.output_failed = true;
+    fprintf(stderr, "__process read done__\n");
+    return 0;
+}
+
+void print_stats(const Run &rs) {
+    const Shared &sh = rs.sh;
+    fprintf(stderr, "[stats] ingest %s: blocks_framed=%llu records=%llu gz_on_device=%llu fallback=%s\n", rs.feed ? "device" : "host", (unsigned long long)rs.st_blocks,
+            (unsigned long long)sh.st_records, (unsigned long long)rs.st_gz, rs.st_fallback.c_str());
+    fprintf(stderr, "[stats] seconds: read=%.3f upload=%.3f kernels=%.3f rows=%.3f read_phase=%.3f\n", rs.st_read, rs.st_upload, sh.st_kernels, sh.st_rows, now_s() - rs.t_phase);
+    if (rs.o.bin_reads)
+        fprintf(stderr, "[stats] bins: haplotype0=%llu haplotype1=%llu ambiguous=%llu bytes_on_device=%llu bytes_on_host=%llu gz=%d\n", (unsigned long long)sh.st_bin.cls[0],
+                (unsigned long long)sh.st_bin.cls[1], (unsigned long long)sh.st_bin.cls[2], (unsigned long long)sh.st_bin.dev, (unsigned long long)sh.st_bin.host, rs.o.gz_out ? 1 : 0);
+}
+
+}  // namespace
+
+int main(int argc, char **argv) {
+    Options o;
+    if (!parse_options(argc, argv, o)) return -1;
+    Run rs(o);
+    fprintf(stderr, "__START__\n");
+    load_kmers(rs);
+    clone_to_other_gpus(rs);
+    HostRoute host(rs);
+    create_device_feed(rs);
+    std::unique_ptr<DeviceRoute> dev(rs.feed ? new DeviceRoute(rs) : nullptr);
+    rs.t_phase = now_s();
+    for (size_t ri = 0; ri < o.read.size(); ++ri)
+        if (process_input(rs, host, dev.get(), ri)) return 1;
+    if (o.stats) print_stats(rs);
+    if (rs.feed) hast_rs_destroy(rs.feed);
     // (mkoutput_by_fabulous2.0.sh redirects stdout into a file and goes on: a full disk or a closed pipe must not pass as exit 0)
-    if (fflush(stdout) != 0) output_failed = true;
-    if (output_failed) {
+    if (fflush(stdout) != 0) rs.output_failed = true;
+    if (rs.output_failed) {
         fprintf(stderr, "classify: ERROR: writing the result to stdout failed (%s)\n", strerror(errno));
         return 2;
     }
     fprintf(stderr, "__END__\n");
-    for (hast_ctx *c : ctxs) hast_ctx_destroy(c);
+    for (hast_ctx *c : rs.ctxs) hast_ctx_destroy(c);
     return 0;
 }
+

@@ -26,7 +26,6 @@
 #include <zlib.h>
 
 #include <algorithm>
-#include <chrono>
 #include <condition_variable>
 #include <mutex>
 #include <string>
@@ -34,6 +33,7 @@
 #include <vector>
 
 #include "../../include/hast.h"
+#include "cli_common.h"
 #include "ingest.h"
 
 namespace {
@@ -45,7 +45,7 @@ struct Options {
     size_t block = 16u << 20;
 };
 
-double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+using hast::now_s;
 
 int usage() {
     fprintf(stderr, "usage: fake_10x READ1.gz READ2.gz MERGE.txt [--inflate host|zlib|device] [--block-mb N] [--plain-out] [--stats]\n"
@@ -141,11 +141,11 @@ struct Writer {
                 if (!have) return;
                 const Job j = job;
                 lk.unlock();
-                const double t0 = now();
+                const double t0 = now_s();
                 const bool good = j.deflate ? out->write_host(side, j.p, j.n) : out->write(side, j.p, j.n);
                 if (j.free_me) hast_tx_free(j.free_me);
                 lk.lock();
-                busy += now() - t0;
+                busy += now_s() - t0;
                 ok = ok && good;
                 have = false;
                 cv.notify_all();
@@ -534,7 +534,7 @@ int main(int argc, char **argv) {
         fprintf(stderr, "fake_10x: cannot create the outputs in the working directory\n");
         return 3;
     }
-    const double t0 = now();
+    const double t0 = now_s();
     if (r.tx)
         for (int s = 0; s < 2; ++s) r.writer[s].start(&r.out, s);
     int rc = r.feed ? run_feed(r) : run(r);
@@ -562,7 +562,7 @@ int main(int argc, char **argv) {
         fprintf(stderr, "[stats] transform device: steps=%llu pairs_on_device=%llu pairs_on_host=%llu fallback=%s\n", (unsigned long long)r.steps,
                 (unsigned long long)r.pairs_device, (unsigned long long)r.pairs_host, r.fallback.c_str());
         fprintf(stderr, "[stats] seconds: upload=%.3f kernels=%.3f deflate=%.3f download=%.3f write=%.3f read_phase=%.3f plain_in_bytes=%llu out_bytes=%llu+%llu\n",
-                r.times.upload_s, r.times.kernel_s, r.times.deflate_s, r.times.download_s, r.write_s, now() - t0, (unsigned long long)r.plain_in,
+                r.times.upload_s, r.times.kernel_s, r.times.deflate_s, r.times.download_s, r.write_s, now_s() - t0, (unsigned long long)r.plain_in,
                 (unsigned long long)r.out.bytes[0], (unsigned long long)r.out.bytes[1]);
         if (r.o.inflate == "device")
             fprintf(stderr, "[stats] ingest device: gz_on_device=%d host_sides=%d steps_on_host=%llu collect_wait=%.3f fallback=%s\n", r.gz_on_device, r.host_sides,
@@ -570,7 +570,7 @@ int main(int argc, char **argv) {
     } else if (r.o.stats) {
         fprintf(stderr, "[stats] transform host: steps=%llu pairs_on_device=0 pairs_on_host=%llu fallback=none\n", (unsigned long long)r.steps,
                 (unsigned long long)r.st.headers);
-        fprintf(stderr, "[stats] seconds: read_phase=%.3f plain_in_bytes=%llu out_bytes=%llu+%llu\n", now() - t0, (unsigned long long)r.plain_in,
+        fprintf(stderr, "[stats] seconds: read_phase=%.3f plain_in_bytes=%llu out_bytes=%llu+%llu\n", now_s() - t0, (unsigned long long)r.plain_in,
                 (unsigned long long)r.out.bytes[0], (unsigned long long)r.out.bytes[1]);
     }
     return 0;

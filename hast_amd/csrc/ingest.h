@@ -426,4 +426,65 @@ class BlockSource {
     bool eof_ = false, stop_ = false;
 };
 
+// work area of a host parser over one block source: what the last area left unparsed (the carry) in front of the next block's bytes, and
+// the positions of its newlines.  Per area: next(), index(), then keep(consumed) unless it was the last one.
+class BlockWork {
+  public:
+    const char *data = nullptr;                    // the area [data, data + len)
+    size_t len = 0;
+    bool last = false;                             // the input is over and the area is the carry alone
+    std::vector<uint32_t> nl;                      // index(): the offsets of every '\n' of the area, ascending (len < 4 GB is the caller's check)
+
+    // false: the source failed (src.error()).  Source: BlockSource, or what has its next(), error(), recycle()
+    template <class Source>
+    bool next(Source &src) {
+        blk_ = src.next();
+        last = blk_.empty();
+        if (last && !src.error().empty()) return false;
+        constexpr size_t kPad = BlockSource::kFrontPad;
+        if (last) {
+            data = carry_.data();
+            len = carry_.size();
+        } else if (carry_.size() <= kPad) {
+            if (!carry_.empty()) memcpy(blk_.data() + kPad - carry_.size(), carry_.data(), carry_.size());   // in front, no block copy
+            data = blk_.data() + kPad - carry_.size();
+            len = blk_.size() - kPad + carry_.size();
+        } else {                                                                     // giant record: slow path
+            carry_.insert(carry_.end(), blk_.begin() + kPad, blk_.end());
+            data = carry_.data();
+            len = carry_.size();
+        }
+        return true;
+    }
+    // every worker indexes its share of the area, the shares' lists are then copied into one, side by side as well
+    void index(WorkerPool &pool) {
+        const int T = pool.size();
+        part_.resize((size_t)T);
+        pool.run([&](int t) {
+            auto &v = part_[t];
+            v.clear();
+            const char *p = data + len * (size_t)t / T, *e = data + len * (size_t)(t + 1) / T;
+            while (p < e && (p = (const char *)memchr(p, '\n', (size_t)(e - p)))) {
+                v.push_back((uint32_t)(p - data));
+                ++p;
+            }
+        });
+        std::vector<size_t> cum(T + 1, 0);
+        for (int t = 0; t < T; t++) cum[t + 1] = cum[t] + part_[t].size();
+        nl.resize(cum[T]);
+        pool.run([&](int t) { if (!part_[t].empty()) memcpy(nl.data() + cum[t], part_[t].data(), part_[t].size() * 4); });
+    }
+    // [consumed, len) is the next area's front; the block goes back to the source
+    template <class Source>
+    void keep(Source &src, size_t consumed) {
+        std::vector<char> rest(data + consumed, data + len);
+        carry_.swap(rest);
+        src.recycle(std::move(blk_));
+    }
+
+  private:
+    std::vector<char> carry_, blk_;
+    std::vector<std::vector<uint32_t>> part_;
+};
+
 }  // namespace hast

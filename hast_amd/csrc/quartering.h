@@ -150,8 +150,6 @@ int route(const std::string &prefix, const ClassMap &cls_of, Source &src, const 
     FILE *out[4] = {nullptr, nullptr, nullptr, nullptr};
     long long counts[5] = {0, 0, 0, 0, 0};                         // no, pa, ma, ho, total
     bool any_input = false;
-    std::vector<std::vector<uint32_t>> nl(T);
-    std::vector<uint32_t> allnl;
     struct Local {
         std::string buf[4], err, zbuf;
         long long n[4] = {0, 0, 0, 0};
@@ -208,38 +206,19 @@ int route(const std::string &prefix, const ClassMap &cls_of, Source &src, const 
             }
         }
     };
-    std::vector<char> carry;
+    hast::BlockWork work;                                          // (carry + block, newline index: ingest.h)
     for (;;) {
-        std::vector<char> blk = src.next();
-        const bool last = blk.empty();
-        if (last && !src.error().empty()) {
+        if (!work.next(src)) {
             fprintf(stderr, "%s: %s\n", who, src.error().c_str());
             for (FILE *f : out) if (f) fclose(f);
             return 2;
         }
-        constexpr size_t kPad = hast::BlockSource::kFrontPad;
-        const char *data;
-        size_t len;
-        if (last) { data = carry.data(); len = carry.size(); }
-        else if (carry.size() <= kPad) {
-            if (!carry.empty()) memcpy(blk.data() + kPad - carry.size(), carry.data(), carry.size());
-            data = blk.data() + kPad - carry.size();
-            len = blk.size() - kPad + carry.size();
-        } else {
-            carry.insert(carry.end(), blk.begin() + kPad, blk.end());
-            data = carry.data();
-            len = carry.size();
-        }
+        const char *data = work.data;
+        const size_t len = work.len;
         if (len) any_input = true;
         if (len >= (1ull << 32)) { fprintf(stderr, "%s: record larger than 4 GB\n", who); return 3; }
-        pool.run([&](int t) {
-            auto &v = nl[t];
-            v.clear();
-            const char *p = data + len * (size_t)t / T, *e = data + len * (size_t)(t + 1) / T;
-            while (p < e && (p = (const char *)memchr(p, '\n', (size_t)(e - p)))) { v.push_back((uint32_t)(p - data)); ++p; }
-        });
-        allnl.clear();
-        for (int t = 0; t < T; t++) allnl.insert(allnl.end(), nl[t].begin(), nl[t].end());
+        work.index(pool);
+        const std::vector<uint32_t> &allnl = work.nl;
         const size_t n_rec = allnl.size() / 4;
         pool.run([&](int t) {
             Local &L = loc[t];
@@ -257,7 +236,7 @@ int route(const std::string &prefix, const ClassMap &cls_of, Source &src, const 
         emit();
         if (write_failed) break;
         const size_t consumed = n_rec ? (size_t)allnl[4 * n_rec - 1] + 1 : 0;
-        if (last) {
+        if (work.last) {
             // trailing partial record: awk still treats every remaining line (terminated or not) as a record (:21,41-49)
             std::string_view rest(data + consumed, len - consumed);
             if (!rest.empty()) {
@@ -276,9 +255,7 @@ int route(const std::string &prefix, const ClassMap &cls_of, Source &src, const 
             }
             break;
         }
-        std::vector<char> keep(data + consumed, data + len);
-        carry.swap(keep);
-        src.recycle(std::move(blk));
+        work.keep(src, consumed);
     }
     for (FILE *f : out) {
         if (!f) continue;

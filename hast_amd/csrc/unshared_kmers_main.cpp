@@ -21,7 +21,6 @@
 // the device framer's), which share the job list, the worker threads and the folding of their results, and one sweep over the inputs.
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -35,12 +34,14 @@
 #include <unistd.h>
 
 #include "../../include/hast.h"
+#include "cli_common.h"
 #include "ingest.h"
+#include "raw_blocks.h"
 #include "seqstream.h"
 
 namespace {
 
-double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+using hast::now_s;
 
 void usage(FILE *f) {
     fputs("Usage: unshared_kmers [options]\n"
@@ -65,7 +66,7 @@ void usage(FILE *f) {
 
 const char *const kParentName[2] = {"paternal", "maternal"};
 
-bool ends_gz(const std::string &s) { return s.size() >= 3 && s.compare(s.size() - 3, 3, ".gz") == 0; }   // s00:169
+bool ends_gz(const std::string &s) { return hast::ends_gz(s, 0); }   // s00:169: the last three bytes alone
 
 struct Options {
     long mer = 21, cpu = 8, memory = 10, lower[2] = {9, 9}, upper[2] = {33, 33};     // s00:44-55; [0] paternal, [1] maternal
@@ -317,7 +318,7 @@ struct DeviceIngest {
 };
 
 // One job on its way through the framer.  At most one block is ahead of the framer (submit), every block a file has submitted is framed
-// before its decoder is closed (from_gz_on_device), and the tail goes to the parser only at the end of an input (end_of_input).
+// before its decoder is closed (file), and the tail goes to the parser only at the end of an input (end_of_input).
 // Locks: hast_sq_feed_create, _next, _take_tail and _destroy are called under the table's mutex (dev_mu[0], which hast_kc_count inside
 // ChunkSink::flush holds too: "the caller serialises it with the table's other users", include/hast.h); hast_sq_feed_submit,
 // _device_block, _host_block and hast_gz_open / _read_device / _close are called without it, so that one parent's thread reads, inflates
@@ -396,70 +397,37 @@ struct DeviceStream {
         sink.flush(true);
         return true;
     }
-    uint8_t *host_block() {          // the pinned block the next upload is written to
-        uint8_t *h = nullptr;
-        return ck(hast_sq_feed_host_block(feed, &h)) ? h : nullptr;
-    }
-
-    void from_gz_on_device(hast_gz *z) {
-        ++gz_dev;
-        while (good()) {
-            uint8_t *d = nullptr;
+    // one file's bytes (raw_blocks.h) into the feed's blocks; the block asked for last stays unsubmitted
+    void file(const std::string &path) {
+        hast::RawBlocks raw;
+        std::string err;
+        if (!raw.open(path, job.gz, gpu.gz_ctx, di.block, &res.error)) return;
+        const bool dev = raw.kind() == hast::RawBlocks::gz_on_device;
+        gz_dev += dev;
+        for (bool first = raw.kind() == hast::RawBlocks::plain; good(); first = false) {
+            uint8_t *b = nullptr;
             size_t n = 0;
-            if (!ck(hast_sq_feed_device_block(feed, &d))) break;
-            if (hast_gz_read_device(z, d, di.block, &n, hast_kc_stream(gpu.kc)) != HAST_OK) {
-                di.refuse("hast_gz: " + std::string(hast_last_error()));
+            if (!ck(dev ? hast_sq_feed_device_block(feed, &b) : hast_sq_feed_host_block(feed, &b))) break;
+            if (!(dev ? raw.read_device(b, hast_kc_stream(gpu.kc), &n) : raw.read_host(b, &n, &err))) {
+                if (dev) di.refuse("hast_gz: " + std::string(hast_last_error()));
+                else if (raw.kind() == hast::RawBlocks::gz_on_host) res.error = path + ": " + err;
+                break;                               // (a plain file that cannot be read on ends there)
+            }
+            if (n == 0) break;                       // (only a read that returns nothing ends the stream, include/hast.h)
+            if (first && b[0] != '@' && !(di.fasta && b[0] == '>')) {
+                di.refuse(b[0] == '>' ? path + " is FASTA" : path + " does not start with '@'");
                 break;
             }
-            if (n == 0) break;               // (only a call that returns nothing ends the stream, include/hast.h)
             if (!submit(n)) break;
         }
-        while (pending && good())            // before the decoder goes: its kernels wrote the blocks still waiting
+        while (dev && pending && good())             // before the decoder goes: its kernels wrote the blocks still waiting
             if (!step()) break;
-        hast_gz_close(z);
-    }
-    bool upload(const char *p, size_t n) {   // inflated on the host: through the pinned block, a feed's block at a time
-        for (size_t at = 0; at < n && good(); at += di.block) {
-            uint8_t *h = host_block();
-            if (!h) break;
-            const size_t take = std::min(di.block, n - at);
-            memcpy(h, p + at, take);
-            if (!submit(take)) break;
-        }
-        return good();
-    }
-    void from_gz_on_host(const std::string &path) {
-        for_each_block(path, di.block, res.error, [&](const char *p, size_t n) { return upload(p, n); });
-    }
-    void from_plain_file(const std::string &path) {   // read into the pinned block
-        FILE *fp = fopen(path.c_str(), "rb");
-        if (!fp) {
-            res.error = "cannot open " + path;
-            return;
-        }
-        for (bool first = true; good(); first = false) {
-            uint8_t *h = host_block();
-            if (!h) break;
-            const size_t n = fread(h, 1, di.block, fp);
-            if (n == 0) break;
-            if (first && h[0] != '@' && !(di.fasta && h[0] == '>')) {
-                di.refuse(h[0] == '>' ? path + " is FASTA" : path + " does not start with '@'");
-                break;
-            }
-            if (!submit(n)) break;
-        }
-        fclose(fp);
     }
 
     void run() {
         for (size_t i = 0; i < job.paths.size() && good(); ++i) {
-            const std::string &path = job.paths[i];
-            hast_gz *z = nullptr;
-            if (job.gz && gpu.gz_ctx && hast_gz_open(gpu.gz_ctx, path.c_str(), &z) != HAST_OK) z = nullptr;   // (not for the GPU, or not readable: BlockSource's words)
-            if (z) from_gz_on_device(z);
-            else if (job.gz) from_gz_on_host(path);
-            else from_plain_file(path);
-            if (good() && (!job.one_stream || i + 1 == job.paths.size())) end_of_input(path);
+            file(job.paths[i]);
+            if (good() && (!job.one_stream || i + 1 == job.paths.size())) end_of_input(job.paths[i]);
         }
         {
             std::lock_guard<std::mutex> g(table_mu);
@@ -741,9 +709,9 @@ Sweep sweep(Run &r, bool take_histo, bool take_sets) {
         for (long d = 0; d < n_dev; ++d)
             if (hast_kc_set_slice(gpu.all[d], (uint32_t)(s * n_dev + d), (uint32_t)(r.slices * n_dev)) != HAST_OK) return Sweep::GpuError;
         std::string err;
-        const double t_in = now();
+        const double t_in = now_s();
         const Sweep in = ingest(r, err);
-        r.t_ingest += now() - t_in;
+        r.t_ingest += now_s() - t_in;
         if (in == Sweep::InputError) {
             // A count the table refused leaves gpu.error, and then the tables decide: one of them full is a reason to start over,
             // whatever an input said meanwhile; anything else of the GPU's goes to stderr, an input's error to stdout.
@@ -905,20 +873,20 @@ int main(int argc, char **argv) {
     if (!parse_command_line(argc, argv, r.o, status)) return leave(r, status);
     if (!check_arguments(r.o)) return leave(r, 1);
     r.slices = r.o.slices;
-    r.t_start = now();
+    r.t_start = now_s();
     estimate_windows_and_size_table(r);
     if ((status = create_tables(r))) return leave(r, status);
     set_up_device_ingest(r);
-    r.t_table = now();
+    r.t_table = now_s();
     if ((status = count_and_select(r))) return leave(r, status);
-    r.t_count = now();
+    r.t_count = now_s();
     printf("bounds used for maternal: [%ld, %ld]\n", r.o.lower[1], r.o.upper[1]);   // s00:254-255
     printf("bounds used for paternal: [%ld, %ld]\n", r.o.lower[0], r.o.upper[0]);
     if ((status = sort_and_write_mer_files(r))) return leave(r, status);
     if ((status = save_table(r))) return leave(r, status);
     printf("paternal-unique k-mers kept: %zu (paternal.unique.filter.mer)\n", r.n_sel[0]);      // s00:300-303 (wc -l of the products)
     printf("maternal-unique k-mers kept: %zu (maternal.unique.filter.mer)\n", r.n_sel[1]);
-    r.t_end = now();
+    r.t_end = now_s();
     if (r.o.stats) print_stats(r);
     return leave(r, 0);
 }

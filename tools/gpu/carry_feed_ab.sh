@@ -1,10 +1,14 @@
 # The device ingests of another commit's build (OLD=dir with its libhast.so and programs, built by hand, not committed) against this
-# tree's, on one box, alternating, PAUSE s apart: every route that goes through carry_feed.h or the encoder slot of dz_device.h.
+# tree's, on one box, alternating, PAUSE s apart: every route that goes through carry_feed.h or the encoder slot of dz_device.h, and the
+# host routes over the work area of ingest.h (BlockWork).
 #   s00_fq / s00_fq_gz / s00_fa60   unshared_kmers --ingest device (hast_sq_feed; the inputs of tools/gpu/s00_ingest.sh and s00_ingest_fasta.sh)
 #   s03_fq / s03_fq_bins_gz / s03_fa_bins_gz   classify_read --ingest device, without bins and with --bin-reads --gz-out (hast_rs; the
 #                                   long reads of tools/gpu/classify_read_device.sh and classify_read_bins.sh)
 #   route_gz                        classify --phase-reads --gz-out (hast_fq_set_route_gz; the sample of tools/gpu/route_gz.sh)
 #   fake10x_feed                    fake_10x --convert device --inflate device (hast_tx_feed; the sample of tools/gpu/fake10x_feed.sh)
+#   s03_fq_host                     classify_read --ingest host on the same long reads
+#   s01_host_parse                  classify --host-parse on the routed-pairs sample
+# LEGS="a b ..." runs only those legs (default: all of them).
 # Per run: whole-process seconds, the phase's seconds as the program's --stats give them, the md5 of what it wrote (.gz files through
 # gzip -dc).  Every run has its own time limit and the job ends at the first run that fails or whose products differ from the
 # other build's.  At the end, per leg: both builds' means, OLD's spread (max - min) over its runs, and whether this tree's mean lies
@@ -18,6 +22,8 @@ ROOT=$PWD
 OLD=$(cd $OLD && pwd)
 GENOME=${GENOME:-20000000}; COVERAGE=${COVERAGE:-20}; NLONG=${NLONG:-5000}; KEYS=${KEYS:-2000000}; NPAIRS=${NPAIRS:-2000000}; TXPAIRS=${TXPAIRS:-1000000}
 BARCODES=${BARCODES:-200000}; RUNS=${RUNS:-3}; PAUSE=${PAUSE:-3}
+LEGS=${LEGS:-s00_fq s00_fq_gz s00_fa60 s03_fq s03_fq_bins_gz s03_fa_bins_gz route_gz fake10x_feed s03_fq_host s01_host_parse}
+wanted() { case " $LEGS " in *" $1 "*) return 0;; esac; return 1; }
 D=$(mktemp -d /dev/shm/hast_cfab.XXXXXX) || exit 1
 ( while sleep 45; do echo "[still running $(date +%T)]"; done ) &
 HB=$!
@@ -34,8 +40,11 @@ mkdir -p $D/long && tools/gen_fastq $D/long $NLONG $KEYS 1 31 20000 16 > /dev/nu
 rm -f $D/long/r2.fq
 awk 'NR%4==1{print ">" substr($0,2)} NR%4==2{print}' $D/long/r1.fq | fold -w 60 > $D/long/r1.fa || exit 1
 mkdir -p $D/pairs && tools/gen_fastq $D/pairs $NPAIRS $KEYS $BARCODES 21 150 16 0 > /dev/null || exit 1
-mkdir -p $D/tx && tools/gen_fastq $D/tx $TXPAIRS 1000 $BARCODES 21 150 16 0 > /dev/null || exit 1
+mkdir -p $D/tx
+if wanted fake10x_feed; then
+tools/gen_fastq $D/tx $TXPAIRS 1000 $BARCODES 21 150 16 0 > /dev/null || exit 1
 gzip $D/tx/r1.fq & Z1=$!; gzip $D/tx/r2.fq & Z2=$!; wait $Z1 $Z2 || exit 1
+fi
 python3 - $BARCODES > $D/tx/map.txt <<'EOF'
 import sys
 for i in range(int(sys.argv[1])):
@@ -59,6 +68,7 @@ run() { local leg=$1 build=$2 phase=$3; shift 3
   sleep $PAUSE; return 0; }
 # one leg: $1 = name, $2 = program, $3 = phase expression, the rest = its arguments
 leg() { local name=$1 exe=$2 phase=$3; shift 3
+  wanted $name || return 0
   for i in $(seq 1 $RUNS); do
     run $name old "$phase" $OLD/$exe "$@" || exit 1; local m=$MD5
     run $name new "$phase" $ROOT/hast_amd/$exe "$@" || exit 1
@@ -67,6 +77,7 @@ leg() { local name=$1 exe=$2 phase=$3; shift 3
 S00='s/.*read+parse+count \([0-9.]*\) s.*/\1/p'
 S03='s/.*read_phase=\([0-9.]*\).*/\1/p'
 RGZ='s/.*lists_and_routing_s=\([0-9.]*\).*/\1/p'
+S01='s/.* read_phase_s=\([0-9.]*\).*/\1/p'
 T=$D/trio; L=$D/long; P=$D/pairs
 {
 leg s00_fq unshared_kmers "$S00" --paternal $T/paternal_0.fq --maternal $T/maternal_0.fq --thread 8 --table-gb 48 --stats --ingest device
@@ -77,6 +88,8 @@ leg s03_fq_bins_gz classify_read "$S03" --hap $L/hap0.mer --hap $L/hap1.mer --re
 leg s03_fa_bins_gz classify_read "$S03" --hap $L/hap0.mer --hap $L/hap1.mer --read $L/r1.fa --format fasta --thread 16 --ingest device --stats --bin-reads --gz-out --bin-dir .
 leg route_gz classify "$RGZ" --hap0 $P/hap0.mer --hap1 $P/hap1.mer --weight0 1.04 -t 16 --stats --phase-reads --read $P/r1.fq --read $P/r2.fq --gz-out
 leg fake10x_feed fake_10x "$S03" $D/tx/r1.fq.gz $D/tx/r2.fq.gz $D/tx/map.txt --stats --convert device --inflate device
+leg s03_fq_host classify_read "$S03" --hap $L/hap0.mer --hap $L/hap1.mer --read $L/r1.fq --format fastq --thread 16 --ingest host --stats
+leg s01_host_parse classify "$S01" --hap0 $P/hap0.mer --hap1 $P/hap1.mer --weight0 1.04 -t 16 --stats --host-parse --read $P/r1.fq --read $P/r2.fq
 } | tee $D/log.txt
 [ ${PIPESTATUS[0]} -eq 0 ] || exit 1
 python3 - $D/log.txt <<'EOF'
