@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/hast.h"
+#include "classify_plan.h"
 #include "hast_common.h"
 #include "hast_device.h"
 #include "kc_device.h"
@@ -1102,8 +1103,8 @@ static hast_status ensure_filter(hast_ctx *c, hipStream_t hs) {
     return HAST_OK;
 }
 
-static constexpr uint32_t kSegWindows = 482;     // + K-1 <= 513 bases per segment row for K <= 32
-static constexpr uint32_t kLongRead = 4096;      // longer reads go through the segmented path: a row's positions must fit the 12 bits tmer_order gives them
+using classify::kLongRead;        // (classify_plan.h)
+using classify::kSegWindows;
 
 // Per-barcode bookkeeping of n_reads (vote0, vote1) pairs: one atomic per read, or -- large batches over many barcodes -- the pairs
 // partitioned by barcode range and summed in LDS (hast_kernels.hip, "partitioned commit"; hast_ctx_set_option "commit" / HAST_COMMIT
@@ -1170,7 +1171,7 @@ static hast_status classify_rows(hast_ctx *c, const uint8_t *d_bases, size_t bas
     // the caller the votes go to library scratch.
     if (reinterpret_cast<uintptr_t>(d_votes) & 7) return set_error(HAST_ERR_INVALID, "d_votes must be 8-byte aligned (a row is stored as one 64-bit word)");
     hipStream_t hs = s ? (hipStream_t)s : c->stream;
-    const uint32_t max_pos = read_len >= (uint32_t)c->k ? read_len - c->k + 1 : 0;
+    const uint32_t max_pos = read_len >= (uint32_t)c->k ? read_len - c->k + 1 : 0;      // the most votes a row can have
     // How the votes will be committed is decided here, in front of the probe launch: whatever scratch has to grow does so before
     // the first kernel, never between the two.  When the partitioned commit is the rows' only reader (ids given, no buffer of the
     // caller's, rows are reads) they cross HBM as the 8 + 8 bits it keeps of them: max_pos <= 255 is commit::usable's condition.
@@ -1202,65 +1203,29 @@ static hast_status classify_rows(hast_ctx *c, const uint8_t *d_bases, size_t bas
     a.k = c->k;
     a.wide = c->k == 32;
     a.m = c->m;
-    a.max_pos = max_pos;
-    a.mh_stride = read_len >= (uint32_t)c->m ? read_len - c->m + 1 : 0;
-    a.w64 = (read_len + 31) / 32;
-    // Reads per tile: at most what fits the LDS budget of a workgroup and at most 64; among the
-    // candidates take the one whose windows fill the waves' 64-window blocks best (a workgroup walks
-    // 4 waves x 2 blocks per iteration: 150-bp reads => 31 reads = 4030 windows = 63 of 64 block slots).
     if (c->use_filter)
         if (hast_status st = ensure_filter(c, hs)) return st;        // (may switch the filter off when HBM is short)
     const bool filt = c->use_filter;
-    size_t per_read, pad;
-    if (filt) {
-        a.filter = c->d_filter;
-        a.fg = c->fg;
-        // (a dense filter is probed on a fixed grid: no first-level minima, a read costs its packed bases and header only)
-        a.l1_stride = c->fg.dense ? 0 : ((read_len >= (uint32_t)c->fg.t ? read_len - (uint32_t)c->fg.t + 1 : 0) + 1 + 3) & ~3u;
-        per_read = (size_t)(a.w64 + 1) * 8 + 8 + 8 + 4 + 4 + (size_t)a.l1_stride * 4 + (strict ? (size_t)(2 * a.w64 + 1) * 4 : 0);
-        pad = 16 + classify_f_queue_bytes() + 64 * 4 + 64;
-    } else {
-        // The m-mer hash array is padded by W entries so window-min reads past a read's last window stay in bounds.
-        const uint32_t wlen = (uint32_t)(c->k - c->m + 1);
-        a.filter = nullptr;
-        a.fg = FilterGeom{};
-        a.l1_stride = 0;
-        per_read = (size_t)(a.w64 + 1) * 8 + 8 + 8 + 4 + 4 + (size_t)a.mh_stride * 4 + (strict ? (size_t)(2 * a.w64 + 1) * 4 : 0);
-        pad = (size_t)wlen * 4 + 64 + 64 + 16;
-    }
-    // 5 / 8 workgroups per CU; k_classify_f's static 2 KB (the t-mer level table) comes off its share (150-bp reads: 35 reads
-    // per tile, 31768 B in all, as with the 1-KB class table before it)
-    const size_t lds_budget = c->tile_lds ? c->tile_lds : (filt ? (size_t)32000 - (size_t)kTmerLevelTableWords * 4 : (size_t)19968);
-    const uint32_t tr_max = (uint32_t)std::min<size_t>(64, std::max<size_t>(1, lds_budget > pad + per_read ? (lds_budget - pad) / per_read : 1));
-    uint32_t tr = tr_max;
-    if (a.max_pos > 0) {
-        double best = -1;
-        for (uint32_t t = tr_max; t >= 1 && t + 8 > tr_max; --t) {
-            const uint64_t q = (uint64_t)t * a.max_pos, blocks = (q + 63) / 64, slots = filt ? (blocks + 3) / 4 * 4 : (blocks + 7) / 8 * 8;
-            const double eff = (double)q / (double)(slots * 64);
-            if (eff > best + 1e-9) { best = eff; tr = t; }
-        }
-    }
-    a.tile_reads = tr;
-    const size_t smem = per_read * tr + pad;
-    if (smem + (filt ? (size_t)kTmerLevelTableWords * 4 : 0) > (160u << 10)) return set_error(HAST_ERR_INVALID, "read_len %u needs %zu B of LDS", read_len, smem);
-    // __umulhi(q, magic) == q / d for every q the kernel forms (exact while q*d < 2^32)
-    auto magic = [](uint64_t qmax, uint32_t d) -> uint32_t {
-        if (d <= 1 || qmax * d >= (1ull << 32)) return 0;
-        return (uint32_t)((1ull << 32) / d) + 1;
-    };
-    a.div_magic = magic((uint64_t)tr * a.max_pos + 1024, a.max_pos);
-    a.div_mh = magic((uint64_t)tr * a.mh_stride + 1024, a.mh_stride);
-    a.div_hw = magic((uint64_t)tr * a.w64 * 2 + 1024, a.w64 * 2);
-    a.div_l1g = magic((uint64_t)tr * (a.l1_stride / 4) + 1024, a.l1_stride / 4);
-    const uint64_t n_tiles = (n_reads + tr - 1) / tr;
-    const int grid = (int)std::min<uint64_t>(n_tiles, (uint64_t)c->n_cu * 8);
+    a.filter = filt ? c->d_filter : nullptr;
+    a.fg = filt ? c->fg : FilterGeom{};
+    // the row shape, the tile and its LDS, the divisors and the grid: classify_plan.h
+    const classify::Plan p = classify::plan_for(c->k, c->m, read_len, strict != 0, filt, a.fg, c->tile_lds, c->n_cu, n_reads);
+    if (!p.fits) return set_error(HAST_ERR_INVALID, "read_len %u needs %zu B of LDS", read_len, p.smem);
+    a.max_pos = p.max_pos;
+    a.mh_stride = p.mh_stride;
+    a.w64 = p.w64;
+    a.l1_stride = p.l1_stride;
+    a.tile_reads = p.tile_reads;
+    a.div_magic = p.div_magic;
+    a.div_mh = p.div_mh;
+    a.div_hw = p.div_hw;
+    a.div_l1g = p.div_l1g;
     a.tile_queue = c->d_cnt + 3;
     a.lookups = (filt && c->count_lookups) ? c->d_cnt + 5 : nullptr;
     HAST_HIP_TRY(hipMemsetAsync(a.tile_queue, 0, sizeof(unsigned long long), hs));
     hipEvent_t *ev = c->t_slots ? &c->t_ev[3 * (c->t_next % c->t_slots)] : nullptr;
     if (ev) HAST_HIP_TRY(hipEventRecord(ev[0], hs));
-    HAST_HIP_TRY(filt ? launch_classify_f(a, grid, smem, (c->kernel_geo ? 1 : 0) | (c->kernel_rl ? 2 : 0), hs) : launch_classify(a, grid, smem, hs));
+    HAST_HIP_TRY(filt ? launch_classify_f(a, p.grid, p.smem, (c->kernel_geo ? 1 : 0) | (c->kernel_rl ? 2 : 0), hs) : launch_classify(a, p.grid, p.smem, hs));
     if (ev) HAST_HIP_TRY(hipEventRecord(ev[1], hs));
     if (d_barcode_ids) {
         // per-barcode bookkeeping: one atomic per read, or -- large batches over many barcodes -- the pairs partitioned by barcode

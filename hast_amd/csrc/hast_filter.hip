@@ -7,6 +7,7 @@
 // are exactly those of hast_kernels.hip:
 //   classify.cpp:182-209 (containN + process_reads), kmer/kmer.h:11,153-166,169-194 (coding, canonical k-mers).
 #include "hast_common.h"
+#include "classify_tile.h"
 #include "hast_device.h"
 #include "hast_devutil.h"
 
@@ -138,7 +139,6 @@ hipError_t launch_filter_build(const uint64_t *slots, TableGeom tg, void *filter
 //   C  votes  : one lane per read stores {vote0, vote1}; k_commit_votes does the per-barcode bookkeeping.
 // ------------------------------------------------------------------------------------------
 constexpr int kThreadsF = 256;
-constexpr int kQCap = 128;                                    // queue entries per wave: < 64 waiting + <= 64 new
 #ifndef HAST_F_MINWAVES
 #define HAST_F_MINWAVES 5      // 96 VGPRs: measured best of 4/5/6/8 (242 vs 226-228 Gbp/s with prints; exact entries: 4, 5, 6 within 1.5 %)
 #endif
@@ -148,8 +148,6 @@ constexpr int kQCap = 128;                                    // queue entries p
 typedef unsigned long long u64x2f __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4f __attribute__((ext_vector_type(4)));
 typedef unsigned short u16x2f __attribute__((ext_vector_type(2)));
-
-size_t classify_f_queue_bytes() { return (size_t)4 * kQCap * 3 * sizeof(uint32_t); }
 
 __device__ __forceinline__ uint32_t pk_min_u16(uint32_t a, uint32_t b) {
     const u16x2f r = __builtin_elementwise_min(__builtin_bit_cast(u16x2f, a), __builtin_bit_cast(u16x2f, b));
@@ -199,18 +197,21 @@ __global__ void __launch_bounds__(kThreadsF, DENSE ? HAST_F_MINWAVES_DENSE : HAS
     const uint32_t TR = a.tile_reads;
     const uint32_t W64 = RLC ? (uint32_t)((RL + 31) / 32) : a.w64;
     const uint32_t WS = W64 + 1;                                     // LDS words per read incl. pad
-    const uint32_t L1S = DENSE ? 0u : RLC ? (uint32_t)((RL - GC0::t + 1 + 1 + 3) & ~3) : a.l1_stride;   // (DENSE: no first-level minima)
-    unsigned long long *s_tile = reinterpret_cast<unsigned long long *>(smem);            // next tile of this workgroup
+    const uint32_t L1S = RLC ? l1_stride_for(RL, GC0::t, DENSE) : DENSE ? 0u : a.l1_stride;            // (DENSE: no first-level minima)
+    const FilterTile L{TR, W64, L1S, STRICT};                                              // where everything lies: classify_tile.h
+    // (only the first pointer is an offset of the layout's; the others are stepped from it by its extents, array by array in its
+    // order: with every pointer formed as smem + offset most instantiations spilled other scalar registers, profiles/classify_tile_ab.txt)
+    unsigned long long *s_tile = reinterpret_cast<unsigned long long *>(smem + L.tile_at());   // next tile of this workgroup
     uint32_t *s_dirty = reinterpret_cast<uint32_t *>(s_tile + 1);                          // STRICT: some row of the tile holds a byte outside ACGT
-    uint32_t *s_l1 = reinterpret_cast<uint32_t *>(s_tile + 2);                             // [TR][L1S] (+ 64 pad), 16-B aligned rows
-    unsigned long long *s_pack = reinterpret_cast<unsigned long long *>(s_l1 + (size_t)TR * L1S + 64);   // [TR][WS]
-    unsigned long long *s_vote = s_pack + (size_t)TR * WS;                                 // [TR]
+    uint32_t *s_l1 = reinterpret_cast<uint32_t *>(s_tile + kTileHeadBytes / 8);            // [TR][L1S], 16-B aligned rows
+    unsigned long long *s_pack = reinterpret_cast<unsigned long long *>(s_l1 + L.l1_words());   // [TR][WS]
+    unsigned long long *s_vote = s_pack + (size_t)TR * L.ws();                            // [TR]
     unsigned long long *s_off = s_vote + TR;                                               // [TR]
     uint32_t *s_len = reinterpret_cast<uint32_t *>(s_off + TR);                            // [TR]
     uint32_t *s_flag = s_len + TR;                                                         // [TR]
     uint32_t *s_q = s_flag + TR;                                                           // [4][3][kQCap]
     const uint32_t IW = 2 * W64 + 1;                                                       // invalid-byte mask words per read
-    uint32_t *s_inv = s_q + 4 * 3 * kQCap;                                                 // [TR][IW], STRICT only
+    uint32_t *s_inv = s_q + kQueueBytes / 4;                                               // [TR][IW], STRICT only
 
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & 63;
@@ -646,7 +647,7 @@ static hipError_t launch_f_t(const ClassifyArgs &a, int grid, size_t smem, hipSt
 // the row shape the host computed is the one a kernel with RL compiled in assumes
 static bool rows_are(const ClassifyArgs &a, uint32_t rl, int k, int t) {
     return a.read_len == rl && a.w64 == (rl + 31) / 32 && a.max_pos == rl - (uint32_t)k + 1 &&
-           a.l1_stride == (a.fg.dense ? 0u : ((rl - (uint32_t)t + 1 + 1 + 3) & ~3u));
+           a.l1_stride == l1_stride_for(rl, (uint32_t)t, a.fg.dense != 0);
 }
 static bool geo_is(const ClassifyArgs &a, int k, int m, int t, int kp) {
     return a.k == k && a.fg.k == k && a.fg.m == m && a.fg.t == t && a.fg.kp == kp && a.fg.g == 4;

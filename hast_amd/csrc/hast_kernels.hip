@@ -13,6 +13,7 @@
 //   classify.cpp:30-46 (load_kmers), :182-209 (containN + process_reads), :314-339 (InitAdaptor),
 //   kmer/kmer.h:11,153-166,169-194 (coding, str2Kmer, chopRead2Kmer).
 #include "hast_common.h"
+#include "classify_tile.h"
 #include "hast_device.h"
 #include "hast_devutil.h"
 
@@ -245,15 +246,17 @@ __global__ void __launch_bounds__(kThreads, HAST_MINWAVES) k_classify(ClassifyAr
     const uint32_t TR = a.tile_reads;
     const uint32_t WS = a.w64 + 1;                                   // LDS words per read incl. pad
     const uint32_t MS = a.mh_stride;                                 // m-mer positions per read (stride)
-    unsigned long long *s_tile = reinterpret_cast<unsigned long long *>(smem);            // next tile of this workgroup
-    unsigned long long *s_pack = s_tile + 2;                                               // [TR][WS]
-    unsigned long long *s_vote = s_pack + (size_t)TR * WS;                                 // [TR]
+    const ExactTile L{TR, a.w64, MS, STRICT};                                              // where everything lies: classify_tile.h
+    // (the first pointer is an offset of the layout's; the others are stepped from it by its extents, array by array in its order)
+    unsigned long long *s_tile = reinterpret_cast<unsigned long long *>(smem + L.tile_at());   // next tile of this workgroup
+    unsigned long long *s_pack = s_tile + kTileHeadBytes / 8;                              // [TR][WS]
+    unsigned long long *s_vote = s_pack + (size_t)TR * L.ws();                            // [TR]
     unsigned long long *s_off = s_vote + TR;                                               // [TR]
     uint32_t *s_len = reinterpret_cast<uint32_t *>(s_off + TR);                            // [TR]
     uint32_t *s_flag = s_len + TR;                                                         // [TR]
-    uint32_t *s_mh = s_flag + TR;                                                          // [TR][MS] (+ W pad)
+    uint32_t *s_mh = s_flag + TR;                                                          // [TR][MS]
     const uint32_t IW = 2 * a.w64 + 1;                                                     // invalid-byte mask words per read
-    uint32_t *s_inv = s_mh + (size_t)TR * MS + 16;                                         // [TR][IW], STRICT only
+    uint32_t *s_inv = s_mh + L.mh_words();                                                 // [TR][IW], STRICT only
 
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & 63;

@@ -145,6 +145,14 @@ __device__ __forceinline__ void kc_tile_pack(uintptr_t base_addr, uintptr_t end_
     }
 }
 
+// k_kc_count's tile (as kc_emit4_mh_at for k_kc_emit4): where s_mh ends and -- EMIT -- the tile's records begin, 16-byte aligned.  s_mh is
+// [tile_bases + w] and kKcCountPad entries more: the last wave-block of a tile looks up to 63 window starts past the tile (those lanes
+// are masked off afterwards)
+constexpr uint32_t kKcCountPad = 64;
+__host__ __device__ inline size_t kc_count_rec_at(uint32_t nw, uint32_t tile_bases, uint32_t w) {
+    return (16 + (size_t)nw * 8 + (size_t)nw * 4 + (size_t)(tile_bases + w + kKcCountPad) * 4 + 15) & ~(size_t)15;
+}
+
 // EMIT: instead of updating the table, write the windows out as records (a.rec_out; what finds no room there is counted on the spot)
 template <int WT, bool EMIT>
 __global__ void __launch_bounds__(kKcThreads) k_kc_count(KcCountArgs a) {
@@ -157,10 +165,10 @@ __global__ void __launch_bounds__(kKcThreads) k_kc_count(KcCountArgs a) {
     unsigned long long *s_tile = reinterpret_cast<unsigned long long *>(smem);
     unsigned long long *s_pack = s_tile + 2;                         // [NW]
     uint32_t *s_inv = reinterpret_cast<uint32_t *>(s_pack + NW);     // [NW] invalid-byte masks (bit 31 = first base)
-    uint32_t *s_mh = s_inv + NW;                                     // [TB + W] (+ 64: kc_count_smem)
+    uint32_t *s_mh = s_inv + NW;                                     // [TB + W] (+ kKcCountPad)
     // EMIT: the tile's records are gathered here and go out with ONE reservation per tile -- a reservation per wave step is 160 M
     // atomic adds on one word per 10 G windows, and adds to ONE address serialise at the memory side (measured: 10 x the kernel's time)
-    unsigned long long *s_rec = reinterpret_cast<unsigned long long *>(smem + ((16 + (size_t)NW * 8 + (size_t)NW * 4 + (size_t)(TB + W + 64) * 4 + 15) & ~(size_t)15));   // [RC]
+    unsigned long long *s_rec = reinterpret_cast<unsigned long long *>(smem + kc_count_rec_at(NW, TB, W));   // [RC]
     const uint32_t RC = TB / 2;
     __shared__ uint32_t s_nrec;
     // EMIT: a workgroup reserves room for its records a.rec_chunk at a time and fills the end of a chunk it cannot use (and of its
@@ -513,8 +521,7 @@ static hipError_t launch_kc_count_t(const KcCountArgs &a, unsigned grid, size_t 
 }
 size_t kc_count_smem(uint32_t tile_bases, int k, int m) {
     const uint32_t span = tile_bases + (uint32_t)k - 1, nw = (span + 31) / 32 + 2, w = (uint32_t)(k - m + 1);
-    // + 64 entries: the last wave-block of a tile looks up to 63 window starts past the tile (those lanes are masked off afterwards)
-    return 16 + (size_t)nw * 8 + (size_t)nw * 4 + (size_t)(tile_bases + w + 64) * 4 + 16;
+    return kc_count_rec_at(nw, tile_bases, w) + 16;
 }
 hipError_t launch_kc_count(const KcCountArgs &a, unsigned grid, hipStream_t s) {
     if (kc_emit4_takes(a)) {
