@@ -10,5 +10,5 @@ from .binding import (HastError, Context, SynthParams, lib, lib_path, classify_e
                       ABI_SYMBOLS, B_ALG_PER_READ, KmerCounter, SqFramer, SqFeed, SqResult, SQ_NOT_FOUR_LINE, SQ_NO_RECORD, SQ_TAIL_TOO_LONG, SQ_FA_OPEN, SQ_FA_LAST, SQ_TAKE_FASTQ, SQ_TAKE_FASTA, KcSynth, KC_HISTO_HIGH, kc_find_bounds, kc_synth_host,
                       unshared_kmers_exe, GzReader, GzStats, GzBlockedStats, dz_bound, dz_bound_blocked,
                       fake_10x_exe, TxMap, TxState, TxResult, TxMapInfo, TxConverter, TxTimes, TxFeed, TX_ON_HOST, TX_TAIL_TOO_LONG, TX_ENDS,
-                      barcode_freq_exe, Tally, FqTallied,
+                      barcode_freq_exe, Tally, FqTallied, Rows, RowsInfo,
                       ReadStream, RsBlock, RS_FASTA, RS_FASTQ, RS_FORMAT_ERROR, RS_RECORD_TOO_LONG)

@@ -85,6 +85,11 @@ class TxTimes(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("upload_s", "kernel_s", "deflate_s", "download_s")]
 
 
+class RowsInfo(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64), ("table_bytes", C.c_uint64), ("list_bytes", C.c_uint64 * 3), ("any_sep", C.c_int), ("past_int", C.c_int),
+                ("keys_s", C.c_double), ("sort_s", C.c_double), ("format_s", C.c_double)]
+
+
 SQ_NOT_FOUR_LINE, SQ_NO_RECORD, SQ_TAIL_TOO_LONG = 1, 2, 4
 SQ_FA_OPEN, SQ_FA_LAST = 1, 2
 SQ_TAKE_FASTQ, SQ_TAKE_FASTA = 1, 2
@@ -192,6 +197,13 @@ ABI_SYMBOLS = {
     "hast_dz_compress_device_ex": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_uint, vp]),
     "hast_dz_bound_blocked": (C.c_size_t, [C.c_size_t]),
     "hast_dz_compress_blocked_device": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), vp]),
+    "hast_rows_build_device": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_uint64, C.c_uint64, C.c_double, C.c_double, C.c_int, C.POINTER(vp)]),
+    "hast_rows_build": (C.c_int, [vp, vp, C.c_size_t, C.c_uint64, C.c_uint64, C.c_double, C.c_double, C.c_int, C.POINTER(vp)]),
+    "hast_rows_get_info": (C.c_int, [vp, C.POINTER(RowsInfo)]),
+    "hast_rows_read": (C.c_int, [vp, C.c_int, C.c_uint64, C.c_size_t, vp]),
+    "hast_rows_order": (C.c_int, [vp, C.POINTER(C.c_uint32)]),
+    "hast_rows_classes": (C.c_int, [vp, C.POINTER(C.c_uint8)]),
+    "hast_rows_destroy": (None, [vp]),
     "hast_gz_open": (C.c_int, [vp, C.c_char_p, C.POINTER(vp)]),
     "hast_gz_open_ex": (C.c_int, [vp, C.c_char_p, C.c_size_t, C.c_size_t, C.c_double, C.POINTER(vp)]),
     "hast_gz_open_multi": (C.c_int, [C.POINTER(vp), C.c_int, C.c_char_p, C.POINTER(vp)]),
@@ -676,6 +688,51 @@ def kc_synth_host(p: KcSynth, parent, first, n_reads):
     out = np.empty(n_reads * (p.read_len + 1), dtype=np.uint8)
     _ck(lib().hast_kc_synth_host(C.byref(p), parent, first, n_reads, _ptr(out)))
     return out
+
+
+class Rows:
+    """hast_rows: the output table of `classify`, and with_lists the three barcode lists, made on the GPU from text records and counters
+    in device memory (raw pointers: torch tensors' data_ptr(), Context.alloc)."""
+
+    def __init__(self, ctx, d_text16, d_counts, n, n0, n1, w0=1.0, w1=1.0, with_lists=True):
+        self._lib = lib()
+        self._h = C.c_void_p()
+        _ck(self._lib.hast_rows_build_device(ctx._h, C.c_void_p(d_text16), C.c_void_p(d_counts), n, n0, n1, w0, w1, int(with_lists), C.byref(self._h)))
+        self.n = n
+
+    def info(self) -> RowsInfo:
+        r = RowsInfo()
+        _ck(self._lib.hast_rows_get_info(self._h, C.byref(r)))
+        return r
+
+    def read(self, which, offset=0, n=None) -> bytes:
+        if n is None:
+            i = self.info()
+            n = (i.list_bytes[which - 1] if which else i.table_bytes) - offset
+        out = np.empty(max(n, 1), dtype=np.uint8)
+        _ck(self._lib.hast_rows_read(self._h, which, offset, n, _ptr(out)))
+        return out[:n].tobytes()
+
+    def order(self) -> np.ndarray:
+        out = np.empty(max(self.n, 1), dtype=np.uint32)
+        _ck(self._lib.hast_rows_order(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out[:self.n]
+
+    def classes(self) -> np.ndarray:
+        out = np.empty(max(self.n, 1), dtype=np.uint8)
+        _ck(self._lib.hast_rows_classes(self._h, out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out[:self.n]
+
+    def close(self):
+        if self._h:
+            self._lib.hast_rows_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
 
 
 class GzReader:

@@ -34,6 +34,7 @@
 #include <cerrno>
 #include <chrono>
 #include <deque>
+#include <future>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -98,6 +99,9 @@ void print_usage() {                              // same flags as the reference
           "                        numbered by the host\n"
           "                        (N: digits, optionally followed by K, M or G = 2^10, 2^20, 2^30; X: a decimal number such as 1.5)\n"
           "      --deal MODE       with --devices: blocks (default) | files (HAST_DEAL)\n"
+          "      --rows MODE       host (default) | device: who sorts and formats the output table, and with --phase-reads the three\n"
+          "                        barcode lists: host threads, or the GPU, from which only the finished text comes back (HAST_ROWS);\n"
+          "                        a run the GPU cannot do this for says why (fallback=...) and does it on the host, same bytes\n"
           "  -h, --help            this text\n\n"
           "stdout: barcode <TAB> haplotype(0/1/-1) <TAB> hits_hap0 <TAB> hits_hap1, sorted by barcode\n\n",
           stderr);
@@ -227,6 +231,7 @@ struct Counts {                                    // host accumulators behind t
     std::vector<uint64_t> c0, c1, neg;             // by device-dictionary id (one dictionary), by merged id (several), by host id (no device dictionary)
     std::vector<uint64_t> h0, h1, hneg;            // by host-dictionary id, for what a device dictionary left to the host
     size_t device_cap = 0;
+    bool folded = false;                           // device counters have been read back and added to the sums above
 };
 
 // Who numbers the barcodes.  Round 6: the GPU's own dictionary (hast_names_create_dict) -- ids 0 .. limit-1 in the order in which its
@@ -266,6 +271,7 @@ struct Options {
     hast::quartering::GzFormat gz_format() const {
         return !gz_out ? hast::quartering::GzFormat::kNone : gz_bgzf ? hast::quartering::GzFormat::kBgzf : hast::quartering::GzFormat::kGzip;
     }
+    bool rows_device = false;                      // --rows device: the table (and the lists) are sorted and formatted on the GPU (hast_rows_*)
     bool bgzf_device = false;                      // --bgzf device: blocked gzip is inflated on the GPU per member (hast_gz_open_blocked)
     double w0 = 1.0, w1 = 1.0;
     // worked out from the above
@@ -312,27 +318,27 @@ struct Run {
     std::vector<std::string_view> names;
     std::vector<uint32_t> order;
     size_t n_dev_names = 0, n_host_names = 0, n_rows_summed = 0;
+    size_t n_rows = 0;                             // rows of the table
     bool past_int = false;
+    // --rows device: the table made on the GPU (null: made on the host, rows_fallback says why when the device was asked for)
+    hast_rows *rows = nullptr;
+    bool counts_summed = false;                    // the all-reduce has run and nothing was counted since
+    const char *rows_fallback = "none";
+    double rows_download_write_s = 0;
     double t_start = 0, t_ctx = 0, t_loaded = 0, t_scrubbed = 0, t_read_done = 0, t_classified = 0, t_printed = 0, t_pre_waited = 0;
 };
 
-void flush_counts(Run &rs, size_t new_cap) {
+// The counters of all contexts summed ON the devices, nothing read back: the dictionaries of several GPUs merged into the first one's
+// numbering and their contexts' counters renumbered, then ONE all-reduce(sum,u64) over RCCL/xGMI, which leaves the totals on every
+// device (collectBarcodes + data.Add, classify.cpp:226-229,277).  flush_counts reads them back behind it; --rows device goes on from
+// them where they lie.
+void sum_counts_on_devices(Run &rs) {
     std::vector<hast_ctx *> &ctxs = rs.ctxs;
     Counts &acc = rs.acc;
     Naming &nm = rs.naming;
     hast::BarcodeDict &dict = rs.dict;
     hast::BarcodeDict::Cache &dict_cache = rs.caches[0];
-    // fold what the devices have counted so far into the host sums, then (re)size the device arrays.  Several GPUs: ONE
-    // all-reduce(sum,u64) over RCCL/xGMI leaves the totals on every device (collectBarcodes + data.Add, classify.cpp:226-229,277)
-    hast_ctx *ctx = ctxs[0];
-    if (acc.device_cap) {
-        std::vector<uint64_t> a, b, c;
-        auto read_range = [&](size_t first, size_t n, std::vector<uint64_t> &d0, std::vector<uint64_t> &d1, std::vector<uint64_t> &d2) {
-            n = first < acc.device_cap ? std::min(n, acc.device_cap - first) : 0;
-            a.assign(n, 0); b.assign(n, 0); c.assign(n, 0);
-            if (n) CK(hast_counts_read_range(ctx, first, n, a.data(), b.data(), c.data()), "reading counters");
-            add_into(d0, a, n); add_into(d1, b, n); add_into(d2, c, n);
-        };
+    {
         if (nm.device_dict && nm.groups.size() > 1) {
             // several dictionaries: what each has learnt since the last merge into the first one's numbering, its contexts' counters with it
             const double t0 = now_s();
@@ -374,6 +380,27 @@ void flush_counts(Run &rs, size_t new_cap) {
             nm.merge_s += now_s() - t0;
         }
         if (ctxs.size() > 1) CK(hast_counts_allreduce(ctxs.data(), (int)ctxs.size()), "summing the counters of the GPUs");
+    }
+}
+
+void flush_counts(Run &rs, size_t new_cap) {
+    std::vector<hast_ctx *> &ctxs = rs.ctxs;
+    Counts &acc = rs.acc;
+    Naming &nm = rs.naming;
+    hast::BarcodeDict &dict = rs.dict;
+    // fold what the devices have counted so far into the host sums, then (re)size the device arrays
+    hast_ctx *ctx = ctxs[0];
+    if (acc.device_cap) {
+        std::vector<uint64_t> a, b, c;
+        auto read_range = [&](size_t first, size_t n, std::vector<uint64_t> &d0, std::vector<uint64_t> &d1, std::vector<uint64_t> &d2) {
+            n = first < acc.device_cap ? std::min(n, acc.device_cap - first) : 0;
+            a.assign(n, 0); b.assign(n, 0); c.assign(n, 0);
+            if (n) CK(hast_counts_read_range(ctx, first, n, a.data(), b.data(), c.data()), "reading counters");
+            add_into(d0, a, n); add_into(d1, b, n); add_into(d2, c, n);
+        };
+        if (!rs.counts_summed) sum_counts_on_devices(rs);           // (--rows device summed them and then had no room for its table)
+        rs.counts_summed = false;
+        acc.folded = true;
         const size_t n_host = dict.size();                                         // (after the merge: it may have named texts)
         if (!nm.device_dict) read_range(0, n_host, acc.c0, acc.c1, acc.neg);      // (only the barcodes that exist: the counters are sized ahead of the dictionary)
         else {
@@ -417,13 +444,14 @@ bool parse_options(int argc, char **argv, Options &o) {
         {"park-gb", required_argument, NULL, 1014},     {"name-cache", required_argument, NULL, 1015},
         {"deal", required_argument, NULL, 1016},        {"route", required_argument, NULL, 1017},
         {"gz-out", no_argument, NULL, 1018},            {"bgzf", required_argument, NULL, 1019},
-        {"gz-format", required_argument, NULL, 1020},
+        {"gz-format", required_argument, NULL, 1020},   {"rows", required_argument, NULL, 1021},
         {0, 0, 0, 0}};
     static char optstring[] = "p:m:l:r:t:w:u:f:q:h";             // classify.cpp:387
     bool gz_out_flag = false;
     int device = 0;
     const char *bgzf = getenv("HAST_BGZF");                       // (the alias for runs of the unchanged wrapper; the flag wins)
     const char *gz_format = getenv("HAST_PHASE_GZ_FORMAT");       // (the same; ignored where nothing is written as gzip)
+    const char *rows = getenv("HAST_ROWS");                       // (the same)
     bool gz_format_flag = false;
     {
         const char *pr = getenv("HAST_PHASE_READS");
@@ -486,6 +514,7 @@ bool parse_options(int argc, char **argv, Options &o) {
         case 1018: o.gz_out = gz_out_flag = true; break;
         case 1019: bgzf = optarg; break;
         case 1020: gz_format = optarg; gz_format_flag = true; break;
+        case 1021: rows = optarg; break;
         case 1008:
             if (!hast::parse_device_list(optarg, o.devices)) { print_usage(); return false; }
             break;
@@ -518,6 +547,10 @@ bool parse_options(int argc, char **argv, Options &o) {
     if (bgzf && *bgzf) {
         if (strcmp(bgzf, "host") && strcmp(bgzf, "device")) { print_usage(); return false; }
         o.bgzf_device = !strcmp(bgzf, "device");
+    }
+    if (rows && *rows) {
+        if (strcmp(rows, "host") && strcmp(rows, "device")) { print_usage(); return false; }
+        o.rows_device = !strcmp(rows, "device");
     }
     if (o.devices.empty()) o.devices.push_back(device);
     // --batch-reads N (tests / small inputs): shrink the blocks so that a batch holds about N records
@@ -1254,6 +1287,7 @@ void counters_back(Run &rs) {
     rs.n_dev_names = n_dev_names;
     rs.n_host_names = n_host_names;
     rs.n_rows_summed = n_rows_summed;
+    rs.n_rows = names.size();
 }
 
 // ---- printBarcodeInfos (classify.cpp:93-102): byte-wise sorted rows ------------------------
@@ -1404,6 +1438,74 @@ void print_rows(Run &rs) {
     if (fflush(stdout) != 0) die_output();
 }
 
+// ---- --rows device: the table keyed, called, sorted, sized and formatted in HBM (hast_rows_*, rows_kernels.hip) ---------------------
+// The texts lie in the device dictionary and the counters in the context's arrays: 16 + 32 bytes a barcode that the host route reads
+// back, sorts and formats with its threads.  Here only the finished text crosses PCIe.  What the device cannot do this for goes the
+// host's way, whole, and says why: texts or counts that only the host holds would have to be merged into a table sorted elsewhere.
+// Returns null when the table is in rs.rows, else the reason.
+const char *rows_on_device(Run &rs) {
+    const Options &o = rs.o;
+    Naming &naming = rs.naming;
+    if (!naming.device_dict) return "no_device_dictionary";
+    if (naming.groups.size() != 1) return "several_dictionaries";
+    if (rs.dict.size() != 0) return "host_names";                     // (texts the dictionary left to the host: their rows are not on the device)
+    if (rs.acc.folded) return "counts_on_host";                       // (the counters were read back and sized anew on the way)
+    size_t n = 0;
+    CK(hast_names_count(naming.groups[0], &n), "asking the dictionary for its size");
+    if (n > rs.acc.device_cap) return "counts_on_host";
+    sum_counts_on_devices(rs);                                        // (several contexts of the one GPU: the totals, where they lie)
+    rs.counts_summed = true;
+    const hast_status st = hast_rows_build(rs.ctx, naming.groups[0], n, rs.n_set[0], rs.n_set[1], o.w0, o.w1, o.phase_reads ? 1 : 0, &rs.rows);
+    if (st == HAST_ERR_OOM) return "no_room";
+    if (st != HAST_OK) die(4, "making the table on the GPU");
+    rs.t_classified = now_s();
+    rs.n_dev_names = rs.n_rows = n;
+    return nullptr;
+}
+
+// text `which` of the device's table to f: piece k is written while piece k + 1 comes down (the library stages through two pinned buffers)
+bool write_rows_text(hast_rows *rows, int which, uint64_t total, FILE *f) {
+    const size_t kPiece = 8u << 20;
+    std::vector<uint8_t> buf[2];
+    const uint64_t pieces = (total + kPiece - 1) / kPiece;
+    auto fetch = [&](uint64_t k) {
+        const size_t n = (size_t)std::min<uint64_t>(kPiece, total - k * kPiece);
+        buf[k & 1].resize(n);
+        return std::async(std::launch::async, [=, &buf] { return hast_rows_read(rows, which, k * kPiece, n, buf[k & 1].data()); });
+    };
+    std::future<hast_status> pending;
+    if (pieces) pending = fetch(0);
+    for (uint64_t k = 0; k < pieces; k++) {
+        if (pending.get() != HAST_OK) die(4, "reading the table from the GPU");
+        if (k + 1 < pieces) pending = fetch(k + 1);
+        if (fwrite(buf[k & 1].data(), 1, buf[k & 1].size(), f) != buf[k & 1].size()) {
+            if (pending.valid()) pending.wait();
+            return false;
+        }
+    }
+    return true;
+}
+
+void print_rows_from_device(Run &rs) {
+    fprintf(stderr, "__print result__\n");
+    hast_rows_info info;
+    CK(hast_rows_get_info(rs.rows, &info), "asking for the table's sizes");
+    const double t0 = now_s();
+    // (as print_rows: a full disk or a closed pipe must not leave a truncated table behind exit 0)
+    if (!write_rows_text(rs.rows, 0, info.table_bytes, stdout)) die_output();
+    if (fflush(stdout) != 0) die_output();
+    rs.rows_download_write_s = now_s() - t0;
+    rs.past_int = info.past_int != 0;
+}
+
+void stat_rows(const Run &rs) {
+    hast_rows_info info = {};
+    if (rs.rows) (void)hast_rows_get_info(rs.rows, &info);
+    stat_line("__stats_rows__ route=%s fallback=%s rows=%zu table_bytes=%llu list_bytes=%llu,%llu,%llu keys_s=%.3f sort_s=%.3f format_s=%.3f download_write_s=%.3f\n",
+              rs.rows ? "device" : "host", rs.rows_fallback, rs.n_rows, (unsigned long long)info.table_bytes, (unsigned long long)info.list_bytes[0],
+              (unsigned long long)info.list_bytes[1], (unsigned long long)info.list_bytes[2], info.keys_s, info.sort_s, info.format_s, rs.rows_download_write_s);
+}
+
 // ---- HAST_PHASE_READS=1: steps 10 and 11 of the wrapper (classify_stlfr_reads.sh:155-190) done here -------------------------
 // The wrapper derives three barcode lists from the table above with awk and then routes every record of every input to
 // <name>.{paternal,maternal,homozygous,nobarcode}.fastq with a single-threaded awk program, re-reading (and re-inflating) every
@@ -1469,6 +1571,28 @@ void write_lists(Run &rs, PhaseReads &pr) {
         }
     }
     for (char c : has_sep) pr.any_sep = pr.any_sep || c;
+}
+
+// --rows device: the three lists as the GPU wrote them.  The router still goes by names, order and classes on the host (need_cls,
+// host_class, build_routing_tables): downloads, no sort and no call is made here
+void write_lists_from_device(Run &rs, PhaseReads &pr) {
+    const char *list_name[3] = {"paternal.unique.barcodes", "maternal.unique.barcodes", "homozygous.unique.barcodes"};
+    hast_rows_info info;
+    CK(hast_rows_get_info(rs.rows, &info), "asking for the lists' sizes");
+    for (int l = 0; l < 3; l++) {
+        FILE *lf = fopen(list_name[l], "wb");                     // (a list with no line is created all the same)
+        if (!lf || !write_rows_text(rs.rows, l + 1, info.list_bytes[l], lf) || fclose(lf) != 0) die(2, (std::string("cannot write ") + list_name[l]).c_str());
+    }
+    const size_t n = rs.n_rows;
+    rs.dev_texts.resize(16 * n);
+    CK(hast_names_texts(rs.naming.groups[0], 0, n, rs.dev_texts.data()), "reading the dictionary's texts");
+    rs.names.assign(n, std::string_view());
+    for (size_t i = 0; i < n; i++) rs.names[i] = std::string_view(reinterpret_cast<const char *>(rs.dev_texts.data()) + 16 * i + 1, rs.dev_texts[16 * i]);
+    rs.order.assign(n, 0);
+    CK(hast_rows_order(rs.rows, rs.order.data()), "reading the order of the rows");
+    pr.list_of.assign(n, 0);
+    CK(hast_rows_classes(rs.rows, pr.list_of.data()), "reading the barcodes' lists");
+    pr.any_sep = info.any_sep != 0;
 }
 
 void need_cls(const Run &rs, PhaseReads &pr) {
@@ -1896,7 +2020,8 @@ void phase_reads(Run &rs) {
     const double t_ph0 = now_s();
     PhaseReads pr;
     pr.gz_in.resize(o.read.size());
-    write_lists(rs, pr);
+    if (rs.rows) write_lists_from_device(rs, pr);
+    else write_lists(rs, pr);
     const double t_lists = now_s();
     // On the GPU (default).  On the host (--route host; --host-parse; a barcode that itself holds '#' or '/', whose list line awk cuts
     // short).
@@ -1940,8 +2065,9 @@ void print_statistics(Run &rs) {
         double dt = rs.t_classified - rs.t_loaded;
         stat_line("__stats__ K=%zu set0=%llu set1=%llu reads=%llu bases=%llu barcodes=%zu load_s=%.3f classify_s=%.3f Mbp_per_s=%.1f\n",
                 rs.K, (unsigned long long)rs.n_set[0], (unsigned long long)rs.n_set[1], (unsigned long long)rs.total_reads,
-                (unsigned long long)rs.total_bases, rs.names.size(), rs.t_loaded - rs.t_start, dt, dt > 0 ? rs.total_bases / dt / 1e6 : 0.0);
+                (unsigned long long)rs.total_bases, rs.n_rows, rs.t_loaded - rs.t_start, dt, dt > 0 ? rs.total_bases / dt / 1e6 : 0.0);
     }
+    if (o.stats && o.rows_device) stat_rows(rs);
     if (o.stats && rs.naming.device_dict)
         stat_line("__stats_dictionary__ on=device dictionaries=%zu ids_limit=%zu ids_from_device=%zu ids_from_host=%zu merge_by_text_s=%.3f texts_merged_to_host=%zu rows_summed_by_text=%zu\n", rs.naming.groups.size(), rs.naming.host_base, rs.n_dev_names, rs.n_host_names, rs.naming.merge_s,
                   rs.naming.merged_to_host, rs.n_rows_summed);
@@ -2001,6 +2127,7 @@ int leave(Run &rs) {
     }
     for (std::thread &t : rs.gz_closers) t.join();
     for (hast_fq *f : rs.done_fq) hast_fq_destroy(f);
+    hast_rows_destroy(rs.rows);
     for (hast_names *nm : rs.own_caches) hast_names_destroy(nm);
     for (hast_names *nm : rs.own_tabs) hast_names_destroy(nm);       // (after the routing streams that refer to them)
     for (hast_ctx *c : rs.ctxs) hast_ctx_destroy(c);
@@ -2047,10 +2174,19 @@ int main(int argc, char **argv) {
     if (o.host_parse) read_phase_host(rs);
     else read_phase_device(rs);
     rs.t_read_done = now_s();
-    // 5. counters back, device and host names merged, 6. sort and print
-    counters_back(rs);
-    sort_rows(rs);
-    print_rows(rs);
+    // 5. counters back, device and host names merged, 6. sort and print -- or, with --rows device, all of it where the counters lie
+    if (o.rows_device) {
+        if (const char *reason = rows_on_device(rs)) {
+            rs.rows_fallback = reason;
+            fprintf(stderr, " WARN : --rows device: the table is made on the host (fallback=%s)\n", reason);
+        }
+    }
+    if (rs.rows) print_rows_from_device(rs);
+    else {
+        counters_back(rs);
+        sort_rows(rs);
+        print_rows(rs);
+    }
     // 7. --phase-reads: the lists, then the device router or the host router
     if (o.phase_reads) phase_reads(rs);
     // 8. statistics and leaving

@@ -1290,3 +1290,13 @@ hast_status hast_fq_commit(hast_fq *f) {
 }
 
 }  // extern "C"
+
+// ---- hook for rows_api.cpp (hast_internal.h): the dictionary's texts where they lie
+namespace hast {
+const uint8_t *names_texts_of(const hast_names *nm, size_t *limit, int *device) {
+    if (!nm || !nm->dict) return nullptr;
+    *limit = nm->limit;
+    *device = nm->device;
+    return static_cast<const uint8_t *>(nm->d_text_of_id);
+}
+}  // namespace hast

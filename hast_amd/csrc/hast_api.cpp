@@ -1615,6 +1615,7 @@ hast_status framed_err(hast_ctx *c, hipStream_t hs) { return check_classify_err(
 int ctx_device_of(const hast_ctx *c) { return c->device; }
 hipStream_t ctx_stream_of(hast_ctx *c) { return c->stream; }
 size_t ctx_n_barcodes(const hast_ctx *c) { return c->n_barcodes; }
+const uint64_t *ctx_counts_of(const hast_ctx *c) { return reinterpret_cast<const uint64_t *>(c->d_counts); }
 }  // namespace hast
 
 extern "C" {

@@ -27,6 +27,9 @@ hast_status framed_err(hast_ctx *c, hipStream_t hs);
 int ctx_device_of(const hast_ctx *c);
 hipStream_t ctx_stream_of(hast_ctx *c);
 size_t ctx_n_barcodes(const hast_ctx *c);
+const uint64_t *ctx_counts_of(const hast_ctx *c);                                                    // the bound counters [n_barcodes][4], or null (rows_api.cpp)
+// a device dictionary's text records by id, [*limit][16], on *device; null when nm is not one (rows_api.cpp)
+const uint8_t *names_texts_of(const hast_names *nm, size_t *limit, int *device);
 int kc_device_of(const hast_kc *c);                                                                  // the count table's device (sq_api.cpp)
 int kc_k_of(const hast_kc *c);                                                                       // ... and its K
 // FREES THAT DO NOT STOP THE DEVICE.  hipFree and hipHostFree wait for every stream of the device and hold the runtime's lock while

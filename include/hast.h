@@ -513,6 +513,36 @@ hast_status hast_dz_compress_device_ex(hast_ctx *, const uint8_t *d_src, size_t 
 size_t      hast_dz_bound_blocked(size_t n_bytes);
 hast_status hast_dz_compress_blocked_device(hast_ctx *, const uint8_t *d_src, size_t n_bytes, uint8_t *d_dst, size_t cap, size_t *n_out, hast_stream);
 
+/* ---- the output table on the GPU: printBarcodeInfos (classify.cpp:93-102) and the wrapper's three barcode lists ----------------
+ * From the text records of n barcodes (16 bytes each: length byte + up to 15 bytes of text, as a device dictionary keeps them by id)
+ * and their counters ([n][4] 64-bit words, {c0, c1, ..}), both in device memory: the table `text \t hap \t c0 \t c1 \n`, one row per
+ * id, sorted byte-wise by text (a prefix in front of what it is a prefix of), the call by hast_get_hap's rule (n0, n1: the set
+ * sizes, w0, w1: the weights); with_lists != 0 also the three lists `text \n` of the barcodes called 0 (list 1, paternal), 1 (list
+ * 2, maternal) and -1 (list 3, homozygous), each in row order.  Keyed, sorted, sized and formatted on the device; only the finished
+ * text is read back.  The bytes are those `classify` writes on the host (hast_amd/csrc/rows_core.h has the rules).
+ * hast_rows_build_device takes raw device pointers (d_text16 16-byte aligned, d_counts 32-byte aligned; n < 2^32; n == 0 is valid
+ * and gives empty texts); hast_rows_build takes the texts of ids [0, n) of a device dictionary (hast_names_create_dict) and the
+ * counters bound to the context, which must be on the dictionary's GPU and hold at least n barcodes.  Both wait for the work.
+ * HAST_ERR_OOM when the device has no room (what closed streams have parked is freed first): the caller makes the table on the host.
+ * hast_rows_get_info: the sizes; any_sep: a barcode holds '#' or '/'; past_int: a count is above INT_MAX; the seconds of the three
+ * steps.  hast_rows_read: n bytes from `offset` of the table (which = 0) or of list 1..3, through pinned staging of the handle's
+ * own (one call at a time per handle); beyond the text's end: HAST_ERR_INVALID.  hast_rows_order: the n ids in row order.
+ * hast_rows_classes: the list (1..3) of every id. */
+typedef struct hast_rows hast_rows;
+typedef struct {
+    uint64_t n_rows, table_bytes, list_bytes[3];
+    int      any_sep, past_int;
+    double   keys_s, sort_s, format_s;
+} hast_rows_info;
+hast_status hast_rows_build_device(hast_ctx *, const uint8_t *d_text16, const uint64_t *d_counts, size_t n, uint64_t n0, uint64_t n1, double w0, double w1,
+                                   int with_lists, hast_rows **out);
+hast_status hast_rows_build(hast_ctx *, hast_names *dict, size_t n, uint64_t n0, uint64_t n1, double w0, double w1, int with_lists, hast_rows **out);
+hast_status hast_rows_get_info(hast_rows *, hast_rows_info *);
+hast_status hast_rows_read(hast_rows *, int which, uint64_t offset, size_t n, void *host);
+hast_status hast_rows_order(hast_rows *, uint32_t *ids_in_row_order);
+hast_status hast_rows_classes(hast_rows *, uint8_t *cls_by_id);
+void        hast_rows_destroy(hast_rows *);
+
 /* ---- gzip input decoded on the device (gzstream.h:47, classify.cpp:245-254: one zlib stream per .gz file) -----------------
  * HAST's real inputs are ordinary .fq.gz files: ONE deflate stream per file, which the reference inflates on the thread that
  * also frames the records.  hast_gz inflates such a file on the GPU: the COMPRESSED bytes cross PCIe (5-6 x fewer than the
