@@ -11,4 +11,4 @@ from .binding import (HastError, Context, SynthParams, lib, lib_path, classify_e
                       unshared_kmers_exe, GzReader, GzStats, GzBlockedStats, dz_bound, dz_bound_blocked,
                       fake_10x_exe, TxMap, TxState, TxResult, TxMapInfo, TxConverter, TxTimes, TxFeed, TX_ON_HOST, TX_TAIL_TOO_LONG, TX_ENDS,
                       barcode_freq_exe, Tally, FqTallied, Rows, RowsInfo,
-                      ReadStream, RsBlock, RS_FASTA, RS_FASTQ, RS_FORMAT_ERROR, RS_RECORD_TOO_LONG)
+                      ReadStream, RsBlock, RsRows, rs_rows_device, RS_FASTA, RS_FASTQ, RS_FORMAT_ERROR, RS_RECORD_TOO_LONG)

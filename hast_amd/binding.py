@@ -68,6 +68,10 @@ class RsBinned(C.Structure):
     _fields_ = [("run", C.POINTER(C.c_uint8) * 3), ("run_bytes", C.c_uint64 * 3), ("raw_bytes", C.c_uint64 * 3), ("count", C.c_uint64 * 3)]
 
 
+class RsRows(C.Structure):
+    _fields_ = [("text", C.POINTER(C.c_uint8)), ("bytes", C.c_uint64), ("count", C.c_uint64 * 3), ("on_host", C.c_uint32)]
+
+
 class TxMapInfo(C.Structure):
     _fields_ = [("n_keys", C.c_uint64), ("device_ok", C.c_int), ("reason", C.c_char * 60)]
 
@@ -270,6 +274,9 @@ ABI_SYMBOLS = {
     "hast_rs_take_tail": (C.c_int, [vp, vp, C.POINTER(C.c_size_t)]),
     "hast_rs_set_bins": (C.c_int, [vp, C.c_int, C.c_uint32, C.c_uint32]),
     "hast_rs_next_binned": (C.c_int, [vp, C.POINTER(RsBlock), C.POINTER(RsBinned)]),
+    "hast_rs_rows_device": (C.c_int, [vp, vp, vp, vp, C.c_size_t, C.c_uint32, C.c_uint32, vp, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64 * 3)]),
+    "hast_rs_set_rows": (C.c_int, [vp, C.c_int, C.c_uint32, C.c_uint32]),
+    "hast_rs_next_rows": (C.c_int, [vp, C.POINTER(RsBlock), C.POINTER(RsBinned), C.POINTER(RsRows)]),
     "hast_rs_destroy": (None, [vp]),
     # stage 02: stLFR pairs -> 10x FASTQ (fake_10x.pl)
     "hast_tx_map_load": (C.c_int, [C.c_char_p, C.POINTER(vp), C.POINTER(TxMapInfo)]),
@@ -1027,10 +1034,29 @@ class ReadStream:
         runs = [C.string_at(bins.run[c], bins.run_bytes[c]) if bins.run_bytes[c] else b"" for c in range(3)]
         return out + (runs, [int(x) for x in bins.raw_bytes], [int(x) for x in bins.count])
 
-    def next(self, _bins=None):
+    def set_rows(self, mode, total0, total1):
+        """the rows (hast_rs_set_rows): 0 off, 1 on; total0 / total1: the two set sizes, at least 1 each"""
+        _ck(self._lib.hast_rs_set_rows(self._h, mode, total0, total1))
+
+    def next_rows(self, binned=False):
+        """next() or next_binned(), and behind it the rows of the same view: (text or None, count [3], on_host).  With the text there
+        are no names and votes (names is None then); an on_host view has them and no text"""
+        bins, rows = RsBinned(), RsRows()
+        out = self.next(bins if binned else None, rows)
+        if binned:
+            runs = [C.string_at(bins.run[c], bins.run_bytes[c]) if bins.run_bytes[c] else b"" for c in range(3)]
+            out = out + (runs, [int(x) for x in bins.raw_bytes], [int(x) for x in bins.count])
+        text = None if rows.on_host else (C.string_at(rows.text, rows.bytes) if rows.bytes else b"")
+        return out + (text, [int(x) for x in rows.count], bool(rows.on_host))
+
+    def next(self, _bins=None, _rows=None):
         """(flags, consumed, bases, names, votes[records, 2]) of the oldest submitted block; copies of the feed's pinned buffers"""
         b = RsBlock()
-        if _bins is None:
+        if _rows is not None:
+            _ck(self._lib.hast_rs_next_rows(self._h, C.byref(b), None if _bins is None else C.byref(_bins), C.byref(_rows)))
+            if b.records and not b.names and not b.votes and not b.name_off:
+                return b.flags, b.consumed, b.bases, None, None
+        elif _bins is None:
             _ck(self._lib.hast_rs_next(self._h, C.byref(b)))
         else:
             _ck(self._lib.hast_rs_next_binned(self._h, C.byref(b), C.byref(_bins)))
@@ -1059,6 +1085,17 @@ class ReadStream:
 
     def __exit__(self, *a):
         self.close()
+
+
+def rs_rows_device(ctx, d_names, d_name_off, d_votes, n, total0, total1, d_out, cap):
+    """hast_rs_rows_device over device pointers -> (bytes, count [3]); HastError(UNSUPPORTED).needed = the bytes a too small cap lacks"""
+    nbytes, count = C.c_uint64(), (C.c_uint64 * 3)()
+    st = lib().hast_rs_rows_device(ctx._h, _ptr(d_names), _ptr(d_name_off), _ptr(d_votes), n, total0, total1, _ptr(d_out), cap, C.byref(nbytes), C.byref(count))
+    if st != 0:
+        e = HastError(st, lib().hast_last_error().decode())
+        e.needed = int(nbytes.value)
+        raise e
+    return int(nbytes.value), [int(x) for x in count]
 
 
 # ---- stage 02: stLFR pairs -> 10x FASTQ ----------------------------------------------------------

@@ -24,6 +24,11 @@
 // tail write through the model of rb_host.h (zlib members with --gz-out).  A class without reads gets no file; an input that ends in
 // the format error leaves none of its files; a failed write is exit 3.
 //
+// --rows device (additive, with --ingest device; the default is host): the rows are made on the GPU too (hast_rs_next_rows; the rule,
+// integer code that prints the density as "%0.6f" does: rr_core.h), so that names and votes stay in HBM and only text comes back.
+// format_rows (rr_host.h) stays the route of --rows host, of every fallback above, of the FASTQ tail, of a view whose rows outgrow the
+// feed's buffer, and of a run with an empty k-mer set (its rows print inf / nan; one WARN line, fallback=empty_set).
+//
 // Requirement (deviation): k-mer lines must be upper-case A/C/G/T of one length K <= 32 -- what jellyfish/meryl
 // dumps are.  The reference would also store other bytes literally (s03:59-65); we stop with exit 3 instead.
 #include <getopt.h>
@@ -47,10 +52,12 @@
 #include "ingest.h"
 #include "raw_blocks.h"
 #include "rb_host.h"
+#include "rr_host.h"
 #include "rs_host.h"
 
 namespace {
 
+using hast::format_rows;
 using hast::now_s;
 
 [[noreturn]] void die(int code, const std::string &what) {
@@ -71,26 +78,12 @@ void print_usage() {   // same flags as the reference (s03:316-324); stderr is f
           "  --device N / --devices A,B,..   GPU(s); with several, every batch of reads is shared out between them\n"
           "  --ingest host|device            device: reads are inflated and framed on the GPU (one GPU; default host)\n"
           "  --block-mb N                    block of the device ingest (default 64)\n"
+          "  --rows host|device              device (with --ingest device): the rows are formatted on the GPU too (default host)\n"
           "  --stats                         counts and seconds of the read phase on stderr\n"
           "  --bin-reads                     also write every input's reads to B.haplotype0|haplotype1|ambiguous.fasta|fastq\n"
           "  --gz-out                        (with --bin-reads) gzip those files, names end in .gz\n"
           "  --bin-dir DIR                   (with --bin-reads) where they go (default: the working directory)\n",
           stderr);
-}
-
-// the rows of n reads: names[name_off[i], name_off[i + 1]) and votes[2 i], votes[2 i + 1] -> "name \t haplotypeN|ambiguous \t density"
-void format_rows(std::string &out, const uint8_t *names, const uint32_t *name_off, const uint32_t *votes, size_t n, const int *total_kmers) {
-    char row[96];
-    for (size_t i = 0; i < n; i++) {
-        const double d0 = hast::rb::density(votes[2 * i], total_kmers[0]), d1 = hast::rb::density(votes[2 * i + 1], total_kmers[1]);   // s03:215-216
-        // s03:110-133 for two haplotypes: both zero -> ambiguous 0.0; else the larger density, ties to haplotype0 (rb_core.h: the bins' rule)
-        const uint32_t cls = hast::rb::class_of(d0, d1);
-        if (cls == hast::rb::kAmbiguous) snprintf(row, sizeof(row), "\tambiguous\t0.0\n");
-        else if (cls == hast::rb::kHap1) snprintf(row, sizeof(row), "\thaplotype1\t%0.6f\n", d1);
-        else snprintf(row, sizeof(row), "\thaplotype0\t%0.6f\n", d0);
-        out.append(reinterpret_cast<const char *>(names) + name_off[i], name_off[i + 1] - name_off[i]);
-        out += row;
-    }
 }
 
 // What a FASTQ file's end leaves behind its last complete record (fewer than four newlines) as a batch of one read: the header needs
@@ -185,6 +178,7 @@ struct Options {
     std::string format = "fasta", bin_dir = ".";
     std::vector<int> devices;
     bool fastq = false, ingest_device = false, stats = false, bin_reads = false, gz_out = false;
+    bool rows_device = false, rows_given = false;          // --rows device; --rows was said at all (--stats then has a line on it)
     long t_num = 8, block_mb = 64;
 };
 
@@ -231,6 +225,9 @@ struct Run {
     hast::WorkerPool pool;
     hast_rs *feed = nullptr;                                // --ingest device
     uint64_t st_blocks = 0, st_gz = 0;                      // the main thread's part of --stats
+    bool rows_on_device = false;                            // --rows device, and the feed makes them
+    uint64_t st_row_views[2] = {0, 0}, st_row_bytes = 0;    // views whose rows came as text / were formatted here; bytes of that text
+    std::string st_rows_fallback = "none";
     double st_read = 0, st_upload = 0, t_phase = 0;
     std::string st_fallback = "none";
     bool output_failed = false;
@@ -245,7 +242,7 @@ bool parse_options(int argc, char **argv, Options &o) {
                                            {"devices", required_argument, NULL, 1002}, {"ingest", required_argument, NULL, 1003},
                                            {"block-mb", required_argument, NULL, 1004}, {"stats", no_argument, NULL, 1005},
                                            {"bin-reads", no_argument, NULL, 1006},   {"gz-out", no_argument, NULL, 1007},
-                                           {"bin-dir", required_argument, NULL, 1008},
+                                           {"bin-dir", required_argument, NULL, 1008}, {"rows", required_argument, NULL, 1009},
                                            {0, 0, 0, 0}};
     int device = 0;
     bool ok = true;
@@ -265,12 +262,14 @@ bool parse_options(int argc, char **argv, Options &o) {
         case 1006: o.bin_reads = true; break;
         case 1007: o.gz_out = true; break;
         case 1008: o.bin_dir = optarg; break;
+        case 1009: o.rows_given = true; o.rows_device = strcmp(optarg, "device") == 0; ok = o.rows_device || strcmp(optarg, "host") == 0; break;
         case 'h':
         default: ok = false;
         }
     }
     ok = ok && o.haps.size() == 2 && !o.read.empty() && o.t_num >= 1;        // s03:351-354
     ok = ok && !(o.gz_out && !o.bin_reads);
+    ok = ok && !(o.rows_device && !o.ingest_device);
     for (size_t i = 0; ok && o.bin_reads && i < o.read.size(); ++i) {
         const std::string &r = o.read[i];
         std::string b = r.substr(r.find_last_of('/') == std::string::npos ? 0 : r.find_last_of('/') + 1);
@@ -341,10 +340,19 @@ void create_device_feed(Run &rs) {
     if (rs.ctxs.size() > 1) {
         fprintf(stderr, "classify_read: WARN: --ingest device takes one GPU: host ingest for this run (fallback=several_devices)\n");
         rs.st_fallback = "several_devices";
+        if (o.rows_device) rs.st_rows_fallback = "several_devices";
         return;
     }
     if (hast_rs_create(rs.ctx, o.fastq ? HAST_RS_FASTQ : HAST_RS_FASTA, rs.rs_block, &rs.feed) != HAST_OK) die(4, "cannot create the device ingest");
     if (o.bin_reads && hast_rs_set_bins(rs.feed, o.gz_out ? 2 : 1, (uint32_t)rs.total_kmers[0], (uint32_t)rs.total_kmers[1]) != HAST_OK) die(4, "cannot create the device ingest's bins");
+    if (!o.rows_device) return;
+    if (rs.total_kmers[0] < 1 || rs.total_kmers[1] < 1) {
+        fprintf(stderr, "classify_read: WARN: a k-mer set is empty: --rows device: rows are made on the host (fallback=empty_set)\n");
+        rs.st_rows_fallback = "empty_set";
+        return;
+    }
+    if (hast_rs_set_rows(rs.feed, 1, (uint32_t)rs.total_kmers[0], (uint32_t)rs.total_kmers[1]) != HAST_OK) die(4, "cannot create the device ingest's rows");
+    rs.rows_on_device = true;
 }
 
 // the votes of b's reads, one contiguous share of the reads per GPU; what went wrong, or nothing
@@ -573,8 +581,12 @@ struct DeviceRoute {
     void step() {                                           // frame and classify the oldest submitted block, format its rows
         hast_rs_block b;
         hast_rs_binned rb;
+        hast_rs_rows rw{};
         const double t0 = now_s();
-        if ((rs.o.bin_reads ? hast_rs_next_binned(feed, &b, &rb) : hast_rs_next(feed, &b)) != HAST_OK) die(4, "framing and classifying a block");
+        const hast_status st = rs.rows_on_device ? hast_rs_next_rows(feed, &b, rs.o.bin_reads ? &rb : nullptr, &rw)
+                               : rs.o.bin_reads  ? hast_rs_next_binned(feed, &b, &rb)
+                                                 : hast_rs_next(feed, &b);
+        if (st != HAST_OK) die(4, "framing and classifying a block");
         const double t1 = now_s();
         --pending;
         ++rs.st_blocks;
@@ -582,7 +594,14 @@ struct DeviceRoute {
         if (b.flags & HAST_RS_FORMAT_ERROR) verdict = 1;
         else if (b.flags & HAST_RS_RECORD_TOO_LONG) verdict = 2;
         if (verdict) return;
-        format_rows(sh.out_rows, b.names, b.name_off, b.votes, (size_t)b.records, rs.total_kmers);
+        if (rs.rows_on_device && !rw.on_host) {              // finished text: nothing is formatted here
+            sh.out_rows.append(reinterpret_cast<const char *>(rw.text), (size_t)rw.bytes);
+            ++rs.st_row_views[0];
+            rs.st_row_bytes += rw.bytes;
+        } else {
+            format_rows(sh.out_rows, b.names, b.name_off, b.votes, (size_t)b.records, rs.total_kmers);
+            ++rs.st_row_views[1];
+        }
         framed_records += b.records;
         if (rs.o.bin_reads)
             for (int c = 0; c < 3; ++c) {
@@ -664,11 +683,13 @@ int process_input(Run &rs, HostRoute &host, DeviceRoute *dev, size_t ri) {
     if (dev && (stat(r.c_str(), &sb) != 0 || !S_ISREG(sb.st_mode))) {
         fprintf(stderr, "classify_read: WARN: %s is not a regular file: host ingest for this input (fallback=not_a_regular_file)\n", r.c_str());
         rs.st_fallback = "not_a_regular_file";
+        if (rs.rows_on_device) rs.st_rows_fallback = "not_a_regular_file";
     } else if (dev) v = dev->file(r);
     if (v == 2) {
         fprintf(stderr, "classify_read: WARN: a record of %s does not fit two blocks of %zu bytes: host ingest for this input (fallback=record_too_long)\n",
                 r.c_str(), rs.rs_block);
         rs.st_fallback = "record_too_long";
+        if (rs.rows_on_device) rs.st_rows_fallback = "record_too_long";
         if (o.bin_reads) {                                  // the file is read again from its start: so are its bins
             sh.bins.discard();
             sh.bins.start(o.bin_dir, o.bin_base[ri], o.fastq ? "fastq" : "fasta", o.gz_out);
@@ -692,6 +713,10 @@ void print_stats(const Run &rs) {
     fprintf(stderr, "[stats] ingest %s: blocks_framed=%llu records=%llu gz_on_device=%llu fallback=%s\n", rs.feed ? "device" : "host", (unsigned long long)rs.st_blocks,
             (unsigned long long)sh.st_records, (unsigned long long)rs.st_gz, rs.st_fallback.c_str());
     fprintf(stderr, "[stats] seconds: read=%.3f upload=%.3f kernels=%.3f rows=%.3f read_phase=%.3f\n", rs.st_read, rs.st_upload, sh.st_kernels, sh.st_rows, now_s() - rs.t_phase);
+    if (rs.o.rows_given)
+        fprintf(stderr, "[stats] rows: route=%s views_on_device=%llu views_on_host=%llu bytes=%llu fallback=%s\n", rs.rows_on_device ? "device" : "host",
+                (unsigned long long)(rs.rows_on_device ? rs.st_row_views[0] : 0), (unsigned long long)(rs.rows_on_device ? rs.st_row_views[1] : 0),
+                (unsigned long long)rs.st_row_bytes, rs.st_rows_fallback.c_str());
     if (rs.o.bin_reads)
         fprintf(stderr, "[stats] bins: haplotype0=%llu haplotype1=%llu ambiguous=%llu bytes_on_device=%llu bytes_on_host=%llu gz=%d\n", (unsigned long long)sh.st_bin.cls[0],
                 (unsigned long long)sh.st_bin.cls[1], (unsigned long long)sh.st_bin.cls[2], (unsigned long long)sh.st_bin.dev, (unsigned long long)sh.st_bin.host, rs.o.gz_out ? 1 : 0);

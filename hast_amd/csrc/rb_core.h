@@ -1,7 +1,7 @@
 // rb_core.h -- "read bins": the rules by which `classify_read --bin-reads` routes every read, as its bytes lie in the input, to one of
 // three runs (haplotype0, haplotype1, ambiguous).  Plain integer and double code: the kernels (rs_kernels.hip: k_rb_*) and the host
-// model (rb_host.h, tests/native/test_rb_core.cpp) step the same functions, and so does format_rows of classify_read_main.cpp, so that
-// a row and a bin can never disagree.
+// model (rb_host.h, tests/native/test_rb_core.cpp) step the same functions, and so do the rows (format_rows of rr_host.h, rr_core.h),
+// so that a row and a bin can never disagree.
 //
 //   class    from the votes v0, v1 and the two set sizes t0, t1 (s03:110-133, 215-216): d0 = (double)v0 / t0, d1 = (double)v1 / t1;
 //            neither above 0: ambiguous (2); else d1 > d0: haplotype1 (1); else haplotype0 (0).  A set size of 0 (inf, NaN) goes through

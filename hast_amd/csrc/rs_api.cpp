@@ -1,5 +1,6 @@
 // rs_api.cpp -- the part of the C ABI behind `classify_read --ingest device` (include/hast.h "stage 03 ingest on the device"): raw
-// FASTA / FASTQ bytes in HBM are framed into reads (rs_kernels.hip, rules: rs_core.h) and classified per read where they lie.
+// FASTA / FASTQ bytes in HBM are framed into reads (rs_kernels.hip, rules: rs_core.h) and classified per read where they lie; with
+// the rows switched on (`--rows device`; rr_kernels.hip, rules: rr_core.h) their rows are made there too and only text comes back.
 #include <hip/hip_runtime.h>
 
 #include <new>
@@ -39,7 +40,19 @@ struct hast_rs {
     dz::EncoderSlot enc;
     dz::Result *h_dzres = nullptr;                           // pinned
     size_t gz_cap = 0;
+    // the rows (hast_rs_set_rows): nothing of this is allocated before they are first switched on
+    int row_mode = 0;
+    uint32_t row_total[2] = {0, 0};
+    RrScratchPlan rr_plan{};
+    uint8_t *d_rr = nullptr, *d_rows = nullptr, *h_rows = nullptr;     // tile sums and state; the text of a view, device and pinned
+    RrState *h_rr = nullptr;                                 // pinned
+    size_t rows_cap = 0;
 };
+
+// The room for a view's rows, device and pinned: block_bytes, half of what a view can hold.  Reads as sequencers name them need about
+// 0.15 x their bytes, long reads next to nothing; only records of a few bytes each need more than half (">\n" makes a row of 15), and
+// such a view goes to the host.
+static size_t rows_room(size_t block_bytes) { return block_bytes; }
 
 extern "C" {
 
@@ -140,17 +153,72 @@ hast_status hast_rs_set_bins(hast_rs *f, int mode, uint32_t total0, uint32_t tot
     return HAST_OK;
 }
 
-static hast_status rs_next(hast_rs *f, hast_rs_block *out, hast_rs_binned *bins);
+hast_status hast_rs_set_rows(hast_rs *f, int mode, uint32_t total0, uint32_t total1) {
+    if (!f) return set_error(HAST_ERR_INVALID, "null feed");
+    if (mode < 0 || mode > 1) return set_error(HAST_ERR_INVALID, "hast_rs_set_rows: mode %d", mode);
+    if (f->in.plan.waiting()) return set_error(HAST_ERR_INVALID, "hast_rs_set_rows: a submitted block waits for hast_rs_next");
+    if (mode && (!total0 || !total1)) return set_error(HAST_ERR_INVALID, "hast_rs_set_rows: a set size of 0 (the rows of an empty set are the host's)");
+    if (mode && f->bin_mode && (f->bin_total[0] != total0 || f->bin_total[1] != total1))
+        return set_error(HAST_ERR_INVALID, "hast_rs_set_rows: set sizes %u, %u, the bins have %u, %u", total0, total1, f->bin_total[0], f->bin_total[1]);
+    HAST_HIP_TRY(hipSetDevice(f->in.device));
+    if (mode && !f->d_rr) {                          // the buffers of the rows, at the first switch-on
+        f->rr_plan = rr_scratch_plan(f->plan.max_rec);
+        f->rows_cap = rows_room(f->in.plan.block);
+        HAST_HIP_TRY(dev_malloc(&f->d_rr, f->rr_plan.total));
+        HAST_HIP_TRY(dev_malloc(&f->d_rows, f->rows_cap));
+        HAST_HIP_TRY(pinned_malloc(&f->h_rows, f->rows_cap));
+        HAST_HIP_TRY(pinned_malloc(&f->h_rr, sizeof(RrState)));
+    }
+    f->row_mode = mode;
+    f->row_total[0] = total0;
+    f->row_total[1] = total1;
+    return HAST_OK;
+}
 
-hast_status hast_rs_next(hast_rs *f, hast_rs_block *out) { return rs_next(f, out, nullptr); }
+static hast_status rs_next(hast_rs *f, hast_rs_block *out, hast_rs_binned *bins, hast_rs_rows *rows);
+
+hast_status hast_rs_next(hast_rs *f, hast_rs_block *out) { return rs_next(f, out, nullptr, nullptr); }
 
 hast_status hast_rs_next_binned(hast_rs *f, hast_rs_block *out, hast_rs_binned *bins) {
     if (!bins) return set_error(HAST_ERR_INVALID, "null argument");
     *bins = hast_rs_binned{};
-    return rs_next(f, out, bins);
+    return rs_next(f, out, bins, nullptr);
 }
 
-static hast_status rs_next(hast_rs *f, hast_rs_block *out, hast_rs_binned *bins) {
+hast_status hast_rs_next_rows(hast_rs *f, hast_rs_block *out, hast_rs_binned *bins, hast_rs_rows *rows) {
+    if (!rows) return set_error(HAST_ERR_INVALID, "null argument");
+    *rows = hast_rs_rows{};
+    if (bins) *bins = hast_rs_binned{};
+    return rs_next(f, out, bins, rows);
+}
+
+hast_status hast_rs_rows_device(hast_ctx *ctx, const uint8_t *d_names, const uint32_t *d_name_off, const uint32_t *d_votes, size_t n, uint32_t total0,
+                                uint32_t total1, uint8_t *d_out, size_t cap, uint64_t *bytes, uint64_t count[3]) {
+    if (!ctx || !bytes || !count) return set_error(HAST_ERR_INVALID, "null argument");
+    *bytes = 0;
+    count[0] = count[1] = count[2] = 0;
+    if (!total0 || !total1) return set_error(HAST_ERR_INVALID, "hast_rs_rows_device: a set size of 0");
+    if (n >= (1ull << 32) - 1) return set_error(HAST_ERR_INVALID, "hast_rs_rows_device: %zu reads", n);
+    if (!n) return HAST_OK;
+    if (!d_names || !d_name_off || !d_votes || (cap && !d_out)) return set_error(HAST_ERR_INVALID, "null argument");
+    HAST_HIP_TRY(hipSetDevice(ctx_device_of(ctx)));
+    hipStream_t stream = ctx_stream_of(ctx);
+    const RrScratchPlan plan = rr_scratch_plan(n);
+    uint8_t *d_rr = nullptr;
+    HAST_HIP_TRY(dev_malloc(&d_rr, plan.total));
+    RrState st{};
+    hipError_t e = launch_rr_rows(d_names, d_name_off, d_votes, n, total0, total1, d_rr, plan, d_out, cap, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&st, d_rr + plan.state, sizeof(RrState), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    park_device(d_rr, plan.total, 3);
+    HAST_HIP_TRY(e);
+    *bytes = st.total;
+    if (!st.written) return set_error(HAST_ERR_UNSUPPORTED, "hast_rs_rows_device: the rows need %llu bytes, the output has room for %zu", (unsigned long long)st.total, cap);
+    for (int c = 0; c < 3; ++c) count[c] = st.count[c];
+    return HAST_OK;
+}
+
+static hast_status rs_next(hast_rs *f, hast_rs_block *out, hast_rs_binned *bins, hast_rs_rows *rows) {
     if (!f || !out) return set_error(HAST_ERR_INVALID, "null argument");
     if (hast_status st = f->in.wait_step()) return st;
     carry::Plan &p = f->in.plan;
@@ -190,17 +258,30 @@ static hast_status rs_next(hast_rs *f, hast_rs_block *out, hast_rs_binned *bins)
     if (n_rec > f->plan.max_rec) return set_error(HAST_ERR_INVALID,"hast_rs_next: %zu records, scratch for %zu", n_rec, f->plan.max_rec);
     if (hast_status st = rs_grow(f, n_rec, (size_t)s.name_bytes)) return st;
     uint32_t *d_votes = reinterpret_cast<uint32_t *>(f->d_scratch + f->plan.votes);
+    const uint32_t *d_name_off = reinterpret_cast<const uint32_t *>(f->d_scratch + f->plan.name_off);
+    const bool rowed = rows && f->row_mode;          // names and votes stay where they are, unless the rows turn out not to fit
+    auto download_block = [&]() -> hast_status {
+        if (n_rec) {
+            HAST_HIP_TRY(hipMemcpyAsync(f->h_votes, d_votes, n_rec * 8, hipMemcpyDeviceToHost, stream));
+            if (s.name_bytes) HAST_HIP_TRY(hipMemcpyAsync(f->h_names, f->d_names, (size_t)s.name_bytes, hipMemcpyDeviceToHost, stream));
+        }
+        HAST_HIP_TRY(hipMemcpyAsync(f->h_name_off, d_name_off, (n_rec + 1) * 4, hipMemcpyDeviceToHost, stream));
+        return HAST_OK;
+    };
     if (n_rec) {
         const uint64_t *d_off = reinterpret_cast<const uint64_t *>(f->d_scratch + f->plan.off);
         const uint32_t *d_len = reinterpret_cast<const uint32_t *>(f->d_scratch + f->plan.len);
         const uint8_t *d_buf = fastq ? d_in : f->d_seq;
         const size_t buf_bytes = fastq ? v.off + v.bytes : (size_t)s.bases;
         if (hast_status st = classify_framed_perread(f->ctx, d_buf, buf_bytes, d_off, d_len, d_votes, n_rec, stream)) return st;
-        HAST_HIP_TRY(hipMemcpyAsync(f->h_votes, d_votes, n_rec * 8, hipMemcpyDeviceToHost, stream));
-        if (s.name_bytes) HAST_HIP_TRY(hipMemcpyAsync(f->h_names, f->d_names, (size_t)s.name_bytes, hipMemcpyDeviceToHost, stream));
     }
-    HAST_HIP_TRY(hipMemcpyAsync(f->h_name_off, f->d_scratch + f->plan.name_off, (n_rec + 1) * 4, hipMemcpyDeviceToHost, stream));
+    if (!rowed)
+        if (hast_status st = download_block()) return st;
     if (hast_status st = f->in.carry(v, left, (size_t)s.consumed)) return st;
+    if (rowed) {                                     // behind the classification: names and votes are read where they lie
+        HAST_HIP_TRY(launch_rr_rows(f->d_names, d_name_off, d_votes, n_rec, f->row_total[0], f->row_total[1], f->d_rr, f->rr_plan, f->d_rows, f->rows_cap, stream));
+        HAST_HIP_TRY(hipMemcpyAsync(f->h_rr, f->d_rr + f->rr_plan.state, sizeof(RrState), hipMemcpyDeviceToHost, stream));
+    }
     const bool binned = bins && f->bin_mode && n_rec;
     if (binned) {                                    // behind the classification: the votes are read where they lie
         HAST_HIP_TRY(launch_rb_bin(f->format, d_in, v.off, v.bytes, f->bin_total[0], f->bin_total[1], f->d_scratch, f->plan, f->d_rb, f->rb_plan, f->d_out, stream));
@@ -213,6 +294,22 @@ static hast_status rs_next(hast_rs *f, hast_rs_block *out, hast_rs_binned *bins)
         }
     }
     if (hast_status st = framed_err(f->ctx, stream)) return st;              // (waits for the stream)
+    bool rows_on_host = false;
+    if (rowed) {                                     // the size is known now: the text comes down, or, if it did not fit, names and votes as ever
+        const RrState r = *f->h_rr;
+        if (r.count[0] + r.count[1] + r.count[2] != n_rec || (r.written && r.total > f->rows_cap)) return set_error(HAST_ERR_INVALID, "hast_rs_next_rows: the rows do not add up");
+        rows_on_host = !r.written;
+        if (rows_on_host) {
+            if (hast_status st = download_block()) return st;
+        } else if (r.total) {
+            HAST_HIP_TRY(hipMemcpyAsync(f->h_rows, f->d_rows, (size_t)r.total, hipMemcpyDeviceToHost, stream));
+        }
+        rows->on_host = rows_on_host;
+        rows->text = rows_on_host ? nullptr : f->h_rows;
+        rows->bytes = rows_on_host ? 0 : r.total;
+        for (int c = 0; c < 3; ++c) rows->count[c] = r.count[c];
+        if (!binned) HAST_HIP_TRY(hipStreamSynchronize(stream));
+    }
     if (binned) {                                    // the sizes are known now: the runs (or their members) come down, and are waited for
         const RbState b = *f->h_rb;
         if (b.total > v.bytes || b.count[0] + b.count[1] + b.count[2] != n_rec) return set_error(HAST_ERR_INVALID, "hast_rs_next_binned: the runs do not add up");
@@ -245,9 +342,11 @@ static hast_status rs_next(hast_rs *f, hast_rs_block *out, hast_rs_binned *bins)
     out->records = n_rec;
     out->bases = s.bases;
     out->name_bytes = s.name_bytes;
-    out->votes = f->h_votes;
-    out->name_off = f->h_name_off;
-    out->names = f->h_names;
+    if (!rowed || rows_on_host) {
+        out->votes = f->h_votes;
+        out->name_off = f->h_name_off;
+        out->names = f->h_names;
+    }
     return HAST_OK;
 }
 
@@ -277,6 +376,10 @@ void hast_rs_destroy(hast_rs *f) {
     park_pinned(f->h_gz, f->gz_cap, 3);
     dz::slot_release(&f->enc, true);
     park_pinned(f->h_dzres, sizeof(dz::Result), 3);
+    park_device(f->d_rr, f->rr_plan.total, 3);
+    park_device(f->d_rows, f->rows_cap, 3);
+    park_pinned(f->h_rows, f->rows_cap, 3);
+    park_pinned(f->h_rr, sizeof(RrState), 3);
     delete f;
 }
 

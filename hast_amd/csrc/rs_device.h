@@ -88,4 +88,35 @@ inline RbScratchPlan rb_scratch_plan(const RsScratchPlan &rs) {
 hipError_t launch_rb_bin(int format, const uint8_t *d_base, size_t origin, size_t n, uint32_t total0, uint32_t total1, const uint8_t *d_scratch,
                          const RsScratchPlan &plan, uint8_t *d_rb, const RbScratchPlan &rb, uint8_t *d_out, hipStream_t s);
 
+// ---- the rows (`classify_read --rows device`, rules: rr_core.h; kernels: rr_kernels.hip) -----------------------------------------
+struct RrState {               // device memory, copied to the host behind the rows
+    uint64_t total;            // bytes of all rows, whether they were written or not
+    uint64_t count[3];         // reads per class
+    uint32_t written;          // 1: the rows lie in the output; 0: they did not fit and not one byte was stored
+    uint32_t pad;
+};
+
+// scratch for the rows of up to max_rec reads: per tile of kRsTile reads the bytes of its rows (64 bits) and its reads per class
+struct RrScratchPlan {
+    size_t tile_bytes, tile_cnt, state, total;
+};
+inline RrScratchPlan rr_scratch_plan(size_t max_rec) {
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t rec_tiles = max_rec / kRsTile + 2;
+    RrScratchPlan p;
+    size_t at = 0;
+    p.tile_bytes = at; at += up(rec_tiles * 8);
+    p.tile_cnt = at;   at += up(3 * rec_tiles * 4);
+    p.state = at;      at += up(sizeof(RrState));
+    p.total = at;
+    return p;
+}
+
+// The rows of the n reads (n < 2^32) with the names d_names[d_name_off[r], d_name_off[r + 1]) and the votes d_votes[2 r], d_votes[2 r + 1]
+// against the set sizes t0, t1 (both at least 1), back to back in read order to d_out (room for cap bytes).  When the stream has run,
+// the RrState of d_rr holds the size and the counts; rows that need more than cap bytes, or 2^32 and more, are not written: nothing
+// is stored at or behind d_out + min(total, cap) either way.  Reads the names and votes only.
+hipError_t launch_rr_rows(const uint8_t *d_names, const uint32_t *d_name_off, const uint32_t *d_votes, size_t n, uint32_t t0, uint32_t t1, uint8_t *d_rr,
+                          const RrScratchPlan &plan, uint8_t *d_out, uint64_t cap, hipStream_t s);
+
 }  // namespace hast

@@ -861,7 +861,25 @@ hast_status hast_sq_feed_finish(hast_sq_feed *, int parent, hast_sq_result *res)
  *                         sizes.  Only while no submitted block waits for _next (HAST_ERR_INVALID otherwise).  The buffers of the bins
  *                         are allocated at the first switch-on and go with hast_rs_destroy: a feed that never asks has none.
  *   hast_rs_next_binned   hast_rs_next plus the bins of the same view; returns when the runs lie in pinned memory.  With flags != 0,
- *                         or with the bins switched off, *bins is all zero. */
+ *                         or with the bins switched off, *bins is all zero.
+ * The rows (`classify_read --rows device`; rules: hast_amd/csrc/rr_core.h, model: rr_host.h): the text the program prints per read,
+ * "name \t haplotype0|haplotype1 \t D \n" or "name \t ambiguous \t 0.0 \n", made on the GPU from the names and votes where the framer
+ * and the classifier leave them, in read order.  The class is the bins' (rb_core.h); D is what printf("%0.6f") prints for
+ * (double)votes / (double)total, worked out from the double's bits in integers (rounded to nearest, ties to even).  Both set sizes must
+ * be at least 1: the rows of an empty set ("inf", "nan") are the host's.
+ *   hast_rs_rows_device   the rows of n reads from device arrays (names back to back, name_off[n + 1], votes[n][2]) to d_out, on the
+ *                         context's stream; returns when they are written.  *bytes = their size, count[] = reads per class.  More than
+ *                         cap bytes (or 2^32 and more): HAST_ERR_UNSUPPORTED, *bytes = what is needed, nothing written.  A set size of
+ *                         0: HAST_ERR_INVALID.
+ *   hast_rs_set_rows      mode 0 off, 1 on; total0 / total1: the two set sizes, at least 1 each, and the bins' if those are on
+ *                         (HAST_ERR_INVALID otherwise).  Only while no submitted block waits for _next.  The row buffers, device and
+ *                         pinned, hold block_bytes of text (half a view; real reads need about 0.15 x their bytes); they are allocated
+ *                         at the first switch-on and go with hast_rs_destroy.
+ *   hast_rs_next_rows     hast_rs_next_binned (bins may be NULL) plus the rows of the same view: rows->text (pinned, valid until the next
+ *                         call), rows->bytes, rows->count[].  Names and votes are then NOT downloaded: out->names, name_off and votes
+ *                         are NULL.  A view whose rows outgrow the buffer -- records of a few bytes each: ">\nA\n" needs 3.75 x its
+ *                         bytes -- comes back with rows->on_host = 1, text = NULL and names and votes as hast_rs_next gives them, for the
+ *                         caller to format.  flags != 0 as in hast_rs_next, *rows all zero; so it is with the rows switched off. */
 typedef struct hast_rs hast_rs;
 typedef struct {
     uint64_t consumed, records, bases, name_bytes;
@@ -887,6 +905,16 @@ typedef struct {
 } hast_rs_binned;
 hast_status hast_rs_set_bins(hast_rs *, int mode /* 0 off, 1 plain, 2 gzip */, uint32_t total0, uint32_t total1);
 hast_status hast_rs_next_binned(hast_rs *, hast_rs_block *out, hast_rs_binned *bins);
+typedef struct {
+    const uint8_t *text;        /* pinned, valid until the next hast_rs_next_rows; NULL with on_host */
+    uint64_t bytes;
+    uint64_t count[3];          /* reads per class */
+    uint32_t on_host;           /* 1: the rows did not fit; names and votes of *out are there instead */
+} hast_rs_rows;
+hast_status hast_rs_rows_device(hast_ctx *, const uint8_t *d_names, const uint32_t *d_name_off, const uint32_t *d_votes, size_t n, uint32_t total0,
+                                uint32_t total1, uint8_t *d_out, size_t cap, uint64_t *bytes, uint64_t count[3]);
+hast_status hast_rs_set_rows(hast_rs *, int mode /* 0 off, 1 on */, uint32_t total0, uint32_t total1);
+hast_status hast_rs_next_rows(hast_rs *, hast_rs_block *out, hast_rs_binned *bins_or_null, hast_rs_rows *rows);
 hast_status hast_rs_take_tail(hast_rs *, uint8_t *dst, size_t *n_bytes);
 void        hast_rs_destroy(hast_rs *);
 
