@@ -48,6 +48,7 @@ struct Stats {
 };
 
 using hast::now_s;
+namespace sw = hast::sw;
 
 int usage() {
     fprintf(stderr, "usage: barcode_freq [--count device|host] [--device N | --devices a,b,...] [--inflate device|host|zlib] [--block-mb N]\n"
@@ -284,8 +285,7 @@ int main(int argc, char **argv) {
         else o.in.push_back(a);
     }
     if (o.in.empty()) return usage();
-    if (const char *e = getenv("HAST_BF_BLOCK"))             // tests: blocks of a few hundred bytes
-        if (!o.block_given && atol(e) >= 1) { o.block = (size_t)atol(e); o.block_given = true; }
+    if (!o.block_given) o.block_given = sw::size(sw::HAST_BF_BLOCK, &o.block);            // tests: blocks of a few hundred bytes
     if (o.inflate == "zlib") setenv("HAST_INFLATE", "zlib", 1);
 
     const double t_start = now_s();

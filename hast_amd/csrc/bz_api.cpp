@@ -31,6 +31,7 @@
 #include "bz_core.h"
 #include "bz_device.h"
 #include "hast_internal.h"
+#include "switches.h"
 
 namespace hast {
 namespace bz {
@@ -301,10 +302,8 @@ hast_status stream_open(hast_ctx *ctx, const char *path, size_t batch_in_bytes, 
     z->fd = fd;
     z->path = path;
     z->file_size = (uint64_t)sb.st_size;
-    if (!batch_in_bytes)
-        if (const char *e = getenv("HAST_BZ_BATCH_IN_BYTES")) batch_in_bytes = (size_t)std::max(0L, atol(e));
-    if (!batch_out_bytes)
-        if (const char *e = getenv("HAST_BZ_BATCH_OUT_BYTES")) batch_out_bytes = (size_t)std::max(0L, atol(e));
+    if (!batch_in_bytes) sw::size(sw::HAST_BZ_BATCH_IN_BYTES, &batch_in_bytes);
+    if (!batch_out_bytes) sw::size(sw::HAST_BZ_BATCH_OUT_BYTES, &batch_out_bytes);
     z->batch_in = std::max<size_t>(batch_in_bytes ? batch_in_bytes : kBatchIn, kMaxMember);
     z->batch_out = std::max<size_t>(batch_out_bytes ? batch_out_bytes : kBatchOut, kMaxIsize);
     if (z->batch_in > (1u << 30) || z->batch_out > (1ull << 32)) {

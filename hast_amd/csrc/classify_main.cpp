@@ -58,6 +58,7 @@
 namespace {
 
 using hast::now_s;
+namespace sw = hast::sw;
 using hast::parse_count;
 
 void logtime() {                                  // classify.cpp:17-21
@@ -449,16 +450,14 @@ bool parse_options(int argc, char **argv, Options &o) {
     static char optstring[] = "p:m:l:r:t:w:u:f:q:h";             // classify.cpp:387
     bool gz_out_flag = false;
     int device = 0;
-    const char *bgzf = getenv("HAST_BGZF");                       // (the alias for runs of the unchanged wrapper; the flag wins)
-    const char *gz_format = getenv("HAST_PHASE_GZ_FORMAT");       // (the same; ignored where nothing is written as gzip)
-    const char *rows = getenv("HAST_ROWS");                       // (the same)
+    // (the aliases for runs of the unchanged wrapper; a flag wins.  These three are held to the rule of their flag below: a wrong word
+    // is the usage text, not a variable that is ignored)
+    const char *bgzf = sw::text(sw::HAST_BGZF);
+    const char *gz_format = sw::text(sw::HAST_PHASE_GZ_FORMAT);   // (ignored where nothing is written as gzip)
+    const char *rows = sw::text(sw::HAST_ROWS);
     bool gz_format_flag = false;
-    {
-        const char *pr = getenv("HAST_PHASE_READS");
-        o.phase_reads = pr && *pr && strcmp(pr, "0") != 0;
-        const char *pg = getenv("HAST_PHASE_GZ");
-        o.gz_out = pg && *pg && strcmp(pg, "0") != 0;
-    }
+    o.phase_reads = sw::flag(sw::HAST_PHASE_READS);
+    o.gz_out = sw::flag(sw::HAST_PHASE_GZ);
     for (;;) {
         int c = getopt_long(argc, argv, optstring, long_options, NULL);
         if (c < 0) break;
@@ -594,10 +593,9 @@ size_t inputs_open_at_once(const Run &rs, bool same_prefix) {
 // --bgzf device: a blocked-gzip input goes to the GPU too, inflated member by member (hast_gz_open_blocked) -- with one context or
 // whole files dealt to the contexts; a striped run keeps it on the host.
 void find_device_gz_inputs(Run &rs) {
-    const char *which = getenv("HAST_INFLATE");
-    const bool allow = !rs.o.host_parse && (!which || !strcmp(which, "device"));
-    const char *deal = getenv("HAST_DEAL");
-    const bool blocked_ok = rs.o.bgzf_device && (rs.o.devices.size() <= 1 || (deal && !strcmp(deal, "files")));
+    const int which = sw::word(sw::HAST_INFLATE);                 // (device 0, host 1, zlib 2; unset -1)
+    const bool allow = !rs.o.host_parse && which <= 0;
+    const bool blocked_ok = rs.o.bgzf_device && (rs.o.devices.size() <= 1 || sw::word_is(sw::HAST_DEAL, "files"));
     for (size_t i = 0; allow && i < rs.o.read.size(); i++) {
         const std::string &r = rs.o.read[i];
         struct stat sb;
@@ -683,12 +681,11 @@ void create_dictionaries(Run &rs) {
     // (2 x 32 B per barcode it can hold + 16 B of text by id: 1.3 GB for 16M -- BASELINE config 3 has 10M barcodes; what does not fit
     // is named by the host, in an id range of its own)
     size_t name_cap = std::max<size_t>(o.initial_barcodes, 1u << 24);
-    if (const char *e = getenv("HAST_NAME_CACHE")) name_cap = (size_t)atol(e);
+    sw::size(sw::HAST_NAME_CACHE, &name_cap);
     // HAST_NAME_DICT=0: the table only caches what the host's dictionary names (up to round 5); HAST_NAME_DICT=context: a dictionary
     // per CONTEXT even where contexts share a GPU (tests: the merge by text of several GPUs' dictionaries, on one GPU)
-    const char *nd = getenv("HAST_NAME_DICT");
-    rs.naming.device_dict = name_cap && !(nd && !strcmp(nd, "0"));
-    const bool per_context = nd && !strcmp(nd, "context");
+    rs.naming.device_dict = name_cap && !sw::word_is(sw::HAST_NAME_DICT, "0");
+    const bool per_context = sw::word_is(sw::HAST_NAME_DICT, "context");
     for (size_t i = 0; i < rs.ctxs.size(); i++) {
         // one per GPU: contexts that share a device (--devices 0,0) share it
         hast_names *nm = nullptr;
@@ -737,8 +734,7 @@ void contexts_ready(Run &rs) {
     create_other_contexts(rs);
     if (rs.o.host_parse) return;
     // several GPUs: the blocks of every file go to all of them in turn (a striped stream); HAST_DEAL=files deals whole files
-    const char *deal = getenv("HAST_DEAL");
-    rs.stripe = rs.ctxs.size() > 1 && !(deal && !strcmp(deal, "files"));
+    rs.stripe = rs.ctxs.size() > 1 && !sw::word_is(sw::HAST_DEAL, "files");
     create_dictionaries(rs);
     start_stream_setup(rs);
 }
@@ -2072,7 +2068,7 @@ void print_statistics(Run &rs) {
         stat_line("__stats_dictionary__ on=device dictionaries=%zu ids_limit=%zu ids_from_device=%zu ids_from_host=%zu merge_by_text_s=%.3f texts_merged_to_host=%zu rows_summed_by_text=%zu\n", rs.naming.groups.size(), rs.naming.host_base, rs.n_dev_names, rs.n_host_names, rs.naming.merge_s,
                   rs.naming.merged_to_host, rs.n_rows_summed);
     if (o.stats) {                                   // the sizes as the library reads them: what a flag with a suffix came to
-        const char *nc = getenv("HAST_NAME_CACHE"), *rb = getenv("HAST_GZ_RING_BYTES"), *pg = getenv("HAST_PARK_GB");
+        const char *nc = sw::text(sw::HAST_NAME_CACHE), *rb = sw::text(sw::HAST_GZ_RING_BYTES), *pg = sw::text(sw::HAST_PARK_GB);
         stat_line("__stats_sizes__ name_cache=%s gz_ring_bytes=%s park_gb=%s\n", nc ? nc : "default", rb ? rb : "default", pg ? pg : "default");
     }
     if (o.stats) stat_line("__stats_setup__ waited_for_stream_setup_s=%.3f (inside scrub_sizes_clone_s: .gz inputs opened, FASTQ streams created while the table was built)\n", rs.t_pre_waited);
@@ -2116,9 +2112,7 @@ void print_statistics(Run &rs) {
 // unless a profiler is listening (rocprofv3 preloads its tool library and writes its files when the process ends in an orderly way).
 int leave(Run &rs) {
     const Options &o = rs.o;
-    const char *preload = getenv("LD_PRELOAD");
-    const bool profiled = getenv("ROCP_TOOL_LIBRARIES") || (preload && strstr(preload, "rocprofiler"));
-    if (!getenv("HAST_TEARDOWN") && !profiled) {
+    if (!sw::flag(sw::HAST_TEARDOWN) && !sw::profiler_listening()) {
         if (o.stats) stat_phases(rs, nullptr);
         if (!o.stats_json.empty() && !write_stats_json(o.stats_json)) fprintf(stderr, "classify: cannot write %s\n", o.stats_json.c_str());
         if (fflush(stdout) != 0) die_output();

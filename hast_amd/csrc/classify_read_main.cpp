@@ -59,6 +59,7 @@ namespace {
 
 using hast::format_rows;
 using hast::now_s;
+namespace sw = hast::sw;
 
 [[noreturn]] void die(int code, const std::string &what) {
     fprintf(stderr, "classify_read: ERROR: %s", what.c_str());
@@ -335,7 +336,7 @@ void clone_to_other_gpus(Run &rs) {
 void create_device_feed(Run &rs) {
     const Options &o = rs.o;
     rs.rs_block = (size_t)o.block_mb << 20;
-    if (getenv("HAST_RS_BLOCK")) rs.rs_block = (size_t)std::max(64L, atol(getenv("HAST_RS_BLOCK")));
+    sw::size(sw::HAST_RS_BLOCK, &rs.rs_block);
     if (!o.ingest_device) return;
     if (rs.ctxs.size() > 1) {
         fprintf(stderr, "classify_read: WARN: --ingest device takes one GPU: host ingest for this run (fallback=several_devices)\n");
@@ -424,10 +425,10 @@ void bin_tail(Batch &b, const char *tail, size_t n_tail) {
 // FASTA = '>' lines start a record, other non-empty lines are appended, a last line without '\n' is dropped
 // (s03:279-296).  Rows of a file are printed when the file is done, like PrintOutput after the loop (s03:269,301).
 struct HostRoute {
-    explicit HostRoute(Run &run) : rs(run), T(run.pool.size()), part((size_t)T + 1), bad((size_t)T), hl((size_t)T) {}
+    explicit HostRoute(Run &run) : rs(run), T(run.pool.size()), part((size_t)T + 1), bad((size_t)T), hl((size_t)T) { sw::size(sw::HAST_READ_BLOCK_BYTES, &block_bytes); }
     Run &rs;
     const int T;
-    const size_t block_bytes = (size_t)std::max(1L, getenv("HAST_READ_BLOCK_BYTES") ? atol(getenv("HAST_READ_BLOCK_BYTES")) : (256L << 20));
+    size_t block_bytes = (size_t)256 << 20;                 // HAST_READ_BLOCK_BYTES
     Batch w;                                                // the batch being parsed: classify_batch hands it to the background thread
     struct RecSpan { uint32_t head, seq_first, seq_end; };  // line indices; sequence lines [seq_first, seq_end)
     std::vector<RecSpan> recs;

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/hast.h"
+#include "switches.h"
 
 namespace hast {
 
@@ -41,25 +42,7 @@ inline bool slurp(const std::string &path, std::vector<char> &out) {
 // 0: stage 00's script looks at the last three bytes alone, s00:169)
 inline bool ends_gz(const std::string &s, size_t stem = 1) { return s.size() >= 3 + stem && s.compare(s.size() - 3, 3, ".gz") == 0; }
 
-// a count or a size on the command line: decimal digits and at most one of K, M, G behind them (powers of 1024, either case); anything
-// else -- no digits, a sign, a fraction, another suffix, trailing bytes, more than 64 bits hold -- is not a number
-inline bool parse_count(const char *text, uint64_t *out) {
-    if (!text || *text < '0' || *text > '9') return false;
-    errno = 0;
-    char *end = nullptr;
-    const unsigned long long v = strtoull(text, &end, 10);
-    if (errno || end == text) return false;
-    int shift = 0;
-    switch (*end) {
-    case 'K': case 'k': shift = 10; end++; break;
-    case 'M': case 'm': shift = 20; end++; break;
-    case 'G': case 'g': shift = 30; end++; break;
-    default: break;
-    }
-    if (*end || (shift && v > (~0ull >> shift))) return false;
-    *out = (uint64_t)v << shift;
-    return true;
-}
+// (parse_count, the grammar of a count or a size on the command line, is switches.h's: the environment takes the same)
 
 // --devices A,B,...: non-negative numbers with commas between them, appended to out; false: not such a list
 inline bool parse_device_list(const char *text, std::vector<int> &out) {

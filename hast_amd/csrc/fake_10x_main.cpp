@@ -46,6 +46,7 @@ struct Options {
 };
 
 using hast::now_s;
+namespace sw = hast::sw;
 
 int usage() {
     fprintf(stderr, "usage: fake_10x READ1.gz READ2.gz MERGE.txt [--inflate host|zlib|device] [--block-mb N] [--plain-out] [--stats]\n"
@@ -496,8 +497,7 @@ int main(int argc, char **argv) {
     r.o.in[0] = pos[0];
     r.o.in[1] = pos[1];
     r.o.map = pos[2];
-    if (const char *e = getenv("HAST_TX_BLOCK"))         // tests: blocks of a few KB
-        if (!block_given && atol(e) >= 64) r.o.block = (size_t)atol(e);
+    if (!block_given) sw::size(sw::HAST_TX_BLOCK, &r.o.block);         // tests: blocks of a few KB
     if (r.o.inflate == "zlib") setenv("HAST_INFLATE", "zlib", 1);
     printf("Merge stLFR reads into 10X format !\n read1 :  %s \n. read2 : %s \n map file : %s\n", pos[0].c_str(), pos[1].c_str(), pos[2].c_str());
     fflush(stdout);

@@ -22,6 +22,7 @@
 
 #include "../../include/hast.h"
 #include "ingest.h"
+#include "switches.h"
 
 namespace hast {
 
@@ -55,7 +56,7 @@ enum class FeedStatus {
 };
 
 inline bool feed_trace_blocks() {                     // HAST_TRACE_BLOCKS: a line on stderr per fill and per submit
-    static const bool on = getenv("HAST_TRACE_BLOCKS") != nullptr;
+    static const bool on = sw::flag(sw::HAST_TRACE_BLOCKS);
     return on;
 }
 inline double feed_now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }

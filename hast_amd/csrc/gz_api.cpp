@@ -37,6 +37,7 @@
 #include "gz_core.h"
 #include "gz_device.h"
 #include "hast_internal.h"
+#include "switches.h"
 #include "worker_pool.h"
 
 using namespace hast;
@@ -165,7 +166,7 @@ struct hast_gz {
     // stats
     hast_gz_stats st{};
     Unit &unit_of(size_t k) { return *units[k % units.size()]; }
-    int n_arenas = 3;                         // symbol arenas a unit takes turns with (3 with `ahead`, else 2; HAST_GZ_ARENAS)
+    int n_arenas = 3;                         // symbol arenas a unit takes turns with (ahead + 2)
     Arena &arena_of(size_t k) { return unit_of(k).arena[(k / units.size()) % (size_t)n_arenas]; }
     int jobs_of(size_t k) const { return (int)((k / units.size()) % (size_t)(ahead + 2)); }
     // ahead = 1: a unit's passes j and j + 1 are on the GPU TOGETHER (two streams, three arenas, three job arrays): a pass lasts as long as
@@ -198,7 +199,7 @@ namespace {
 
 // HAST_GZ_TRACE=1: where a segment's time goes on the producer's thread (allocations, waits), one line per step that took > 1 ms
 bool gz_trace() {
-    static const bool on = getenv("HAST_GZ_TRACE") != nullptr;
+    static const bool on = sw::flag(sw::HAST_GZ_TRACE);
     return on;
 }
 struct TraceStep {
@@ -484,7 +485,7 @@ std::string finish_segment(hast_gz *g, const Nominal &N, bool &finished) {
     const uint64_t input_bits = N.input_bits;
     const bool all_in = N.all_in;
     g->st.chunks += N.n_jobs;
-    if (getenv("HAST_GZ_TRACE_JOBS"))                               // (debugging: every pass's first jobs and all its candidates, as they came back)
+    if (sw::flag(sw::HAST_GZ_TRACE_JOBS))                              // (debugging: every pass's first jobs and all its candidates, as they came back)
         for (size_t i = 0; i < N.n_jobs; ++i) {
             const ChunkJob &j = U.h_jobs[g->jobs_of(N.k)][i];
             if (!(j.status & kStFound) && N.k >= 1) continue;
@@ -721,10 +722,7 @@ hast_status hast_gz_open_multi_ex(hast_ctx *const *ctxs, int n_ctx, const char *
     g->file_size = (uint64_t)sb.st_size;
     // one unit per GPU: contexts that share a device share the unit (HAST_GZ_SPLIT=contexts: a unit per context all the same, and
     // every reader's bytes through the bounce buffer + peer copy -- the several-GPU code on one GPU, for tests)
-    {
-        const char *e = getenv("HAST_GZ_SPLIT");
-        g->split_same_device = e && !strcmp(e, "contexts");
-    }
+    g->split_same_device = sw::word_is(sw::HAST_GZ_SPLIT, "contexts");
     for (int i = 0; i < n_ctx; ++i) {
         const int dev = hast_ctx_device(ctxs[i]);
         bool have = false;
@@ -739,10 +737,8 @@ hast_status hast_gz_open_multi_ex(hast_ctx *const *ctxs, int n_ctx, const char *
         g->units.push_back(std::move(u));
     }
     // (test switches for callers that cannot pass a geometry, e.g. the classify program: a small file then spans many passes)
-    if (!chunk_bytes)
-        if (const char *e = getenv("HAST_GZ_CHUNK_BYTES")) chunk_bytes = (size_t)std::max(0L, atol(e));
-    if (!seg_chunks)
-        if (const char *e = getenv("HAST_GZ_PASS_CHUNKS")) seg_chunks = (size_t)std::max(0L, atol(e));
+    if (!chunk_bytes) sw::size(sw::HAST_GZ_CHUNK_BYTES, &chunk_bytes);
+    if (!seg_chunks) sw::size(sw::HAST_GZ_PASS_CHUNKS, &seg_chunks);
     // Round 6: 16-KB chunks, 6144 a pass, 20 symbols of room per compressed byte (until then 32 KB / 4096 / 12).  A decode pass lasts as long
     // as its slowest wave and its waves issue for 39 % of their lifetime (profiles/round5_gz_kernels_pmc.txt): what it loses is occupancy,
     // so a pass wants more and finer work units than the GPU has wave slots (4480).  With 16-KB chunks a wave's work is ~one deflate block
@@ -757,20 +753,17 @@ hast_status hast_gz_open_multi_ex(hast_ctx *const *ctxs, int n_ctx, const char *
     // footprint small: on some boxes of the pool ONE HIP call of a process that starts right after another one freed tens of GB blocks
     // for 0.7-6 s (hipMalloc or hipStreamCreate, whichever comes first -- tools/probe/malloc_probe.py; the tree before did the same there).
     g->seg_chunks = seg_chunks ? seg_chunks : (chunk_bytes ? 4096 : 6144);
-    if (const char *e = getenv("HAST_GZ_AHEAD")) g->ahead = std::min(Unit::kDecStreams - 1, std::max(0, atoi(e)));
+    static_assert(sw::kRows[sw::HAST_GZ_AHEAD].hi == Unit::kDecStreams - 1 && Unit::kDecStreams + 1 <= Unit::kArenas, "a stream and an arena per pass in flight");
+    sw::integer(sw::HAST_GZ_AHEAD, &g->ahead);
     g->n_arenas = g->ahead + 2;
-    if (const char *e = getenv("HAST_GZ_ARENAS")) g->n_arenas = std::min((int)Unit::kArenas, std::max(g->ahead + 2, atoi(e)));
-    if (room <= 0)
-        if (const char *e = getenv("HAST_GZ_ROOM")) room = atof(e);          // (measurements: symbols of room per compressed byte of a chunk)
-    if (const char *e = getenv("HAST_GZ_SLOT_FRACTION")) {
-        g->slot_fraction = std::min(1.0, std::max(0.01, atof(e)));
-        g->slot_adaptive = false;
-    }
+    if (room <= 0) sw::real(sw::HAST_GZ_ROOM, &room);                     // (measurements: symbols of room per compressed byte of a chunk)
+    if (sw::real(sw::HAST_GZ_SLOT_FRACTION, &g->slot_fraction)) g->slot_adaptive = false;
     g->room = room > 0 ? room : (default_geometry ? 20.0 : 12.0);
     if (g->chunk_bytes > (1u << 26)) { close(fd); return set_error(HAST_ERR_INVALID, "chunk_bytes too large"); }
     g->slot_syms = (uint32_t)std::min<double>((double)(1u << 27), (double)g->chunk_bytes * g->room + 600);
     g->slot_syms = (g->slot_syms + 7) & ~7u;
-    if (const char *e = getenv("HAST_GZ_PIECE_BYTES")) g->piece = (size_t)std::min<long>((long)kPiece, std::max(4096L, atol(e) & ~4095L));
+    static_assert(sw::kRows[sw::HAST_GZ_PIECE_BYTES].hi == kPiece, "the row's upper bound is the default piece");
+    if (sw::size(sw::HAST_GZ_PIECE_BYTES, &g->piece)) g->piece &= ~(size_t)4095;
     const int cfd = fd;
     g->chain.begin(g->file_size, [cfd](uint64_t off, size_t n, uint8_t *dst, size_t *got) { return read_at(cfd, off, n, dst, got); });
     if (g->chain.failed()) {
@@ -795,7 +788,7 @@ hast_status hast_gz_open_multi_ex(hast_ctx *const *ctxs, int n_ctx, const char *
         const uint64_t pass = (uint64_t)seg * g->chunk_bytes;
         const uint64_t need = (uint64_t)(nu * (size_t)(1 + g->ahead) + 2) * pass + std::min<uint64_t>(pass, 16u << 20) + 4 * (uint64_t)g->piece;
         uint64_t ring = 2ull << 30;
-        if (const char *e = getenv("HAST_GZ_RING_BYTES")) ring = (uint64_t)std::max(0L, atol(e));
+        sw::size(sw::HAST_GZ_RING_BYTES, &ring);
         ring = std::max(ring, need);
         ring = (ring + g->piece - 1) / g->piece * g->piece;
         if (g->file_size + kInPad > ring + g->piece) g->ring = ring;
@@ -803,7 +796,7 @@ hast_status hast_gz_open_multi_ex(hast_ctx *const *ctxs, int n_ctx, const char *
     }
     hipError_t e = hipSuccess;
     auto step = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-    const bool trace = getenv("HAST_GZ_TRACE") != nullptr;
+    const bool trace = sw::flag(sw::HAST_GZ_TRACE);
     double t_tr = now_s();
     auto tr = [&](const char *what) {
         if (trace) fprintf(stderr, "gz open %s: %s %.3f s\n", path, what, now_s() - t_tr);
@@ -832,7 +825,7 @@ hast_status hast_gz_open_multi_ex(hast_ctx *const *ctxs, int n_ctx, const char *
             int n_cu = 0, free_cus = 32;
             hipDeviceProp_t prop;
             if (hipGetDeviceProperties(&prop, U.device) == hipSuccess) n_cu = prop.multiProcessorCount;
-            if (const char *fc = getenv("HAST_GZ_FREE_CUS")) free_cus = atoi(fc);
+            sw::integer(sw::HAST_GZ_FREE_CUS, &free_cus);
             if (e == hipSuccess && n_cu > 0 && free_cus > 0 && free_cus < n_cu) {
                 U.dec_stream[0] = masked_stream_get(U.device, n_cu, free_cus);
                 if (U.dec_stream[0]) U.dec_masked_free[0] = free_cus;
@@ -868,15 +861,8 @@ hast_status hast_gz_open_multi_ex(hast_ctx *const *ctxs, int n_ctx, const char *
         // by side: three) and the first one has its
         // final size at once although the file's first pass is a short one (it would be parked and allocated again two passes on).
         // That there IS room for the later one is checked here, so that a device without it is refused at the door (the caller then
-        // inflates on the host) instead of failing in mid-file
-        // HAST_GZ_PREALLOC=1: EVERYTHING a stream's passes will need is allocated here instead of at its first use (the later arenas, every
-        // arena's window / map / CRC buffers).  Tried on the round's last day against the runs whose read phase takes 0.6-1.7 s instead of
-        // 0.2 s (one in five on some boxes of the pool, none on others): there a hipMalloc in the middle of the read phase took 0.6-1.3 s
-        // and held up every stream of the process while it did ("windows / maps / crc buffers (ensure) 1.330 s" in both files' producers
-        // at once, profiles/round6_gz_slow_hunt.txt).  Allocating here MOVES that stall (open_s 0.8-2.5 s, the k-mer load beside it waiting
-        // as long), it does not remove it: the whole process takes as long either way (40 runs each, alternating) -- a process that starts
-        // right behind another one's exit pays it at one of its first large allocations.  Off by default
-        static const bool prealloc = getenv("HAST_GZ_PREALLOC") && atoi(getenv("HAST_GZ_PREALLOC")) > 0;
+        // inflates on the host) instead of failing in mid-file.  (Allocating everything here was tried and only moves a slow hipMalloc
+        // from the read phase into the open: docs/history.md)
         size_t later = 0;
         for (int i = 0; i < g->n_arenas && e == hipSuccess; ++i) {
             const size_t k = ui + (size_t)i * nu;
@@ -885,26 +871,8 @@ hast_status hast_gz_open_multi_ex(hast_ctx *const *ctxs, int n_ctx, const char *
             const size_t chunks = k == 0 ? (n_seg > (size_t)g->n_arenas * nu ? std::max(first, seg) : first) : seg;
             const size_t bytes = g->pool_slots(chunks) * (size_t)g->slot_syms * sizeof(uint16_t) + 64;
             Arena &a = U.arena[i];
-            if (i == 0 || prealloc) step(a.syms.ensure(bytes));
+            if (i == 0) step(a.syms.ensure(bytes));
             else later += bytes + chunks * ((size_t)kWindow * 3 + 64);              // (+ windows, maps, per-chunk words of a batch)
-            if (prealloc) {
-                const size_t n_max = chunks + 64;                                   // accepted chunks of a batch: a pass's, and a few follow-up jobs'
-                step(a.cursor.ensure(64));
-                step(a.acc.ensure(n_max * sizeof(AccDev)));
-                step(a.windows.ensure(n_max * (size_t)kWindow));
-                step(a.need.ensure(windows_scratch_bytes((uint32_t)n_max)));
-                step(a.crc.ensure(2 * n_max * sizeof(uint32_t)));
-                step(a.carry.ensure(kWindow));
-                a.gap.emplace_back();
-                step(a.gap[0].ensure(8u << 20));                                    // (a round of follow-up jobs' symbols; grows when one needs more)
-                if (U.h_crc_cap < n_max && e == hipSuccess) {
-                    park_pinned(U.h_crc, 0, 2);
-                    U.h_crc = nullptr;
-                    U.h_crc_cap = 0;
-                    step(pinned_malloc((void **)&U.h_crc, 2 * (n_max + n_max / 2 + 64) * sizeof(uint32_t), hipHostMallocDefault));
-                    if (e == hipSuccess) U.h_crc_cap = n_max + n_max / 2 + 64;
-                }
-            }
         }
         if (e == hipSuccess && later) {
             size_t free_b = 0, total_b = 0;
@@ -942,7 +910,7 @@ void hast_gz_close(hast_gz *g) {
         delete g;
         return;
     }
-    const bool trace = getenv("HAST_GZ_TRACE") != nullptr;
+    const bool trace = sw::flag(sw::HAST_GZ_TRACE);
     auto tr = [&](const char *what) {
         if (trace) fprintf(stderr, "gz close: %s\n", what);
     };

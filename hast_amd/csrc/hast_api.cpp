@@ -28,6 +28,7 @@
 #include "kc_device.h"
 #include "fq_device.h"
 #include "hast_internal.h"
+#include "switches.h"
 #include "worker_pool.h"
 
 using namespace hast;
@@ -121,10 +122,8 @@ size_t table_slots(const hast_ctx *c) { return (size_t)c->nbuckets * kSlotsPerBu
 // loaded; measured sweep in DESIGN.md
 int default_minimizer_plain(int k) { return k <= 16 ? k : std::max(16, k - 8); }
 int default_minimizer(int k) {
-    if (const char *e = getenv("HAST_MINIMIZER")) {
-        int v = atoi(e);
-        if (v >= 1 && v <= k) return v;
-    }
+    int v = 0;
+    if (sw::integer(sw::HAST_MINIMIZER, &v) && v <= k) return v;
     return default_minimizer_plain(k);
 }
 
@@ -213,15 +212,17 @@ Parked &parked() {
 }
 size_t park_limit() {                                      // (the environment is read once, like every other switch: INTEGRATION.md)
     static const size_t limit = [] {
-        const char *e = getenv("HAST_PARK_GB");
-        return (size_t)((e ? atof(e) : 32.0) * 1073741824.0);
+        double gb = 32.0;
+        sw::real(sw::HAST_PARK_GB, &gb);
+        return (size_t)(gb * 1073741824.0);
     }();
     return limit;
 }
 int park_sites() {
     static const int sites = [] {
-        const char *e = getenv("HAST_PARK_SITES");
-        return e ? atoi(e) : -1;
+        int mask = -1;
+        sw::integer(sw::HAST_PARK_SITES, &mask);
+        return mask;
     }();
     return sites;
 }
@@ -296,7 +297,7 @@ hast_status hast_ctx_create(int device, int k, hast_ctx **out) {
     *out = nullptr;
     if (k < 1 || k > 32) return set_error(HAST_ERR_INVALID, "K=%d out of [1,32]", k);
     // HAST_TRACE_INIT=1: which call of the context's creation a box makes wait (0.07 - 0.26 s from run to run on one box)
-    const bool trace = getenv("HAST_TRACE_INIT") != nullptr;
+    const bool trace = sw::flag(sw::HAST_TRACE_INIT);
     auto now_s = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double t_tr = now_s();
     auto tr = [&](const char *what) {
@@ -316,26 +317,21 @@ hast_status hast_ctx_create(int device, int k, hast_ctx **out) {
     c->device = device;
     c->k = k;
     c->m = default_minimizer(k);
-    if (const char *e = getenv("HAST_CLASSIFY")) c->use_filter = strcmp(e, "exact") != 0;
-    if (const char *e = getenv("HAST_TEST_FILTER_OOM")) c->test_filter_oom = atoi(e) != 0;
-    if (const char *e = getenv("HAST_FILTER_M")) c->filter_m = atoi(e);
-    if (const char *e = getenv("HAST_FILTER_T")) c->filter_t = atoi(e);
-    if (const char *e = getenv("HAST_FILTER_KP")) c->filter_kp = atoi(e);
-    if (const char *e = getenv("HAST_FILTER_EXACT")) {
-        if (!strcmp(e, "once")) c->exact_env_once = true;             // (before the atoi, which would read the word as 0 = prints)
-        else c->exact_env_off = atoi(e) == 0;
-    }
+    c->use_filter = !sw::word_is(sw::HAST_CLASSIFY, "exact");
+    c->test_filter_oom = sw::flag(sw::HAST_TEST_FILTER_OOM);
+    sw::integer(sw::HAST_FILTER_M, &c->filter_m);
+    sw::integer(sw::HAST_FILTER_T, &c->filter_t);
+    sw::integer(sw::HAST_FILTER_KP, &c->filter_kp);
+    c->exact_env_once = sw::word_is(sw::HAST_FILTER_EXACT, "once");
+    c->exact_env_off = sw::word_is(sw::HAST_FILTER_EXACT, "0");
     if (c->exact_env_off) c->filter_exact = 0;
     else if (c->exact_env_once) c->filter_exact = 1;
-    if (const char *e = getenv("HAST_COMMIT")) c->commit_mode = !strcmp(e, "atomic") ? 1 : !strcmp(e, "partition") ? 2 : 0;
-    if (const char *e = getenv("HAST_PART_SPAN")) c->part_span = (uint32_t)atoi(e);      // (out of commit_plan.h's range: ignored)
-    if (const char *e = getenv("HAST_F_GEO")) c->kernel_geo = e[0] != '0';
-    if (const char *e = getenv("HAST_F_RL")) c->kernel_rl = e[0] != '0';
-    if (const char *e = getenv("HAST_COUNT_LOOKUPS")) c->count_lookups = atoi(e) != 0;
-    if (const char *e = getenv("HAST_TILE_LDS")) {
-        const long v = atol(e);
-        if (v >= 4096 && v <= 160 * 1024) c->tile_lds = (size_t)v;
-    }
+    c->commit_mode = sw::word(sw::HAST_COMMIT) + 1;                 // (the row's words in the order of the modes: atomic 1, partition 2; unset 0)
+    sw::integer(sw::HAST_PART_SPAN, &c->part_span);                 // (out of commit_plan.h's range: ignored)
+    c->kernel_geo = sw::flag(sw::HAST_F_GEO);
+    c->kernel_rl = sw::flag(sw::HAST_F_RL);
+    c->count_lookups = sw::flag(sw::HAST_COUNT_LOOKUPS);
+    sw::size(sw::HAST_TILE_LDS, &c->tile_lds);
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->n_cu = prop.multiProcessorCount;
     tr("hipGetDeviceProperties");
@@ -1000,7 +996,7 @@ hast_status hast_counts_allreduce(hast_ctx *const *ctxs, int n) {
     // a single GPU needs no exchange; HAST_FORCE_RCCL=1 still runs the RCCL path (1-rank communicator), which
     // is how a 1-GPU box checks the library loading, symbols and enum values used for N > 1
     const int nl = (int)lead.size();
-    if (nl == 1 && !getenv("HAST_FORCE_RCCL")) return hand_back();
+    if (nl == 1 && !sw::flag(sw::HAST_FORCE_RCCL)) return hand_back();
     typedef void *comm_t;
     typedef int (*init_all_t)(comm_t *, int, const int *);
     typedef int (*allreduce_t)(const void *, void *, size_t, int, int, comm_t, hipStream_t);

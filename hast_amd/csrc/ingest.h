@@ -35,6 +35,7 @@
 #include "bgzf_reader.h"
 #include "fast_inflate.h"
 #include "par_inflate.h"
+#include "switches.h"
 #include "worker_pool.h"
 
 namespace hast {
@@ -173,8 +174,7 @@ class BlockSource {
         close();
         const size_t n = path.size();
         gz_mode_ = n > 3 && path.compare(n - 3, 3, ".gz") == 0;               // classify.cpp:245-249
-        const char *which = getenv("HAST_INFLATE");
-        use_zlib_ = which && strcmp(which, "zlib") == 0;
+        use_zlib_ = sw::word_is(sw::HAST_INFLATE, "zlib");
         error_.clear();
         if (gz_mode_ && use_zlib_) {
             gz_ = gzopen(path.c_str(), "rb");
@@ -187,8 +187,9 @@ class BlockSource {
             bgzf_ = BgzfReader::probe(fp_);
             if (bgzf_) {
                 const unsigned hw = std::thread::hardware_concurrency();
-                const char *e = getenv("HAST_BGZF_THREADS");
-                bgzf_reader_.open(fp_, e ? atoi(e) : (int)std::min(16u, std::max(2u, hw / 8)));
+                int threads = (int)std::min(16u, std::max(2u, hw / 8));
+                sw::integer(sw::HAST_BGZF_THREADS, &threads);
+                bgzf_reader_.open(fp_, threads);
             } else if (gz_threads() > 1 && ParGzReader::usable(fp_)) {
                 // an ordinary gzip stream in a regular file: several threads at once (par_inflate.h).  The files open at
                 // the same time share a budget of inflate threads (a thread inflates ~1 GB/s alone, ~0.6 GB/s as one of 16:
@@ -383,13 +384,15 @@ class BlockSource {
     // machine, at most 8 -- several files are open at once, and on the 1-GPU share of an MI355X host two files x 8 threads
     // was the fastest setting (one file alone: 9.3 GB/s with 16 threads, 6.7 with 8, 1.4 serial; profiles/r02p_gz_e2e.log)
     static int gz_threads() {
-        if (const char *e = getenv("HAST_GZ_THREADS")) return std::max(1, atoi(e));
+        int n = 0;
+        if (sw::integer(sw::HAST_GZ_THREADS, &n)) return n;
         const unsigned hw = std::thread::hardware_concurrency();
         return (int)std::min(8u, std::max(2u, hw / 8));
     }
     // inflate threads over all ordinary .gz files open at once (HAST_GZ_BUDGET)
     static int gz_budget() {
-        if (const char *e = getenv("HAST_GZ_BUDGET")) return std::max(1, atoi(e));
+        int n = 0;
+        if (sw::integer(sw::HAST_GZ_BUDGET, &n)) return n;
         // what the container may really use (cgroup v2 cpu.max: a 1-GPU share of an MI355X host shows 256 hardware threads and
         // grants 16 cores), else 16
         static const int quota = [] {

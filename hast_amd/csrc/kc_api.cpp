@@ -12,6 +12,7 @@
 
 #include "hast_internal.h"
 #include "kc_device.h"
+#include "switches.h"
 
 using namespace hast;
 
@@ -103,9 +104,9 @@ hast_status check_synth(const hast_kc_synth *p) {
 // of the direct kernel.  The buffers take what is left of the device memory next to the table: ~22.5 B per record of capacity.
 // HAST_KC_FLUSH=sweep|atomic pins how a flush is applied (default: by the number of records, launch_kc_flush).
 static void part_setup(hast_kc *c) {
-    const char *e = getenv("HAST_KC_COUNT");
-    const bool forced = e && !strcmp(e, "partition"), off = e && !strcmp(e, "atomic");
-    if (const char *fl = getenv("HAST_KC_FLUSH")) c->small_flush = !strcmp(fl, "sweep") ? 1 : !strcmp(fl, "atomic") ? 2 : 0;
+    const int count = sw::word(sw::HAST_KC_COUNT);                    // (the row's words: atomic 0, partition 1)
+    const bool forced = count == 1, off = count == 0;
+    c->small_flush = sw::word(sw::HAST_KC_FLUSH) + 1;                  // (sweep 1, atomic 2)
     if (off || kc_run_max(c->k, c->m) == 0 || (!forced && c->nbuckets < (1u << 20))) return;
     c->fine_shift = ((uint64_t)c->nbuckets >> 9) > (1u << 20) ? 10 : 9;
     const uint64_t n_fine = ((uint64_t)c->nbuckets + (1u << c->fine_shift) - 1) >> c->fine_shift;
@@ -114,7 +115,7 @@ static void part_setup(hast_kc *c) {
     c->f2 = 1;                                                         // fine bins per level-1 bin: a power of two (a shift in the kernels)
     while ((n_fine + c->f2 - 1) / c->f2 > 1024) c->f2 <<= 1;
     c->n_l1 = (uint32_t)((n_fine + c->f2 - 1) / c->f2);
-    if (const char *sp = getenv("HAST_KC_L1_SPLIT")) c->l1_split = (uint32_t)std::min(32l, std::max(1l, atol(sp)));
+    sw::integer(sw::HAST_KC_L1_SPLIT, &c->l1_split);
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return;
     const uint64_t fixed = 8ull * (64ull * c->n_fine + 4096ull * c->n_l1 * c->l1_split + (1u << 20)) + 8ull * ((uint64_t)c->n_l1 * c->l1_split * kKcL1FillWords + c->n_fine) + (64u << 20);
@@ -128,7 +129,8 @@ static void part_setup(hast_kc *c) {
     // ... nor more than the input can write (a record holds 3.3 windows on average, never fewer than one per two here: the bound the
     // flush logic works with): a 20-Mbp trio then takes 16 GB of record buffers, not the 60 GB that happened to be free
     if (c->expected_windows) R = std::min<uint64_t>(R, std::max<uint64_t>(c->expected_windows / 2 + (1u << 20), 16ull << 20));
-    if (const char *m = getenv("HAST_KC_RECORD_MB")) R = std::min<uint64_t>(R, ((uint64_t)atol(m) << 20) / 8);     // (the record buffer itself)
+    uint64_t record_mb = 0;
+    if (sw::integer(sw::HAST_KC_RECORD_MB, &record_mb)) R = std::min<uint64_t>(R, (record_mb << 20) / 8);     // (the record buffer itself)
     if (R < (forced ? 4096u : (16u << 20))) return;
     c->rec_cap = R;
     c->a_cap = R + R / 2 + 64ull * c->n_fine + 1024;
@@ -159,9 +161,7 @@ static hast_status table_real(hast_kc *c) {
 // an empty table: the partitioned path's first flush writes every slice anyway, so it is only DECLARED empty (the clear is 9 ms of a
 // 110-ms step on the bench's 64-GB table; HAST_KC_FRESH=0: always cleared)
 static hast_status table_empty(hast_kc *c) {
-    const char *e = getenv("HAST_KC_FRESH");
-    const bool lazy = !(e && !strcmp(e, "0"));
-    c->fresh = c->part_on && lazy;
+    c->fresh = c->part_on && sw::flag(sw::HAST_KC_FRESH);
     if (c->fresh) return HAST_OK;
     HAST_HIP_TRY(launch_kc_clear(c->d_table, c->nbuckets, c->stream));
     return HAST_OK;
@@ -237,10 +237,8 @@ hast_status hast_kc_create_ex(int device, int k, size_t table_bytes, uint64_t ex
     c->k = k;
     c->m = default_minimizer_for(k);
     c->expected_windows = expected_windows;
-    if (const char *t = getenv("HAST_KC_TILE")) {
-        const long v = atol(t);
-        if (v >= 256 && v <= 16384) c->tile_bases = (uint32_t)(v & ~31l);
-    }
+    uint32_t tile = 0;
+    if (sw::integer(sw::HAST_KC_TILE, &tile)) c->tile_bases = tile & ~31u;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->n_cu = prop.multiProcessorCount;
     hast_status st = HAST_OK;

@@ -19,6 +19,7 @@
 #include "hast_devutil.h"
 #include "kc_common.h"
 #include "kc_device.h"
+#include "switches.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -487,8 +488,7 @@ __global__ void __launch_bounds__(kKcThreads) k_kc_emit4(KcCountArgs a) {
 }
 // does k_kc_emit4 take this launch?  (HAST_KC_EMIT=lanes keeps k_kc_count<W, true>: A/B runs, and the tests of that kernel)
 static bool kc_emit4_takes(const KcCountArgs &a) {
-    const char *e = getenv("HAST_KC_EMIT");
-    const bool off = e && !strcmp(e, "lanes");
+    const bool off = sw::word_is(sw::HAST_KC_EMIT, "lanes");
     const int w = a.k - a.m + 1;
     return !off && a.rec_out && a.m == 16 && w >= 2 && w <= 6 && a.rec_run_max >= (uint32_t)w && a.k + w + 2 <= 32 && a.tile_bases % 1024 == 0 &&
            a.tile_bases <= 16384 && a.rec_chunk >= a.tile_bases;

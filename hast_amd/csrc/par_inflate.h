@@ -51,6 +51,7 @@
 #include <vector>
 
 #include "fast_inflate.h"
+#include "switches.h"
 #include "worker_pool.h"
 
 namespace hast {
@@ -698,7 +699,7 @@ class ParGzReader {
             c.hist_lo = kWindow - (size_t)std::min<uint64_t>(carry_member_out_, kWindow);
         }
         const uint64_t buf_end_bit = (in_base_ + in_len_) * 8;
-        const bool trace = getenv("HAST_GZ_TRACE") != nullptr;
+        const bool trace = sw::flag(sw::HAST_GZ_TRACE);
         const auto t0 = std::chrono::steady_clock::now();
         std::atomic<size_t> next{0};
         pool_->run([&](int) {

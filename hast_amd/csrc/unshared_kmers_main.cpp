@@ -42,6 +42,7 @@
 namespace {
 
 using hast::now_s;
+namespace sw = hast::sw;
 
 void usage(FILE *f) {
     fputs("Usage: unshared_kmers [options]\n"
@@ -541,10 +542,8 @@ bool parse_command_line(int argc, char **argv, Options &o, int &status) {
             return false;
         }
     }
-    if (!ingest_given)
-        if (const char *e = getenv("HAST_KC_INGEST")) o.ingest = e;
-    if (!device_fasta_given)
-        if (const char *e = getenv("HAST_KC_DEVICE_FASTA")) o.device_fasta = atol(e) != 0;
+    if (!ingest_given && sw::word_is(sw::HAST_KC_INGEST, "device")) o.ingest = "device";
+    if (!device_fasta_given) o.device_fasta = sw::flag(sw::HAST_KC_DEVICE_FASTA);
     if (o.ingest != "host" && o.ingest != "device") {
         printf("ERROR: --ingest %s: host or device\n", o.ingest.c_str());
         status = 1;
@@ -632,8 +631,7 @@ void set_up_device_ingest(Run &r) {
     }
     r.di.on = true;
     r.di.fasta = o.device_fasta;
-    if (const char *e = getenv("HAST_KC_INGEST_BLOCK"))
-        if (atol(e) >= 64) r.di.block = (size_t)atol(e);
+    sw::size(sw::HAST_KC_INGEST_BLOCK, &r.di.block);
     bool any_gz = false;
     for (int p = 0; p < 2; ++p) any_gz = any_gz || ends_gz(o.files[p][0]);
     // (without a context the .gz files are inflated on the host and uploaded)

@@ -34,6 +34,13 @@ def geometry(tmp_path_factory):
     return {r[:2]: r[2:] for r in rows}
 
 
+def switch_row(name):
+    """(name, kind, lo, hi, policy, words) of a row of switches.h's table, as the header spells them"""
+    mt = re.search(r'^\s*X\((%s), (\w+), ([^,]+), ([^,]+), (\w+), ("[^"]*"),' % name, src("switches.h"), re.M)
+    assert mt, "switches.h has no row %s" % name
+    return mt.groups()
+
+
 class Dispatch:
     """what the sources say"""
 
@@ -57,7 +64,7 @@ class Dispatch:
         takes = re.search(r"static bool kc_emit4_takes\(const KcCountArgs &a\) \{\n(.*?)\n\}\n", text, re.S)
         assert takes, "kc_emit4_takes" + GAIN
         t = takes.group(1)
-        assert 'getenv("HAST_KC_EMIT")' in t and re.search(r'const bool off = e && !strcmp\(e, "lanes"\);', t), t
+        assert re.search(r'const bool off = sw::word_is\(sw::HAST_KC_EMIT, "lanes"\);', t) and switch_row("HAST_KC_EMIT")[1::4] == ("Word", '"lanes"'), t
         assert "const int w = a.k - a.m + 1;" in t, t
         ret = re.search(r"return (.*?);", t, re.S).group(1)
         self.takes_terms = [" ".join(x.split()) for x in ret.split("&&")]
@@ -86,9 +93,10 @@ class Dispatch:
         mt = re.search(r"uint32_t tile_bases = (\d+);", api)
         assert mt, "hast_kc::tile_bases"
         self.default_tile = int(mt.group(1))
-        mt = re.search(r'getenv\("HAST_KC_TILE"\)\) \{\s*const long v = atol\(t\);\s*if \(v >= (\d+) && v <= (\d+)\) c->tile_bases = \(uint32_t\)\(v & ~(\d+)l\);', api)
-        assert mt, "HAST_KC_TILE"
-        self.tile_lo, self.tile_hi, self.tile_round = int(mt.group(1)), int(mt.group(2)), int(mt.group(3)) + 1
+        mt = re.search(r"uint32_t tile = 0;\s*if \(sw::integer\(sw::HAST_KC_TILE, &tile\)\) c->tile_bases = tile & ~(\d+)u;", api)
+        row = switch_row("HAST_KC_TILE")
+        assert mt and row[1] == "Int" and row[4] == "Ignore", "HAST_KC_TILE: an integer of the row's [lo, hi], ignored outside it"
+        self.tile_lo, self.tile_hi, self.tile_round = int(row[2]), int(row[3]), int(mt.group(1)) + 1
         mt = re.search(r"a\.rec_chunk = (\d+) \* a\.tile_bases;", api)
         assert mt, "rec_chunk"
         self.chunk_tiles = int(mt.group(1))
@@ -99,7 +107,8 @@ class Dispatch:
         mt = re.search(r"int default_minimizer_plain\(int k\) \{ return k <= (\d+) \? k : std::max\((\d+), k - (\d+)\); \}", host)
         assert mt, "default_minimizer_plain is no longer `k <= a ? k : max(b, k - c)`" + GAIN
         self.dm = tuple(int(x) for x in mt.groups())
-        assert re.search(r'getenv\("HAST_MINIMIZER"\)\) \{\s*int v = atoi\(e\);\s*if \(v >= 1 && v <= k\) return v;', host), "HAST_MINIMIZER"
+        row = switch_row("HAST_MINIMIZER")
+        assert re.search(r"int v = 0;\s*if \(sw::integer\(sw::HAST_MINIMIZER, &v\) && v <= k\) return v;", host) and row[1:5] == ("Int", "1", "32", "Ignore"), "HAST_MINIMIZER"
         assert "int default_minimizer_for(int k) { return default_minimizer(k); }" in host
 
     def default_m(self, k):

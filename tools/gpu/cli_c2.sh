@@ -28,7 +28,7 @@ el() { python3 -c "print(round($2-$1,2))"; }
 echo "== box: $(nproc) hardware threads, cpu.max $(cat /sys/fs/cgroup/cpu.max 2>/dev/null), memory.max $(cat /sys/fs/cgroup/memory.max 2>/dev/null), /dev/shm $(df -h /dev/shm | tail -1 | awk '{print $4}') free"
 t0=$(now); GEN_FASTQ_MAX_GB=90 tools/gen_fastq $D $NPAIRS $KEYS $BARCODES 21 150 32 0 || exit 1; t1=$(now)
 echo "== generated in $(el $t0 $t1) s: $((2*NPAIRS)) reads of 150 bp, $KEYS + $KEYS 21-mers, $BARCODES barcodes; $(stat -c %s $D/r1.fq) bytes per FASTQ file, $(stat -c %s $D/hap0.mer) per k-mer file"
-if has runs || has route || has prof || has blocks || has ab || has abname || has abcus || has abids || has abahead || has paused; then
+if has runs || has route || has prof || has blocks || has ab || has abcus || has abahead || has paused; then
 t0=$(now); tools/pgzip1 $D/r1.fq $D/r1.fq.gz $LEVEL 16 32 && tools/pgzip1 $D/r2.fq $D/r2.fq.gz $LEVEL 16 32 || exit 1; t1=$(now)
 echo "== compressed in $(el $t0 $t1) s (tools/pgzip1 level $LEVEL: ONE gzip member per file): $(stat -c %s $D/r1.fq.gz) + $(stat -c %s $D/r2.fq.gz) bytes"
 fi
@@ -94,14 +94,6 @@ if has ab; then              # the block size that follows the input's size (def
     echo "   cpu.stat: $(thr)"
   done
 fi
-if has abname; then          # a dictionary names a block behind its framing (HAST_NAME_EARLY=1, tried in round 6) against in hast_fq_next on the context's stream (the default)
-  for rep in 1 2 3; do
-    HAST_NAME_EARLY=1 run gz_name_early_$rep $PY $ARGS --read $D/r1.fq.gz --read $D/r2.fq.gz
-    HAST_NAME_EARLY=0 run gz_name_in_next_$rep $PY $ARGS --read $D/r1.fq.gz --read $D/r2.fq.gz
-    HAST_NAME_EARLY=1 run plain_name_early_$rep $PY $ARGS --read $D/r1.fq --read $D/r2.fq
-    HAST_NAME_EARLY=0 run plain_name_in_next_$rep $PY $ARGS --read $D/r1.fq --read $D/r2.fq
-  done
-fi
 if has abcus; then           # CUs the decode passes leave to the kernels behind them (HAST_GZ_FREE_CUS, default 32), alternating
   for rep in ${CUS_REPS:-1 2 3}; do
     for cus in ${CUS_LIST:-32 16 0 64}; do
@@ -127,17 +119,6 @@ if has abahead; then         # two passes of a file on the GPU together (HAST_GZ
   HAST_GZ_AHEAD=1 run gz_ahead1_devices_0_0 $PY $ARGS --read $D/r1.fq.gz --read $D/r2.fq.gz --devices 0,0
   HAST_GZ_AHEAD=1 run gz_ahead1_one_gz $PY $ARGS --read $D/r1.fq.gz --read $D/r2.fq
   HAST_GZ_AHEAD=0 run gz_ahead0_one_gz $PY $ARGS --read $D/r1.fq.gz --read $D/r2.fq
-fi
-if has abids; then           # the bookkeeping kernel reads a block's ids in device memory (default, round 6) against out of pinned host memory (HAST_COMMIT_IDS=host)
-  for rep in 1 2 3; do
-    run gz_ids_device_$rep $PY $ARGS --read $D/r1.fq.gz --read $D/r2.fq.gz
-    HAST_COMMIT_IDS=host run gz_ids_host_$rep $PY $ARGS --read $D/r1.fq.gz --read $D/r2.fq.gz
-    run plain_ids_device_$rep $PY $ARGS --read $D/r1.fq --read $D/r2.fq
-    HAST_COMMIT_IDS=host run plain_ids_host_$rep $PY $ARGS --read $D/r1.fq --read $D/r2.fq
-  done
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/round6_prof_c2 -- $PY $ARGS --read $D/r1.fq.gz --read $D/r2.fq.gz > $D/out.prof 2> $D/err.prof
-  f=$(ls $O/round6_prof_c2/*/*kernel_stats.csv 2>/dev/null | head -1); [ -n "$f" ] && cp $f $O/round6_cli_c2_gz_kernel_stats_ids_on_device.csv && head -12 $f | cut -c1-200
-  rm -rf $O/round6_prof_c2
 fi
 if has route; then
   KEEP=plain_route run plain_route $PY $ARGS --read $D/r1.fq --read $D/r2.fq --phase-reads

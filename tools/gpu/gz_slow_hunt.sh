@@ -8,7 +8,7 @@ export GEN_FASTQ_QUAL=${QUAL:-noisy}
 tools/gen_fastq $D 10000000 5000000 100000 21 150 32 0 || exit 1
 tools/pgzip1 $D/r1.fq $D/r1.fq.gz 6 16 32; tools/pgzip1 $D/r2.fq $D/r2.fq.gz 6 16 32
 ARGS="--hap0 $D/hap0.mer --hap1 $D/hap1.mer --weight0 1.04 -t 32 --stats --read $D/r1.fq.gz --read $D/r2.fq.gz"
-# ALT="A=1 A=0": the runs alternate between these settings of one environment variable (e.g. HAST_GZ_PREALLOC=1 HAST_GZ_PREALLOC=0)
+# ALT="A=1 A=0": the runs alternate between these settings of one environment variable (e.g. HAST_GZ_AHEAD=1 HAST_GZ_AHEAD=0)
 for rep in $(seq 1 ${N:-30}); do
  for alt in ${ALT:-HAST_UNUSED=1}; do
   case $alt in SLEEP_BEFORE=*) sleep ${alt#SLEEP_BEFORE=};; esac      # (ALT="SLEEP_BEFORE=0 SLEEP_BEFORE=3": does a pause behind the previous process's exit matter?)
