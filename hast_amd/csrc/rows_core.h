@@ -43,7 +43,9 @@ ROWS_HD uint32_t text_len(const uint8_t rec[16]) { return rec[0] < kMaxText ? re
 //     all 0x00 ("ab" against "ab\0"), all 15 text bytes of the keys agree and the length byte, the least significant one, decides:
 //     a < b, A first.
 //   * equal texts have equal keys, and only they: the length byte tells texts apart that differ only in trailing 0x00 bytes.
-// Ids are one per text, so no two rows have the same key and the sort's stability is not needed for the result.
+// Ids are one per text, so no two rows have the same 128-bit key: the ORDER has no ties for a sort to break.  The device's sort of it
+// does: it is two 64-bit passes, by lo and then by hi (rows_api.cpp), and the pass by hi must be stable -- rows with the same first
+// eight bytes have equal keys there and keep the order the pass by lo left.  Never an unstable sort in its place.
 ROWS_HD Key row_key(const uint8_t rec[16]) {
     const uint32_t n = text_len(rec);
     Key k = {0, 0};

@@ -1,7 +1,7 @@
 """`classify --rows device` (HAST_ROWS): the output table, and with --phase-reads the three barcode lists, keyed, called, sorted and
 formatted on the GPU (hast_rows_*).  The bytes are the reference's on every golden case, with one and with several contexts; every
 run the device cannot do this for goes the host's way with its reason and the same bytes; --phase-reads leaves the same files as
---rows host; the flag's alias, its usage error, a full disk, and no word of it in the stats of a run that did not ask."""
+--rows host, also with a table of several tiles of barcodes; the flag's alias, its usage error, a full disk, and no word of it in the stats of a run that did not ask."""
 import gzip
 import os
 import shutil
@@ -163,12 +163,34 @@ def phase_reads_files(exe, src, tmp_path, reads, mode, make_inputs):
     return r.stdout, err, files, markers, rows_line(r), route
 
 
+MANY_TILES = 5                                      # many_barcodes: more rows than this many tiles of 512 (rows::kTile)
+
+
+def many_barcodes_fastq(d):
+    """rand_k21's reads under other headers: nearly every record a barcode of its own, of at most 15 bytes, in no order of the texts --
+    some 2800 rows, six tiles of k_rows_write; every tenth record of the second file shares its mate's barcode, every 97th has 0_0_0"""
+    out = []
+    for k, name in enumerate(("r1.fq.gz", "r2.fq.gz")):
+        with gzip.open(d / name, "rb") as f:
+            lines = f.read().split(b"\n")
+        recs = []
+        for i in range(len(lines) // 4):
+            j = i if k == 0 or i % 10 == 3 else 1500 + i
+            code = b"0_0_0" if i % 97 == 5 else b"%d_%d_%d" % (1 + j * 7 % 1536, 1 + j * 11 % 1536, 1 + j)
+            assert len(code) <= 15
+            recs.append(b"@M%d#%s/%d\n" % (i, code, k + 1) + b"\n".join(lines[4 * i + 1:4 * i + 4]) + b"\n")
+        out.append(b"".join(recs))
+    assert len({r.split(b"#")[1].split(b"/")[0] for o in out for r in o.split(b"\n")[0::4] if r}) > MANY_TILES * 512
+    return out
+
+
 JOBS = {
     # name: (inputs, the route of the table with --rows device, its reason, the router)
     "rand_k21": (None, "device", "none", "route=device"),
     "edge": (dict(), "host", "host_names", "route=device"),                          # (barcodes of 16 bytes and more are the host's to name)
     "edge_short": (dict(long_barcodes=False), "device", "none", "route=device"),
     "edge_with_separator": (dict(long_barcodes=False, sep=True), "device", "none", "route=host"),
+    "many_barcodes": ("many", "device", "none", "route=device"),                     # (the table has a second tile, and a sixth)
 }
 
 
@@ -178,6 +200,12 @@ def test_phase_reads_leaves_the_same_files_as_rows_host(exe, golden_workdir, tmp
 
     def make_inputs(d):
         if edge is None:
+            return
+        if edge == "many":
+            one, two = many_barcodes_fastq(d)
+            (d / "e1.fq").write_bytes(one)
+            with gzip.open(d / "e2.fq.gz", "wb") as g:
+                g.write(two)
             return
         recs = edge_fastq(**edge)
         (d / "e1.fq").write_bytes("".join(recs).encode())
@@ -195,3 +223,5 @@ def test_phase_reads_leaves_the_same_files_as_rows_host(exe, golden_workdir, tmp
     if route == "device":
         sizes = [len(host[2][n + ".unique.barcodes"]) for n in ("paternal", "maternal", "homozygous")]
         assert dev[4]["list_bytes"] == "%d,%d,%d" % tuple(sizes) and int(dev[4]["table_bytes"]) == len(host[0])
+    if job == "many_barcodes":
+        assert int(dev[4]["rows"]) > MANY_TILES * 512 and int(dev[4]["rows"]) == host[0].count(b"\n"), dev[4]

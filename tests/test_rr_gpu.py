@@ -1,6 +1,6 @@
 """GPU test of stage 03's rows made on the device (rr_kernels.hip; rules: hast_amd/csrc/rr_core.h).  The direct entry
 hast_rs_rows_device over crafted names and votes -- every tile boundary, more than 1024 tiles, names from nothing to kilobytes in one
-call, votes and set sizes up to 2^32 - 1 -- against the restatement of tests/rr_model.py, byte for byte; and the feed
+call, votes and set sizes up to 2^32 - 1, and once more tiles than the capped grid has workgroups -- against the restatement of tests/rr_model.py, byte for byte; and the feed
 (hast_rs_set_rows / hast_rs_next_rows) over every file of tests/rs_corpus.py against the model's rows of what hast_rs_next hands out
 for the same file, with the views whose rows outgrow the feed's buffer coming back for the host."""
 import random
@@ -10,6 +10,7 @@ import pytest
 
 import hast_amd
 from hast_amd import ReadStream
+from tests import past_grid_corpus as pg
 from tests import rr_model as rr
 from tests import rs_corpus as rc
 
@@ -105,6 +106,50 @@ def test_rows_of_crafted_arrays_are_the_models(ctx, inputs, n, totals):
         at = next(i for i in range(len(want)) if buf[i] != want[i])
         assert False, (n, totals, at, buf[max(0, at - 40):at + 40], want[max(0, at - 40):at + 40])
     assert buf[len(want):] == b"\xaa" * GUARD, (n, totals)
+
+
+def sliced(n, seed):
+    """names of 0 to 65 bytes cut out of one random buffer at random places (no byte of them drawn one by one: half a million names in
+    a second), votes of crafted()'s ten kinds"""
+    rng = np.random.default_rng(seed)
+    soup = rng.integers(33, 127, size=1 << 16, dtype=np.uint8).tobytes()
+    at, lens = rng.integers(0, len(soup) - 65, size=n).tolist(), rng.integers(0, 66, size=n).tolist()
+    names = [soup[a:a + k] for a, k in zip(at, lens)]
+    a, kind = rng.integers(1, 301, size=n), rng.integers(0, 10, size=n)
+    r0, r1, zero, one, top = rng.integers(0, M32 + 1, size=n), rng.integers(0, M32 + 1, size=n), 0 * a, 0 * a + 1, 0 * a + M32
+    votes = np.zeros((n, 2), dtype=np.uint32)
+    votes[:, 0] = np.choose(kind, [zero, a, a, zero, 2 * a + 1, one, top, r0, r0, a])
+    votes[:, 1] = np.choose(kind, [zero, a, zero, a, one, 2 * a + 1, r1, top, r1, a - 1])
+    return names, votes
+
+
+@pytest.fixture(scope="module")
+def past_grid():
+    """past_grid_corpus.N2 rows, in the layout of `inputs`"""
+    n = pg.N2
+    names, votes = sliced(n, 4100)
+    off = np.zeros(n + 1, dtype=np.uint32)
+    off[1:] = np.cumsum([len(x) for x in names], dtype=np.uint64)
+    return {n: (names, votes, off, np.frombuffer(b"".join(names) + b"\0", dtype=np.uint8), {})}
+
+
+def test_rows_past_one_grid_are_the_models(ctx, past_grid):
+    """2050 tiles of 256 rows: workgroups 0 and 1 of the capped grids walk a second tile, the last tile is partial; the block scan of the
+    tiles' sums gives its threads three tiles each"""
+    n, totals = pg.N2, TOTALS[0]
+    names, votes = past_grid[n][:2]
+    tiles = -(-n // pg.TILE)
+    assert tiles > pg.GRID_CAP and tiles > 2 * pg.SCAN_THREADS and {len(x) for x in names} == set(range(66)) and len(set(names[:5000])) > 4900
+    want, count, sizes = model(past_grid, n, totals)
+    assert min(count) > 1000
+    nbytes, got_count, buf = run_direct(ctx, past_grid, n, totals)
+    assert nbytes == len(want) and got_count == count, (nbytes, len(want), got_count, count)
+    same = buf[:len(want)] == want
+    if not same:
+        at = int(np.flatnonzero(np.frombuffer(buf, dtype=np.uint8, count=len(want)) != np.frombuffer(want, dtype=np.uint8))[0])
+        row = int(np.searchsorted(np.cumsum(sizes), at, side="right"))
+        pytest.fail("the rows differ at offset %d: row %d, tile %d\n got  %r\n want %r" % (at, row, row // pg.TILE, buf[max(0, at - 40):at + 40], want[max(0, at - 40):at + 40]))
+    assert buf[len(want):] == b"\xaa" * GUARD
 
 
 @pytest.mark.parametrize("n", (1, 257, 256 * 1024 + 1))
